@@ -9,6 +9,12 @@ A step = forward + fused losses + backward + (bucketed RCCL gradient all-reduce)
 batch of synthetic clips already resident in HBM.  Workload at every N: (B,T,N_slots)=(32,16,64),
 d=256 per GPU (weak scaling: per-GPU clips fixed, global batch = 32 * N).  One JSON line on rank 0.
 
+`--steps K` is the number of timed steps; `ms_per_step` on the line = their wall time / K.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last of them computed as float32 DIR/<name>.npy (loss,
+params, grads, class_logits, boxes; see dump_outputs): inputs and initial weights are seeded, so two builds run with the
+same arguments can be compared array for array.
+
 Objects on the line besides the contract's fields:
   roofline        the dominant kernel (largest summed device time of the step: gemm_pair_kernel - since round 3 a projection's
                   weight gradient and data gradient run as ONE launch; with VLG_GEMM_PAIR=0 | 1 the weight-gradient GEMM alone):
@@ -329,6 +335,31 @@ def timed_steps(step_fn, n: int) -> float:
     return (time.perf_counter() - t0) / n
 
 
+# --dump-outputs: elements kept per array (4 B each, 48 MB in all); a larger array is written as a fixed, seeded sample
+DUMP_CAP = {"loss": 4, "params": 4 << 20, "grads": 4 << 20, "class_logits": 2 << 20, "boxes": 2 << 20}
+DUMP_SAMPLE_SEED = 20260101
+
+
+def dump_outputs(eng, out_dir: str) -> dict:
+    """What the caller of the timed step holds after its last iteration, as float32 DIR/<name>.npy: the loss scalars it
+    returned {total, smooth_l1, iou, ce}, the updated parameters, the step's gradients and the last forward's class logits
+    (B,T,N,C) and raw boxes (B,T,N,4).  An array above its DUMP_CAP is flattened and sampled at sorted indices drawn with
+    a fixed seed, the same indices on every run of the same shape.  Returns {name: shape written}."""
+    import numpy as np
+    logits, boxes = eng.outputs_btn()
+    arrays = {"loss": eng.loss_out, "params": eng.params, "grads": eng.grads, "class_logits": logits, "boxes": boxes}
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().contiguous().numpy()
+        if a.size > DUMP_CAP[name]:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, DUMP_CAP[name], replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -349,7 +380,12 @@ def main():
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the informational legs (other modes, B=4 shard)")
     ap.add_argument("--no-reference-step", action="store_true", help="skip the reference's own pixel step (reference_step object)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (loss, parameters, gradients, logits, "
+                         "boxes) to DIR/<name>.npy as float32 (rank 0; at most 48 MB, larger arrays as a fixed seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args.gpus))
@@ -455,6 +491,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     loss = [float(x) / world for x in eng.loss_out.cpu()]     # summed over ranks inside the first bucket
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before anything below steps the engine again: these are the last timed step's results
+        dumped = dump_outputs(eng, args.dump_outputs)
     comm = None
     if reducer is not None:
         # communication evidence: who took part, what moved, and what it cost on top of the same ranks' compute
@@ -502,6 +542,7 @@ def main():
                        "final_loss": [round(x, 5) for x in loss]},
         }
         line["comm"] = comm
+        line["dumped_outputs"] = dumped
         roof, roof_hbm = None, None
         if eng.timer is not None:
             summ = eng.timer.summary()

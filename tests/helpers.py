@@ -5,6 +5,7 @@ product has no CPU path."""
 import argparse
 import logging
 import math
+import os
 
 import torch
 
@@ -99,11 +100,15 @@ def oracle_factory(cfg, args):
 
 def reference_args(path, rank=0, gpus=1, **over):
     """Namespace with the fields reference src/main.py:86-160 parses (defaults from there) plus the ones
-    main.worker injects (main.py:51-52,164,173,183)."""
+    main.worker injects (main.py:51-52,164,173,183).  The dataset directories are the one exception: the reference's
+    defaults name its authors' machine, so they point inside `path` at directories that do not exist (synthetic
+    frames) and a test never reads data from outside its own temporary tree."""
     logger = logging.getLogger("vlg-test-%d" % rank)
     logger.setLevel(logging.DEBUG)
+    data = os.path.join(str(path), "no-dataset")
     a = argparse.Namespace(
-        dataset="cityscape", train_dir="/data/agong/train", val_dir="/data/agong/val", test_dir="/data/agong/test",
+        dataset="cityscape", train_dir=os.path.join(data, "train"), val_dir=os.path.join(data, "val"),
+        test_dir=os.path.join(data, "test"),
         validate=False, edge=False, val_interval=1, arch="CoordGridNet", discriminator="NLayerDiscriminator",
         generator="ResnetGenerator", batch_size=32, epochs=10, resume=None, img1=None, img2=None, seg1=None,
         seg2=None, workers=4, port=None, seed=1024, print_freq=10, path=str(path), ckpt=None, start_epoch=1,
