@@ -41,8 +41,9 @@ int         vlg_abi_version(void);
 const char* vlg_build_arch(void);          /* "gfx950" */
 
 /* DIAGNOSTIC BUILD ONLY (`make -C csrc diag` -> libvlg_hip_diag.so, compiled with -DVLG_DIAG; the product library does
- * NOT export these and keeps no mutable process-wide state - its only configuration is environment variables read once).
- * Development tools load that build through VLG_HIP_LIB (tools/diag, tools/ab). */
+ * NOT export these, keeps no mutable process-wide state and reads no environment: every kernel and slab plan follows from
+ * the call's arguments).  That build also honours the development tuning variables (VLG_TUNE in csrc/common.h, read once).
+ * Development tools load it through VLG_HIP_LIB (tools/diag, tools/ab). */
 #ifdef VLG_DIAG
 /* when set to a device buffer of 2*blocks uint64, every block of the next GEMM launches records {shader-clock ticks,
  * 100 MHz ticks} of its main loop; NULL switches it off (tools/diag/gemm_shader_clock.py) */
@@ -51,8 +52,7 @@ void vlg_debug_set_conv_probe(unsigned long long* buf);
 /* force the contraction depth per LDS tile of the 128x128 fp32 GEMM kernels (16 | 32; 0 = the library's own choice per
  * epilogue; the VLG_GEMM_BK environment variable sets the initial value) (tools/ab/gemm_ab.py) */
 void vlg_debug_set_gemm_bk(int bk);
-/* consecutive N tiles per block of the chained fp32 GEMM path (0 = never chain, -1 = the library's choice; bit 16: chained
- * launches as ping-pong pairs of four-wave groups - measured slower, see csrc/gemm.hip) */
+/* consecutive N tiles per block of the chained fp32 GEMM path (0 = never chain, -1 = the library's choice) */
 void vlg_debug_set_gemm_run(int run);
 #endif
 
@@ -140,10 +140,11 @@ int vlg_linear_wgrad_slabs_for(int64_t M, int N, int K, int flags);  /* slab cou
 int vlg_linear_wgrad(const void* dY, int ldy, const void* X, int ldx,
                      float* slabs, int64_t slab_stride, int64_t slab_capacity,
                      int64_t M, int N, int K, int flags /* VLG_EPI_BF16 | storage bits */, void* stream);
-/* vlg_linear_wgrad and vlg_linear_dgrad of ONE projection (same dY) as one call - and, for native fp32 tensors where it pays
- * (few tokens: neither product fills the chip alone), as ONE launch whose blocks are dealt both problems at once; results
- * are bit for bit those of the two calls.  epilogue: VLG_EPI_NONE | VLG_EPI_MUL (+ VLG_EPI_BF16 / VLG_EPI_SPLIT3 with fp32
- * storage: two launches).  Replaces the two autograd nodes of one nn.Linear backward. */
+/* vlg_linear_wgrad and vlg_linear_dgrad of ONE projection (same dY) as one call: accepts exactly what the two calls accept
+ * (the weight gradient takes the mode and the dY / X storage bits of `epilogue`), and results are bit for bit those of the
+ * two calls.  Native fp32 tensors and the bf16-storage step (bf16 W / X / dX) with epilogue VLG_EPI_NONE | VLG_EPI_MUL can
+ * run as ONE launch whose blocks are dealt both problems at once (the plan depends on the shape and flags alone: csrc/gemm.hip);
+ * everything else runs as the two launches.  Replaces the two autograd nodes of one nn.Linear backward. */
 int vlg_linear_dgrad_wgrad(const void* dY, int ldy, const void* W, int ldw, void* dX, int ldx, const void* aux_in,
                            const void* X, int ldxx, float* slabs, int64_t slab_stride, int64_t slab_capacity,
                            int64_t M, int N, int K, int epilogue,

@@ -61,3 +61,13 @@ def test_product_library_has_no_debug_setters():
     lib = ctypes.CDLL(hip.LIB_PATH)
     for name in ("vlg_debug_set_clock_probe", "vlg_debug_set_conv_probe", "vlg_debug_set_gemm_bk", "vlg_debug_set_gemm_run"):
         assert not hasattr(lib, name), name
+
+
+def test_product_library_reads_no_tuning_variables():
+    """Every kernel and slab plan of the product library follows from the call's arguments: the development tuning
+    variables (VLG_TUNE in csrc/common.h) are read by the diagnostic build only, so their names are not in the product .so."""
+    from vlg import hip
+    data = open(hip.LIB_PATH, "rb").read()
+    for name in ("VLG_GEMM_BK", "VLG_GEMM_SMALL", "VLG_GEMM_SMALL_BELOW", "VLG_GEMM_SMALL_BELOW_WGRAD", "VLG_WGRAD_SMALL_SLOTS",
+                 "VLG_GEMM_PAIR", "VLG_CONV_NARROW_BK", "VLG_CONV_TAIL", "VLG_CONV_WGRAD_TALL", "VLG_EMBED_PREFETCH"):
+        assert name.encode() not in data, name

@@ -319,7 +319,7 @@ def test_linear_dgrad_wgrad_bf16_storage_is_the_two_calls(H, dev, M, N, K, mul, 
 def test_linear_chained_tiles(H, dev):
     """Multi-round launches: a block computes a run of N tiles back to back (the K loop continues into the next tile).
     1024 tiles here -> runs of two; forward with bias, forward with GELU + saved derivative, data gradient with the
-    multiply epilogue.  (The ping-pong variant of this path is a diagnostic-build option: csrc/gemm.hip, VLG_DIAG.)"""
+    multiply epilogue."""
     M, N, K = 8192, 2048, 128
     if True:
         torch.manual_seed(21)

@@ -1,9 +1,10 @@
 #!/usr/bin/env python
 """A/B of fp32 GEMM builds in ONE process, interleaved rounds (guide rule 24: separate invocations differ by several per
 cent on one box).  Every argument is `tag=path/to/libvlg.so[:BK[:RUN]]` (BK = forced contraction depth 16 | 32 | 0 through
-vlg_debug_set_gemm_bk, RUN = argument of vlg_debug_set_gemm_run, e.g. 0x1ffff = chained tiles as ping-pong pairs, 0 = no
-chaining; when the build exports them); `cur` = the in-tree build.
-    python tools/ab/gemm_ab.py base=tools/ab/libvlg_base.so cur [--only gelu] [--rounds 7]
+vlg_debug_set_gemm_bk, RUN = argument of vlg_debug_set_gemm_run: -1 = the library's choice, 0 = no chaining, > 0 = tiles
+per block); `cur` = the in-tree build.  BK and RUN need diagnostic builds (make -C video-layout-generation_amd/csrc diag ->
+libvlg_hip_diag.so): the product library exports no switches and reads no tuning variables.
+    python tools/ab/gemm_ab.py base=tools/ab/libvlg_base.so cur=video-layout-generation_amd/libvlg_hip_diag.so [--only gelu] [--rounds 7]
 """
 import ctypes
 import os

@@ -11,10 +11,7 @@ dev = torch.device("cuda:0")
 cfg = LayoutConfig(B=32, T=16, N=64, d=256, n_layers=4)
 eng = LayoutEngine(cfg, dev, seed=SEED)
 batch = to_device(synthetic_clips(cfg.B, cfg.T, cfg.N, seed=SEED), dev)
-variants = {"serial": dict(overlap_wgrad=False, overlap_small=False), "overlap_wgrad": dict(overlap_wgrad=True, overlap_small=False),
-            "overlap_small": dict(overlap_wgrad=False, overlap_small=True)}
-if len(sys.argv) > 1 and sys.argv[1] == "gelu":
-    variants = {"store_gl": dict(gelu_on_load=False), "gelu_on_load": dict(gelu_on_load=True)}
+variants = {"serial": dict(overlap_wgrad=False), "overlap_wgrad": dict(overlap_wgrad=True)}
 res = {k: [] for k in variants}
 for rnd in range(6):
     for name, kv in variants.items():

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Diagnostic: per-CU timeline of one 3x3 convolution launch (needs the -DVLG_TIMELINE build of conv.hip):
 
-    cd video-layout-generation_amd/csrc && hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -DVLG_TIMELINE -c conv.hip -o /tmp/conv_tl.o && \
+    cd video-layout-generation_amd/csrc && hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -DVLG_DIAG -DVLG_TIMELINE -c conv.hip -o /tmp/conv_tl.o && \
         hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/ab/libvlg_tl.so /tmp/conv_tl.o $(ls *.o | grep -v '^conv.o')
     VLG_HIP_LIB=$PWD/tools/ab/libvlg_tl.so python tools/diag/conv_timeline.py [hw cin cout [batch [fwd|dgrad|wgrad]]]
 

@@ -5,9 +5,11 @@ Every block stamps s_memrealtime (100 MHz) at entry, main-loop start, main-loop 
 drained) together with HW_ID / XCC_ID.  Grouped by CU this shows whether the co-resident blocks of a CU run their
 main loops and epilogues in lockstep, and how long no block of a CU has matrix work.
     cd video-layout-generation_amd/csrc && hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Xclang -target-feature -Xclang -load-store-opt \
-        -DVLG_TIMELINE -c gemm.hip -o /tmp/gemm_tl.o && hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/ab/libvlg_tl.so \
+        -DVLG_DIAG -DVLG_TIMELINE -c gemm.hip -o /tmp/gemm_tl.o && hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/ab/libvlg_tl.so \
         /tmp/gemm_tl.o $(ls *.o | grep -v '^gemm.o')
-    VLG_HIP_LIB=$PWD/tools/ab/libvlg_tl.so python tools/diag/gemm_timeline.py [ff1|dgelu|mul|dplain|qkv|proj|wgrad ...] [sweep]
+    [VLG_GEMM_BK=16|32] VLG_HIP_LIB=$PWD/tools/ab/libvlg_tl.so python tools/diag/gemm_timeline.py [ff1|dgelu|mul|dplain|qkv|proj|wgrad ...] [sweep]
+The clock probe and VLG_GEMM_BK exist in diagnostic builds only (-DVLG_DIAG, as above; or VLG_HIP_LIB=.../libvlg_hip_diag.so
+from `make diag` for the probe without the timeline): the product library ignores tuning variables.
 """
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -9,6 +9,21 @@
 // launch-status helper: kernels never synchronise, so only configuration errors surface here
 static inline int vlg_last_error() { return (int)hipGetLastError(); }
 
+// A tuning knob of the host-side kernel choice: VLG_TUNE("VLG_NAME", default).  The product library keeps no mutable
+// process-wide state, so there it IS the default: a kernel plan follows from the call's arguments alone.  The diagnostic
+// build (`make diag`, -DVLG_DIAG) reads the named environment variable once per use site (a function-local static const:
+// thread-safe initialisation) for A/B runs of the development tools.
+#ifdef VLG_DIAG
+#include <stdlib.h>
+static inline int vlg_tune_env(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+#define VLG_TUNE(name, dflt) ([] { static const int v_ = vlg_tune_env(name, dflt); return v_; }())
+#else
+#define VLG_TUNE(name, dflt) (dflt)
+#endif
+
 static inline bool vlg_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 __device__ __forceinline__ float wave_sum(float v) {

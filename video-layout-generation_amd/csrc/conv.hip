@@ -19,7 +19,6 @@
 // one of gemm.hip (gemm_tile.h).
 #include "gemm_tile.h"
 #include <type_traits>
-#include <stdlib.h>
 
 #define CONV_FWD 0
 #define CONV_DGRAD 1
@@ -903,12 +902,9 @@ static void fill_shifts(ConvArgs& g, int wp, int sign) {
     g.wp = wp; g.sign = sign;
 }
 
-// development switch: VLG_CONV_NARROW_BK=16|32 selects the K-tile depth of the 32-channel tiles
-static int conv_narrow_bk() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("VLG_CONV_NARROW_BK"); v = e ? atoi(e) : 16; }   // 16: +2.7 % on CoordGridNet b=4 256x256 (more blocks per CU)
-    return v;
-}
+// K-tile depth of the 32-channel tiles: 16, +2.7 % on CoordGridNet b=4 256x256 against 32 (more blocks per CU).
+// VLG_CONV_NARROW_BK=16|32 (diagnostic build) for A/B runs.
+static int conv_narrow_bk() { return VLG_TUNE("VLG_CONV_NARROW_BK", 16); }
 
 // Tile choice at small batch / coarse levels.  Blocks on one CU share its MFMA pipes, so a launch takes about
 // max-blocks-per-CU x (work of one block): 529 blocks of 128 rows cost 3 units on 256 CUs, 1057 blocks of 64 rows
@@ -930,13 +926,9 @@ struct ConvTile { int bm, bn, bk; };
 // pixels, exactly 1024 tiles, 156 us; at 4 x 128 x 128, 1057 tiles, 199 us).  Plan: the tiles beyond the last full round of 256
 // (whole row tiles) are cut along K into `splits` ranges, computed by the last blocks of the same launch into a workspace and
 // summed (+ epilogue) by the finish kernel - when the tile is long enough to pay for that second launch.
-// VLG_CONV_TAIL=0 switches it off (development).
+// VLG_CONV_TAIL=0 (diagnostic build) switches it off.
 struct ConvTail { int tiles, splits; int64_t kc, row0, floats; };
-static bool conv_tail_on() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("VLG_CONV_TAIL"); v = e ? atoi(e) : 1; }
-    return v != 0;
-}
+static bool conv_tail_on() { return VLG_TUNE("VLG_CONV_TAIL", 1) != 0; }
 static ConvTail conv_tail_plan(int64_t rows, const ConvTile t, int n_cols, int64_t kc, int ldc) {
     ConvTail none{0, 1, 0, 0, 0};
     if (!conv_tail_on() || (kc % t.bk) != 0) return none;
@@ -1199,11 +1191,9 @@ extern "C" int vlg_conv3x3_dgrad(const float* dout, const float* w, float* din, 
 }
 
 // row-tile height of the weight gradient: all of Cout for the GridNet widths (one pass over the gathered activation
-// tile serves every output channel), 32-row tiles otherwise.  VLG_CONV_WGRAD_TALL=0 forces 32 (development switch).
+// tile serves every output channel), 32-row tiles otherwise.  VLG_CONV_WGRAD_TALL=0 (diagnostic build) forces 32.
 static int conv_wgrad_bm(int cout_p) {
-    static int tall = -1;
-    if (tall < 0) { const char* e = getenv("VLG_CONV_WGRAD_TALL"); tall = e ? atoi(e) : 1; }
-    return (tall && (cout_p == 64 || cout_p == 96)) ? cout_p : 32;
+    return (VLG_TUNE("VLG_CONV_WGRAD_TALL", 1) != 0 && (cout_p == 64 || cout_p == 96)) ? cout_p : 32;
 }
 static void conv_wgrad_plan(int64_t rows, int cin_p, int cout_p, int* splits, int64_t* per) {
     const int64_t tiles = (cout_p / conv_wgrad_bm(cout_p)) * (int64_t)((9 * cin_p + 127) / 128);

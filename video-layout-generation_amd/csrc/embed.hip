@@ -9,7 +9,6 @@
 //        [cls_emb | box_w | box_b | time_emb] which vlg_reduce_slabs sums (bitwise
 //        reproducible - no float atomics).  Algorithmic bytes: 4*M*d read.
 #include "common.h"
-#include <stdlib.h>
 
 #define EMBED_BWD_SLABS 256
 
@@ -63,7 +62,7 @@ __device__ __forceinline__ float4 f4_fma(float s, float4 v, float4 a) {
 }
 __device__ __forceinline__ float4 f4_scale(float4 v, float s) { return make_float4(v.x * s, v.y * s, v.z * s, v.w * s); }
 
-template <int TT, bool PF>
+template <int TT>
 __global__ __launch_bounds__(256) void embed_bwd_kernel(const float* __restrict__ dx, const int64_t* __restrict__ slot_class,
                                                        const float* __restrict__ slot_box, float* __restrict__ slabs,
                                                        int64_t slab_stride, int B, int N, int d, int vocab, int rows, int G) {
@@ -91,13 +90,11 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const float* __restrict_
     // 384 / 448 a wave mixes two groups (and their trip counts), so those widths - and d = 64 with T = 32 - load directly
     const bool shuffled = lpr >= TT && (lpr < 64 ? (64 % lpr) == 0 : (lpr & 63) == 0);
     if (live) {
-        // the rows, ids and boxes of the NEXT sequence are requested before the current one is accumulated (two sequences
-        // per group at the metric shape: the second one's HBM latency hides behind the first one's LDS read-modify-writes)
         const int64_t stride = (int64_t)gridDim.x * G;
         int64_t seq = (int64_t)blockIdx.x * G + grp;
-        float4 gv[TT], gn[TT];
-        int my_cls = 0, nx_cls = 0;
-        float4 my_box = f4_zero(), nx_box = f4_zero();
+        float4 gv[TT];
+        int my_cls = 0;
+        float4 my_box = f4_zero();
         auto fetch = [&](int64_t sq, float4 (&rows_)[TT], int& cls_, float4& box_) __attribute__((always_inline)) {
 #pragma unroll
             for (int t = 0; t < TT; ++t) rows_[t] = ld4(dx + (sq * TT + t) * d + c);       // TT independent 16-B loads in flight
@@ -109,14 +106,10 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const float* __restrict_
                 box_ = ld4(slot_box + src * 4);
             }
         };
-        constexpr bool PREFETCH = PF && TT <= 16;          // (TT = 32: two row sets would not fit the register file)
-        if (PREFETCH && seq < n_seq) fetch(seq, gv, my_cls, my_box);
         for (; seq < n_seq; seq += stride) {
             const int64_t b = seq / N;
             const int n = (int)(seq - b * N);
-            if constexpr (!PREFETCH) fetch(seq, gv, my_cls, my_box);
-            const bool more = PREFETCH && seq + stride < n_seq;
-            if (more) fetch(seq + stride, gn, nx_cls, nx_box);
+            fetch(seq, gv, my_cls, my_box);
 #pragma unroll
             for (int t = 0; t < TT; ++t) {
                 const float4 g = gv[t];
@@ -137,12 +130,6 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const float* __restrict_
                 b_acc = f4_add(b_acc, g);
                 w_acc0 = f4_fma(bx.x, g, w_acc0); w_acc1 = f4_fma(bx.y, g, w_acc1);
                 w_acc2 = f4_fma(bx.z, g, w_acc2); w_acc3 = f4_fma(bx.w, g, w_acc3);
-            }
-            if (more) {
-#pragma unroll
-                for (int t = 0; t < TT; ++t) gv[t] = gn[t];
-                my_cls = nx_cls;
-                my_box = nx_box;
             }
         }
     }
@@ -236,26 +223,17 @@ extern "C" int vlg_embed_bwd(const float* dx, const int64_t* slot_class, const f
     const size_t lds = (size_t)G * rows * d * sizeof(float);
     if (lds > 160 * 1024 || (slab_stride & 3) || (((int64_t)vocab * d) & 3)) return VLG_ERR_SHAPE;
     const dim3 grid((unsigned)n_blocks), block(256);
-    // VLG_EMBED_PREFETCH=1 (read once): request the next sequence's rows before accumulating the current one.  Measured
-    // (tools/kernel_bench.py, one box): 20.3 us against 19.3 us without at the metric shape - the second row set takes the
-    // kernel to 256 registers and the accumulation is not what the loads wait for.  OFF.
-    static int prefetch = -1;
-    if (prefetch < 0) { const char* e = getenv("VLG_EMBED_PREFETCH"); prefetch = e ? atoi(e) : 0; }
     hipStream_t s = (hipStream_t)stream;
 #define EMBED_BWD_LAUNCH(TT)                                                                                    \
     {                                                                                                           \
         static size_t granted = 0;        /* the attribute call costs tens of microseconds of host time: once per size */ \
         if (lds > granted) {                                                                                    \
-            (void)hipFuncSetAttribute((const void*)embed_bwd_kernel<TT, true>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                (int)lds);                                                                      \
-            (void)hipFuncSetAttribute((const void*)embed_bwd_kernel<TT, false>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
+            (void)hipFuncSetAttribute((const void*)embed_bwd_kernel<TT>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                 (int)lds);                                                                      \
             granted = lds;                                                                                      \
         }                                                                                                       \
-        if (prefetch) hipLaunchKernelGGL((embed_bwd_kernel<TT, true>), grid, block, lds, s, dx, slot_class, slot_box, slabs, \
-                                         slab_stride, B, N, d, vocab, rows, G);                                 \
-        else hipLaunchKernelGGL((embed_bwd_kernel<TT, false>), grid, block, lds, s, dx, slot_class, slot_box, slabs,        \
-                                slab_stride, B, N, d, vocab, rows, G);                                          \
+        hipLaunchKernelGGL((embed_bwd_kernel<TT>), grid, block, lds, s, dx, slot_class, slot_box, slabs,        \
+                           slab_stride, B, N, d, vocab, rows, G);                                               \
     }
     switch (T) {
         case 4:  EMBED_BWD_LAUNCH(4) break;

@@ -36,7 +36,6 @@
 // Algorithmic work per launch: 2*M*N*K flop; bytes 4*(M*K + N*K + M*N) (+ aux operands).
 #include "common.h"
 #include <type_traits>
-#include <stdlib.h>
 
 #include "gemm_tile.h"
 #include "reduce_body.h"
@@ -79,23 +78,14 @@ __device__ __forceinline__ void vlg_epi_pace(int issued) {
 #define VLG_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 #endif
 
-// PP ("ping-pong", chained BK = 32 launches only; a diagnostic option, OFF - measured 25-30 % slower than independent
-// workgroups, cause not found): a workgroup is TWO groups of four waves, each computing its own run of
-// tiles exactly as a 256-thread workgroup would (own LDS half, own virtual block id), but sharing the workgroup barrier -
-// and running half a K range apart.  The vector ALU serves the oldest wave first, so two independent workgroups on a CU do
-// not alternate: the older one streams its tiles, the younger one fills its gaps and is left alone with its own gaps
-// (epilogue store issue, auxiliary loads) exposed.  With a common barrier per K tile the older group must wait for the
-// younger every iteration, the two take the matrix pipe in turns, and one group's epilogue (cut into four slices, a
-// barrier each) always runs beside the other group's main loop.  Both groups execute the same number of barriers: the
-// second group starts with nk / 2 empty slots, the first ends with them.
-// LDS floats of one four-wave group: both operand tiles, double-buffered
+// LDS floats of one block: both operand tiles, double-buffered
 template <int BM, int BN, int BK, bool A_KC, bool B_KC>
 constexpr int gemm_smem_floats() { return 2 * (Tile<BM, A_KC, BK>::FLOATS + Tile<BN, B_KC, BK>::FLOATS); }
 
 // The kernel body as a device function of (arguments, LDS, block number, block count): gemm_f32_kernel runs one problem per
 // launch, gemm_pair_kernel two independent ones (a projection's data gradient and weight gradient) side by side.
-template <int BM, int BN, int BK, bool A_KC, bool B_KC, int EPI, bool COLSUM, bool PP = false>
-__device__ __forceinline__ void gemm_f32_body(const GemmArgs& g, float* const smem_all, const int blk, const int nblk) {
+template <int BM, int BN, int BK, bool A_KC, bool B_KC, int EPI, bool COLSUM>
+__device__ __forceinline__ void gemm_f32_body(const GemmArgs& g, float* const smem, const int bid, const int nwg) {
     // Raised priority until the main loop starts.  It does NOT get this block's vector instructions past an older block's
     // MFMA stream (the vector ALU serves the oldest wave that has a matrix or vector instruction ready, whatever s_setprio
     // says: tools/micro/mfma_f32_valu_share.hip prio / two), but the prologue's loads and LDS writes are issued ahead of the
@@ -113,16 +103,11 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs& g, float* const sm
     constexpr int NCH = BK / 8;                    // 8-deep MFMA chunks per tile
     using TA = Tile<BM, A_KC, BK>;
     using TB = Tile<BN, B_KC, BK>;
-    constexpr int SMEM_FLOATS = gemm_smem_floats<BM, BN, BK, A_KC, B_KC>();
-    const int grp = PP ? (int)(threadIdx.x >> 8) : 0;          // ping-pong: which of the two four-wave groups
-    float* const smem = smem_all + grp * SMEM_FLOATS;
     float* const As0 = smem;                       // As[buf] = As0 + buf * TA::FLOATS
     float* const Bs0 = smem + 2 * TA::FLOATS;      // Bs[buf] = Bs0 + buf * TB::FLOATS
 
     // XCD-aware remap: hardware deals blocks round-robin over 8 XCDs; give each XCD a
     // contiguous run of logical tiles (bijective for any grid size)
-    // (ping-pong: the second group takes the upper half of the virtual block ids, so id & 7 still says which XCD)
-    const int nwg = (PP ? 2 : 1) * nblk, bid = blk + grp * nblk;
     const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7;
     const int swz = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
     // N tiles per block: the fast path of the BK = 32 kernels without bias-gradient sums (the host sets it); a compile-time 1
@@ -140,6 +125,7 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs& g, float* const sm
     int64_t kend = kbeg + g.kc_per_split;
     if (kend > g.Kc) kend = g.Kc;
 
+    // (the mask is a no-op at 256 threads, but the range it states, tid < 256, keeps the compiled kernels shorter)
     const int tid = threadIdx.x & (GEMM_THREADS - 1), lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, h = lane >> 5;
     const int wm = wave / WN, wn = wave - wm * WN;
@@ -592,13 +578,8 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs& g, float* const sm
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[q].y), dc, vc + j * 128, soff(2 * q + 1), 0);
                     vlg_epi_pace(2 * q + 2);
                 }
-                if constexpr (PP) __syncthreads();          // one epilogue slice per slot of the other group's main loop
             }
     };
-    if constexpr (PP) {
-        if (!fast_tile) return;                    // (never: the host launches this variant only where every block is fast)
-        if (grp == 1) for (int i = 0; i < nk / 2; ++i) __syncthreads();
-    }
     if (fast_tile) {
         // the tiles of the run: [main loop, epilogue] per tile; the next tile's bias is fetched ahead of the main loop
         for (int rt = 0; rt < run; ++rt) {
@@ -608,9 +589,6 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs& g, float* const sm
             if (has_next) load_bias(n0v + BN);
             emit_fast(n0v);
             if (has_next) init_acc();
-        }
-        if constexpr (PP) {
-            if (grp == 0) for (int i = 0; i < nk / 2; ++i) __syncthreads();
         }
     } else if (full) emit(std::false_type{});
     else emit(std::true_type{});
@@ -644,10 +622,10 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs& g, float* const sm
     }
 }
 
-template <int BM, int BN, int BK, bool A_KC, bool B_KC, int EPI, bool COLSUM, bool PP = false>
-__global__ __launch_bounds__(PP ? 2 * GEMM_THREADS : GEMM_THREADS, (BM == 64 && BN == 64) ? 4 : (BK == 16 ? 3 : 2)) void gemm_f32_kernel(const GemmArgs g) {
-    __shared__ __attribute__((aligned(16))) float smem_all[(PP ? 2 : 1) * gemm_smem_floats<BM, BN, BK, A_KC, B_KC>()];
-    gemm_f32_body<BM, BN, BK, A_KC, B_KC, EPI, COLSUM, PP>(g, smem_all, (int)blockIdx.x, (int)gridDim.x);
+template <int BM, int BN, int BK, bool A_KC, bool B_KC, int EPI, bool COLSUM>
+__global__ __launch_bounds__(GEMM_THREADS, (BM == 64 && BN == 64) ? 4 : (BK == 16 ? 3 : 2)) void gemm_f32_kernel(const GemmArgs g) {
+    __shared__ __attribute__((aligned(16))) float smem[gemm_smem_floats<BM, BN, BK, A_KC, B_KC>()];
+    gemm_f32_body<BM, BN, BK, A_KC, B_KC, EPI, COLSUM>(g, smem, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // A projection's data gradient dX = dY . W and weight gradient dW = dY^T . X need nothing from each other: ONE launch runs
@@ -678,7 +656,7 @@ __global__ __launch_bounds__(GEMM_THREADS, BT == 64 ? 4 : 2) void gemm_pair_kern
 
 // The library keeps NO mutable process-wide state (include/vlg_hip.h).  The development switches below exist only in the
 // diagnostic build (`make diag` -> libvlg_hip_diag.so, -DVLG_DIAG; loaded by tools/diag, tools/ab through VLG_HIP_LIB); in
-// the product build they are constants and the vlg_debug_set_* entry points do not exist.
+// the product build they are constants (VLG_TUNE, common.h) and the vlg_debug_set_* entry points do not exist.
 #ifdef VLG_DIAG
 // a device buffer of 2 * blocks uint64 set through vlg_debug_set_clock_probe (NULL = off)
 static unsigned long long* vlg_gemm_clock_probe = nullptr;
@@ -691,37 +669,25 @@ static constexpr unsigned long long* vlg_gemm_clock_probe = nullptr;
 // BK = 32 (2 blocks / CU) is 3-5 % faster for plain epilogues, BK = 16 (41 KB LDS, 4 blocks / CU)
 // is 8-11 % faster when the epilogue is heavy (GELU / dGELU: two extra 134 MB streams), because more
 // resident blocks de-synchronise the store bursts from the other blocks' MFMA phases.
-// VLG_GEMM_BK=16|32 forces one value for A/B runs.
+// VLG_GEMM_BK=16|32 (or vlg_debug_set_gemm_bk) forces one value for A/B runs.
 #ifdef VLG_DIAG
 static int vlg_gemm_bk_forced = -1;
-static int gemm_bk_override() {
-    if (vlg_gemm_bk_forced < 0) {
-        const char* e = getenv("VLG_GEMM_BK");
-        vlg_gemm_bk_forced = e ? atoi(e) : 0;
-    }
-    return vlg_gemm_bk_forced;
-}
 extern "C" void vlg_debug_set_gemm_bk(int bk) { vlg_gemm_bk_forced = (bk == 16 || bk == 32) ? bk : 0; }
-#else
-static int gemm_bk_override() {                  // the environment variable, read once: configuration, not state
-    static const int forced = [] { const char* e = getenv("VLG_GEMM_BK"); return e ? atoi(e) : 0; }();
-    return forced;
-}
 #endif
+static int gemm_bk_override() {
+#ifdef VLG_DIAG
+    if (vlg_gemm_bk_forced >= 0) return vlg_gemm_bk_forced;
+#endif
+    return VLG_TUNE("VLG_GEMM_BK", 0);
+}
 
 // Consecutive N tiles per block (GemmArgs::run) for a launch that would otherwise take several rounds of blocks: the
 // largest divisor of the N tile count that still leaves one block per slot.  Only where EVERY block takes the fast path
 // (no edge tiles, an even number of K tiles, 32-bit spans): a block that does not computes one tile only.
 #ifdef VLG_DIAG
 static int vlg_gemm_run_forced = -1;
-static int vlg_gemm_pingpong = 0;
-// run: 0 = never chain, -1 = the library's choice, > 0 = that many; bit 16 set: chained launches as ping-pong pairs (two
-// four-wave groups per workgroup, see the kernel) instead of independent 256-thread workgroups - MEASURED 25-30 % SLOWER
-// (tools/ab/gemm_ab.py: fwd qkv 95 -> 120 us, FFN1 + GELU 139 -> 188 us), so it stays a diagnostic switch
-extern "C" void vlg_debug_set_gemm_run(int run) {
-    vlg_gemm_pingpong = (run >= 0 && (run & 0x10000)) ? 1 : 0;
-    vlg_gemm_run_forced = run < 0 ? -1 : (run & 0xffff) == 0xffff ? -1 : (run & 0xffff);
-}
+// run: 0 = never chain, -1 = the library's choice, > 0 = that many
+extern "C" void vlg_debug_set_gemm_run(int run) { vlg_gemm_run_forced = run < 0 ? -1 : run; }
 #else
 static constexpr int vlg_gemm_run_forced = -1;
 #endif
@@ -742,36 +708,17 @@ static int gemm_run(const GemmArgs& g, int slots) {
 
 // 64x64 tiles (four 32x32 waves, four blocks per CU) for launches whose 128x128 tiles would leave CUs without a block: the
 // per-GPU share of a GLOBAL batch (reference src/trainer.py:148: 32 // 8 = 4 clips, M = 4 096 tokens) gives the N = 256
-// products 64 tiles for 256 CUs.  VLG_GEMM_SMALL=0 (read once) keeps 128x128 everywhere (A/B runs).
-static bool gemm_small_tiles() {
-    static int on = -1;
-    if (on < 0) {
-        const char* e = getenv("VLG_GEMM_SMALL");
-        on = (e && atoi(e) == 0) ? 0 : 1;
-    }
-    return on == 1;
-}
+// products 64 tiles for 256 CUs.  VLG_GEMM_SMALL=0 keeps 128x128 everywhere (A/B runs).
+static bool gemm_small_tiles() { return VLG_TUNE("VLG_GEMM_SMALL", 1) != 0; }
 // Measured (tools/shard_bench.py, interleaved repeated runs on one box): 64x64 tiles pay while the 128x128 tiles would not fill
 // the 512 block slots of the chip (2 per CU) - four resident 64x64 blocks overlap one block's prologue / epilogue with the
 // others' MFMAs: B = 4: 1.75 -> 1.05 ms, B = 8: 1.79 -> 1.76, B = 16: 3.11 -> 3.05.  A launch of exactly 512 blocks (the d x d
 // products of the headline step) is FASTER on 128x128 tiles (their higher arithmetic intensity: K = 4096 asymptote 150 vs 140
 // TFLOP/s; the step 5.55 vs 5.63 ms with a threshold of 1 025 - a first single-run sweep had suggested the opposite).
-static int gemm_small_below() {                  // VLG_GEMM_SMALL_BELOW (read once): 128x128 block count under which 64x64 tiles are taken
-    static int thr = -1;
-    if (thr < 0) {
-        const char* e = getenv("VLG_GEMM_SMALL_BELOW");
-        thr = e ? atoi(e) : 512;
-    }
-    return thr;
-}
-static int gemm_small_below_wgrad() {            // the same for the weight-gradient plan (VLG_GEMM_SMALL_BELOW_WGRAD)
-    static int thr = -1;
-    if (thr < 0) {
-        const char* e = getenv("VLG_GEMM_SMALL_BELOW_WGRAD");
-        thr = e ? atoi(e) : 385;                     // under 3/4 of the 512 slots of the 128x128 plan (B = 32 keeps that plan: 504-512 blocks)
-    }
-    return thr;
-}
+// 128x128 block count under which 64x64 tiles are taken
+static int gemm_small_below() { return VLG_TUNE("VLG_GEMM_SMALL_BELOW", 512); }
+// the same for the weight-gradient plan: under 3/4 of the 512 slots of the 128x128 plan (B = 32 keeps that plan: 504-512 blocks)
+static int gemm_small_below_wgrad() { return VLG_TUNE("VLG_GEMM_SMALL_BELOW_WGRAD", 385); }
 static bool gemm_wants_small(int64_t M, int N, int splits) {
     return gemm_small_tiles() && ((M + 127) / 128) * (int64_t)((N + 127) / 128) * splits < gemm_small_below();
 }
@@ -803,16 +750,6 @@ static int launch_gemm(GemmArgs g, hipStream_t s) {
     }
     const int64_t blocks = (int64_t)g.tiles_m * (g.tiles_n / g.run) * g.splits;
     if (blocks < 1 || blocks > 0x7fffffff) return VLG_ERR_SHAPE;
-    if constexpr (CAN_RUN) {
-        // chained launches: two four-wave groups per workgroup taking the matrix pipe in turns (see the kernel); the virtual
-        // block ids of a group must keep their XCD (multiple of 8 workgroups)
-#ifdef VLG_DIAG
-        if (g.run > 1 && vlg_gemm_pingpong && (blocks % 16) == 0) {
-            hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, 32, A_KC, B_KC, EPI, COLSUM, true>), dim3((unsigned)(blocks / 2)), dim3(2 * GEMM_THREADS), 0, s, g);
-            return vlg_last_error();
-        }
-#endif
-    }
     hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, 32, A_KC, B_KC, EPI, COLSUM>), dim3((unsigned)blocks), block, 0, s, g);
     return vlg_last_error();
 }
@@ -881,31 +818,56 @@ extern "C" int vlg_linear_fwd(const void* A, int lda, const void* W, int ldw, co
     }
 }
 
-extern "C" int vlg_linear_dgrad(const void* dY, int ldy, const void* W, int ldw, void* dX, int ldx,
-                                const void* aux_in, int64_t M, int N, int K, int epilogue, void* stream) {
-    // dX[M,K] = dY[M,N] . W[N,K]  : contraction over N, W is contraction-major
+// Argument checks of the two backward calls, shared with vlg_linear_dgrad_wgrad: the pair accepts exactly what the two single
+// calls accept.  0 = valid.  (The bf16 and split kernels add the 8-element granularity of their slots.)
+static int check_dgrad(const void* dY, int ldy, const void* W, int ldw, const void* dX, int ldx, const void* aux_in,
+                       int64_t M, int N, int K, int flags) {
     if (M < 1 || N < 4 || (N & 3) || K < 4 || (K & 3) || ldy < N || ldw < K || ldx < K) return VLG_ERR_SHAPE;
     if (!gemm_ptr_ok(dY, ldy) || !gemm_ptr_ok(W, ldw) || !dX) return VLG_ERR_ALIGN;
+    const bool bf16 = (flags & VLG_EPI_BF16) != 0, split3 = (flags & VLG_EPI_SPLIT3) != 0;
+    const int io = gemm_io_bits(flags);
+    const int epi = flags & ~(VLG_EPI_BF16 | VLG_EPI_STORAGE | VLG_EPI_SPLIT3);
+    if (split3 && (bf16 || io != 0)) return VLG_ERR_SHAPE;
+    if (io != 0 && !bf16) return VLG_ERR_SHAPE;
+    if (((io & 1) && (ldy & 7)) || ((io & 2) && (ldw & 7))) return VLG_ERR_ALIGN;
+    if ((epi == VLG_EPI_DGELU || epi == VLG_EPI_MUL) && !aux_in) return VLG_ERR_SHAPE;
+    if (epi == VLG_EPI_MUL && split3) return VLG_ERR_SHAPE;                                           // native fp32 and bf16 paths
+    return 0;
+}
+static int check_wgrad(const void* dY, int ldy, const void* X, int ldx, const float* slabs, int64_t slab_stride,
+                       int64_t M, int N, int K, int flags) {
+    if (M < 1 || N < 4 || (N & 3) || K < 4 || (K & 3) || ldy < N || ldx < K) return VLG_ERR_SHAPE;
+    if (slab_stride < (int64_t)N * K + N) return VLG_ERR_SHAPE;
+    if (!gemm_ptr_ok(dY, ldy) || !gemm_ptr_ok(X, ldx) || !slabs) return VLG_ERR_ALIGN;
+    const int io = gemm_io_bits(flags);
+    if (io != 0 && !(flags & VLG_EPI_BF16)) return VLG_ERR_SHAPE;
+    if (((io & 1) && (ldy & 7)) || ((io & 2) && (ldx & 7))) return VLG_ERR_ALIGN;
+    return 0;
+}
+
+// dX[M,K] = dY[M,N] . W[N,K]  : contraction over N, W is contraction-major
+static GemmArgs dgrad_args(const void* dY, int ldy, const void* W, int ldw, void* dX, int ldx, const void* aux_in, int64_t M, int N, int K) {
     GemmArgs g{};
     g.A = dY; g.B = W; g.C = dX; g.aux_in = aux_in;
     g.M = M; g.N = K; g.Kc = N; g.lda = ldy; g.ldb = ldw; g.ldc = ldx;
     g.splits = 1; g.kc_per_split = N;
+    return g;
+}
+
+extern "C" int vlg_linear_dgrad(const void* dY, int ldy, const void* W, int ldw, void* dX, int ldx,
+                                const void* aux_in, int64_t M, int N, int K, int epilogue, void* stream) {
+    if (const int rc = check_dgrad(dY, ldy, W, ldw, dX, ldx, aux_in, M, N, K, epilogue)) return rc;
+    const GemmArgs g = dgrad_args(dY, ldy, W, ldw, dX, ldx, aux_in, M, N, K);
     hipStream_t s = (hipStream_t)stream;
     const bool bf16 = (epilogue & VLG_EPI_BF16) != 0, split3 = (epilogue & VLG_EPI_SPLIT3) != 0;
     const int io = gemm_io_bits(epilogue);
     epilogue &= ~(VLG_EPI_BF16 | VLG_EPI_STORAGE | VLG_EPI_SPLIT3);
-    if (split3 && (bf16 || io != 0)) return VLG_ERR_SHAPE;
-    if (io != 0 && !bf16) return VLG_ERR_SHAPE;
-    if (((io & 1) && (ldy & 7)) || ((io & 2) && (ldw & 7))) return VLG_ERR_ALIGN;
-    if ((epilogue == VLG_EPI_DGELU || epilogue == VLG_EPI_MUL) && !aux_in) return VLG_ERR_SHAPE;
-    if (epilogue == VLG_EPI_MUL && split3) return VLG_ERR_SHAPE;                                      // native fp32 and bf16 paths
     if (bf16) return vlg_gemm16_dgrad(g, epilogue, io, s);
     if (split3) return vlg_gemm_split_dgrad(g, epilogue, s);
     switch (epilogue) {
         case VLG_EPI_NONE:
             return launch_gemm<128, 128, true, false, VLG_EPI_NONE, false>(g, s);
         case VLG_EPI_DGELU:
-            if (!aux_in) return VLG_ERR_SHAPE;
             return launch_gemm<128, 128, true, false, VLG_EPI_DGELU, false>(g, s);
         case VLG_EPI_MUL:
             return launch_gemm<128, 128, true, false, VLG_EPI_MUL, false>(g, s);
@@ -914,27 +876,27 @@ extern "C" int vlg_linear_dgrad(const void* dY, int ldy, const void* W, int ldw,
     }
 }
 
-// split plan for the weight gradient: enough blocks to fill 256 CUs x 2 blocks, each split a
-// multiple of BK token rows
-// *small (native fp32 kernel only): 64x64 tiles, four resident blocks per CU, token ranges down to 128 rows - taken when the
-// 128x128 plan would leave CUs without a block (few tokens: the strong-scaling shard)
-static void wgrad_plan(int64_t M, int N, int K, int* splits, int64_t* per, bool bf16 = false, bool* small = nullptr) {
+// Split plan for the weight gradient: enough blocks to fill 256 CUs x 2 blocks, each split a multiple of BK token rows.
+// small (native fp32 kernel only: flags without the bf16 / split / GELU-on-load bits): 64x64 tiles, four resident blocks per
+// CU, token ranges down to 128 rows - taken when the 128x128 plan would leave CUs without a block (few tokens: the
+// strong-scaling shard).  The ONE plan of every weight-gradient launch and of the slab-count queries (M >= 1).
+struct WgradPlan { int splits; int64_t per; bool small; };
+static WgradPlan wgrad_plan(int64_t M, int N, int K, int flags) {
+    const bool native = (flags & (VLG_EPI_BF16 | VLG_EPI_SPLIT3 | VLG_EPI_ACT_GELU)) == 0;
+    WgradPlan r{1, 0, false};
     const int bm = N <= 32 ? 32 : 128;
     int64_t tiles = ((N + bm - 1) / bm) * (int64_t)((K + 127) / 128);
     int64_t want = 512 / tiles;                      // blocks <= 512 = 256 CUs x 2 resident blocks: one full wave, no tail
     int64_t max_splits = (M + 255) / 256;
-    if (small) *small = false;
-    if (small && bm == 128 && gemm_small_tiles() && tiles * (want < max_splits ? (want < 1 ? 1 : want) : max_splits) < gemm_small_below_wgrad()) {
-        *small = true;
+    if (native && bm == 128 && gemm_small_tiles() && tiles * (want < max_splits ? (want < 1 ? 1 : want) : max_splits) < gemm_small_below_wgrad()) {
+        r.small = true;
         tiles = ((N + 63) / 64) * (int64_t)((K + 63) / 64);
-        static int slots = -1;                       // VLG_WGRAD_SMALL_SLOTS (read once; A/B runs)
-        if (slots < 0) { const char* e = getenv("VLG_WGRAD_SMALL_SLOTS"); slots = e ? atoi(e) : 1024; }
-        want = slots / tiles;
+        want = VLG_TUNE("VLG_WGRAD_SMALL_SLOTS", 1024) / tiles;
         max_splits = (M + 127) / 128;
     }
     if (want > max_splits) want = max_splits;
     if (want < 1) want = 1;
-    if (small && *small) {
+    if (r.small) {
         // equal token ranges where a slightly smaller count allows them (a ragged last range costs a whole block round)
         for (int64_t c = want; c >= 1 && 4 * c >= 3 * want; --c)
             if (M % (c * 64) == 0) { want = c; break; }
@@ -943,59 +905,48 @@ static void wgrad_plan(int64_t M, int N, int K, int* splits, int64_t* per, bool 
     const int kt = 64;                               // whole K tiles, and an even number of the fp32 kernel's 32-row tiles (its
                                                      // loop runs them in pairs: an odd count costs one iteration on zeros)
     p = (p + kt - 1) / kt * kt;
-    *per = p;
-    *splits = (int)((M + p - 1) / p);
+    r.per = p;
+    r.splits = (int)((M + p - 1) / p);
+    return r;
 }
 
-// (the small-tile plan exists for the native fp32 kernel only: flags without the bf16 / split bits)
-static bool wgrad_native(int flags) { return (flags & (VLG_EPI_BF16 | VLG_EPI_SPLIT3 | VLG_EPI_ACT_GELU)) == 0; }
-extern "C" int vlg_linear_wgrad_slabs(int64_t M, int N, int K) {
-    int splits; int64_t per; bool small;
-    wgrad_plan(M, N, K, &splits, &per, false, &small);
-    return splits;
-}
-extern "C" int vlg_linear_wgrad_slabs_for(int64_t M, int N, int K, int flags) {
-    int splits; int64_t per; bool small;
-    wgrad_plan(M, N, K, &splits, &per, (flags & VLG_EPI_BF16) != 0, wgrad_native(flags) ? &small : nullptr);
-    return splits;
+extern "C" int vlg_linear_wgrad_slabs_for(int64_t M, int N, int K, int flags) { return wgrad_plan(M, N, K, flags).splits; }
+extern "C" int vlg_linear_wgrad_slabs(int64_t M, int N, int K) { return vlg_linear_wgrad_slabs_for(M, N, K, 0); }
+
+// slab[s][n*K + k] = sum_{m in split s} dY[m,n] X[m,k] ;  slab[s][N*K + n] = sum_m dY[m,n]
+static GemmArgs wgrad_args(const void* dY, int ldy, const void* X, int ldx, float* slabs, int64_t slab_stride, int64_t M, int N, int K,
+                           const WgradPlan& plan) {
+    GemmArgs g{};
+    g.A = dY; g.B = X; g.C = slabs;
+    g.M = N; g.N = K; g.Kc = M; g.lda = ldy; g.ldb = ldx; g.ldc = K;
+    g.splits = plan.splits; g.kc_per_split = plan.per;
+    g.slab_stride = slab_stride; g.colsum_off = (int64_t)N * K;
+    return g;
 }
 
 extern "C" int vlg_linear_wgrad(const void* dY, int ldy, const void* X, int ldx, float* slabs,
                                 int64_t slab_stride, int64_t slab_capacity, int64_t M, int N, int K, int flags, void* stream) {
-    // slab[s][n*K + k] = sum_{m in split s} dY[m,n] X[m,k] ;  slab[s][N*K + n] = sum_m dY[m,n]
-    if (M < 1 || N < 4 || (N & 3) || K < 4 || (K & 3) || ldy < N || ldx < K) return VLG_ERR_SHAPE;
-    if (slab_stride < (int64_t)N * K + N) return VLG_ERR_SHAPE;
-    if (!gemm_ptr_ok(dY, ldy) || !gemm_ptr_ok(X, ldx) || !slabs) return VLG_ERR_ALIGN;
-    GemmArgs g{};
-    g.A = dY; g.B = X; g.C = slabs;
-    g.M = N; g.N = K; g.Kc = M; g.lda = ldy; g.ldb = ldx; g.ldc = K;
-    bool small = false;
-    wgrad_plan(M, N, K, &g.splits, &g.kc_per_split, (flags & VLG_EPI_BF16) != 0, wgrad_native(flags) ? &small : nullptr);
-    if (slab_capacity < (int64_t)g.splits * slab_stride) return VLG_ERR_SHAPE;      // the caller's buffer must hold every slab
-    g.slab_stride = slab_stride; g.colsum_off = (int64_t)N * K;
+    if (const int rc = check_wgrad(dY, ldy, X, ldx, slabs, slab_stride, M, N, K, flags)) return rc;
+    const WgradPlan plan = wgrad_plan(M, N, K, flags);
+    if (slab_capacity < (int64_t)plan.splits * slab_stride) return VLG_ERR_SHAPE;   // the caller's buffer must hold every slab
+    const GemmArgs g = wgrad_args(dY, ldy, X, ldx, slabs, slab_stride, M, N, K, plan);
     hipStream_t s = (hipStream_t)stream;
-    const bool bf16 = (flags & VLG_EPI_BF16) != 0;
     const int io = gemm_io_bits(flags);
-    if (io != 0 && !bf16) return VLG_ERR_SHAPE;
-    if (((io & 1) && (ldy & 7)) || ((io & 2) && (ldx & 7))) return VLG_ERR_ALIGN;
-    if (bf16) return (flags & VLG_EPI_ACT_GELU) ? VLG_ERR_SHAPE : vlg_gemm16_wgrad(g, io, s);
+    if (flags & VLG_EPI_BF16) return (flags & VLG_EPI_ACT_GELU) ? VLG_ERR_SHAPE : vlg_gemm16_wgrad(g, io, s);
     if (flags & VLG_EPI_SPLIT3) return (io == 0 && !(flags & VLG_EPI_ACT_GELU)) ? vlg_gemm_split_wgrad(g, s) : VLG_ERR_SHAPE;
     if (flags & VLG_EPI_ACT_GELU)                     // X = gelu(stored pre-activation): weight gradient of the FFN's second projection
         return N <= 32 ? VLG_ERR_SHAPE : launch_gemm<128, 128, false, false, GEMM_B_GELU, true>(g, s);
-    if (small) return launch_gemm<64, 64, false, false, VLG_EPI_NONE, true>(g, s);
+    if (plan.small) return launch_gemm<64, 64, false, false, VLG_EPI_NONE, true>(g, s);
     return N <= 32 ? launch_gemm<32, 128, false, false, VLG_EPI_NONE, true>(g, s)
                    : launch_gemm<128, 128, false, false, VLG_EPI_NONE, true>(g, s);
 }
 
 // ---- data gradient + weight gradient of one projection in ONE launch (gemm_pair_kernel)
-// VLG_GEMM_PAIR (read once): 0 = always two launches, 1 = one launch only where both problems take the 64x64 tiles (few
+// VLG_GEMM_PAIR (diagnostic build): 0 = always two launches, 1 = one launch only where both problems take the 64x64 tiles (few
 // tokens: neither fills the chip alone), 2 (default) = also on 128x128 tiles.  Measured at the metric shape (interleaved
 // repeated runs, one box): 5.553 -> 5.500 ms per step (-1.0 %, three of three pairs of runs) - each launch pays one ramp
 // and one drain for two problems, and the second problem's blocks fill the slots the first one's stragglers leave.
-static int gemm_pair_mode() {
-    static const int mode = [] { const char* e = getenv("VLG_GEMM_PAIR"); return e ? atoi(e) : 2; }();
-    return mode;
-}
+static int gemm_pair_mode() { return VLG_TUNE("VLG_GEMM_PAIR", 2); }
 #define VLG_RIDER_BPR 128          /* blocks per table row: what vlg_reduce_slabs_table launches get from the engine */
 template <int BT, int EPI_D>
 static int launch_pair(GemmArgs gd, GemmArgs gw, const int64_t* rider, int rider_rows, hipStream_t s) {
@@ -1022,55 +973,38 @@ extern "C" int vlg_linear_dgrad_wgrad(const void* dY, int ldy, const void* W, in
     // a slab-reduction table (vlg_reduce_slabs_table) over OTHER buffers than this call writes, reduced by extra blocks of the
     // same launch where the two products are fused, by a launch of their own otherwise - same sums either way.
     if (rider_table != nullptr && (rider_rows < 1 || rider_rows > 4096)) return VLG_ERR_SHAPE;
-    auto rider_alone = [&]() -> int { return rider_table ? vlg_reduce_slabs_table(rider_table, rider_rows, VLG_RIDER_BPR, stream) : 0; };
-    // the bf16-storage step (bf16 W / X / dX, dY bf16 or fp32): one launch of the bf16-tile kernels at every shape
-    const int st_bits = epilogue & (VLG_EPI_A_BF16 | VLG_EPI_B_BF16 | VLG_EPI_OUT_BF16);
-    if ((epilogue & VLG_EPI_BF16) && (st_bits & ~VLG_EPI_A_BF16) == (VLG_EPI_B_BF16 | VLG_EPI_OUT_BF16) && gemm_pair_mode() > 1 && N > 32 && K > 32) {
-        const int epi = epilogue & ~(VLG_EPI_BF16 | VLG_EPI_A_BF16 | VLG_EPI_B_BF16 | VLG_EPI_OUT_BF16);
-        if (epi != VLG_EPI_NONE && epi != VLG_EPI_MUL) return VLG_ERR_SHAPE;
-        if (M < 1 || (N & 7) || (K & 7) || ldy < N || ldw < K || ldx < K || ldxx < K) return VLG_ERR_SHAPE;
-        const bool a16 = (st_bits & VLG_EPI_A_BF16) != 0;
-        if (!vlg_aligned16(dY) || !vlg_aligned16(W) || !vlg_aligned16(X) || !dX || !slabs || (a16 && (ldy & 7)) || (ldw & 7) || (ldxx & 7) || (ldx & 7))
-            return VLG_ERR_ALIGN;
-        if (epi == VLG_EPI_MUL && !aux_in) return VLG_ERR_SHAPE;
-        GemmArgs gd{}, gw{};
-        gd.A = dY; gd.B = W; gd.C = dX; gd.aux_in = aux_in;
-        gd.M = M; gd.N = K; gd.Kc = N; gd.lda = ldy; gd.ldb = ldw; gd.ldc = ldx;
-        gd.splits = 1; gd.kc_per_split = N;
-        gw.A = dY; gw.B = X; gw.C = slabs;
-        gw.M = N; gw.N = K; gw.Kc = M; gw.lda = ldy; gw.ldb = ldxx; gw.ldc = K;
-        wgrad_plan(M, N, K, &gw.splits, &gw.kc_per_split, true);
-        if (slab_stride < (int64_t)N * K + N || slab_capacity < (int64_t)gw.splits * slab_stride) return VLG_ERR_SHAPE;
-        gw.slab_stride = slab_stride; gw.colsum_off = (int64_t)N * K;
-        return vlg_gemm16_pair(gd, gw, epi, a16, rider_table, rider_rows, VLG_RIDER_BPR, (hipStream_t)stream);
-    }
-    const bool native = (epilogue & ~VLG_EPI_MUL) == 0;
-    bool small_w = false;
-    int splits = 1; int64_t per = 0;
-    if (native && gemm_pair_mode() > 0 && M >= 1 && N >= 4 && K >= 4) wgrad_plan(M, N, K, &splits, &per, false, &small_w);
+    // the weight gradient's flags (bf16 storage: A = the shared dY, B = W of the data gradient AND X of the weight gradient)
+    const int wflags = epilogue & (VLG_EPI_BF16 | VLG_EPI_SPLIT3 | VLG_EPI_A_BF16 | VLG_EPI_B_BF16);
+    if (const int rc = check_wgrad(dY, ldy, X, ldxx, slabs, slab_stride, M, N, K, wflags)) return rc;
+    if (const int rc = check_dgrad(dY, ldy, W, ldw, dX, ldx, aux_in, M, N, K, epilogue)) return rc;
+    const WgradPlan plan = wgrad_plan(M, N, K, wflags);
+    if (slab_capacity < (int64_t)plan.splits * slab_stride) return VLG_ERR_SHAPE;
+
+    // fusable into one launch: the data gradient's epilogue is NONE or MUL and both products are wide, and
+    //   native fp32: both problems on the same tiles (64x64 at few tokens, 128x128 elsewhere - VLG_GEMM_PAIR >= 2)
+    //   bf16 storage (bf16 W / X / dX, dY bf16 or fp32; VLG_GEMM_PAIR >= 2): the bf16-tile pair kernel at every shape - but
+    //   not MUL with a bf16 dY, which the single data gradient has no kernel for
+    const int epi = epilogue & ~(VLG_EPI_BF16 | VLG_EPI_STORAGE);
+    const int st_bits = epilogue & VLG_EPI_STORAGE;
+    const bool a16 = (st_bits & VLG_EPI_A_BF16) != 0, mul = epi == VLG_EPI_MUL;
+    const bool bf16_pair = (epilogue & VLG_EPI_BF16) && (st_bits & ~VLG_EPI_A_BF16) == (VLG_EPI_B_BF16 | VLG_EPI_OUT_BF16);
+    const bool native = (epilogue & VLG_EPI_BF16) == 0 && st_bits == 0;
     const bool small_d = gemm_wants_small(M, K, 1);
-    const bool pair = native && gemm_pair_mode() > 0 && small_w == small_d && (small_d || gemm_pair_mode() > 1) && N > 32 && K > 32;
-    if (!pair) {
-        // (bf16 storage: A = the shared dY, B = W of the data gradient AND X of the weight gradient, OUT = dX)
-        const int wflags = epilogue & (VLG_EPI_BF16 | VLG_EPI_SPLIT3 | VLG_EPI_A_BF16 | VLG_EPI_B_BF16);
-        if (const int rc0 = rider_alone()) return rc0;
-        const int rc = vlg_linear_wgrad(dY, ldy, X, ldxx, slabs, slab_stride, slab_capacity, M, N, K, wflags, stream);
-        if (rc != 0) return rc;
+    const int mode = gemm_pair_mode();
+    const bool fusable = (epi == VLG_EPI_NONE || mul) && N > 32 && K > 32 &&
+                         (bf16_pair ? (mode > 1 && !(mul && a16))
+                                    : (native && mode > 0 && plan.small == small_d && (small_d || mode > 1)));
+    if (!fusable) {
+        if (rider_table != nullptr) {
+            if (const int rc = vlg_reduce_slabs_table(rider_table, rider_rows, VLG_RIDER_BPR, stream)) return rc;
+        }
+        if (const int rc = vlg_linear_wgrad(dY, ldy, X, ldxx, slabs, slab_stride, slab_capacity, M, N, K, wflags, stream)) return rc;
         return vlg_linear_dgrad(dY, ldy, W, ldw, dX, ldx, aux_in, M, N, K, epilogue, stream);
     }
-    if ((N & 3) || (K & 3) || ldy < N || ldw < K || ldx < K || ldxx < K) return VLG_ERR_SHAPE;
-    if (!gemm_ptr_ok(dY, ldy) || !gemm_ptr_ok(W, ldw) || !gemm_ptr_ok(X, ldxx) || !dX || !slabs) return VLG_ERR_ALIGN;
-    if ((epilogue & VLG_EPI_MUL) && !aux_in) return VLG_ERR_SHAPE;
-    if (slab_stride < (int64_t)N * K + N || slab_capacity < (int64_t)splits * slab_stride) return VLG_ERR_SHAPE;
-    GemmArgs gd{}, gw{};
-    gd.A = dY; gd.B = W; gd.C = dX; gd.aux_in = aux_in;
-    gd.M = M; gd.N = K; gd.Kc = N; gd.lda = ldy; gd.ldb = ldw; gd.ldc = ldx;
-    gd.splits = 1; gd.kc_per_split = N;
-    gw.A = dY; gw.B = X; gw.C = slabs;
-    gw.M = N; gw.N = K; gw.Kc = M; gw.lda = ldy; gw.ldb = ldxx; gw.ldc = K;
-    gw.splits = splits; gw.kc_per_split = per; gw.slab_stride = slab_stride; gw.colsum_off = (int64_t)N * K;
+    const GemmArgs gd = dgrad_args(dY, ldy, W, ldw, dX, ldx, aux_in, M, N, K);
+    const GemmArgs gw = wgrad_args(dY, ldy, X, ldxx, slabs, slab_stride, M, N, K, plan);
     hipStream_t s = (hipStream_t)stream;
-    const bool mul = (epilogue & VLG_EPI_MUL) != 0;
+    if (bf16_pair) return vlg_gemm16_pair(gd, gw, epi, a16, rider_table, rider_rows, VLG_RIDER_BPR, s);
     if (small_d) return mul ? launch_pair<64, VLG_EPI_MUL>(gd, gw, rider_table, rider_rows, s) : launch_pair<64, VLG_EPI_NONE>(gd, gw, rider_table, rider_rows, s);
     return mul ? launch_pair<128, VLG_EPI_MUL>(gd, gw, rider_table, rider_rows, s) : launch_pair<128, VLG_EPI_NONE>(gd, gw, rider_table, rider_rows, s);
 }

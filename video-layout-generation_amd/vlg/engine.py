@@ -22,7 +22,7 @@ from typing import Dict, Optional
 import torch
 
 from . import hip
-from .hip import (EPI_A_BF16, EPI_ACT_GELU, EPI_B_BF16, EPI_BIAS, EPI_DGELU, EPI_GELU, EPI_NONE, EPI_OUT_BF16, EPI_RESID,
+from .hip import (EPI_A_BF16, EPI_B_BF16, EPI_BIAS, EPI_DGELU, EPI_GELU, EPI_NONE, EPI_OUT_BF16, EPI_RESID,
                   call, ptr)
 from .spec import (ADAM_BETA1, ADAM_BETA2, ADAM_EPS, ADAM_LR, BOX_DIM, IOU_EPS, LN_EPS, LOSS_W_CE,
                    LOSS_W_REG, LOSS_W_STRUCT, SMOOTH_L1_BETA, LayoutConfig, param_layout)
@@ -82,13 +82,10 @@ class LayoutEngine:
         self.precision = precision
         self.gemm_flags = {"fp32": 0, "fp32x3": hip.EPI_SPLIT3}.get(precision, hip.EPI_BF16)
         self.bf16_store = precision == "bf16"
-        # optional (native fp32 only): gelu(u) is never stored - the FFN's first projection writes the pre-activation u
-        # only and the second projection / its weight gradient apply GELU while staging their operand (VLG_EPI_ACT_GELU)
-        self.gelu_on_load = False      # measured slower end to end (GEMM notes): the recomputation is not hidden
         # native fp32 and the bf16 modes: the FFN's first projection stores gelu'(u) in the pre-activation buffer instead of u (VLG_EPI_GELU_GRAD;
         # nothing else reads u) and the second projection's data gradient multiplies by it (VLG_EPI_MUL): ~20 vector
         # instructions per element less in a kernel that pays for each of them in matrix time (csrc/common.h)
-        self.gelu_grad_saved = precision in ("fp32", "bf16", "bf16_mfma") and not self.gelu_on_load and os.environ.get("VLG_GELU_GRAD_SAVED", "1") != "0"
+        self.gelu_grad_saved = precision in ("fp32", "bf16", "bf16_mfma") and os.environ.get("VLG_GELU_GRAD_SAVED", "1") != "0"
         self._epi_ff1 = EPI_BIAS | EPI_GELU | (hip.EPI_GELU_GRAD if self.gelu_grad_saved else 0)
         self._epi_dff2 = hip.EPI_MUL if self.gelu_grad_saved else EPI_DGELU
         self._sfx = "_bf16" if self.bf16_store else ""
@@ -192,7 +189,7 @@ class LayoutEngine:
         self.xmid = torch.empty(L, M, d, **f32)
         self.h2 = torch.empty(L, M, d, **act)
         self.u = torch.empty(L, M, ff, **act)             # FFN pre-activation
-        self.gl = None if self.gelu_on_load else torch.empty(L, M, ff, **act)            # gelu(u)
+        self.gl = torch.empty(L, M, ff, **act)            # gelu(u)
         self.stats = torch.empty(2 * L + 1, 2, M, **f32)  # mean / rstd of every layer-norm
         self.xf = torch.empty(M, d, **act)
         self.out = torch.empty(M, cfg.n_out, **f32)
@@ -216,17 +213,14 @@ class LayoutEngine:
         # a kernel's own duration no longer says anything about that kernel (bench.py's per-kernel roofline).
         self.side = torch.cuda.Stream(device=self.device)
         self.overlap_wgrad = os.environ.get("VLG_OVERLAP_WGRAD", "0") == "1"
-        # second option: the bandwidth-bound kernels of backward (layer-norm backward, attention backward) run on the side
-        # stream BESIDE the weight-gradient GEMM that does not depend on them (see backward)
-        self.overlap_small = os.environ.get("VLG_OVERLAP_SMALL", "0") == "1" and cfg.attention == "slot"
-        # Default (VLG_GROUP_REDUCE=1, single-stream backward): the partial-sum producers of one bucket (a layer: four weight
-        # gradients + two layer-norms) write side by side into ONE arena and ONE table-driven launch (vlg_reduce_slabs_table,
-        # the form the GridNet path uses) reduces them all when the bucket is complete: 27 launches of ~5.5 us -> 6 per step.
-        self.group_reduce = os.environ.get("VLG_GROUP_REDUCE", "1") == "1" and not self.overlap_wgrad and not self.overlap_small
-        # a projection's data gradient and weight gradient through one call (one launch at few tokens): fp32 tensors, single
-        # stream; the library decides per shape (VLG_GEMM_PAIR)
-        self.pair_backward = (not self.overlap_wgrad and not self.overlap_small and not self.gelu_on_load
-                              and self.precision in ("fp32", "bf16") and os.environ.get("VLG_PAIR_BACKWARD", "1") == "1")
+        # Single-stream backward (the default): the partial-sum producers of one bucket (a layer: four weight gradients + two
+        # layer-norms) write side by side into ONE arena and ONE table-driven launch (vlg_reduce_slabs_table, the form the
+        # GridNet path uses) reduces them all when the bucket is complete: 27 launches of ~5.5 us -> 6 per step.
+        self.group_reduce = not self.overlap_wgrad
+        # a projection's data gradient and weight gradient through one call (vlg_linear_dgrad_wgrad: one launch where the
+        # library can fuse them), single stream
+        self.pair_backward = (not self.overlap_wgrad and self.precision in ("fp32", "bf16")
+                              and os.environ.get("VLG_PAIR_BACKWARD", "1") == "1")
         self.ride_reduces = False
         if self.group_reduce:
             pad = lambda v: (v + 3) // 4 * 4
@@ -345,17 +339,17 @@ class LayoutEngine:
         self._timed("gemm_dgrad", 2.0 * M * N * K, "vlg_linear_dgrad", ptr(dy), N, ptr(w), K, ptr(dx), K,
                     ptr(aux_in), M, N, K, flags, self._stream(), nbytes=nb)
 
-    def _wgrad(self, dy, x, wname, M, N, K, extra=0):
-        """grad[w | b] = (dy^T . x | colsum dy): split partials -> slab arena -> flat gradient.  extra = EPI_ACT_GELU: x holds
-        pre-activations, the kernel applies GELU while staging it.  Runs on the CURRENT stream (backward makes that the
-        side stream)."""
+    def _wgrad(self, dy, x, wname, M, N, K):
+        """grad[w | b] = (dy^T . x | colsum dy): split partials -> slab arena -> flat gradient.  Runs on the CURRENT stream
+        (backward makes that the side stream)."""
         lib = hip.load()
         stride = N * K + N
-        n_slabs = lib.vlg_linear_wgrad_slabs_for(M, N, K, self.gemm_flags)
+        flags = self.gemm_flags | self._storage_bits(dy, x)
+        n_slabs = lib.vlg_linear_wgrad_slabs_for(M, N, K, flags)
         arena = self._arena("w", n_slabs * stride)
         s = self._stream()
         self._timed("gemm_wgrad" if N > 32 else "gemm_head", 2.0 * M * N * K, "vlg_linear_wgrad", ptr(dy), N, ptr(x),
-                    K, ptr(arena), stride, arena.numel(), M, N, K, self.gemm_flags | self._storage_bits(dy, x) | extra, s,
+                    K, ptr(arena), stride, arena.numel(), M, N, K, flags, s,
                     nbytes=dy.element_size() * M * N + x.element_size() * M * K + 4.0 * n_slabs * stride)
         self._reduce("w", stride, n_slabs, self.layout[wname][0], stride)
 
@@ -454,15 +448,10 @@ class LayoutEngine:
             self._linear(self.att[l], self.pw(pre + "proj_w"), self.p(pre + "proj_b"), self.xmid[l], M, d, d,
                          EPI_BIAS | EPI_RESID, aux_in=x)
             self._ln_fwd(self.xmid[l], pre + "ln2_g", self.h2[l], self.stats[2 * l + 1], M)
-            if self.gelu_on_load:
-                self._linear(self.h2[l], self.pw(pre + "ff1_w"), self.p(pre + "ff1_b"), self.u[l], M, ff, d, EPI_BIAS)
-                self._linear(self.u[l], self.pw(pre + "ff2_w"), self.p(pre + "ff2_b"), self.x[l + 1], M, d, ff,
-                             EPI_BIAS | EPI_RESID | EPI_ACT_GELU, aux_in=self.xmid[l])
-            else:
-                self._linear(self.h2[l], self.pw(pre + "ff1_w"), self.p(pre + "ff1_b"), self.gl[l], M, ff, d,
-                             self._epi_ff1, aux_out=self.u[l])
-                self._linear(self.gl[l], self.pw(pre + "ff2_w"), self.p(pre + "ff2_b"), self.x[l + 1], M, d, ff,
-                             EPI_BIAS | EPI_RESID, aux_in=self.xmid[l])
+            self._linear(self.h2[l], self.pw(pre + "ff1_w"), self.p(pre + "ff1_b"), self.gl[l], M, ff, d,
+                         self._epi_ff1, aux_out=self.u[l])
+            self._linear(self.gl[l], self.pw(pre + "ff2_w"), self.p(pre + "ff2_b"), self.x[l + 1], M, d, ff,
+                         EPI_BIAS | EPI_RESID, aux_in=self.xmid[l])
         L = cfg.n_layers
         self._ln_fwd(self.x[L], "lnf_g", self.xf, self.stats[2 * L], M)
         self._linear(self.xf, self.pw("head_w"), self.p("head_b"), self.out, M, cfg.n_out, d, EPI_BIAS)
@@ -523,23 +512,20 @@ class LayoutEngine:
                 last_read.clear()
 
         if self.group_reduce:
-            self._gsel = 0          # every step uses the arenas in the same order: the reduction tables (device memory, cached by
-                                    # their rows) are the same from step to step - also what a captured hipGraph needs
+            # every step uses the arenas in the same order: the reduction tables (device memory, cached by their rows) are
+            # the same from step to step - also what a captured hipGraph needs.  A backward that raised half way leaves
+            # nothing behind for this one.
+            self._gsel, self._goff, self._grows, self._pending = 0, 0, [], None
         on_side(("dout",), lambda: self._wgrad(self.dout, self.xf, "head_w", M, cfg.n_out, d))
         self._dgrad(self.dout, self.pw("head_w"), self.dh, M, cfg.n_out, d)
         self._ln_bwd(self.dh, self.x[L], self.stats[2 * L], "lnf_g", None, self.dx, M)
-        paired = self.pair_backward and self._pair_shapes(M)
         ready = (lambda tag: (lambda: reducer.ready(tag))) if reducer is not None else (lambda tag: None)
         if reducer is not None or self.group_reduce:
             join()
-            self._join_reduces(defer=paired, then=ready("head"))      # (paired: rides in the last layer's first launch)
-        if self.overlap_small and not self.overlap_wgrad:
-            self._backward_layers_paired(B, T, N, M, reducer)
-            self._backward_tail(batch, B, T, N, M, reducer)
-            return
+            self._join_reduces(defer=self.pair_backward, then=ready("head"))      # (paired: rides in the last layer's first launch)
         for l in reversed(range(L)):
             pre = "l%d." % l
-            if paired:
+            if self.pair_backward:
                 self._dgrad_wgrad(self.dx, self.pw(pre + "ff2_w"), self.du, self.gl[l], pre + "ff2_w", M, d, ff, self._epi_dff2, aux_in=self.u[l])
                 self._dgrad_wgrad(self.du, self.pw(pre + "ff1_w"), self.dh, self.h2[l], pre + "ff1_w", M, ff, d)
                 self._ln_bwd(self.dh, self.xmid[l], self.stats[2 * l + 1], pre + "ln2_g", self.dx, self.dx, M)
@@ -551,10 +537,7 @@ class LayoutEngine:
                 self._join_reduces(defer=True, then=ready("l%d" % l))
                 continue
             # FFN:  x_out = xmid + W2 gelu(W1 h2 + b1) + b2
-            if self.gelu_on_load:
-                on_side(("dx",), lambda: self._wgrad(self.dx, self.u[l], pre + "ff2_w", M, d, ff, extra=EPI_ACT_GELU))
-            else:
-                on_side(("dx",), lambda: self._wgrad(self.dx, self.gl[l], pre + "ff2_w", M, d, ff))
+            on_side(("dx",), lambda: self._wgrad(self.dx, self.gl[l], pre + "ff2_w", M, d, ff))
             before_write("du")
             self._dgrad(self.dx, self.pw(pre + "ff2_w"), self.du, M, d, ff, self._epi_dff2, aux_in=self.u[l])
             on_side(("du",), lambda: self._wgrad(self.du, self.h2[l], pre + "ff1_w", M, ff, d))
@@ -578,13 +561,6 @@ class LayoutEngine:
         join()
         self._backward_tail(batch, B, T, N, M, reducer)
 
-    def _pair_shapes(self, M: int) -> bool:
-        """the paired backward (one C-ABI call per projection; the library fuses the two launches where its VLG_GEMM_PAIR mode
-        says so: 2 = every shape, the default; 1 = few tokens only - then larger batches keep the separate calls and with
-        them bench.py's per-kernel timing families; 0 = never)"""
-        mode = int(os.environ.get("VLG_GEMM_PAIR", "2"))
-        return mode >= 2 or (mode == 1 and M <= 16384)
-
     def _backward_tail(self, batch, B, T, N, M, reducer) -> None:
         cfg, d = self.cfg, self.cfg.d
         lib = hip.load()
@@ -597,45 +573,6 @@ class LayoutEngine:
         self._reduce("s", emb_len, n_slabs, 0, emb_len)
         # (flushes a bucket still waiting for a ride in the same table: the gradient buffer is complete for whoever runs next)
         self._join_reduces(then=(lambda: reducer.ready("embed")) if reducer is not None else None)
-
-    def _backward_layers_paired(self, B, T, N, M, reducer) -> None:
-        """Backward of the layers with every bandwidth-bound kernel of the chain launched on the side stream BESIDE the
-        weight-gradient GEMM that does not depend on it: layer-norm-2 backward beside the FFN1 weight gradient, attention
-        backward beside the output-projection weight gradient, layer-norm-1 backward beside the QKV weight gradient.  The
-        GEMM is bound by the matrix pipes and leaves most of the HBM bandwidth idle; its partner needs no LDS and few
-        registers, so its blocks fit next to the GEMM's on every CU.  Each pair is fork -> two launches -> join."""
-        cfg, d, ff = self.cfg, self.cfg.d, self.cfg.d_ff
-        main = torch.cuda.current_stream(self.device)
-        side = self.side
-
-        def beside(side_fn, main_fn):
-            e = torch.cuda.Event()
-            e.record(main)
-            side.wait_event(e)
-            with torch.cuda.stream(side):
-                side_fn()
-                done = torch.cuda.Event()
-                done.record(side)
-            main_fn()
-            main.wait_event(done)
-
-        for l in reversed(range(cfg.n_layers)):
-            pre = "l%d." % l
-            self._wgrad(self.dx, self.gl[l], pre + "ff2_w", M, d, ff)
-            self._dgrad(self.dx, self.pw(pre + "ff2_w"), self.du, M, d, ff, self._epi_dff2, aux_in=self.u[l])
-            self._dgrad(self.du, self.pw(pre + "ff1_w"), self.dh, M, ff, d)
-            beside(lambda: self._ln_bwd(self.dh, self.xmid[l], self.stats[2 * l + 1], pre + "ln2_g", self.dx, self.dx, M),
-                   lambda: self._wgrad(self.du, self.h2[l], pre + "ff1_w", M, ff, d))
-            self._dgrad(self.dx, self.pw(pre + "proj_w"), self.dh, M, d, d)
-            beside(lambda: self._timed("attn_bwd", 0.0, "vlg_attention_bwd" + self._sfx, ptr(self.qkv[l]), ptr(self.dh), ptr(self.dqkv),
-                                       B * N, T, d, self._stream(), nbytes=7.0 * self.qkv.element_size() * M * d),
-                   lambda: self._wgrad(self.dx, self.att[l], pre + "proj_w", M, d, d))
-            self._dgrad(self.dqkv, self.pw(pre + "qkv_w"), self.dh, M, 3 * d, d)
-            beside(lambda: self._ln_bwd(self.dh, self.x[l], self.stats[2 * l], pre + "ln1_g", self.dx, self.dx, M),
-                   lambda: self._wgrad(self.dqkv, self.h1[l], pre + "qkv_w", M, 3 * d, d))
-            if reducer is not None:
-                self._join_reduces()
-                reducer.ready("l%d" % l)
 
     def forward_backward(self, batch: Dict[str, torch.Tensor], reducer=None) -> torch.Tensor:
         loss = self.forward(batch)
