@@ -150,7 +150,8 @@ int vlg_linear_dgrad_wgrad(const void* dY, int ldy, const void* W, int ldw, void
                            int64_t M, int N, int K, int epilogue,
                            const int64_t* rider_table /* NULL, or a vlg_reduce_slabs_table table over OTHER buffers (a finished
                               gradient bucket's partial sums): reduced by extra blocks of the same launch where the products are
-                              fused, by its own launch otherwise */, int rider_rows, void* stream);
+                              fused, by its own launch otherwise; rows as vlg_reduce_slabs_table requires, 1 <= rider_rows
+                              <= 4096 */, int rider_rows, void* stream);
 
 
 /* ------------------------------------------------------------------- attention
@@ -207,8 +208,11 @@ int vlg_adam_step_graph(float* param, const float* grad, float* exp_avg, float* 
 
 /* Many reductions in one launch, driven by a DEVICE table (static graphs: the reference GridNet's 61 convolutions).
  * vlg_reduce_slabs_table: row i = {slabs pointer, slab stride, slab count, destination pointer, length} (int64 each);
- * every row is reduced exactly as vlg_reduce_slabs would.  vlg_sum_partials_table: row i = {partials pointer, count,
- * destination pointer}: dst[0] = sum (vlg_sum_partials with accumulate = 0). */
+ * every row is reduced exactly as vlg_reduce_slabs would.  The table lives in device memory, so the host checks
+ * vlg_reduce_slabs makes cannot be made on its rows: the CALLER guarantees, per row, length >= 4 and slab stride multiples of 4,
+ * slab stride >= length, slab count >= 1, and 16-byte-aligned slabs and destination pointers (a length that is not a
+ * multiple of 4 loses its tail silently).  The same holds for the rider_table of vlg_linear_dgrad_wgrad.
+ * vlg_sum_partials_table: row i = {partials pointer, count, destination pointer}: dst[0] = sum (vlg_sum_partials with accumulate = 0). */
 int vlg_reduce_slabs_table(const int64_t* table, int n_rows, int blocks_per_row, void* stream);
 int vlg_sum_partials_table(const int64_t* table, int n_rows, void* stream);
 

@@ -155,6 +155,52 @@ def test_full_size_properties(dev, shape):
     assert last < first, (first, last)
 
 
+FULL_SIZE = [
+    # exactly the bench.py configuration (128-tile pairs, chained forwards, rider reductions across four layers)
+    pytest.param(dict(B=32, T=16, N=64, d=256, n_layers=4), "fp32", False, id="metric-4L"),
+    # the strong-scaling shard (64x64 pairs)
+    pytest.param(dict(B=4, T=16, N=64, d=256, n_layers=2), "fp32", False, id="shard-2L"),
+    # one GPU's share of BASELINE.json configs[3]
+    pytest.param(dict(B=8, T=32, N=64, d=512, n_layers=2), "fp32", False, id="configs3-share-2L"),
+    pytest.param(dict(B=32, T=16, N=64, d=256, n_layers=2), "fp32x3", False, id="metric-2L-fp32x3"),
+    pytest.param(dict(B=4, T=16, N=64, d=256, n_layers=2), "fp32", True, id="shard-2L-variable-n"),
+]
+
+
+@pytest.mark.parametrize("kw,precision,variable_n", FULL_SIZE)
+def test_full_size_step_matches_fp64_oracle(dev, kw, precision, variable_n):
+    """The step at the shapes the benchmark reports, against the oracle evaluated in fp64 (parameters and batch cast to
+    float64): loss parts, logits, box outputs and every gradient tensor at the bar of test_step_matches_oracle.  Prints the
+    worst relative error (max |err| / max |want|) per gradient tensor."""
+    from vlg.spec import LayoutConfig
+    cfg = LayoutConfig(**kw)
+    eng, p = build(cfg, dev, precision=precision)
+    batch = O.synthetic_batch(cfg.B, cfg.T, cfg.N, seed=7, variable_n=variable_n, min_valid=3)
+    loss = eng.forward_backward(to_dev(batch, dev)).cpu()
+    gl, gb = (t.cpu() for t in eng.outputs_btn())
+    got = {name: g.cpu() for name, g in eng.named_grads().items()}
+    p64 = {k: v.double() for k, v in p.items()}
+    b64 = {k: v.double() if v.is_floating_point() else v for k, v in batch.items()}
+    parts, grads = O.loss_and_grads(p64, b64, cfg.n_layers)
+    with torch.no_grad():
+        logits, box_raw = O.forward(p64, b64["slot_class"], b64["slot_box"], cfg.n_layers)
+    # (a NaN passes assert_close's `err > tol` test: refuse non-finite results first)
+    for what, t in [("loss parts", loss), ("logits", gl), ("box outputs", gb)] + [("grad " + n, g) for n, g in got.items()]:
+        assert bool(torch.isfinite(t).all()), "%s: not finite" % what
+    assert_close(loss, torch.tensor(parts, dtype=torch.float64), rtol=1e-4, atol=1e-6, what="loss parts")
+    assert_close(gl, logits, rtol=1e-4, atol=1e-4, what="logits")
+    assert_close(gb, box_raw, rtol=1e-4, atol=1e-4, what="box outputs")
+    worst = {}
+    for name, g in got.items():
+        w = grads[name]
+        scale = max(float(w.abs().max()), 1e-6)
+        worst[name] = float((g.double() - w).abs().max()) / scale
+        assert_close(g / scale, w / scale, rtol=1e-4, atol=2e-5, what="grad " + name)
+    print("\nworst relative gradient error vs fp64 (%s, %s%s): %s" % (
+        kw, precision, ", variable_n" if variable_n else "",
+        ", ".join("%s %.2e" % (k, v) for k, v in sorted(worst.items(), key=lambda kv: -kv[1]))))
+
+
 @pytest.mark.parametrize("precision,T", [("bf16", 16), ("bf16_mfma", 16), ("bf16", 8)])
 def test_bf16_projection_mode(dev, precision, T):
     """BASELINE.json configs[2]: the same step with bf16 MFMA projections (fp32 accumulate), either with the
