@@ -61,6 +61,22 @@ __device__ __forceinline__ float4 slope4(float a, int c, int act_ch) {
     return make_float4(c < act_ch ? a : 1.f, c + 1 < act_ch ? a : 1.f, c + 2 < act_ch ? a : 1.f, c + 3 < act_ch ? a : 1.f);
 }
 
+// PReLU of a staged operand (fast path): v > 0 ? v : a v  ==  a <= 1 ? max(v, a v) : min(v, a v)  ==  med3(v, a v, sel = +-inf),
+// bit for bit what the general path computes (one rounding, in a v)
+template <int NV>
+__device__ __forceinline__ void prelu_stage(v4f (&x)[NV], v2f slope2, float sel) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        // (as asm: left to itself hipcc multiplies the four lanes one by one)
+        v2f lo, hi;
+        const v2f p0 = __builtin_shufflevector(x[i], x[i], 0, 1), p1 = __builtin_shufflevector(x[i], x[i], 2, 3);
+        asm("v_pk_mul_f32 %0, %1, %2" : "=v"(lo) : "v"(p0), "v"(slope2));
+        asm("v_pk_mul_f32 %0, %1, %2" : "=v"(hi) : "v"(p1), "v"(slope2));
+        x[i] = v4f{__builtin_amdgcn_fmed3f(x[i].x, lo.x, sel), __builtin_amdgcn_fmed3f(x[i].y, lo.y, sel),
+                   __builtin_amdgcn_fmed3f(x[i].z, hi.x, sel), __builtin_amdgcn_fmed3f(x[i].w, hi.y, sel)};
+    }
+}
+
 template <int MODE, int BM, int BN, int BK>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void conv_gemm_kernel(const ConvArgs g) {
     constexpr int NCH = BK / 8;                            // 8-deep MFMA chunks per K tile
@@ -309,20 +325,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void conv_gemm_kernel(const ConvAr
                 if constexpr (LOAD) gload(kbeg + (int64_t)(kt + 2) * BK);
             }
             mma(fa[s & 1], fb[s & 1]);
-            if (s == SS && (STORE || LOAD)) {
-                constexpr int N_MFMA = 4 * TM * TN, N_ST = (STORE ? TA::NV + TB::NV : 0), N_LD = (LOAD ? TA::NV + TB::NV : 0);
-                constexpr int PER = (N_ST + N_LD + N_MFMA - 1) / N_MFMA;
-#pragma unroll
-                for (int i = 0; i < N_MFMA; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-#pragma unroll
-                    for (int q = 0; q < PER; ++q) {
-                        const int slot = i * PER + q;
-                        if (slot < N_ST) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-                        else if (slot < N_ST + N_LD) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                    }
-                }
-            }
+            if (s == SS && (STORE || LOAD)) pin_staging<4 * TM * TN, (STORE ? TA::NV + TB::NV : 0), (LOAD ? TA::NV + TB::NV : 0)>();
         }
     };
 #ifdef VLG_TIMELINE
@@ -387,8 +390,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void conv_gemm_kernel(const ConvAr
                 l_kx = wrap_x ? 0 : l_kx + (wrap_c ? 1 : 0);
                 l_ky += wrap_x ? 1 : 0;
             };
-            // PReLU of the staged operand: v > 0 ? v : a v  ==  a <= 1 ? max(v, a v) : min(v, a v)  ==  med3(v, a v, +-inf), bit for
-            // bit what the general path computes (one rounding, in a v); slope 1 (no activation) skips it
+            // PReLU of the staged operand (prelu_stage); slope 1 (no activation) skips it
             const bool act_on = MODE == CONV_FWD && slope != 1.0f;
             const float sel = slope <= 1.0f ? __builtin_inff() : -__builtin_inff();
             const v2f slope2 = v2(slope);
@@ -400,18 +402,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void conv_gemm_kernel(const ConvAr
                     tl_vm += __builtin_amdgcn_s_memtime() - w0;
                 }
 #endif
-                if constexpr (decltype(act_tag)::value) {
-#pragma unroll
-                    for (int i = 0; i < TA::NV; ++i) {
-                        // (as asm: left to itself hipcc multiplies the four lanes one by one)
-                        v2f lo, hi;
-                        const v2f p0 = __builtin_shufflevector(xa[i], xa[i], 0, 1), p1 = __builtin_shufflevector(xa[i], xa[i], 2, 3);
-                        asm("v_pk_mul_f32 %0, %1, %2" : "=v"(lo) : "v"(p0), "v"(slope2));
-                        asm("v_pk_mul_f32 %0, %1, %2" : "=v"(hi) : "v"(p1), "v"(slope2));
-                        xa[i] = v4f{__builtin_amdgcn_fmed3f(xa[i].x, lo.x, sel), __builtin_amdgcn_fmed3f(xa[i].y, lo.y, sel),
-                                    __builtin_amdgcn_fmed3f(xa[i].z, hi.x, sel), __builtin_amdgcn_fmed3f(xa[i].w, hi.y, sel)};
-                    }
-                }
+                if constexpr (decltype(act_tag)::value) prelu_stage(xa, slope2, sel);
 #pragma unroll
                 for (int i = 0; i < TA::NV; ++i) *reinterpret_cast<v4f*>(aw + c * TA::FLOATS + i * TA::SSTEP) = xa[i];
 #pragma unroll
@@ -440,20 +431,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void conv_gemm_kernel(const ConvAr
                     __builtin_amdgcn_sched_barrier(0);
                     if (sch == SS) { store(cur ^ 1, act_tag); load(); }
                     mma(fa[sch & 1], fb[sch & 1]);
-                    if (sch == SS) {
-                        constexpr int N_MFMA = 4 * TM * TN, N_ST = TA::NV + TB::NV, N_LD = TA::NV + TB::NV;
-                        constexpr int PER = (N_ST + N_LD + N_MFMA - 1) / N_MFMA;
-#pragma unroll
-                        for (int i = 0; i < N_MFMA; ++i) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-#pragma unroll
-                            for (int q = 0; q < PER; ++q) {
-                                const int slot = i * PER + q;
-                                if (slot < N_ST) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-                                else if (slot < N_ST + N_LD) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                            }
-                        }
-                    }
+                    if (sch == SS) pin_staging<4 * TM * TN, TA::NV + TB::NV, TA::NV + TB::NV>();
                 }
             };
             load();
@@ -535,17 +513,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void conv_gemm_kernel(const ConvAr
                     asm("v_pk_add_f32 %0, %0, %1" : "+v"(wcol[i][0]) : "v"(lo));
                     asm("v_pk_add_f32 %0, %0, %1" : "+v"(wcol[i][1]) : "v"(hi));
                 }
-                if constexpr (decltype(act_tag)::value) {
-#pragma unroll
-                    for (int i = 0; i < TB::NV; ++i) {
-                        v2f lo, hi;
-                        const v2f p0 = __builtin_shufflevector(xb[i], xb[i], 0, 1), p1 = __builtin_shufflevector(xb[i], xb[i], 2, 3);
-                        asm("v_pk_mul_f32 %0, %1, %2" : "=v"(lo) : "v"(p0), "v"(slope2));
-                        asm("v_pk_mul_f32 %0, %1, %2" : "=v"(hi) : "v"(p1), "v"(slope2));
-                        xb[i] = v4f{__builtin_amdgcn_fmed3f(xb[i].x, lo.x, sel), __builtin_amdgcn_fmed3f(xb[i].y, lo.y, sel),
-                                    __builtin_amdgcn_fmed3f(xb[i].z, hi.x, sel), __builtin_amdgcn_fmed3f(xb[i].w, hi.y, sel)};
-                    }
-                }
+                if constexpr (decltype(act_tag)::value) prelu_stage(xb, slope2, sel);
 #pragma unroll
                 for (int i = 0; i < TA::NV; ++i) *reinterpret_cast<v4f*>(aw + c * TA::FLOATS + i * TA::SSTEP) = xa[i];
 #pragma unroll
@@ -574,20 +542,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void conv_gemm_kernel(const ConvAr
                     __builtin_amdgcn_sched_barrier(0);
                     if (sch == SS) { store(cur ^ 1, act_tag); load(); }
                     mma(fa[sch & 1], fb[sch & 1]);
-                    if (sch == SS) {
-                        constexpr int N_MFMA = 4 * TM * TN, N_ST = TA::NV + TB::NV, N_LD = TA::NV + TB::NV;
-                        constexpr int PER = (N_ST + N_LD + N_MFMA - 1) / N_MFMA;
-#pragma unroll
-                        for (int i = 0; i < N_MFMA; ++i) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-#pragma unroll
-                            for (int q = 0; q < PER; ++q) {
-                                const int slot = i * PER + q;
-                                if (slot < N_ST) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-                                else if (slot < N_ST + N_LD) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                            }
-                        }
-                    }
+                    if (sch == SS) pin_staging<4 * TM * TN, TA::NV + TB::NV, TA::NV + TB::NV>();
                 }
             };
             load();
@@ -1000,16 +955,6 @@ static int conv_fwd_splits(int64_t rows_out, int cin_p, int cout, int cout_p) {
     while (s > 1 && ktiles / s < 8) --s;                       // keep at least 8 K tiles per block
     return s < 2 ? 1 : s;
 }
-extern "C" int vlg_conv3x3_fwd_splits(int64_t rows_out, int cin_p, int cout, int cout_p) {
-    return conv_fwd_splits(rows_out, cin_p, cout, cout_p);
-}
-extern "C" int64_t vlg_conv3x3_fwd_workspace(int64_t rows_out, int cin_p, int cout, int cout_p) {
-    if (rows_out < 1 || cin_p < 32 || cout_p < 32) return 0;
-    const int splits = conv_fwd_splits(rows_out, cin_p, cout, cout_p);
-    if (splits > 1) return (int64_t)splits * rows_out * cout_p;
-    return conv_tail_plan(rows_out, conv_tile(rows_out, cout_p, cout, 9 * (int64_t)cin_p), cout, 9 * (int64_t)cin_p, cout_p).floats;
-}
-
 __global__ __launch_bounds__(256) void conv_finish_kernel(const float* __restrict__ slabs, int splits, int64_t slab_stride,
                                                           const float* __restrict__ bias, const float* __restrict__ resid,
                                                           const float* __restrict__ rowmask, float* __restrict__ out,
@@ -1056,6 +1001,132 @@ __global__ __launch_bounds__(256) void conv_finish_dgrad_kernel(const float* __r
     }
 }
 
+// row-tile height of the weight gradient: all of Cout for the GridNet widths (one pass over the gathered activation
+// tile serves every output channel), 32-row tiles otherwise.  VLG_CONV_WGRAD_TALL=0 (diagnostic build) forces 32.
+static int conv_wgrad_bm(int cout_p) {
+    return (VLG_TUNE("VLG_CONV_WGRAD_TALL", 1) != 0 && (cout_p == 64 || cout_p == 96)) ? cout_p : 32;
+}
+
+// The ONE plan of a conv launch and of its queries, from the call's arguments: the tile, the K ranges of every tile
+// (split-K) or of the tail tiles only (tail split), the workspace floats that needs, and the slope-gradient partials
+// (one per block of a data-gradient launch with da_slab).  ws: whether a workspace was given and whether it is
+// 16-byte aligned (the tail split needs it; the split-K launch rejects a misaligned one), ws_cap its floats (the tail
+// split is taken only if it fits), has the HAS_* operands the call passes.  The queries ask for an aligned workspace of
+// any size and pass no optional operand.
+enum { WS_NONE, WS_MISALIGNED, WS_ALIGNED };
+enum { HAS_TABLES = 1, HAS_DA_SLAB = 2, HAS_PRELU = 4 };     // row tables, slope-gradient buffer, PReLU epilogue
+static int ws_kind(const float* ws) { return ws == nullptr ? WS_NONE : vlg_aligned16(ws) ? WS_ALIGNED : WS_MISALIGNED; }
+struct ConvPlan {
+    ConvTile t;
+    int splits; int64_t kc_per_split;
+    ConvTail tail;
+    int64_t ws_floats;
+    int slopes;
+};
+static ConvPlan conv_plan(int mode, int64_t rows, int cin_p, int cout, int cout_p, int ws, int64_t ws_cap, int has) {
+    const bool tables = (has & HAS_TABLES) != 0, da_slab = (has & HAS_DA_SLAB) != 0, prelu = (has & HAS_PRELU) != 0;
+    ConvPlan p{};
+    p.splits = 1;
+    p.tail = ConvTail{0, 1, 0, 0, 0};
+    if (mode == CONV_WGRAD) {                                  // K = rows: ranges of whole 32-row tiles, ~512 blocks
+        p.t = ConvTile{conv_wgrad_bm(cout_p), 128, 32};
+        const int64_t tiles = (cout_p / p.t.bm) * (int64_t)((9 * cin_p + 127) / 128);
+        int64_t want = 512 / tiles;
+        const int64_t max_splits = (rows + 255) / 256;
+        if (want > max_splits) want = max_splits;
+        if (want < 1) want = 1;
+        int64_t per = (rows + want - 1) / want;
+        per = (per + 31) / 32 * 32;
+        p.kc_per_split = per;
+        p.splits = (int)((rows + per - 1) / per);
+        return p;
+    }
+    // forward: N = cout_p columns (cout of them valid), K = 9 cin_p;  data gradient: N = cin_p, K = 9 cout_p
+    const int n_cols = mode == CONV_FWD ? cout_p : cin_p, n_valid = mode == CONV_FWD ? cout : cin_p;
+    const int64_t kc = 9 * (int64_t)(mode == CONV_FWD ? cin_p : cout_p);
+    p.kc_per_split = kc;
+    // split-K: the data gradient only for frozen trunks (no slope gradient wanted), stride 1
+    const bool split_ok = ws != WS_NONE && (mode == CONV_FWD || (!da_slab && !tables));
+    const int splits = !split_ok ? 1 : mode == CONV_FWD ? conv_fwd_splits(rows, cin_p, cout, cout_p) : conv_fwd_splits(rows, cout_p, cin_p, cin_p);
+    if (splits > 1) {
+        p.t = ConvTile{128, 128, 32};
+        p.splits = splits;
+        p.kc_per_split = (int64_t)((kc / 32 + splits - 1) / splits) * 32;
+        p.ws_floats = (int64_t)splits * rows * n_cols;
+    } else {
+        const bool tail_ok = ws == WS_ALIGNED && !tables && !da_slab && !prelu;
+        p.t = conv_tile(rows, n_cols, n_valid, tail_ok ? kc : 0);
+        if (tail_ok) {
+            const ConvTail tl = conv_tail_plan(rows, p.t, n_valid, kc, n_cols);
+            if (tl.tiles > 0 && tl.floats <= ws_cap) { p.tail = tl; p.ws_floats = tl.floats; }
+        }
+    }
+    p.slopes = (int)((rows + p.t.bm - 1) / p.t.bm) * ((n_cols + p.t.bn - 1) / p.t.bn);
+    return p;
+}
+static ConvPlan conv_query_plan(int mode, int64_t rows, int cin_p, int cout, int cout_p) {
+    return conv_plan(mode, rows, cin_p, cout, cout_p, WS_ALIGNED, INT64_MAX, 0);
+}
+
+extern "C" int vlg_conv3x3_fwd_splits(int64_t rows_out, int cin_p, int cout, int cout_p) {
+    return conv_query_plan(CONV_FWD, rows_out, cin_p, cout, cout_p).splits;
+}
+extern "C" int64_t vlg_conv3x3_fwd_workspace(int64_t rows_out, int cin_p, int cout, int cout_p) {
+    if (rows_out < 1 || cin_p < 32 || cout_p < 32) return 0;
+    return conv_query_plan(CONV_FWD, rows_out, cin_p, cout, cout_p).ws_floats;
+}
+extern "C" int vlg_conv3x3_dgrad_splits(int64_t rows_in, int cin_p, int cout_p) {
+    return conv_query_plan(CONV_DGRAD, rows_in, cin_p, cin_p, cout_p).splits;
+}
+extern "C" int64_t vlg_conv3x3_dgrad_workspace(int64_t rows_in, int cin_p, int cout_p) {
+    if (rows_in < 1 || cin_p < 32 || cout_p < 32) return 0;
+    return conv_query_plan(CONV_DGRAD, rows_in, cin_p, cin_p, cout_p).ws_floats;
+}
+extern "C" int vlg_conv3x3_dgrad_slabs(int64_t rows_in, int cin_p) {
+    // (with da_slab there is no split of any kind, and the tile does not depend on cout_p)
+    return conv_plan(CONV_DGRAD, rows_in, cin_p, cin_p, cin_p, WS_NONE, 0, HAS_DA_SLAB).slopes;
+}
+extern "C" int vlg_conv3x3_wgrad_slabs(int64_t rows, int cin_p, int cout_p) {
+    return conv_query_plan(CONV_WGRAD, rows, cin_p, cout_p, cout_p).splits;
+}
+
+// the epilogue operands of a finish kernel over the whole output (forward: bias, residual, row mask; data gradient: x_in,
+// row mask, slope, act_ch, epilogue flags)
+struct ConvFinish { const float* bias; const float* aux; const float* rowmask; const float* prelu; float* out; int act_ch, epi; };
+static dim3 finish_grid(int64_t n4) { const int64_t b = (n4 + 255) / 256; return dim3((unsigned)(b > 2048 ? 2048 : b)); }
+
+// Launch a forward / data-gradient plan: the main kernel and, for a split-K or tail-split plan, the finish kernel over the
+// rows the partial tiles cover (all of them, or those from the tail's first row on).
+template <int MODE>
+static int launch_conv_plan(const ConvPlan& p, ConvArgs g, float* ws, const ConvFinish& f, hipStream_t s) {
+    int splits = 1;
+    int64_t row0 = 0, stride = 0;
+    if (p.splits > 1) {
+        splits = g.splits = p.splits;
+        g.kc_per_split = p.kc_per_split;
+        stride = g.slab_stride = g.M * (int64_t)g.ldc;
+        g.C = ws; g.bias = nullptr; g.aux_in = nullptr; g.rowmask = nullptr; g.epi = 0;    // raw partial tiles
+        if (MODE == CONV_DGRAD) g.act_ch = g.N;                // (the finish kernel cuts the constant channels)
+    } else if (p.tail.tiles > 0) {
+        splits = p.tail.splits;
+        row0 = p.tail.row0;
+        g.tail_tiles = p.tail.tiles; g.tail_splits = p.tail.splits; g.tail_kc = p.tail.kc; g.tail_row0 = row0;
+        stride = g.tail_stride = (g.M - row0) * (int64_t)g.ldc; g.tail_ws = ws;
+    }
+    if (int e = launch_conv_tile<MODE>(p.t, g, s)) return e;
+    if (splits == 1) return 0;
+    const int64_t off = row0 * (int64_t)g.ldc, rows = g.M - row0;
+    const dim3 grid = finish_grid(rows * (g.ldc / 4));
+    const float* const aux = f.aux ? f.aux + off : nullptr;
+    const float* const rowmask = f.rowmask ? f.rowmask + row0 : nullptr;
+    if constexpr (MODE == CONV_FWD)
+        hipLaunchKernelGGL(conv_finish_kernel, grid, dim3(256), 0, s, ws, splits, stride, f.bias, aux, rowmask, f.out + off, rows, g.ldc / 4);
+    else
+        hipLaunchKernelGGL(conv_finish_dgrad_kernel, grid, dim3(256), 0, s, ws, splits, stride, aux, rowmask, f.prelu ? 1.0f : 0.0f,
+                           f.prelu, f.out + off, rows, g.ldc / 4, f.act_ch, f.epi);
+    return vlg_last_error();
+}
+
 extern "C" int vlg_conv3x3_fwd(const float* in, const float* w, const float* bias, float* out, const float* resid,
                                const float* rowmask, const float* prelu_slope, const int* rowtab, int64_t rows_out,
                                int cin_p, int cout, int cout_p, int wp_in, int act_ch, int epilogue, float* workspace,
@@ -1069,7 +1140,7 @@ extern "C" int vlg_conv3x3_fwd(const float* in, const float* w, const float* bia
     g.M = rows_out; g.N = cout; g.Kc = 9 * (int64_t)cin_p;
     g.lda = cin_p; g.ldb = 9 * cin_p; g.ldc = cout_p; g.cin = cin_p;
     g.splits = 1; g.kc_per_split = g.Kc; g.epi = epilogue & ~(VLG_CEPI_DPRELU | VLG_CEPI_CIN4); g.act_ch = act_ch;
-    fill_shifts(g, wp_in, rowtab ? 1 : 1);
+    fill_shifts(g, wp_in, 1);
     hipStream_t s = (hipStream_t)stream;
     if (epilogue & VLG_CEPI_CIN4) {                            // image-channel first layer: contraction over (tap, 4 channels)
         if (rowtab != nullptr || prelu_slope != nullptr || (epilogue & (VLG_CEPI_RESID | VLG_CEPI_PRELU)) || wp_in < 1) return VLG_ERR_SHAPE;
@@ -1081,54 +1152,14 @@ extern "C" int vlg_conv3x3_fwd(const float* in, const float* w, const float* bia
                            cin_p, 9 * cin_p, cout_p, cout, wp_in);
         return vlg_last_error();
     }
-    const int splits = workspace != nullptr ? conv_fwd_splits(rows_out, cin_p, cout, cout_p) : 1;
-    if (splits > 1) {
+    const ConvPlan p = conv_plan(CONV_FWD, rows_out, cin_p, cout, cout_p, ws_kind(workspace), workspace_capacity,
+                                 (rowtab ? HAS_TABLES : 0) | ((epilogue & VLG_CEPI_PRELU) ? HAS_PRELU : 0));
+    if (p.splits > 1) {
         if (!vlg_aligned16(workspace) || (epilogue & VLG_CEPI_PRELU)) return VLG_ERR_ALIGN;
-        if (workspace_capacity < (int64_t)splits * rows_out * cout_p) return VLG_ERR_SHAPE;     // host-side bound on the partial tiles
-        const int ktiles = 9 * cin_p / 32;
-        g.splits = splits;
-        g.kc_per_split = (int64_t)((ktiles + splits - 1) / splits) * 32;
-        g.slab_stride = rows_out * (int64_t)cout_p;
-        g.C = workspace; g.bias = nullptr; g.aux_in = nullptr; g.rowmask = nullptr; g.epi = 0;    // raw partial tiles
-        if (int e = launch_conv<CONV_FWD, 128, 128>(g, s)) return e;
-        const int64_t n4 = rows_out * (cout_p / 4);
-        int64_t blocks = (n4 + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(conv_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, s, workspace, splits, g.slab_stride, bias,
-                           (epilogue & VLG_CEPI_RESID) ? resid : nullptr, rowmask, out, rows_out, cout_p / 4);
-        return vlg_last_error();
+        if (workspace_capacity < p.ws_floats) return VLG_ERR_SHAPE;      // host-side bound on the partial tiles
     }
-    const bool tail_ok = workspace != nullptr && rowtab == nullptr && !(epilogue & VLG_CEPI_PRELU) && vlg_aligned16(workspace);
-    const ConvTile t = conv_tile(rows_out, cout_p, cout, tail_ok ? g.Kc : 0);
-    if (tail_ok) {
-        const ConvTail tl = conv_tail_plan(rows_out, t, cout, g.Kc, cout_p);
-        if (tl.tiles > 0 && tl.floats <= workspace_capacity) {
-            g.tail_tiles = tl.tiles; g.tail_splits = tl.splits; g.tail_kc = tl.kc; g.tail_row0 = tl.row0;
-            g.tail_stride = (rows_out - tl.row0) * (int64_t)cout_p; g.tail_ws = workspace;
-            if (int e = launch_conv_tile<CONV_FWD>(t, g, s)) return e;
-            const int64_t off = tl.row0 * (int64_t)cout_p, n4 = (rows_out - tl.row0) * (cout_p / 4);
-            hipLaunchKernelGGL(conv_finish_kernel, dim3((unsigned)((n4 + 255) / 256 > 2048 ? 2048 : (n4 + 255) / 256)), dim3(256), 0, s,
-                               workspace, tl.splits, g.tail_stride, bias, (epilogue & VLG_CEPI_RESID) ? resid + off : nullptr,
-                               rowmask ? rowmask + tl.row0 : nullptr, out + off, rows_out - tl.row0, cout_p / 4);
-            return vlg_last_error();
-        }
-    }
-    return launch_conv_tile<CONV_FWD>(t, g, s);
-}
-
-extern "C" int vlg_conv3x3_dgrad_slabs(int64_t rows_in, int cin_p) {
-    const ConvTile t = conv_tile(rows_in, cin_p, cin_p);       // one partial per block of the launch
-    return (int)((rows_in + t.bm - 1) / t.bm) * ((cin_p + t.bn - 1) / t.bn);
-}
-
-// K ranges of the data gradient when given a workspace: frozen trunks only (no slope gradient wanted), stride 1
-static int conv_dgrad_splits(int64_t rows_in, int cin_p, int cout_p) { return conv_fwd_splits(rows_in, cout_p, cin_p, cin_p); }
-extern "C" int vlg_conv3x3_dgrad_splits(int64_t rows_in, int cin_p, int cout_p) { return conv_dgrad_splits(rows_in, cin_p, cout_p); }
-extern "C" int64_t vlg_conv3x3_dgrad_workspace(int64_t rows_in, int cin_p, int cout_p) {
-    if (rows_in < 1 || cin_p < 32 || cout_p < 32) return 0;
-    const int splits = conv_dgrad_splits(rows_in, cin_p, cout_p);
-    if (splits > 1) return (int64_t)splits * rows_in * cin_p;
-    return conv_tail_plan(rows_in, conv_tile(rows_in, cin_p, cin_p, 9 * (int64_t)cout_p), cin_p, 9 * (int64_t)cout_p, cin_p).floats;
+    const ConvFinish f{bias, (epilogue & VLG_CEPI_RESID) ? resid : nullptr, rowmask, nullptr, out, 0, 0};
+    return launch_conv_plan<CONV_FWD>(p, g, workspace, f, s);
 }
 
 extern "C" int vlg_conv3x3_dgrad(const float* dout, const float* w, float* din, const float* x_in,
@@ -1142,7 +1173,9 @@ extern "C" int vlg_conv3x3_dgrad(const float* dout, const float* w, float* din, 
         return VLG_ERR_SHAPE;                                // wide inputs are tiled 128 columns at a time
     if (!conv_ok(dout) || !conv_ok(w) || !conv_ok(din)) return VLG_ERR_ALIGN;
     if ((epilogue & VLG_CEPI_DPRELU) && (!x_in || !prelu_slope)) return VLG_ERR_SHAPE;
-    if (da_slab != nullptr && da_capacity < vlg_conv3x3_dgrad_slabs(rows_in, cin_p)) return VLG_ERR_SHAPE;   // one partial per block
+    const ConvPlan p = conv_plan(CONV_DGRAD, rows_in, cin_p, cin_p, cout_p, ws_kind(workspace), workspace_capacity,
+                                 (tap_tables ? HAS_TABLES : 0) | (da_slab ? HAS_DA_SLAB : 0));
+    if (da_slab != nullptr && da_capacity < p.slopes) return VLG_ERR_SHAPE;   // one partial per block
     ConvArgs g{};
     g.A = dout; g.B = w; g.C = din; g.aux_in = x_in; g.rowmask = rowmask_in; g.prelu = prelu_slope; g.da_slab = da_slab;
     g.rowtab = tap_tables; g.tab_stride = tap_tables ? tab_stride : 0;
@@ -1151,66 +1184,12 @@ extern "C" int vlg_conv3x3_dgrad(const float* dout, const float* w, float* din, 
     g.splits = 1; g.kc_per_split = g.Kc; g.epi = epilogue & (VLG_CEPI_DPRELU | VLG_CEPI_ACCUM); g.act_ch = act_ch;
     if (tap_tables) { for (int t = 0; t < 9; ++t) g.shift[t] = 0; }
     else fill_shifts(g, wp, -1);
-    hipStream_t s = (hipStream_t)stream;
-    const int splits = (workspace != nullptr && da_slab == nullptr && tap_tables == nullptr) ? conv_dgrad_splits(rows_in, cin_p, cout_p) : 1;
-    if (splits > 1) {
+    if (p.splits > 1) {
         if (!vlg_aligned16(workspace)) return VLG_ERR_ALIGN;
-        if (workspace_capacity < (int64_t)splits * rows_in * cin_p) return VLG_ERR_SHAPE;
-        const int ktiles = 9 * cout_p / 32;
-        g.splits = splits;
-        g.kc_per_split = (int64_t)((ktiles + splits - 1) / splits) * 32;
-        g.slab_stride = rows_in * (int64_t)cin_p;
-        g.C = workspace; g.rowmask = nullptr; g.epi = 0; g.aux_in = nullptr;       // raw partial tiles
-        g.act_ch = cin_p;                                                          // (the finish kernel cuts the constant channels)
-        if (int e = launch_conv<CONV_DGRAD, 128, 128>(g, s)) return e;
-        const int64_t n4 = rows_in * (cin_p / 4);
-        int64_t blocks = (n4 + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(conv_finish_dgrad_kernel, dim3((unsigned)blocks), dim3(256), 0, s, workspace, splits, g.slab_stride, x_in,
-                           rowmask_in, prelu_slope ? 1.0f : 0.0f, prelu_slope, din, rows_in, cin_p / 4, act_ch,
-                           epilogue & (VLG_CEPI_DPRELU | VLG_CEPI_ACCUM));
-        return vlg_last_error();
+        if (workspace_capacity < p.ws_floats) return VLG_ERR_SHAPE;
     }
-    const bool tail_ok = workspace != nullptr && da_slab == nullptr && tap_tables == nullptr && vlg_aligned16(workspace);
-    const ConvTile t = conv_tile(rows_in, cin_p, cin_p, tail_ok ? g.Kc : 0);
-    if (tail_ok) {
-        const ConvTail tl = conv_tail_plan(rows_in, t, cin_p, g.Kc, cin_p);
-        if (tl.tiles > 0 && tl.floats <= workspace_capacity) {
-            g.tail_tiles = tl.tiles; g.tail_splits = tl.splits; g.tail_kc = tl.kc; g.tail_row0 = tl.row0;
-            g.tail_stride = (rows_in - tl.row0) * (int64_t)cin_p; g.tail_ws = workspace;
-            if (int e = launch_conv_tile<CONV_DGRAD>(t, g, s)) return e;
-            const int64_t off = tl.row0 * (int64_t)cin_p, n4 = (rows_in - tl.row0) * (cin_p / 4);
-            hipLaunchKernelGGL(conv_finish_dgrad_kernel, dim3((unsigned)((n4 + 255) / 256 > 2048 ? 2048 : (n4 + 255) / 256)), dim3(256), 0, s,
-                               workspace, tl.splits, g.tail_stride, x_in ? x_in + off : nullptr, rowmask_in ? rowmask_in + tl.row0 : nullptr,
-                               prelu_slope ? 1.0f : 0.0f, prelu_slope, din + off, rows_in - tl.row0, cin_p / 4, act_ch,
-                               epilogue & (VLG_CEPI_DPRELU | VLG_CEPI_ACCUM));
-            return vlg_last_error();
-        }
-    }
-    return launch_conv_tile<CONV_DGRAD>(t, g, s);
-}
-
-// row-tile height of the weight gradient: all of Cout for the GridNet widths (one pass over the gathered activation
-// tile serves every output channel), 32-row tiles otherwise.  VLG_CONV_WGRAD_TALL=0 (diagnostic build) forces 32.
-static int conv_wgrad_bm(int cout_p) {
-    return (VLG_TUNE("VLG_CONV_WGRAD_TALL", 1) != 0 && (cout_p == 64 || cout_p == 96)) ? cout_p : 32;
-}
-static void conv_wgrad_plan(int64_t rows, int cin_p, int cout_p, int* splits, int64_t* per) {
-    const int64_t tiles = (cout_p / conv_wgrad_bm(cout_p)) * (int64_t)((9 * cin_p + 127) / 128);
-    int64_t want = 512 / tiles;
-    const int64_t max_splits = (rows + 255) / 256;
-    if (want > max_splits) want = max_splits;
-    if (want < 1) want = 1;
-    int64_t p = (rows + want - 1) / want;
-    p = (p + 31) / 32 * 32;
-    *per = p;
-    *splits = (int)((rows + p - 1) / p);
-}
-
-extern "C" int vlg_conv3x3_wgrad_slabs(int64_t rows, int cin_p, int cout_p) {
-    int splits; int64_t per;
-    conv_wgrad_plan(rows, cin_p, cout_p, &splits, &per);
-    return splits;
+    const ConvFinish f{nullptr, x_in, rowmask_in, prelu_slope, din, act_ch, epilogue & (VLG_CEPI_DPRELU | VLG_CEPI_ACCUM)};
+    return launch_conv_plan<CONV_DGRAD>(p, g, workspace, f, (hipStream_t)stream);
 }
 
 extern "C" int vlg_conv3x3_wgrad(const float* dout, const float* in, float* slabs, int64_t slab_stride,
@@ -1222,15 +1201,16 @@ extern "C" int vlg_conv3x3_wgrad(const float* dout, const float* in, float* slab
     if (rows < 1 || cin_p < 32 || (cin_p & 31) || cout_p < 32 || (cout_p & 31)) return VLG_ERR_SHAPE;
     if (slab_stride < (int64_t)cout_p * 9 * cin_p + cout_p) return VLG_ERR_SHAPE;
     if (!conv_ok(dout) || !conv_ok(in) || !conv_ok(slabs)) return VLG_ERR_ALIGN;
+    const ConvPlan p = conv_plan(CONV_WGRAD, rows, cin_p, cout_p, cout_p, WS_NONE, 0, rowtab ? HAS_TABLES : 0);
     ConvArgs g{};
     g.A = dout; g.B = in; g.C = slabs; g.prelu = prelu_slope; g.rowtab = rowtab;
     g.M = cout_p; g.N = 9 * cin_p; g.Kc = rows;
     g.lda = cout_p; g.ldb = cin_p; g.ldc = 9 * cin_p; g.cin = cin_p;
-    conv_wgrad_plan(rows, cin_p, cout_p, &g.splits, &g.kc_per_split);
+    g.splits = p.splits; g.kc_per_split = p.kc_per_split;
     if (slab_capacity < (int64_t)g.splits * slab_stride) return VLG_ERR_SHAPE;      // the caller's buffer must hold every slab
     g.slab_stride = slab_stride; g.colsum_off = (int64_t)cout_p * 9 * cin_p; g.act_ch = act_ch;
     fill_shifts(g, wp_in, 1);
-    switch (conv_wgrad_bm(cout_p)) {
+    switch (p.t.bm) {
         case 64: return launch_conv<CONV_WGRAD, 64, 128>(g, (hipStream_t)stream);
         case 96: return launch_conv<CONV_WGRAD, 96, 128>(g, (hipStream_t)stream);
         default: return launch_conv<CONV_WGRAD, 32, 128>(g, (hipStream_t)stream);

@@ -250,22 +250,8 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs& g, float* const sm
                     if constexpr (LOAD) load(xa, xb, kt + 1 + DEPTH);
                 }
                 mma(fa[s & 1], fb[s & 1]);
-                if (s == SS && (STORE || LOAD)) {
-                    // pin the interleave: one LDS write (then one global load) behind each MFMA of this chunk, so the
-                    // matrix pipe keeps issuing while the tile is staged (hipcc left alone emits the writes as one blob)
-                    constexpr int N_MFMA = 4 * TM * TN, N_ST = (STORE ? TA::NV + TB::NV : 0), N_LD = (LOAD ? TA::NV + TB::NV : 0);
-                    constexpr int PER = (N_ST + N_LD + N_MFMA - 1) / N_MFMA;
-#pragma unroll
-                    for (int i = 0; i < N_MFMA; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-#pragma unroll
-                        for (int q = 0; q < PER; ++q) {
-                            const int slot = i * PER + q;
-                            if (slot < N_ST) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-                            else if (slot < N_ST + N_LD) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                        }
-                    }
-                }
+                if (s == SS && (STORE || LOAD))
+                    pin_staging<4 * TM * TN, (STORE ? TA::NV + TB::NV : 0), (LOAD ? TA::NV + TB::NV : 0)>();
             }
         };
         static_assert(NCH >= 2 && NCH % 2 == 0, "fragment sets alternate by chunk parity");
@@ -389,20 +375,7 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs& g, float* const sm
                     load(kt + 1 + DEPTH, set);
                 }
                 mma(ffa[s & 1], ffb[s & 1]);
-                if (s == SS) {
-                    constexpr int N_MFMA = 4 * TM * TN, N_ST = TA::NV + TB::NV, N_LD = TA::NV + TB::NV;
-                    constexpr int PER = (N_ST + N_LD + N_MFMA - 1) / N_MFMA;
-#pragma unroll
-                    for (int i = 0; i < N_MFMA; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-#pragma unroll
-                        for (int q = 0; q < PER; ++q) {
-                            const int slot = i * PER + q;
-                            if (slot < N_ST) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-                            else if (slot < N_ST + N_LD) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                        }
-                    }
-                }
+                if (s == SS) pin_staging<4 * TM * TN, TA::NV + TB::NV, TA::NV + TB::NV>();
             }
         };
         if (first) {

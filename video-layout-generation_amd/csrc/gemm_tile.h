@@ -21,6 +21,23 @@ struct GemmArgs {
     unsigned long long* clock_probe;   // diagnostic only (VLG_GEMM_CLOCK_PROBE): {shader ticks, 100 MHz ticks} per block
 };
 
+// Pin the staging interleave of one chunk, placed right behind its N_MFMA MFMAs: one LDS write (then one global load)
+// behind each MFMA, so the matrix pipe keeps issuing while the tile is staged (hipcc left alone emits the writes as one blob).
+template <int N_MFMA, int N_ST, int N_LD>
+__device__ __forceinline__ void pin_staging() {
+    constexpr int PER = (N_ST + N_LD + N_MFMA - 1) / N_MFMA;
+#pragma unroll
+    for (int i = 0; i < N_MFMA; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+#pragma unroll
+        for (int q = 0; q < PER; ++q) {
+            const int slot = i * PER + q;
+            if (slot < N_ST) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+            else if (slot < N_ST + N_LD) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+        }
+    }
+}
+
 
 // One operand tile: BR rows (non-contraction) x BK contraction steps.
 // NT = threads of the block that stages the tile (256 everywhere but the 8-wave persistent GEMM)
