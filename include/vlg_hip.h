@@ -315,6 +315,29 @@ int vlg_conv3x3_wgrad_slabs(int64_t rows, int cin_p, int cout_p);
 int vlg_conv3x3_wgrad(const float* dout, const float* in, float* slabs, int64_t slab_stride, int64_t slab_capacity,
                       const int* rowtab, const float* prelu_slope, int64_t rows, int cin_p, int cout_p,
                       int wp_in, int act_ch, void* stream);
+/* bf16-MFMA twins of the three convolutions (csrc/conv_bf16.hip; VLG_PRECISION=bf16 of the pixel step).  Same arguments,
+ * layouts, validation and return codes as the fp32 entry points; every tensor stays fp32, only the two GEMM operands are
+ * rounded to bf16 (RNE, after the activation on load) and multiplied on v_mfma_f32_32x32x16_bf16 with fp32 accumulation.
+ * Their tile plan is their own: size workspaces, slope partials and slabs from the _bf16 queries.  VLG_CEPI_CIN4 is
+ * accepted and served by the general path over the 32 padded channels. */
+int vlg_conv3x3_fwd_bf16(const float* in, const float* w, const float* bias, float* out, const float* resid,
+                         const float* rowmask, const float* prelu_slope, const int* rowtab, int64_t rows_out,
+                         int cin_p, int cout, int cout_p, int wp_in, int act_ch, int epilogue, float* workspace,
+                         int64_t workspace_capacity, void* stream);
+int vlg_conv3x3_fwd_bf16_splits(int64_t rows_out, int cin_p, int cout, int cout_p);
+int64_t vlg_conv3x3_fwd_bf16_workspace(int64_t rows_out, int cin_p, int cout, int cout_p);
+int vlg_conv3x3_dgrad_bf16_slabs(int64_t rows_in, int cin_p);
+int vlg_conv3x3_dgrad_bf16(const float* dout, const float* w, float* din, const float* x_in,
+                           const float* rowmask_in, const float* prelu_slope, float* da_slab,
+                           const int* tap_tables, int64_t tab_stride, int64_t rows_in, int cin_p, int cout_p,
+                           int wp, int act_ch, int epilogue, float* workspace, int64_t workspace_capacity,
+                           int da_capacity, void* stream);
+int vlg_conv3x3_dgrad_bf16_splits(int64_t rows_in, int cin_p, int cout_p);
+int64_t vlg_conv3x3_dgrad_bf16_workspace(int64_t rows_in, int cin_p, int cout_p);
+int vlg_conv3x3_wgrad_bf16_slabs(int64_t rows, int cin_p, int cout_p);
+int vlg_conv3x3_wgrad_bf16(const float* dout, const float* in, float* slabs, int64_t slab_stride, int64_t slab_capacity,
+                           const int* rowtab, const float* prelu_slope, int64_t rows, int cin_p, int cout_p,
+                           int wp_in, int act_ch, void* stream);
 /* (b,C,H,W) <-> padded NHWC; to_padded can append AddCoords' two channels (modules.py:65-96) at c0, c0+1 */
 int vlg_nchw_to_padded(const float* src, float* dst, int b, int C, int H, int W, int cp, int coord_c0, void* stream);
 int vlg_padded_to_nchw(const float* src, float* dst, int b, int C, int H, int W, int cp, void* stream);

@@ -2,7 +2,8 @@
 """Development tool: per-shape throughput of vlg_conv3x3_{fwd,dgrad,wgrad} on the shapes the reference's step uses
 (GridNet rows 32/64/96 channels, VGG19[:27] / HED VGG16 trunks).  Algorithmic FLOP = 2 * pixels * cin * cout * 9.
 
-    python tools/conv_bench.py [batch] [size]"""
+    python tools/conv_bench.py [batch] [size]
+CONV_BENCH_PRECISION=bf16 times the bf16-MFMA twins (vlg_conv3x3_*_bf16, csrc/conv_bf16.hip) instead."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "video-layout-generation_amd")]
@@ -15,6 +16,8 @@ b = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 ONLY = [int(v) for v in sys.argv[3].split(",")] if len(sys.argv) > 3 else None      # indices into SHAPES
 NOACT = os.environ.get("CONV_BENCH_NOACT") == "1"                                   # no activation on load (slope pointer NULL)
+PREC = os.environ.get("CONV_BENCH_PRECISION", "fp32")                               # fp32 | bf16
+sym = lambda name: hip.conv_sym(name, PREC)
 dev = torch.device("cuda:0")
 lib = hip.load()
 ptr = lambda t: t.data_ptr()
@@ -38,7 +41,7 @@ def timeit(fn, n=10):
     return e0.elapsed_time(e1) / n * 1e-3
 
 
-print("b=%d  %-18s %10s %10s %10s   (TFLOP/s algorithmic; fp32 MFMA peak 157.3)" % (b, "HxW cin->cout", "fwd", "dgrad", "wgrad"))
+print("b=%d %s  %-18s %10s %10s %10s   (TFLOP/s algorithmic; MFMA peak fp32 157.3, bf16 2516)" % (b, PREC, "HxW cin->cout", "fwd", "dgrad", "wgrad"))
 for si, (hw, cin, cout) in enumerate(SHAPES):
     if ONLY is not None and si not in ONLY:
         continue
@@ -49,23 +52,23 @@ for si, (hw, cin, cout) in enumerate(SHAPES):
     w = torch.randn(y.cp * 9 * x.cp, device=dev) * 0.05
     bias = torch.zeros(y.cp, device=dev)
     zero = torch.zeros(1, device=dev)
-    n_slab = lib.vlg_conv3x3_wgrad_slabs(geo.rows, x.cp, y.cp)
+    n_slab = getattr(lib, sym("vlg_conv3x3_wgrad_slabs"))(geo.rows, x.cp, y.cp)
     slab_stride = y.cp * 9 * x.cp + y.cp
     slabs = torch.empty(n_slab * slab_stride, device=dev)
-    da = torch.zeros(lib.vlg_conv3x3_dgrad_slabs(geo.rows, x.cp) + 8, device=dev)
+    da = torch.zeros(getattr(lib, sym("vlg_conv3x3_dgrad_slabs"))(geo.rows, x.cp) + 8, device=dev)
     flop = 2.0 * b * hw * hw * cin * cout * 9
-    nsp = lib.vlg_conv3x3_fwd_splits(geo.rows, x.cp, cout, y.cp)
-    wsn = lib.vlg_conv3x3_fwd_workspace(geo.rows, x.cp, cout, y.cp)       # all tiles split (coarse levels) or the tail plan
+    nsp = getattr(lib, sym("vlg_conv3x3_fwd_splits"))(geo.rows, x.cp, cout, y.cp)
+    wsn = getattr(lib, sym("vlg_conv3x3_fwd_workspace"))(geo.rows, x.cp, cout, y.cp)       # all tiles split (coarse levels) or the tail plan
     ws = torch.empty(wsn, device=dev) if wsn else None
-    f = timeit(lambda: call("vlg_conv3x3_fwd", x.ptr, ptr(w), ptr(bias), y.ptr, 0, ptr(geo.mask), 0 if NOACT else ptr(zero), 0, geo.rows,
+    f = timeit(lambda: call(sym("vlg_conv3x3_fwd"), x.ptr, ptr(w), ptr(bias), y.ptr, 0, ptr(geo.mask), 0 if NOACT else ptr(zero), 0, geo.rows,
                             x.cp, cout, y.cp, geo.wp, x.cp, 0, hip.ptr(ws), ws.numel() if ws is not None else 0, stream))
-    dsp = lib.vlg_conv3x3_dgrad_splits(geo.rows, x.cp, y.cp)
-    dwsn = lib.vlg_conv3x3_dgrad_workspace(geo.rows, x.cp, y.cp)
+    dsp = getattr(lib, sym("vlg_conv3x3_dgrad_splits"))(geo.rows, x.cp, y.cp)
+    dwsn = getattr(lib, sym("vlg_conv3x3_dgrad_workspace"))(geo.rows, x.cp, y.cp)
     dws = torch.empty(dwsn, device=dev) if dwsn else None
     # da = NULL when a split path exists (frozen trunks ask for no slope gradient), else the GridNet form
-    d = timeit(lambda: call("vlg_conv3x3_dgrad", y.ptr, ptr(w), dx.ptr, x.ptr, ptr(geo.mask), ptr(zero), 0 if dwsn else ptr(da),
+    d = timeit(lambda: call(sym("vlg_conv3x3_dgrad"), y.ptr, ptr(w), dx.ptr, x.ptr, ptr(geo.mask), ptr(zero), 0 if dwsn else ptr(da),
                             0, 0, geo.rows, x.cp, y.cp, geo.wp, x.cp, 8, hip.ptr(dws), dws.numel() if dws is not None else 0, da.numel(), stream))
-    g = timeit(lambda: call("vlg_conv3x3_wgrad", y.ptr, x.ptr, ptr(slabs), slab_stride, slabs.numel(), 0, 0 if NOACT else ptr(zero), geo.rows, x.cp, y.cp,
+    g = timeit(lambda: call(sym("vlg_conv3x3_wgrad"), y.ptr, x.ptr, ptr(slabs), slab_stride, slabs.numel(), 0, 0 if NOACT else ptr(zero), geo.rows, x.cp, y.cp,
                             geo.wp, x.cp, stream))
     print("     %4dx%-4d %3d->%-3d %7.1f us %5.1f  %7.1f us %5.1f  %7.1f us %5.1f  (%d slabs%s)" % (
         hw, hw, cin, cout, f * 1e6, flop / f / 1e12, d * 1e6, flop / d / 1e12, g * 1e6, flop / g / 1e12, n_slab,

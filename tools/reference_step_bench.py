@@ -3,7 +3,8 @@
 40 L1 + 20 (VGG + GradientLoss + SSIM) + 10 CE + Adam, 256x256 frames) on one MI355X, next to its torch-CPU
 restatement on the host cores.  Algorithmic work per sample-step: GridNet 188.7 GFLOP fwd+bwd,
 HED 2 x 40.1 GFLOP (the third, tensorboard-only call of trainer.py:214-216 is not made), VGG19[:27] 2 x 46.1 fwd +
-~46 input-gradient.   python tools/reference_step_bench.py [batch] [cpu_batch]"""
+~46 input-gradient.   python tools/reference_step_bench.py [batch] [cpu_batch (0 = no CPU run)]
+REF_STEP_PRECISION=bf16 runs the convolutions on the bf16-MFMA kernels (ImageEngine precision="bf16")."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "video-layout-generation_amd")]
@@ -14,8 +15,9 @@ from vlg.image_engine import ImageEngine, synthetic_frames
 b = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 cb = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 H = W = 256
+prec = os.environ.get("REF_STEP_PRECISION", "fp32")
 dev = torch.device("cuda:0")
-eng = ImageEngine(b, H, W, dev, arch="CoordGridNet", with_hed=True, with_vgg=True)
+eng = ImageEngine(b, H, W, dev, arch="CoordGridNet", with_hed=True, with_vgg=True, precision=prec)
 p = G.test_params(G.param_shapes(10, coord=True), seed=0)
 hp, vp = HS.test_params(0), V.test_params(0)
 eng.load_state_dict(p); eng.hed.load_state_dict(hp); eng.vgg.load_state_dict(vp)
@@ -30,7 +32,9 @@ for _ in range(n):
 torch.cuda.synchronize()
 gpu = (time.perf_counter() - t0) / n
 gflop = b * (188.7 + 2 * 40.1 + 3 * 46.1)
-print("GPU  : b=%d  %.2f ms/step  %.1f samples/s  (%.1f TFLOP/s algorithmic over %.0f GFLOP/step)" % (b, gpu * 1e3, b / gpu, gflop / gpu / 1e3, gflop))
+print("GPU  : b=%d %s  %.2f ms/step  %.1f samples/s  (%.1f TFLOP/s algorithmic over %.0f GFLOP/step)" % (b, prec, gpu * 1e3, b / gpu, gflop / gpu / 1e3, gflop))
+if cb == 0:
+    sys.exit(0)
 torch.set_num_threads(min(len(os.sched_getaffinity(0)), 16))
 cpu_batch = synthetic_frames(cb, H, W, seed=1)
 with torch.no_grad():

@@ -17,49 +17,8 @@
 // (forward: A; weight gradient: B); its derivative and the slope gradient are fused into the data
 // gradient's epilogue.  The MFMA tile machinery (fragment layouts, LDS staging, mid-tile pipeline) is the
 // one of gemm.hip (gemm_tile.h).
-#include "gemm_tile.h"
+#include "conv_common.h"
 #include <type_traits>
-
-#define CONV_FWD 0
-#define CONV_DGRAD 1
-#define CONV_WGRAD 2
-
-struct ConvArgs {
-    const float* A; const float* B; float* C;
-    const float* bias; const float* aux_in; const float* rowmask; const float* prelu; float* da_slab;
-    const int* rowtab; int64_t tab_stride;
-    int64_t M;               // rows of C
-    int N;                   // cols of C that are stored
-    int64_t Kc;              // contraction extent
-    int lda, ldb, ldc;
-    int cin;                 // channels per tap of the gathered operand (multiple of 32)
-    int b_tap_stride;        // dgrad: column offset of one tap inside a weight row
-    int shift[9];
-    int wp, sign;            // shift[tap] = sign * ((tap / 3 - 1) * wp + tap % 3 - 1) (0 / 0 with per-tap row tables)
-    int tiles_m, tiles_n, splits;
-    int64_t kc_per_split, slab_stride, colsum_off;
-    int epi;
-    int act_ch;              // PReLU applies to channels < act_ch only (AddCoords channels stay linear)
-    // tail of the tile order cut along K ("data-parallel + split-K remainder"): the last tail_tiles tiles (whole row tiles)
-    // are computed by tail_splits blocks each, which store raw partial tiles to tail_ws[split][row - tail_row0][ldc];
-    // conv_finish_* sums them and applies the epilogue.  0 = every tile by one block.
-    int tail_tiles, tail_splits;
-    int64_t tail_kc, tail_row0, tail_stride;
-    float* tail_ws;
-    unsigned long long* probe;   // diagnostic build only (-DVLG_TIMELINE, tools/diag/conv_timeline.py)
-};
-
-__device__ __forceinline__ float prelu_f(float v, float a) { return v > 0.f ? v : a * v; }
-// branch-free and exact: max(v,0) + a*min(v,0) is v for v > 0 and the singly-rounded a*v otherwise; a = 1 is the identity,
-// a = 0 is ReLU.  med3 keeps the compiler from inserting NaN-canonicalising moves around max/min.
-__device__ __forceinline__ float act_f(float v, float a) {
-    return __builtin_fmaf(a, __builtin_amdgcn_fmed3f(v, -__builtin_inff(), 0.f), __builtin_amdgcn_fmed3f(v, 0.f, __builtin_inff()));
-}
-__device__ __forceinline__ float4 act4(float4 v, float4 a) { return make_float4(act_f(v.x, a.x), act_f(v.y, a.y), act_f(v.z, a.z), act_f(v.w, a.w)); }
-// slopes of channels c .. c+3: channels >= act_ch (the AddCoords pair, padding) stay linear
-__device__ __forceinline__ float4 slope4(float a, int c, int act_ch) {
-    return make_float4(c < act_ch ? a : 1.f, c + 1 < act_ch ? a : 1.f, c + 2 < act_ch ? a : 1.f, c + 3 < act_ch ? a : 1.f);
-}
 
 // PReLU of a staged operand (fast path): v > 0 ? v : a v  ==  a <= 1 ? max(v, a v) : min(v, a v)  ==  med3(v, a v, sel = +-inf),
 // bit for bit what the general path computes (one rounding, in a v)
@@ -851,12 +810,6 @@ static int launch_conv(ConvArgs g, hipStream_t s) {
     return vlg_last_error();
 }
 
-static void fill_shifts(ConvArgs& g, int wp, int sign) {
-    for (int ky = 0; ky < 3; ++ky)
-        for (int kx = 0; kx < 3; ++kx) g.shift[ky * 3 + kx] = sign * ((ky - 1) * wp + (kx - 1));
-    g.wp = wp; g.sign = sign;
-}
-
 // K-tile depth of the 32-channel tiles: 16, +2.7 % on CoordGridNet b=4 256x256 against 32 (more blocks per CU).
 // VLG_CONV_NARROW_BK=16|32 (diagnostic build) for A/B runs.
 static int conv_narrow_bk() { return VLG_TUNE("VLG_CONV_NARROW_BK", 16); }
@@ -871,8 +824,6 @@ static bool few_blocks(int64_t rows, int tiles_n) {
 }
 // 96 output channels as three 32-wide column tiles when there are too few row tiles to fill the chip
 static bool split_96(int64_t rows) { return (rows + 127) / 128 < 400; }
-
-static bool conv_ok(const void* p) { return p != nullptr && vlg_aligned16(p); }
 
 struct ConvTile { int bm, bn, bk; };
 
@@ -1090,9 +1041,6 @@ extern "C" int vlg_conv3x3_wgrad_slabs(int64_t rows, int cin_p, int cout_p) {
     return conv_query_plan(CONV_WGRAD, rows, cin_p, cout_p, cout_p).splits;
 }
 
-// the epilogue operands of a finish kernel over the whole output (forward: bias, residual, row mask; data gradient: x_in,
-// row mask, slope, act_ch, epilogue flags)
-struct ConvFinish { const float* bias; const float* aux; const float* rowmask; const float* prelu; float* out; int act_ch, epi; };
 static dim3 finish_grid(int64_t n4) { const int64_t b = (n4 + 255) / 256; return dim3((unsigned)(b > 2048 ? 2048 : b)); }
 
 // Launch a forward / data-gradient plan: the main kernel and, for a split-K or tail-split plan, the finish kernel over the
@@ -1115,11 +1063,16 @@ static int launch_conv_plan(const ConvPlan& p, ConvArgs g, float* ws, const Conv
     }
     if (int e = launch_conv_tile<MODE>(p.t, g, s)) return e;
     if (splits == 1) return 0;
+    return conv_launch_finish(MODE, ws, splits, stride, row0, g, f, s);
+}
+
+int conv_launch_finish(int mode, const float* ws, int splits, int64_t stride, int64_t row0, const ConvArgs& g,
+                       const ConvFinish& f, hipStream_t s) {
     const int64_t off = row0 * (int64_t)g.ldc, rows = g.M - row0;
     const dim3 grid = finish_grid(rows * (g.ldc / 4));
     const float* const aux = f.aux ? f.aux + off : nullptr;
     const float* const rowmask = f.rowmask ? f.rowmask + row0 : nullptr;
-    if constexpr (MODE == CONV_FWD)
+    if (mode == CONV_FWD)
         hipLaunchKernelGGL(conv_finish_kernel, grid, dim3(256), 0, s, ws, splits, stride, f.bias, aux, rowmask, f.out + off, rows, g.ldc / 4);
     else
         hipLaunchKernelGGL(conv_finish_dgrad_kernel, grid, dim3(256), 0, s, ws, splits, stride, aux, rowmask, f.prelu ? 1.0f : 0.0f,

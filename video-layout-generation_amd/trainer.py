@@ -13,7 +13,8 @@ reference's own step is a 2-D CNN that BASELINE.json does not ask for (SURVEY.md
 Shape knobs the reference CLI does not have are read with getattr/env defaults so main.py stays
 byte-for-byte unchanged:  VLG_FRAMES (T, 16), VLG_SLOTS (N, 64), VLG_DMODEL (d, 256),
 VLG_LAYERS (4), VLG_TRAIN_CLIPS (1024), VLG_VAL_CLIPS (256), VLG_VARIABLE_N (0), VLG_PRECISION (fp32 | fp32x3 | bf16 |
-bf16_mfma: projection arithmetic / activation storage, vlg/engine.py).
+bf16_mfma: projection arithmetic / activation storage, vlg/engine.py; with VLG_MODEL=gridnet bf16 / bf16_mfma run the 3x3
+convolutions on bf16-rounded operands, csrc/conv_bf16.hip).
 
 VLG_MODEL=gridnet switches the step to the reference's OWN model and losses (vlg/image_engine.py;
 VLG_WITH_HED / VLG_WITH_VGG = 1 add the frozen edge net and the VGG19 term, VLG_HED_CKPT / VLG_VGG_CKPT their weights;
@@ -173,8 +174,18 @@ class _ImageModel:
         with_hed = self.on_disk or bool(_knob(args, "with_hed", "VLG_WITH_HED", 0))
         with_vgg = bool(_knob(args, "with_vgg", "VLG_WITH_VGG", 0))
         self.keys = tuple(k for k in IMAGE_KEYS if not (with_hed and k in ("e1", "e2")))   # HED makes the edge maps itself
+        # VLG_PRECISION as for the layout step: bf16 (and bf16_mfma, the same thing here: every tensor is fp32 already) = the
+        # 3x3 convolutions on bf16-rounded operands (fp32 tensors, gradients and Adam state: checkpoints are interchangeable
+        # with fp32 runs); fp32x3 has no convolution form and runs fp32
+        precision = str(getattr(args, "precision", None) or os.environ.get("VLG_PRECISION", "fp32"))
+        if precision == "bf16_mfma":
+            precision = "bf16"
+        if precision == "fp32x3":
+            args.logger.warning("VLG_PRECISION=fp32x3 has no convolution form: the pixel model runs its convolutions in fp32")
+            precision = "fp32"
         self.engine = ImageEngine(batch, size, size, self.device, arch=arch, lr=float(getattr(args, "lr", ADAM_LR)),
-                                  beta1=float(getattr(args, "beta1", ADAM_BETA1)), with_hed=with_hed, with_vgg=with_vgg)
+                                  beta1=float(getattr(args, "beta1", ADAM_BETA1)), with_hed=with_hed, with_vgg=with_vgg,
+                                  precision=precision)
         for net, env in ((self.engine.hed, "VLG_HED_CKPT"), (self.engine.vgg, "VLG_VGG_CKPT")):
             if net is not None:
                 _load_frozen(net, env, args)

@@ -118,15 +118,19 @@ class GridNetHIP:
 
     def __init__(self, n_channels: int, batch: int, H: int, W: int, device, coord: bool = False,
                  filters=(32, 64, 96), seg_out: int = 20, img_out: int = 3, need_input_grad: bool = False,
-                 params_from: Optional["GridNetHIP"] = None):
+                 params_from: Optional["GridNetHIP"] = None, precision: str = "fp32"):
         """params_from: build a FORWARD-ONLY twin of another instance (other batch / image size) that reads that
-        instance's parameter buffer - the rollout and validation-time shapes share the training weights, no copy."""
+        instance's parameter buffer - the rollout and validation-time shapes share the training weights, no copy.
+        precision: "fp32" (vlg_conv3x3_*) or "bf16" (vlg_conv3x3_*_bf16: bf16-rounded GEMM operands, fp32 storage and
+        accumulation); parameters, gradients and workspaces are fp32 either way."""
         if H % 4 or W % 4:
             raise ValueError("H and W must be divisible by 4 (two stride-2 levels)")
         hip.load()
         if device.type != "cuda":
             raise hip.HipError("GridNetHIP needs a HIP device; there is no CPU path")
         self.device, self.coord, self.filters = device, coord, tuple(filters)
+        hip.conv_sym("vlg_conv3x3_fwd", precision)            # (validates the name)
+        self.precision = precision
         self.n_channels, self.seg_out, self.img_out = n_channels, seg_out, img_out
         self.need_input_grad = need_input_grad
         self.geo = [_Geo(batch, H >> l, W >> l, device) for l in range(3)]
@@ -171,7 +175,7 @@ class GridNetHIP:
         lib = hip.load()
         # workspace of the forward convolutions (tail split: tiles beyond the last full round of 256 CUs; split-K of wide
         # convolutions on small grids, csrc/conv.hip) - sized over EVERY convolution forward() hands it to
-        self.ws_n = max([lib.vlg_conv3x3_fwd_workspace(c.out.geo.rows, c.x.cp, c.cout, c.out.cp)
+        self.ws_n = max([getattr(lib, self._sym("vlg_conv3x3_fwd_workspace"))(c.out.geo.rows, c.x.cp, c.cout, c.out.cp)
                          for c in self.tape if isinstance(c, _Conv)] + [0])
         self.ws = torch.empty(self.ws_n, dtype=torch.float32, device=device) if self.ws_n else None
         self.forward_only = params_from is not None
@@ -183,11 +187,11 @@ class GridNetHIP:
         convs = [op for op in self.tape if isinstance(op, _Conv)]
         off = da_off = 0
         for c in convs:
-            c.n_slabs = lib.vlg_conv3x3_wgrad_slabs(c.out.geo.rows, c.x.cp, c.out.cp)
+            c.n_slabs = getattr(lib, self._sym("vlg_conv3x3_wgrad_slabs"))(c.out.geo.rows, c.x.cp, c.out.cp)
             c.slab_stride = c.out.cp * 9 * c.x.cp + c.out.cp
             c.slab_off = off
             off += (c.n_slabs * c.slab_stride + 3) // 4 * 4
-            c.da_n = lib.vlg_conv3x3_dgrad_slabs(c.x.geo.rows, c.x.cp) if c.prelu else 0
+            c.da_n = getattr(lib, self._sym("vlg_conv3x3_dgrad_slabs"))(c.x.geo.rows, c.x.cp) if c.prelu else 0
             c.da_off = da_off
             da_off += (c.da_n + 3) // 4 * 4
         self.slabs = torch.empty(off, dtype=torch.float32, device=device)
@@ -342,6 +346,9 @@ class GridNetHIP:
         return out
 
     # ------------------------------------------------------------------------------ forward
+    def _sym(self, name: str) -> str:
+        return hip.conv_sym(name, self.precision)
+
     @staticmethod
     def _stream() -> int:
         return torch.cuda.current_stream().cuda_stream
@@ -360,7 +367,7 @@ class GridNetHIP:
             if isinstance(op, _Conv):
                 gx, go = op.x.geo, op.out.geo
                 rowtab = ptr(gx.down_rowtab) if op.stride == 2 else 0
-                call("vlg_conv3x3_fwd", op.x.ptr, self._pp(op.w_off), self._pp(op.b_off), op.out.ptr,
+                call(self._sym("vlg_conv3x3_fwd"), op.x.ptr, self._pp(op.w_off), self._pp(op.b_off), op.out.ptr,
                      op.resid.ptr if op.resid is not None else 0, ptr(go.mask),
                      self._pp(self.p_off[op.prelu]) if op.prelu else 0, rowtab, go.rows, op.x.cp, op.cout, op.out.cp,
                      gx.wp, op.act_ch, CEPI_RESID if op.resid is not None else 0, ptr(self.ws), self.ws_n, s)
@@ -413,7 +420,7 @@ class GridNetHIP:
                     raise RuntimeError("no gradient reached the output of %s" % op.key)
                 slope = self._pp(self.p_off[op.prelu]) if op.prelu else 0
                 # weight + bias gradient
-                call("vlg_conv3x3_wgrad", dout.ptr, op.x.ptr, self.slabs.data_ptr() + 4 * op.slab_off, op.slab_stride,
+                call(self._sym("vlg_conv3x3_wgrad"), dout.ptr, op.x.ptr, self.slabs.data_ptr() + 4 * op.slab_off, op.slab_stride,
                      self.slabs.numel() - op.slab_off,
                      ptr(gx.down_rowtab) if op.stride == 2 else 0, slope, go.rows, op.x.cp, op.out.cp, gx.wp, op.act_ch, s)
                 # data gradient (skipped for the network input unless asked for)
@@ -421,7 +428,7 @@ class GridNetHIP:
                     gin = self._grad_of(op.x)
                     epi = (CEPI_ACCUM if op.x.grad_written else 0) | (CEPI_DPRELU if op.prelu else 0)
                     taps = ptr(gx.down_taptabs) if op.stride == 2 else 0
-                    call("vlg_conv3x3_dgrad", dout.ptr, self._pp(op.w_off), gin.ptr, op.x.ptr, ptr(gx.mask), slope,
+                    call(self._sym("vlg_conv3x3_dgrad"), dout.ptr, self._pp(op.w_off), gin.ptr, op.x.ptr, ptr(gx.mask), slope,
                          self.da_part.data_ptr() + 4 * op.da_off if op.prelu else 0, taps, gx.rows if op.stride == 2 else 0, gx.rows, op.x.cp,
                          op.out.cp, gx.wp, op.act_ch, epi, 0, 0, op.da_n, s)
                     op.x.grad_written = True

@@ -72,6 +72,15 @@ SIGNATURES = {
     "vlg_conv3x3_dgrad_workspace": (L, [L, I, I]),
     "vlg_conv3x3_wgrad_slabs": (I, [L, I, I]),
     "vlg_conv3x3_wgrad": (I, [P, P, P, L, L, P, P, L, I, I, I, I, P]),
+    "vlg_conv3x3_fwd_bf16": (I, [P, P, P, P, P, P, P, P, L, I, I, I, I, I, I, P, L, P]),
+    "vlg_conv3x3_fwd_bf16_splits": (I, [L, I, I, I]),
+    "vlg_conv3x3_fwd_bf16_workspace": (L, [L, I, I, I]),
+    "vlg_conv3x3_dgrad_bf16_slabs": (I, [L, I]),
+    "vlg_conv3x3_dgrad_bf16": (I, [P, P, P, P, P, P, P, P, L, L, I, I, I, I, I, P, L, I, P]),
+    "vlg_conv3x3_dgrad_bf16_splits": (I, [L, I, I]),
+    "vlg_conv3x3_dgrad_bf16_workspace": (L, [L, I, I]),
+    "vlg_conv3x3_wgrad_bf16_slabs": (I, [L, I, I]),
+    "vlg_conv3x3_wgrad_bf16": (I, [P, P, P, L, L, P, P, L, I, I, I, I, P]),
     "vlg_nchw_to_padded": (I, [P, P, I, I, I, I, I, I, P]),
     "vlg_padded_to_nchw": (I, [P, P, I, I, I, I, I, P]),
     "vlg_fill_coords": (I, [P, I, I, I, I, I, P]),
@@ -93,6 +102,19 @@ DIAG_SIGNATURES = {
     "vlg_debug_set_gemm_run": (None, [I]),
 }
 CEPI_BIAS, CEPI_RESID, CEPI_PRELU, CEPI_DPRELU, CEPI_ACCUM, CEPI_CIN4 = 1, 2, 4, 8, 16, 32
+CONV_PRECISIONS = ("fp32", "bf16")     # 3x3 convolutions: fp32 MFMA (conv.hip) or bf16-operand MFMA (conv_bf16.hip)
+
+
+def conv_sym(name: str, precision: str) -> str:
+    """Entry point / planner query of a 3x3 convolution in `precision`: vlg_conv3x3_fwd -> vlg_conv3x3_fwd_bf16,
+    vlg_conv3x3_fwd_workspace -> vlg_conv3x3_fwd_bf16_workspace."""
+    if precision not in CONV_PRECISIONS:
+        raise ValueError("conv precision must be one of %s, not %r" % (CONV_PRECISIONS, precision))
+    if precision == "fp32":
+        return name
+    op = name.split("_")[2]                     # fwd | dgrad | wgrad
+    pre = "vlg_conv3x3_" + op
+    return pre + "_bf16" + name[len(pre):]
 
 _lib = None
 

@@ -29,14 +29,17 @@ BGR_MEAN = (104.00698793, 116.66876762, 122.67891434)      # hned.py:74-76 (appl
 
 
 class HNEDHIP:
-    def __init__(self, batch: int, H: int, W: int, device, params_from: "HNEDHIP" = None):
-        """params_from: twin for another batch / image size reading that instance's weights (no copy)."""
+    def __init__(self, batch: int, H: int, W: int, device, params_from: "HNEDHIP" = None, precision: str = "fp32"):
+        """params_from: twin for another batch / image size reading that instance's weights (no copy).
+        precision: "fp32" or "bf16" 3x3 convolutions (vlg.hip.conv_sym)."""
         if H % 16 or W % 16:
             raise ValueError("H and W must be divisible by 16 (four 2x2 max-pools)")
         hip.load()
         if device.type != "cuda":
             raise hip.HipError("HNEDHIP needs a HIP device; there is no CPU path")
         self.device, self.b, self.H, self.W = device, batch, H, W
+        self.fwd = hip.conv_sym("vlg_conv3x3_fwd", precision)
+        self.precision = precision
         self.geo = [_Geo(batch, H >> k, W >> k, device) for k in range(5)]
         self.pre = torch.empty(batch, 3, H, W, dtype=torch.float32, device=device)
         self.x = _PT(self.geo[0], 3, device)
@@ -77,7 +80,7 @@ class HNEDHIP:
         self.score = [torch.empty(batch, H >> k, W >> k, dtype=torch.float32, device=device) for k in range(5)]
         # split-K workspace (coarse levels: every tile; elsewhere the tiles beyond the last full round of 256 - csrc/conv.hip)
         lib = hip.load()
-        need = max([lib.vlg_conv3x3_fwd_workspace(tout.geo.rows, tin.cp, cout, tout.cp) for _, tin, tout, _, cout, _, _ in self.convs] + [0])
+        need = max([getattr(lib, hip.conv_sym("vlg_conv3x3_fwd_workspace", precision))(tout.geo.rows, tin.cp, cout, tout.cp) for _, tin, tout, _, cout, _, _ in self.convs] + [0])
         self.ws = torch.empty(need, dtype=torch.float32, device=device) if need else None
         self.ws_n = need
         arr = ctypes.c_float * 3
@@ -129,7 +132,7 @@ class HNEDHIP:
                 call("vlg_maxpool2x2", src.ptr, dst.ptr, b, dst.geo.H, dst.geo.W, src.cp, s)
                 done_pool.add(si)
             g = tout.geo
-            call("vlg_conv3x3_fwd", tin.ptr, self._pp(key + ".weight"), self._pp(key + ".bias"), tout.ptr, 0, ptr(g.mask),
+            call(self.fwd, tin.ptr, self._pp(key + ".weight"), self._pp(key + ".bias"), tout.ptr, 0, ptr(g.mask),
                  self._pp("_zero") if relu else 0, 0, g.rows, tin.cp, cout, tout.cp, g.wp, tin.cp,
                  CEPI_CIN4 if (cin <= 4 and not relu) else 0, ptr(self.ws), self.ws_n, s)
         for k, (name, f) in enumerate(zip(SCORES, self.feats)):

@@ -36,20 +36,24 @@ W_L1, W_STYLE, W_CE = 40.0, 20.0, 10.0          # reference src/trainer.py:248-2
 
 class ImageEngine:
     def __init__(self, batch: int, H: int, W: int, device, arch: str = "CoordGridNet", lr: float = ADAM_LR,
-                 beta1: float = ADAM_BETA1, filters=(32, 64, 96), with_hed: bool = False, with_vgg: bool = False):
+                 beta1: float = ADAM_BETA1, filters=(32, 64, 96), with_hed: bool = False, with_vgg: bool = False,
+                 precision: str = "fp32"):
+        """precision: "fp32" (the reference's) or "bf16" - the 3x3 convolutions of GridNet, HED and VGG on bf16-rounded
+        GEMM operands with fp32 accumulation (csrc/conv_bf16.hip); tensors, losses, gradients and Adam stay fp32."""
         if arch not in ("GridNet", "CoordGridNet"):
             raise ValueError("arch must be GridNet or CoordGridNet (reference src/main.py:101-102)")
         self.device, self.lr, self.beta1 = device, float(lr), float(beta1)
         self.b, self.H, self.W = batch, H, W
-        self.net = GridNetHIP(10, batch, H, W, device, coord=(arch == "CoordGridNet"), filters=filters)
+        self.precision = precision
+        self.net = GridNetHIP(10, batch, H, W, device, coord=(arch == "CoordGridNet"), filters=filters, precision=precision)
         self.vgg = None
         if with_vgg:
             from .vgg_loss import VggLossHIP
-            self.vgg = VggLossHIP(batch, H, W, device)
+            self.vgg = VggLossHIP(batch, H, W, device, precision=precision)
         self.hed = None
         if with_hed:
             from .hned import HNEDHIP
-            self.hed = HNEDHIP(batch, H, W, device)
+            self.hed = HNEDHIP(batch, H, W, device, precision=precision)
         n = self.net.params.numel()
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=device)
         self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=device)
@@ -212,8 +216,9 @@ class FrameRollout:
         from .hned import HNEDHIP
         self.device, self.b, self.H, self.W = engine.device, batch, H, W
         src = engine.net
-        self.net = GridNetHIP(10, batch, H, W, self.device, coord=src.coord, filters=src.filters, params_from=src)
-        self.hed = HNEDHIP(batch, H, W, self.device, params_from=hed)
+        self.net = GridNetHIP(10, batch, H, W, self.device, coord=src.coord, filters=src.filters, params_from=src,
+                              precision=src.precision)
+        self.hed = HNEDHIP(batch, H, W, self.device, params_from=hed, precision=src.precision)
         arr = ctypes.c_float * 3
         self._mean, self._istd = arr(*OUT_MEAN), arr(*[1.0 / s for s in OUT_STD])
         # frame in [0,1] = img * img_std + img_mean  (trainer.py:215) as (img - shift) * scale

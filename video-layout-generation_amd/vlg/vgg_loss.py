@@ -40,13 +40,16 @@ def conv_keys():
 
 
 class VggLossHIP:
-    def __init__(self, batch: int, H: int, W: int, device):
+    def __init__(self, batch: int, H: int, W: int, device, precision: str = "fp32"):
+        """precision: "fp32" or "bf16" 3x3 convolutions (vlg.hip.conv_sym); the features and gradients stay fp32."""
         if H % 8 or W % 8:
             raise ValueError("H and W must be divisible by 8 (three 2x2 max-pools)")
         hip.load()
         if device.type != "cuda":
             raise hip.HipError("VggLossHIP needs a HIP device; there is no CPU path")
         self.device, self.b, self.H, self.W = device, batch, H, W
+        self.fwd, self.dgrad = hip.conv_sym("vlg_conv3x3_fwd", precision), hip.conv_sym("vlg_conv3x3_dgrad", precision)
+        self.precision = precision
         self.geo = [_Geo(batch, H >> k, W >> k, device) for k in range(4)]
         self.x = _PT(self.geo[0], 3, device)
         self.ops: List[tuple] = []            # ("conv", key, tin, tout, cin, cout, relu_on_load) | ("pool", tin, tout)
@@ -86,8 +89,10 @@ class VggLossHIP:
         self.loss = torch.zeros(1, dtype=torch.float32, device=device)
         # split-K workspace (coarse levels: every tile; elsewhere the tiles beyond the last full round of 256 - csrc/conv.hip)
         lib = hip.load()
-        need = max([lib.vlg_conv3x3_fwd_workspace(op[3].geo.rows, op[2].cp, op[5], op[3].cp) for op in self.ops if op[0] == "conv"] +
-                   [lib.vlg_conv3x3_dgrad_workspace(op[2].geo.rows, op[2].cp, op[3].cp) for op in self.ops if op[0] == "conv"] + [0])
+        fwd_ws = getattr(lib, hip.conv_sym("vlg_conv3x3_fwd_workspace", precision))
+        dgrad_ws = getattr(lib, hip.conv_sym("vlg_conv3x3_dgrad_workspace", precision))
+        need = max([fwd_ws(op[3].geo.rows, op[2].cp, op[5], op[3].cp) for op in self.ops if op[0] == "conv"] +
+                   [dgrad_ws(op[2].geo.rows, op[2].cp, op[3].cp) for op in self.ops if op[0] == "conv"] + [0])
         self.ws = torch.empty(need, dtype=torch.float32, device=device) if need else None
         self.ws_n = need
 
@@ -129,7 +134,7 @@ class VggLossHIP:
                 _, key, tin, tout, ci, co, relu = op
                 g = tout.geo
                 # (the image layer: 3 channels in a 32-channel padded tensor - contraction over (tap, 4 channels))
-                call("vlg_conv3x3_fwd", tin.ptr, self._pp(key + ".weight"), self._pp(key + ".bias"), tout.ptr, 0, ptr(g.mask),
+                call(self.fwd, tin.ptr, self._pp(key + ".weight"), self._pp(key + ".bias"), tout.ptr, 0, ptr(g.mask),
                      self._pp("_zero") if relu else 0, 0, g.rows, tin.cp, co, tout.cp, g.wp, tin.cp,
                      CEPI_CIN4 if (ci <= 4 and not relu) else 0, ptr(self.ws), self.ws_n, s)
 
@@ -172,7 +177,7 @@ class VggLossHIP:
             else:
                 _, key, tin, tout, ci, co, relu = op
                 g = tin.geo
-                call("vlg_conv3x3_dgrad", tout.grad.ptr, self._pp(key + ".weight"), tin.grad.ptr, tin.ptr, ptr(g.mask),
+                call(self.dgrad, tout.grad.ptr, self._pp(key + ".weight"), tin.grad.ptr, tin.ptr, ptr(g.mask),
                      self._pp("_zero") if relu else 0, 0, 0, 0, g.rows, tin.cp, tout.cp, g.wp, tin.cp,
                      CEPI_DPRELU if relu else 0, ptr(self.ws), self.ws_n, 0, s)
         dimg = torch.empty(b, 3, H, W, dtype=torch.float32, device=self.device)
