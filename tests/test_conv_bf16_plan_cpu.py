@@ -1,4 +1,4 @@
-"""CPU: the planner queries of the bf16-MFMA convolutions (vlg_conv3x3_*_bf16_*, csrc/conv_bf16.hip) are host code -
+"""CPU: the planner queries of the bf16-MFMA convolutions (vlg_conv3x3_*_bf16_*, csrc/conv.hip) are host code -
 callable without a GPU - and the entry points check the capacities the caller passes against exactly those queries,
 refusing one float (one partial, one slab) less with VLG_ERR_SHAPE before anything is launched.  (That the queried
 amounts themselves are accepted is a launch: tests/test_hip_conv_bf16.py.)"""

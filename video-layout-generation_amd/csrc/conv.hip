@@ -810,6 +810,10 @@ static int launch_conv(ConvArgs g, hipStream_t s) {
     return vlg_last_error();
 }
 
+// ---- host side of both precisions: the tile and split policies, the one planner, the finish and plan launchers and the
+// entry points.  The bf16 kernel and its launcher are in conv_bf16.hip.
+enum { CONV_FP32, CONV_BF16 };                                // precision of the GEMM operands
+
 // K-tile depth of the 32-channel tiles: 16, +2.7 % on CoordGridNet b=4 256x256 against 32 (more blocks per CU).
 // VLG_CONV_NARROW_BK=16|32 (diagnostic build) for A/B runs.
 static int conv_narrow_bk() { return VLG_TUNE("VLG_CONV_NARROW_BK", 16); }
@@ -884,6 +888,13 @@ static ConvTile conv_tile(int64_t rows, int n_cols, int n_valid, int64_t kc = 0)
     const bool small = few_blocks(rows, tiles_n);
     return ConvTile{small ? 64 : 128, bn, 32};
 }
+// bf16 forward / data-gradient tile: N = n_cols (cout_p, or cin_p), rows of 128 (64 when 128-row tiles would leave the chip
+// idle; no 64 x 96 wave layout)
+static ConvTile bf16_tile(int64_t rows, int n_cols) {
+    const int bn = n_cols == 32 ? 32 : n_cols == 64 ? 64 : n_cols == 96 ? 96 : 128;
+    const int64_t t128 = ((rows + 127) / 128) * ((n_cols + bn - 1) / bn);
+    return ConvTile{bn != 96 && bn >= 64 && t128 < 512 ? 64 : 128, bn, 32};
+}
 template <int MODE>
 static int launch_conv_tile(const ConvTile t, const ConvArgs& g, hipStream_t s) {
     if (t.bn == 32) return t.bk == 16 ? launch_conv<MODE, 128, 32, 16>(g, s) : launch_conv<MODE, 128, 32>(g, s);
@@ -892,14 +903,17 @@ static int launch_conv_tile(const ConvTile t, const ConvArgs& g, hipStream_t s) 
     return t.bm == 64 ? launch_conv<MODE, 64, 128>(g, s) : launch_conv<MODE, 128, 128>(g, s);
 }
 
-// Split-K forward for the coarse levels of the VGG / HED trunks (4 x 32 x 32 or 16 x 16 pixels, 256-512 channels): the
+// Split-K for the coarse levels of the VGG / HED trunks (4 x 32 x 32 or 16 x 16 pixels, 256-512 channels): the
 // plain launch has 44-148 blocks for 256 CUs while K = 9*cin is 2304-4608, so the contraction is cut into `splits`
 // ranges, every range writes a raw partial tile to the caller's workspace and conv_finish_kernel sums them and applies
-// the epilogue (bias, residual, row mask).  Partial sums are added in a fixed order: reproducible.
-static int conv_fwd_splits(int64_t rows_out, int cin_p, int cout, int cout_p) {
+// the epilogue (bias, residual, row mask).  Partial sums are added in a fixed order: reproducible.  Up to 8 ranges of at
+// least 8 K tiles, ~512 blocks.  fp32 splits launches of fewer than 200 128 x 128 tiles (splitting 200-400 block launches
+// in two was measured: no gain); bf16 fewer than 256, and only whole 128-column tiles.
+static int conv_splits(int prec, int64_t rows_out, int cin_p, int cout, int cout_p) {
     if (cout_p < 128 || cout != cout_p || cin_p < 128) return 1;
+    if (prec == CONV_BF16 && (cout_p & 127)) return 1;
     const int64_t b128 = ((rows_out + 127) / 128) * ((cout_p + 127) / 128);
-    if (b128 >= 200) return 1;                                 // (splitting 200-400 block launches in two was measured: no gain)
+    if (b128 >= (prec == CONV_BF16 ? 256 : 200)) return 1;
     int s = (int)(512 / b128);
     if (s > 8) s = 8;
     const int ktiles = 9 * cin_p / 32;
@@ -952,18 +966,20 @@ __global__ __launch_bounds__(256) void conv_finish_dgrad_kernel(const float* __r
     }
 }
 
-// row-tile height of the weight gradient: all of Cout for the GridNet widths (one pass over the gathered activation
-// tile serves every output channel), 32-row tiles otherwise.  VLG_CONV_WGRAD_TALL=0 (diagnostic build) forces 32.
-static int conv_wgrad_bm(int cout_p) {
+// row-tile height of the weight gradient.  fp32: all of Cout for the GridNet widths (one pass over the gathered activation
+// tile serves every output channel), 32-row tiles otherwise; VLG_CONV_WGRAD_TALL=0 (diagnostic build) forces 32.
+// bf16: 128 where cout_p is a multiple of 128, else 96, 64 or 32.
+static int conv_wgrad_bm(int prec, int cout_p) {
+    if (prec == CONV_BF16) return (cout_p & 127) == 0 ? 128 : cout_p == 96 ? 96 : (cout_p & 63) == 0 ? 64 : 32;
     return (VLG_TUNE("VLG_CONV_WGRAD_TALL", 1) != 0 && (cout_p == 64 || cout_p == 96)) ? cout_p : 32;
 }
 
-// The ONE plan of a conv launch and of its queries, from the call's arguments: the tile, the K ranges of every tile
-// (split-K) or of the tail tiles only (tail split), the workspace floats that needs, and the slope-gradient partials
-// (one per block of a data-gradient launch with da_slab).  ws: whether a workspace was given and whether it is
-// 16-byte aligned (the tail split needs it; the split-K launch rejects a misaligned one), ws_cap its floats (the tail
-// split is taken only if it fits), has the HAS_* operands the call passes.  The queries ask for an aligned workspace of
-// any size and pass no optional operand.
+// The ONE plan of a conv launch and of its queries, in either precision, from the call's arguments: the tile, the K ranges
+// of every tile (split-K) or of the tail tiles only (tail split, fp32 only), the workspace floats that needs, and the
+// slope-gradient partials (one per block of a data-gradient launch with da_slab).  ws: whether a workspace was given and
+// whether it is 16-byte aligned (the tail split needs it; the split-K launch rejects a misaligned one), ws_cap its floats
+// (the tail split is taken only if it fits), has the HAS_* operands the call passes.  The queries ask for an aligned
+// workspace of any size and pass no optional operand.
 enum { WS_NONE, WS_MISALIGNED, WS_ALIGNED };
 enum { HAS_TABLES = 1, HAS_DA_SLAB = 2, HAS_PRELU = 4 };     // row tables, slope-gradient buffer, PReLU epilogue
 static int ws_kind(const float* ws) { return ws == nullptr ? WS_NONE : vlg_aligned16(ws) ? WS_ALIGNED : WS_MISALIGNED; }
@@ -974,13 +990,13 @@ struct ConvPlan {
     int64_t ws_floats;
     int slopes;
 };
-static ConvPlan conv_plan(int mode, int64_t rows, int cin_p, int cout, int cout_p, int ws, int64_t ws_cap, int has) {
+static ConvPlan conv_plan(int prec, int mode, int64_t rows, int cin_p, int cout, int cout_p, int ws, int64_t ws_cap, int has) {
     const bool tables = (has & HAS_TABLES) != 0, da_slab = (has & HAS_DA_SLAB) != 0, prelu = (has & HAS_PRELU) != 0;
     ConvPlan p{};
     p.splits = 1;
     p.tail = ConvTail{0, 1, 0, 0, 0};
     if (mode == CONV_WGRAD) {                                  // K = rows: ranges of whole 32-row tiles, ~512 blocks
-        p.t = ConvTile{conv_wgrad_bm(cout_p), 128, 32};
+        p.t = ConvTile{conv_wgrad_bm(prec, cout_p), 128, 32};
         const int64_t tiles = (cout_p / p.t.bm) * (int64_t)((9 * cin_p + 127) / 128);
         int64_t want = 512 / tiles;
         const int64_t max_splits = (rows + 255) / 256;
@@ -998,12 +1014,14 @@ static ConvPlan conv_plan(int mode, int64_t rows, int cin_p, int cout, int cout_
     p.kc_per_split = kc;
     // split-K: the data gradient only for frozen trunks (no slope gradient wanted), stride 1
     const bool split_ok = ws != WS_NONE && (mode == CONV_FWD || (!da_slab && !tables));
-    const int splits = !split_ok ? 1 : mode == CONV_FWD ? conv_fwd_splits(rows, cin_p, cout, cout_p) : conv_fwd_splits(rows, cout_p, cin_p, cin_p);
+    const int splits = !split_ok ? 1 : mode == CONV_FWD ? conv_splits(prec, rows, cin_p, cout, cout_p) : conv_splits(prec, rows, cout_p, cin_p, cin_p);
     if (splits > 1) {
         p.t = ConvTile{128, 128, 32};
         p.splits = splits;
         p.kc_per_split = (int64_t)((kc / 32 + splits - 1) / splits) * 32;
         p.ws_floats = (int64_t)splits * rows * n_cols;
+    } else if (prec == CONV_BF16) {
+        p.t = bf16_tile(rows, n_cols);                         // (no tail split)
     } else {
         const bool tail_ok = ws == WS_ALIGNED && !tables && !da_slab && !prelu;
         p.t = conv_tile(rows, n_cols, n_valid, tail_ok ? kc : 0);
@@ -1015,38 +1033,53 @@ static ConvPlan conv_plan(int mode, int64_t rows, int cin_p, int cout, int cout_
     p.slopes = (int)((rows + p.t.bm - 1) / p.t.bm) * ((n_cols + p.t.bn - 1) / p.t.bn);
     return p;
 }
-static ConvPlan conv_query_plan(int mode, int64_t rows, int cin_p, int cout, int cout_p) {
-    return conv_plan(mode, rows, cin_p, cout, cout_p, WS_ALIGNED, INT64_MAX, 0);
+static ConvPlan conv_query_plan(int prec, int mode, int64_t rows, int cin_p, int cout, int cout_p) {
+    return conv_plan(prec, mode, rows, cin_p, cout, cout_p, WS_ALIGNED, INT64_MAX, 0);
 }
-
-extern "C" int vlg_conv3x3_fwd_splits(int64_t rows_out, int cin_p, int cout, int cout_p) {
-    return conv_query_plan(CONV_FWD, rows_out, cin_p, cout, cout_p).splits;
+static int64_t conv_query_workspace(int prec, int mode, int64_t rows, int cin_p, int cout, int cout_p) {
+    if (rows < 1 || cin_p < 32 || cout_p < 32) return 0;
+    return conv_query_plan(prec, mode, rows, cin_p, cout, cout_p).ws_floats;
 }
-extern "C" int64_t vlg_conv3x3_fwd_workspace(int64_t rows_out, int cin_p, int cout, int cout_p) {
-    if (rows_out < 1 || cin_p < 32 || cout_p < 32) return 0;
-    return conv_query_plan(CONV_FWD, rows_out, cin_p, cout, cout_p).ws_floats;
-}
-extern "C" int vlg_conv3x3_dgrad_splits(int64_t rows_in, int cin_p, int cout_p) {
-    return conv_query_plan(CONV_DGRAD, rows_in, cin_p, cin_p, cout_p).splits;
-}
-extern "C" int64_t vlg_conv3x3_dgrad_workspace(int64_t rows_in, int cin_p, int cout_p) {
-    if (rows_in < 1 || cin_p < 32 || cout_p < 32) return 0;
-    return conv_query_plan(CONV_DGRAD, rows_in, cin_p, cin_p, cout_p).ws_floats;
-}
-extern "C" int vlg_conv3x3_dgrad_slabs(int64_t rows_in, int cin_p) {
-    // (with da_slab there is no split of any kind, and the tile does not depend on cout_p)
-    return conv_plan(CONV_DGRAD, rows_in, cin_p, cin_p, cin_p, WS_NONE, 0, HAS_DA_SLAB).slopes;
-}
-extern "C" int vlg_conv3x3_wgrad_slabs(int64_t rows, int cin_p, int cout_p) {
-    return conv_query_plan(CONV_WGRAD, rows, cin_p, cout_p, cout_p).splits;
+// (with da_slab there is no split of any kind, and the tile does not depend on cout_p)
+static int conv_query_slopes(int prec, int64_t rows_in, int cin_p) {
+    return conv_plan(prec, CONV_DGRAD, rows_in, cin_p, cin_p, cin_p, WS_NONE, 0, HAS_DA_SLAB).slopes;
 }
 
 static dim3 finish_grid(int64_t n4) { const int64_t b = (n4 + 255) / 256; return dim3((unsigned)(b > 2048 ? 2048 : b)); }
 
+// Sum `splits` raw partial outputs (slab s at ws + s * stride, rows row0 .. g.M - 1 of the output) and apply the epilogue of
+// the call's arguments g (forward: bias, residual, row mask; data gradient: x_in, row mask, slope, act_ch, epilogue flags)
+// with conv_finish_kernel (CONV_FWD) or conv_finish_dgrad_kernel (CONV_DGRAD).
+static int conv_launch_finish(int mode, const float* ws, int splits, int64_t stride, int64_t row0, const ConvArgs& g, hipStream_t s) {
+    const int64_t off = row0 * (int64_t)g.ldc, rows = g.M - row0;
+    const dim3 grid = finish_grid(rows * (g.ldc / 4));
+    const float* const x = mode == CONV_FWD && !(g.epi & VLG_CEPI_RESID) ? nullptr : g.aux_in;     // residual / x_in
+    const float* const aux = x ? x + off : nullptr;
+    const float* const rowmask = g.rowmask ? g.rowmask + row0 : nullptr;
+    if (mode == CONV_FWD)
+        hipLaunchKernelGGL(conv_finish_kernel, grid, dim3(256), 0, s, ws, splits, stride, g.bias, aux, rowmask, g.C + off, rows, g.ldc / 4);
+    else
+        hipLaunchKernelGGL(conv_finish_dgrad_kernel, grid, dim3(256), 0, s, ws, splits, stride, aux, rowmask, g.prelu ? 1.0f : 0.0f,
+                           g.prelu, g.C + off, rows, g.ldc / 4, g.act_ch, g.epi);
+    return vlg_last_error();
+}
+
+// the main kernel of a plan's tile: fp32 here, bf16 in conv_bf16.hip
+static int launch_tile(int prec, int mode, const ConvTile t, const ConvArgs& g, hipStream_t s) {
+    if (prec == CONV_BF16) return conv_bf16_launch(mode, t.bm, t.bn, g, s);
+    if (mode == CONV_FWD) return launch_conv_tile<CONV_FWD>(t, g, s);
+    if (mode == CONV_DGRAD) return launch_conv_tile<CONV_DGRAD>(t, g, s);
+    switch (t.bm) {
+        case 64: return launch_conv<CONV_WGRAD, 64, 128>(g, s);
+        case 96: return launch_conv<CONV_WGRAD, 96, 128>(g, s);
+        default: return launch_conv<CONV_WGRAD, 32, 128>(g, s);
+    }
+}
+
 // Launch a forward / data-gradient plan: the main kernel and, for a split-K or tail-split plan, the finish kernel over the
 // rows the partial tiles cover (all of them, or those from the tail's first row on).
-template <int MODE>
-static int launch_conv_plan(const ConvPlan& p, ConvArgs g, float* ws, const ConvFinish& f, hipStream_t s) {
+static int launch_conv_plan(int prec, int mode, const ConvPlan& p, const ConvArgs& call, float* ws, hipStream_t s) {
+    ConvArgs g = call;
     int splits = 1;
     int64_t row0 = 0, stride = 0;
     if (p.splits > 1) {
@@ -1054,39 +1087,53 @@ static int launch_conv_plan(const ConvPlan& p, ConvArgs g, float* ws, const Conv
         g.kc_per_split = p.kc_per_split;
         stride = g.slab_stride = g.M * (int64_t)g.ldc;
         g.C = ws; g.bias = nullptr; g.aux_in = nullptr; g.rowmask = nullptr; g.epi = 0;    // raw partial tiles
-        if (MODE == CONV_DGRAD) g.act_ch = g.N;                // (the finish kernel cuts the constant channels)
+        if (mode == CONV_DGRAD) g.act_ch = g.N;                // (the finish kernel cuts the constant channels)
     } else if (p.tail.tiles > 0) {
         splits = p.tail.splits;
         row0 = p.tail.row0;
         g.tail_tiles = p.tail.tiles; g.tail_splits = p.tail.splits; g.tail_kc = p.tail.kc; g.tail_row0 = row0;
         stride = g.tail_stride = (g.M - row0) * (int64_t)g.ldc; g.tail_ws = ws;
     }
-    if (int e = launch_conv_tile<MODE>(p.t, g, s)) return e;
+    if (int e = launch_tile(prec, mode, p.t, g, s)) return e;
     if (splits == 1) return 0;
-    return conv_launch_finish(MODE, ws, splits, stride, row0, g, f, s);
+    return conv_launch_finish(mode, ws, splits, stride, row0, call, s);
 }
 
-int conv_launch_finish(int mode, const float* ws, int splits, int64_t stride, int64_t row0, const ConvArgs& g,
-                       const ConvFinish& f, hipStream_t s) {
-    const int64_t off = row0 * (int64_t)g.ldc, rows = g.M - row0;
-    const dim3 grid = finish_grid(rows * (g.ldc / 4));
-    const float* const aux = f.aux ? f.aux + off : nullptr;
-    const float* const rowmask = f.rowmask ? f.rowmask + row0 : nullptr;
-    if (mode == CONV_FWD)
-        hipLaunchKernelGGL(conv_finish_kernel, grid, dim3(256), 0, s, ws, splits, stride, f.bias, aux, rowmask, f.out + off, rows, g.ldc / 4);
-    else
-        hipLaunchKernelGGL(conv_finish_dgrad_kernel, grid, dim3(256), 0, s, ws, splits, stride, aux, rowmask, f.prelu ? 1.0f : 0.0f,
-                           f.prelu, f.out + off, rows, g.ldc / 4, f.act_ch, f.epi);
-    return vlg_last_error();
+static void fill_shifts(ConvArgs& g, int wp, int sign) {
+    for (int ky = 0; ky < 3; ++ky)
+        for (int kx = 0; kx < 3; ++kx) g.shift[ky * 3 + kx] = sign * ((ky - 1) * wp + (kx - 1));
+    g.wp = wp; g.sign = sign;
 }
 
-extern "C" int vlg_conv3x3_fwd(const float* in, const float* w, const float* bias, float* out, const float* resid,
-                               const float* rowmask, const float* prelu_slope, const int* rowtab, int64_t rows_out,
-                               int cin_p, int cout, int cout_p, int wp_in, int act_ch, int epilogue, float* workspace,
-                               int64_t workspace_capacity, void* stream) {
+static bool conv_ok(const void* p) { return p != nullptr && vlg_aligned16(p); }
+
+// ---- the entry points of both precisions: the same validation, in the same order, with the same return codes
+static int conv_fwd(int prec, const float* in, const float* w, const float* bias, float* out, const float* resid,
+                    const float* rowmask, const float* prelu_slope, const int* rowtab, int64_t rows_out, int cin_p, int cout,
+                    int cout_p, int wp_in, int act_ch, int epilogue, float* workspace, int64_t workspace_capacity, void* stream) {
     if (rows_out < 1 || cin_p < 32 || (cin_p & 31) || cout < 1 || cout > cout_p || (cout_p & 31)) return VLG_ERR_SHAPE;
     if (!conv_ok(in) || !conv_ok(w) || !conv_ok(out)) return VLG_ERR_ALIGN;
     if ((epilogue & VLG_CEPI_RESID) && !resid) return VLG_ERR_SHAPE;
+    hipStream_t s = (hipStream_t)stream;
+    if (epilogue & VLG_CEPI_CIN4) {                            // image-channel first layer: 3 channels in a 32-channel tensor
+        if (rowtab != nullptr || prelu_slope != nullptr || (epilogue & (VLG_CEPI_RESID | VLG_CEPI_PRELU)) || wp_in < 1) return VLG_ERR_SHAPE;
+        const int64_t blocks = ((rows_out + 127) / 128) * ((cout + 63) / 64);
+        // (32-bit byte offsets inside conv_first_kernel's buffer descriptors)
+        if (blocks > 0x7fffffff || (rows_out + 2 * (int64_t)(wp_in + 1) + 128) * cin_p * 4 >= (1ll << 31) ||
+            (rows_out + 128) * (int64_t)cout_p * 4 >= (1ll << 31)) return VLG_ERR_SHAPE;
+        // fp32: contraction over (tap, 4 channels); bf16: the general path below over the 32 padded channels (3..31 are zero)
+        if (prec == CONV_FP32) {
+            hipLaunchKernelGGL(conv_first_kernel, dim3((unsigned)blocks), dim3(GEMM_THREADS), 0, s, in, w, bias, out, rowmask,
+                               (int)rows_out, cin_p, 9 * cin_p, cout_p, cout, wp_in);
+            return vlg_last_error();
+        }
+    }
+    const ConvPlan p = conv_plan(prec, CONV_FWD, rows_out, cin_p, cout, cout_p, ws_kind(workspace), workspace_capacity,
+                                 (rowtab ? HAS_TABLES : 0) | ((epilogue & VLG_CEPI_PRELU) ? HAS_PRELU : 0));
+    if (p.splits > 1) {
+        if (!vlg_aligned16(workspace) || (epilogue & VLG_CEPI_PRELU)) return VLG_ERR_ALIGN;
+        if (workspace_capacity < p.ws_floats) return VLG_ERR_SHAPE;      // host-side bound on the partial tiles
+    }
     ConvArgs g{};
     g.A = in; g.B = w; g.C = out; g.bias = bias; g.aux_in = resid; g.rowmask = rowmask; g.prelu = prelu_slope;
     g.rowtab = rowtab; g.tab_stride = 0;
@@ -1094,78 +1141,128 @@ extern "C" int vlg_conv3x3_fwd(const float* in, const float* w, const float* bia
     g.lda = cin_p; g.ldb = 9 * cin_p; g.ldc = cout_p; g.cin = cin_p;
     g.splits = 1; g.kc_per_split = g.Kc; g.epi = epilogue & ~(VLG_CEPI_DPRELU | VLG_CEPI_CIN4); g.act_ch = act_ch;
     fill_shifts(g, wp_in, 1);
-    hipStream_t s = (hipStream_t)stream;
-    if (epilogue & VLG_CEPI_CIN4) {                            // image-channel first layer: contraction over (tap, 4 channels)
-        if (rowtab != nullptr || prelu_slope != nullptr || (epilogue & (VLG_CEPI_RESID | VLG_CEPI_PRELU)) || wp_in < 1) return VLG_ERR_SHAPE;
-        const int64_t blocks = ((rows_out + 127) / 128) * ((cout + 63) / 64);
-        // (32-bit byte offsets inside the kernel's buffer descriptors)
-        if (blocks > 0x7fffffff || (rows_out + 2 * (int64_t)(wp_in + 1) + 128) * cin_p * 4 >= (1ll << 31) ||
-            (rows_out + 128) * (int64_t)cout_p * 4 >= (1ll << 31)) return VLG_ERR_SHAPE;
-        hipLaunchKernelGGL(conv_first_kernel, dim3((unsigned)blocks), dim3(GEMM_THREADS), 0, s, in, w, bias, out, rowmask, (int)rows_out,
-                           cin_p, 9 * cin_p, cout_p, cout, wp_in);
-        return vlg_last_error();
-    }
-    const ConvPlan p = conv_plan(CONV_FWD, rows_out, cin_p, cout, cout_p, ws_kind(workspace), workspace_capacity,
-                                 (rowtab ? HAS_TABLES : 0) | ((epilogue & VLG_CEPI_PRELU) ? HAS_PRELU : 0));
-    if (p.splits > 1) {
-        if (!vlg_aligned16(workspace) || (epilogue & VLG_CEPI_PRELU)) return VLG_ERR_ALIGN;
-        if (workspace_capacity < p.ws_floats) return VLG_ERR_SHAPE;      // host-side bound on the partial tiles
-    }
-    const ConvFinish f{bias, (epilogue & VLG_CEPI_RESID) ? resid : nullptr, rowmask, nullptr, out, 0, 0};
-    return launch_conv_plan<CONV_FWD>(p, g, workspace, f, s);
+    return launch_conv_plan(prec, CONV_FWD, p, g, workspace, s);
 }
 
-extern "C" int vlg_conv3x3_dgrad(const float* dout, const float* w, float* din, const float* x_in,
-                                 const float* rowmask_in, const float* prelu_slope, float* da_slab,
-                                 const int* tap_tables, int64_t tab_stride, int64_t rows_in, int cin_p, int cout_p,
-                                 int wp, int act_ch, int epilogue, float* workspace, int64_t workspace_capacity,
-                                 int da_capacity, void* stream) {
+static int conv_dgrad(int prec, const float* dout, const float* w, float* din, const float* x_in, const float* rowmask_in,
+                      const float* prelu_slope, float* da_slab, const int* tap_tables, int64_t tab_stride, int64_t rows_in,
+                      int cin_p, int cout_p, int wp, int act_ch, int epilogue, float* workspace, int64_t workspace_capacity,
+                      int da_capacity, void* stream) {
     // din[p, ci] = mask[p] * sum_tap sum_co dout[p - shift(tap), co] * W[co][tap][ci]   (stride 1)
     // stride 2: tap_tables[tap][p] = output row feeding input row p through that tap (or a zero guard row)
     if (rows_in < 1 || cin_p < 32 || (cin_p & 31) || (cin_p > 128 && (cin_p & 127)) || cout_p < 32 || (cout_p & 31))
         return VLG_ERR_SHAPE;                                // wide inputs are tiled 128 columns at a time
     if (!conv_ok(dout) || !conv_ok(w) || !conv_ok(din)) return VLG_ERR_ALIGN;
     if ((epilogue & VLG_CEPI_DPRELU) && (!x_in || !prelu_slope)) return VLG_ERR_SHAPE;
-    const ConvPlan p = conv_plan(CONV_DGRAD, rows_in, cin_p, cin_p, cout_p, ws_kind(workspace), workspace_capacity,
+    const ConvPlan p = conv_plan(prec, CONV_DGRAD, rows_in, cin_p, cin_p, cout_p, ws_kind(workspace), workspace_capacity,
                                  (tap_tables ? HAS_TABLES : 0) | (da_slab ? HAS_DA_SLAB : 0));
     if (da_slab != nullptr && da_capacity < p.slopes) return VLG_ERR_SHAPE;   // one partial per block
+    if (p.splits > 1) {
+        if (!vlg_aligned16(workspace)) return VLG_ERR_ALIGN;
+        if (workspace_capacity < p.ws_floats) return VLG_ERR_SHAPE;
+    }
     ConvArgs g{};
     g.A = dout; g.B = w; g.C = din; g.aux_in = x_in; g.rowmask = rowmask_in; g.prelu = prelu_slope; g.da_slab = da_slab;
     g.rowtab = tap_tables; g.tab_stride = tap_tables ? tab_stride : 0;
     g.M = rows_in; g.N = cin_p; g.Kc = 9 * (int64_t)cout_p;
     g.lda = cout_p; g.ldb = 9 * cin_p; g.ldc = cin_p; g.cin = cout_p; g.b_tap_stride = cin_p;
     g.splits = 1; g.kc_per_split = g.Kc; g.epi = epilogue & (VLG_CEPI_DPRELU | VLG_CEPI_ACCUM); g.act_ch = act_ch;
-    if (tap_tables) { for (int t = 0; t < 9; ++t) g.shift[t] = 0; }
-    else fill_shifts(g, wp, -1);
-    if (p.splits > 1) {
-        if (!vlg_aligned16(workspace)) return VLG_ERR_ALIGN;
-        if (workspace_capacity < p.ws_floats) return VLG_ERR_SHAPE;
-    }
-    const ConvFinish f{nullptr, x_in, rowmask_in, prelu_slope, din, act_ch, epilogue & (VLG_CEPI_DPRELU | VLG_CEPI_ACCUM)};
-    return launch_conv_plan<CONV_DGRAD>(p, g, workspace, f, (hipStream_t)stream);
+    if (!tap_tables) fill_shifts(g, wp, -1);                 // (per-tap tables: every shift 0)
+    return launch_conv_plan(prec, CONV_DGRAD, p, g, workspace, (hipStream_t)stream);
 }
 
-extern "C" int vlg_conv3x3_wgrad(const float* dout, const float* in, float* slabs, int64_t slab_stride,
-                                 int64_t slab_capacity, const int* rowtab, const float* prelu_slope, int64_t rows, int cin_p, int cout_p,
-                                 int wp_in, int act_ch, void* stream) {
+static int conv_wgrad(int prec, const float* dout, const float* in, float* slabs, int64_t slab_stride, int64_t slab_capacity,
+                      const int* rowtab, const float* prelu_slope, int64_t rows, int cin_p, int cout_p, int wp_in, int act_ch,
+                      void* stream) {
     // slab[s][co*(9*cin_p) + tap*cin_p + ci] = sum_{p in split s} dout[p, co] * act(in[row(p) + shift(tap), ci])
     // slab[s][cout_p*9*cin_p + co]           = sum_p dout[p, co]                (bias gradient)
     // rows past `rows` are read from the zero guard band (dout there is zero), so no edge handling is needed
     if (rows < 1 || cin_p < 32 || (cin_p & 31) || cout_p < 32 || (cout_p & 31)) return VLG_ERR_SHAPE;
     if (slab_stride < (int64_t)cout_p * 9 * cin_p + cout_p) return VLG_ERR_SHAPE;
     if (!conv_ok(dout) || !conv_ok(in) || !conv_ok(slabs)) return VLG_ERR_ALIGN;
-    const ConvPlan p = conv_plan(CONV_WGRAD, rows, cin_p, cout_p, cout_p, WS_NONE, 0, rowtab ? HAS_TABLES : 0);
+    const ConvPlan p = conv_plan(prec, CONV_WGRAD, rows, cin_p, cout_p, cout_p, WS_NONE, 0, rowtab ? HAS_TABLES : 0);
+    if (slab_capacity < (int64_t)p.splits * slab_stride) return VLG_ERR_SHAPE;      // the caller's buffer must hold every slab
     ConvArgs g{};
     g.A = dout; g.B = in; g.C = slabs; g.prelu = prelu_slope; g.rowtab = rowtab;
     g.M = cout_p; g.N = 9 * cin_p; g.Kc = rows;
     g.lda = cout_p; g.ldb = cin_p; g.ldc = 9 * cin_p; g.cin = cin_p;
     g.splits = p.splits; g.kc_per_split = p.kc_per_split;
-    if (slab_capacity < (int64_t)g.splits * slab_stride) return VLG_ERR_SHAPE;      // the caller's buffer must hold every slab
     g.slab_stride = slab_stride; g.colsum_off = (int64_t)cout_p * 9 * cin_p; g.act_ch = act_ch;
     fill_shifts(g, wp_in, 1);
-    switch (p.t.bm) {
-        case 64: return launch_conv<CONV_WGRAD, 64, 128>(g, (hipStream_t)stream);
-        case 96: return launch_conv<CONV_WGRAD, 96, 128>(g, (hipStream_t)stream);
-        default: return launch_conv<CONV_WGRAD, 32, 128>(g, (hipStream_t)stream);
-    }
+    return launch_tile(prec, CONV_WGRAD, p.t, g, (hipStream_t)stream);
+}
+
+// ---- the C ABI (include/vlg_hip.h): fp32 and its bf16 twins
+extern "C" int vlg_conv3x3_fwd(const float* in, const float* w, const float* bias, float* out, const float* resid,
+                               const float* rowmask, const float* prelu_slope, const int* rowtab, int64_t rows_out,
+                               int cin_p, int cout, int cout_p, int wp_in, int act_ch, int epilogue, float* workspace,
+                               int64_t workspace_capacity, void* stream) {
+    return conv_fwd(CONV_FP32, in, w, bias, out, resid, rowmask, prelu_slope, rowtab, rows_out, cin_p, cout, cout_p, wp_in,
+                    act_ch, epilogue, workspace, workspace_capacity, stream);
+}
+extern "C" int vlg_conv3x3_fwd_bf16(const float* in, const float* w, const float* bias, float* out, const float* resid,
+                                    const float* rowmask, const float* prelu_slope, const int* rowtab, int64_t rows_out,
+                                    int cin_p, int cout, int cout_p, int wp_in, int act_ch, int epilogue, float* workspace,
+                                    int64_t workspace_capacity, void* stream) {
+    return conv_fwd(CONV_BF16, in, w, bias, out, resid, rowmask, prelu_slope, rowtab, rows_out, cin_p, cout, cout_p, wp_in,
+                    act_ch, epilogue, workspace, workspace_capacity, stream);
+}
+extern "C" int vlg_conv3x3_dgrad(const float* dout, const float* w, float* din, const float* x_in,
+                                 const float* rowmask_in, const float* prelu_slope, float* da_slab,
+                                 const int* tap_tables, int64_t tab_stride, int64_t rows_in, int cin_p, int cout_p,
+                                 int wp, int act_ch, int epilogue, float* workspace, int64_t workspace_capacity,
+                                 int da_capacity, void* stream) {
+    return conv_dgrad(CONV_FP32, dout, w, din, x_in, rowmask_in, prelu_slope, da_slab, tap_tables, tab_stride, rows_in, cin_p,
+                      cout_p, wp, act_ch, epilogue, workspace, workspace_capacity, da_capacity, stream);
+}
+extern "C" int vlg_conv3x3_dgrad_bf16(const float* dout, const float* w, float* din, const float* x_in,
+                                      const float* rowmask_in, const float* prelu_slope, float* da_slab,
+                                      const int* tap_tables, int64_t tab_stride, int64_t rows_in, int cin_p, int cout_p,
+                                      int wp, int act_ch, int epilogue, float* workspace, int64_t workspace_capacity,
+                                      int da_capacity, void* stream) {
+    return conv_dgrad(CONV_BF16, dout, w, din, x_in, rowmask_in, prelu_slope, da_slab, tap_tables, tab_stride, rows_in, cin_p,
+                      cout_p, wp, act_ch, epilogue, workspace, workspace_capacity, da_capacity, stream);
+}
+extern "C" int vlg_conv3x3_wgrad(const float* dout, const float* in, float* slabs, int64_t slab_stride,
+                                 int64_t slab_capacity, const int* rowtab, const float* prelu_slope, int64_t rows, int cin_p, int cout_p,
+                                 int wp_in, int act_ch, void* stream) {
+    return conv_wgrad(CONV_FP32, dout, in, slabs, slab_stride, slab_capacity, rowtab, prelu_slope, rows, cin_p, cout_p, wp_in, act_ch, stream);
+}
+extern "C" int vlg_conv3x3_wgrad_bf16(const float* dout, const float* in, float* slabs, int64_t slab_stride,
+                                      int64_t slab_capacity, const int* rowtab, const float* prelu_slope, int64_t rows, int cin_p,
+                                      int cout_p, int wp_in, int act_ch, void* stream) {
+    return conv_wgrad(CONV_BF16, dout, in, slabs, slab_stride, slab_capacity, rowtab, prelu_slope, rows, cin_p, cout_p, wp_in, act_ch, stream);
+}
+
+extern "C" int vlg_conv3x3_fwd_splits(int64_t rows_out, int cin_p, int cout, int cout_p) {
+    return conv_query_plan(CONV_FP32, CONV_FWD, rows_out, cin_p, cout, cout_p).splits;
+}
+extern "C" int vlg_conv3x3_fwd_bf16_splits(int64_t rows_out, int cin_p, int cout, int cout_p) {
+    return conv_query_plan(CONV_BF16, CONV_FWD, rows_out, cin_p, cout, cout_p).splits;
+}
+extern "C" int64_t vlg_conv3x3_fwd_workspace(int64_t rows_out, int cin_p, int cout, int cout_p) {
+    return conv_query_workspace(CONV_FP32, CONV_FWD, rows_out, cin_p, cout, cout_p);
+}
+extern "C" int64_t vlg_conv3x3_fwd_bf16_workspace(int64_t rows_out, int cin_p, int cout, int cout_p) {
+    return conv_query_workspace(CONV_BF16, CONV_FWD, rows_out, cin_p, cout, cout_p);
+}
+extern "C" int vlg_conv3x3_dgrad_splits(int64_t rows_in, int cin_p, int cout_p) {
+    return conv_query_plan(CONV_FP32, CONV_DGRAD, rows_in, cin_p, cin_p, cout_p).splits;
+}
+extern "C" int vlg_conv3x3_dgrad_bf16_splits(int64_t rows_in, int cin_p, int cout_p) {
+    return conv_query_plan(CONV_BF16, CONV_DGRAD, rows_in, cin_p, cin_p, cout_p).splits;
+}
+extern "C" int64_t vlg_conv3x3_dgrad_workspace(int64_t rows_in, int cin_p, int cout_p) {
+    return conv_query_workspace(CONV_FP32, CONV_DGRAD, rows_in, cin_p, cin_p, cout_p);
+}
+extern "C" int64_t vlg_conv3x3_dgrad_bf16_workspace(int64_t rows_in, int cin_p, int cout_p) {
+    return conv_query_workspace(CONV_BF16, CONV_DGRAD, rows_in, cin_p, cin_p, cout_p);
+}
+extern "C" int vlg_conv3x3_dgrad_slabs(int64_t rows_in, int cin_p) { return conv_query_slopes(CONV_FP32, rows_in, cin_p); }
+extern "C" int vlg_conv3x3_dgrad_bf16_slabs(int64_t rows_in, int cin_p) { return conv_query_slopes(CONV_BF16, rows_in, cin_p); }
+extern "C" int vlg_conv3x3_wgrad_slabs(int64_t rows, int cin_p, int cout_p) {
+    return conv_query_plan(CONV_FP32, CONV_WGRAD, rows, cin_p, cout_p, cout_p).splits;
+}
+extern "C" int vlg_conv3x3_wgrad_bf16_slabs(int64_t rows, int cin_p, int cout_p) {
+    return conv_query_plan(CONV_BF16, CONV_WGRAD, rows, cin_p, cout_p, cout_p).splits;
 }

@@ -15,7 +15,8 @@
 //   data gradient    A = dOut rows shifted by -tap / per-tap tables   B = weights, contraction-major [cout][tap cin_p + ci] (MC)
 //   weight gradient  A = dOut [pixel][cout] (MC)                     B = act(input) [pixel + shift(tap)][ci] (MC)
 // Staging: 8 fp32 values (two 16-byte loads) per slot into registers one K tile ahead, converted on the LDS write; LDS double
-// buffered, one barrier per K tile.  Split-K (raw partials + conv.hip's finish kernels) on the coarse 256-512 channel levels.
+// buffered, one barrier per K tile.  Validation, plan (tile, split-K on the coarse 256-512 channel levels) and the finish
+// kernels of split-K are conv.hip's, shared with the fp32 path; this file holds the kernel and its launcher.
 #include "conv_common.h"
 #include "gemm_tile16.h"
 
@@ -291,76 +292,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void conv_bf16_kernel(const ConvAr
     }
 }
 
-// ---- plan: tile, split-K, workspace, slope partials - from the call's arguments alone (the queries read the same plan)
-struct Bf16Plan {
-    int bm, bn;
-    int splits; int64_t kc_per_split;
-    int64_t ws_floats;
-    int slopes;
-};
-
-// Split-K of the coarse 256-512 channel levels (few 128 x 128 tiles, K = 9 * cin_p of 2304-4608): up to 8 ranges of at least
-// 8 K tiles, so that a launch has ~512 blocks.
-int bf16_splits(int64_t rows, int cin_p, int cout, int cout_p) {
-    if (cout_p < 128 || cout != cout_p || cin_p < 128 || (cout_p & 127)) return 1;
-    const int64_t b128 = ((rows + 127) / 128) * (cout_p / 128);
-    if (b128 >= 256) return 1;
-    int s = (int)(512 / b128);
-    if (s > 8) s = 8;
-    const int ktiles = 9 * cin_p / BK16;
-    while (s > 1 && ktiles / s < 8) --s;
-    return s < 2 ? 1 : s;
-}
-
-// forward / data-gradient tile: N = n_cols (cout_p, or cin_p), rows of 128 (64 when 128-row tiles would leave the chip
-// idle)
-void bf16_tile(int64_t rows, int n_cols, int& bm, int& bn) {
-    bn = n_cols == 32 ? 32 : n_cols == 64 ? 64 : n_cols == 96 ? 96 : 128;
-    const int64_t t128 = ((rows + 127) / 128) * ((n_cols + bn - 1) / bn);
-    bm = (bn >= 64 && t128 < 512) ? 64 : 128;
-    if (bn == 96) bm = 128;                                    // (no 64 x 96 wave layout)
-}
-
-enum { HAS_TABLES = 1, HAS_DA_SLAB = 2 };
-Bf16Plan bf16_plan(int mode, int64_t rows, int cin_p, int cout, int cout_p, bool ws, int has) {
-    Bf16Plan p{};
-    p.splits = 1;
-    if (mode == CONV_WGRAD) {                                  // M = cout_p, N = 9 cin_p, K = rows in ranges of 32-row tiles
-        p.bm = (cout_p & 127) == 0 ? 128 : cout_p == 96 ? 96 : (cout_p & 63) == 0 ? 64 : 32;
-        p.bn = 128;
-        const int64_t tiles = (cout_p / p.bm) * (int64_t)((9 * cin_p + 127) / 128);
-        int64_t want = 512 / tiles;
-        const int64_t max_splits = (rows + 255) / 256;
-        if (want > max_splits) want = max_splits;
-        if (want < 1) want = 1;
-        int64_t per = (rows + want - 1) / want;
-        per = (per + 31) / 32 * 32;
-        p.kc_per_split = per;
-        p.splits = (int)((rows + per - 1) / per);
-        return p;
-    }
-    const int n_cols = mode == CONV_FWD ? cout_p : cin_p;
-    const int64_t kc = 9 * (int64_t)(mode == CONV_FWD ? cin_p : cout_p);
-    p.kc_per_split = kc;
-    // split-K: the data gradient only for frozen trunks (no slope gradient wanted), stride 1
-    const bool split_ok = ws && (mode == CONV_FWD || ((has & (HAS_DA_SLAB | HAS_TABLES)) == 0));
-    const int splits = !split_ok ? 1 : mode == CONV_FWD ? bf16_splits(rows, cin_p, cout, cout_p) : bf16_splits(rows, cout_p, cin_p, cin_p);
-    if (splits > 1) {
-        p.bm = 128; p.bn = 128;
-        p.splits = splits;
-        p.kc_per_split = (int64_t)((kc / BK16 + splits - 1) / splits) * BK16;
-        p.splits = (int)((kc + p.kc_per_split - 1) / p.kc_per_split);
-        p.ws_floats = (int64_t)p.splits * rows * n_cols;
-    } else {
-        bf16_tile(rows, n_cols, p.bm, p.bn);
-    }
-    p.slopes = (int)((rows + p.bm - 1) / p.bm) * ((n_cols + p.bn - 1) / p.bn);
-    return p;
-}
-Bf16Plan bf16_query_plan(int mode, int64_t rows, int cin_p, int cout, int cout_p) {
-    return bf16_plan(mode, rows, cin_p, cout, cout_p, true, 0);
-}
-
 template <int MODE, int BM, int BN, int WM>
 int launch_bf16(ConvArgs g, hipStream_t s) {
     g.tiles_m = (int)((g.M + BM - 1) / BM);
@@ -378,123 +309,16 @@ int launch_bf16_tile(int bm, int bn, const ConvArgs& g, hipStream_t s) {
     return bm == 64 ? launch_bf16<MODE, 64, 128, 2>(g, s) : launch_bf16<MODE, 128, 128, 2>(g, s);
 }
 
-// a forward / data-gradient plan: the main kernel, and for split-K conv.hip's finish kernel over the raw partials
-template <int MODE>
-int launch_bf16_plan(const Bf16Plan& p, ConvArgs g, float* ws, const ConvFinish& f, hipStream_t s) {
-    if (p.splits > 1) {
-        g.splits = p.splits;
-        g.kc_per_split = p.kc_per_split;
-        g.slab_stride = g.M * (int64_t)g.ldc;
-        g.C = ws; g.bias = nullptr; g.aux_in = nullptr; g.rowmask = nullptr; g.epi = 0;    // raw partial tiles
-        if (MODE == CONV_DGRAD) g.act_ch = g.N;                // (the finish kernel cuts the constant channels)
-    }
-    if (int e = launch_bf16_tile<MODE>(p.bm, p.bn, g, s)) return e;
-    if (p.splits == 1) return 0;
-    return conv_launch_finish(MODE, ws, p.splits, g.slab_stride, 0, g, f, s);
-}
-
 }  // namespace
 
-extern "C" int vlg_conv3x3_fwd_bf16_splits(int64_t rows_out, int cin_p, int cout, int cout_p) {
-    return bf16_query_plan(CONV_FWD, rows_out, cin_p, cout, cout_p).splits;
-}
-extern "C" int64_t vlg_conv3x3_fwd_bf16_workspace(int64_t rows_out, int cin_p, int cout, int cout_p) {
-    if (rows_out < 1 || cin_p < 32 || cout_p < 32) return 0;
-    return bf16_query_plan(CONV_FWD, rows_out, cin_p, cout, cout_p).ws_floats;
-}
-extern "C" int vlg_conv3x3_dgrad_bf16_splits(int64_t rows_in, int cin_p, int cout_p) {
-    return bf16_query_plan(CONV_DGRAD, rows_in, cin_p, cin_p, cout_p).splits;
-}
-extern "C" int64_t vlg_conv3x3_dgrad_bf16_workspace(int64_t rows_in, int cin_p, int cout_p) {
-    if (rows_in < 1 || cin_p < 32 || cout_p < 32) return 0;
-    return bf16_query_plan(CONV_DGRAD, rows_in, cin_p, cin_p, cout_p).ws_floats;
-}
-extern "C" int vlg_conv3x3_dgrad_bf16_slabs(int64_t rows_in, int cin_p) {
-    // (with da_slab there is no split, and the tile does not depend on cout_p)
-    return bf16_plan(CONV_DGRAD, rows_in, cin_p, cin_p, cin_p, false, HAS_DA_SLAB).slopes;
-}
-extern "C" int vlg_conv3x3_wgrad_bf16_slabs(int64_t rows, int cin_p, int cout_p) {
-    return bf16_query_plan(CONV_WGRAD, rows, cin_p, cout_p, cout_p).splits;
-}
-
-extern "C" int vlg_conv3x3_fwd_bf16(const float* in, const float* w, const float* bias, float* out, const float* resid,
-                                    const float* rowmask, const float* prelu_slope, const int* rowtab, int64_t rows_out,
-                                    int cin_p, int cout, int cout_p, int wp_in, int act_ch, int epilogue, float* workspace,
-                                    int64_t workspace_capacity, void* stream) {
-    if (rows_out < 1 || cin_p < 32 || (cin_p & 31) || cout < 1 || cout > cout_p || (cout_p & 31)) return VLG_ERR_SHAPE;
-    if (!conv_ok(in) || !conv_ok(w) || !conv_ok(out)) return VLG_ERR_ALIGN;
-    if ((epilogue & VLG_CEPI_RESID) && !resid) return VLG_ERR_SHAPE;
-    if (epilogue & VLG_CEPI_CIN4) {
-        // image-channel first layer: the same checks as the fp32 entry point, then the general path over the 32 padded
-        // channels (channels 3..31 are zero)
-        if (rowtab != nullptr || prelu_slope != nullptr || (epilogue & (VLG_CEPI_RESID | VLG_CEPI_PRELU)) || wp_in < 1) return VLG_ERR_SHAPE;
-        const int64_t blocks = ((rows_out + 127) / 128) * ((cout + 63) / 64);
-        if (blocks > 0x7fffffff || (rows_out + 2 * (int64_t)(wp_in + 1) + 128) * cin_p * 4 >= (1ll << 31) ||
-            (rows_out + 128) * (int64_t)cout_p * 4 >= (1ll << 31)) return VLG_ERR_SHAPE;
-    }
-    ConvArgs g{};
-    g.A = in; g.B = w; g.C = out; g.bias = bias; g.aux_in = resid; g.rowmask = rowmask; g.prelu = prelu_slope;
-    g.rowtab = rowtab; g.tab_stride = 0;
-    g.M = rows_out; g.N = cout; g.Kc = 9 * (int64_t)cin_p;
-    g.lda = cin_p; g.ldb = 9 * cin_p; g.ldc = cout_p; g.cin = cin_p;
-    g.splits = 1; g.kc_per_split = g.Kc; g.epi = epilogue & ~(VLG_CEPI_DPRELU | VLG_CEPI_CIN4); g.act_ch = act_ch;
-    fill_shifts(g, wp_in, 1);
-    const Bf16Plan p = bf16_plan(CONV_FWD, rows_out, cin_p, cout, cout_p, workspace != nullptr, rowtab ? HAS_TABLES : 0);
-    if (p.splits > 1) {
-        if (!vlg_aligned16(workspace) || (epilogue & VLG_CEPI_PRELU)) return VLG_ERR_ALIGN;
-        if (workspace_capacity < p.ws_floats) return VLG_ERR_SHAPE;      // host-side bound on the partial tiles
-    }
-    const ConvFinish f{bias, (epilogue & VLG_CEPI_RESID) ? resid : nullptr, rowmask, nullptr, out, 0, 0};
-    return launch_bf16_plan<CONV_FWD>(p, g, workspace, f, (hipStream_t)stream);
-}
-
-extern "C" int vlg_conv3x3_dgrad_bf16(const float* dout, const float* w, float* din, const float* x_in,
-                                      const float* rowmask_in, const float* prelu_slope, float* da_slab,
-                                      const int* tap_tables, int64_t tab_stride, int64_t rows_in, int cin_p, int cout_p,
-                                      int wp, int act_ch, int epilogue, float* workspace, int64_t workspace_capacity,
-                                      int da_capacity, void* stream) {
-    if (rows_in < 1 || cin_p < 32 || (cin_p & 31) || (cin_p > 128 && (cin_p & 127)) || cout_p < 32 || (cout_p & 31))
-        return VLG_ERR_SHAPE;
-    if (!conv_ok(dout) || !conv_ok(w) || !conv_ok(din)) return VLG_ERR_ALIGN;
-    if ((epilogue & VLG_CEPI_DPRELU) && (!x_in || !prelu_slope)) return VLG_ERR_SHAPE;
-    const Bf16Plan p = bf16_plan(CONV_DGRAD, rows_in, cin_p, cin_p, cout_p, workspace != nullptr,
-                                 (tap_tables ? HAS_TABLES : 0) | (da_slab ? HAS_DA_SLAB : 0));
-    if (da_slab != nullptr && da_capacity < p.slopes) return VLG_ERR_SHAPE;   // one partial per block
-    ConvArgs g{};
-    g.A = dout; g.B = w; g.C = din; g.aux_in = x_in; g.rowmask = rowmask_in; g.prelu = prelu_slope; g.da_slab = da_slab;
-    g.rowtab = tap_tables; g.tab_stride = tap_tables ? tab_stride : 0;
-    g.M = rows_in; g.N = cin_p; g.Kc = 9 * (int64_t)cout_p;
-    g.lda = cout_p; g.ldb = 9 * cin_p; g.ldc = cin_p; g.cin = cout_p; g.b_tap_stride = cin_p;
-    g.splits = 1; g.kc_per_split = g.Kc; g.epi = epilogue & (VLG_CEPI_DPRELU | VLG_CEPI_ACCUM); g.act_ch = act_ch;
-    if (tap_tables) { for (int t = 0; t < 9; ++t) g.shift[t] = 0; }
-    else fill_shifts(g, wp, -1);
-    if (p.splits > 1) {
-        if (!vlg_aligned16(workspace)) return VLG_ERR_ALIGN;
-        if (workspace_capacity < p.ws_floats) return VLG_ERR_SHAPE;
-    }
-    const ConvFinish f{nullptr, x_in, rowmask_in, prelu_slope, din, act_ch, epilogue & (VLG_CEPI_DPRELU | VLG_CEPI_ACCUM)};
-    return launch_bf16_plan<CONV_DGRAD>(p, g, workspace, f, (hipStream_t)stream);
-}
-
-extern "C" int vlg_conv3x3_wgrad_bf16(const float* dout, const float* in, float* slabs, int64_t slab_stride,
-                                      int64_t slab_capacity, const int* rowtab, const float* prelu_slope, int64_t rows, int cin_p,
-                                      int cout_p, int wp_in, int act_ch, void* stream) {
-    if (rows < 1 || cin_p < 32 || (cin_p & 31) || cout_p < 32 || (cout_p & 31)) return VLG_ERR_SHAPE;
-    if (slab_stride < (int64_t)cout_p * 9 * cin_p + cout_p) return VLG_ERR_SHAPE;
-    if (!conv_ok(dout) || !conv_ok(in) || !conv_ok(slabs)) return VLG_ERR_ALIGN;
-    const Bf16Plan p = bf16_plan(CONV_WGRAD, rows, cin_p, cout_p, cout_p, false, rowtab ? HAS_TABLES : 0);
-    ConvArgs g{};
-    g.A = dout; g.B = in; g.C = slabs; g.prelu = prelu_slope; g.rowtab = rowtab;
-    g.M = cout_p; g.N = 9 * cin_p; g.Kc = rows;
-    g.lda = cout_p; g.ldb = cin_p; g.ldc = 9 * cin_p; g.cin = cin_p;
-    g.splits = p.splits; g.kc_per_split = p.kc_per_split;
-    if (slab_capacity < (int64_t)g.splits * slab_stride) return VLG_ERR_SHAPE;      // the caller's buffer must hold every slab
-    g.slab_stride = slab_stride; g.colsum_off = (int64_t)cout_p * 9 * cin_p; g.act_ch = act_ch;
-    fill_shifts(g, wp_in, 1);
-    switch (p.bm) {
-        case 128: return launch_bf16<CONV_WGRAD, 128, 128, 1>(g, (hipStream_t)stream);
-        case 96: return launch_bf16<CONV_WGRAD, 96, 128, 1>(g, (hipStream_t)stream);
-        case 64: return launch_bf16<CONV_WGRAD, 64, 128, 1>(g, (hipStream_t)stream);
-        default: return launch_bf16<CONV_WGRAD, 32, 128, 1>(g, (hipStream_t)stream);
+// the bf16 kernel of a tile that conv.hip's plan chose (the weight gradient: BM rows of cout_p, BN = 128)
+int conv_bf16_launch(int mode, int bm, int bn, const ConvArgs& g, hipStream_t s) {
+    if (mode == CONV_FWD) return launch_bf16_tile<CONV_FWD>(bm, bn, g, s);
+    if (mode == CONV_DGRAD) return launch_bf16_tile<CONV_DGRAD>(bm, bn, g, s);
+    switch (bm) {
+        case 128: return launch_bf16<CONV_WGRAD, 128, 128, 1>(g, s);
+        case 96: return launch_bf16<CONV_WGRAD, 96, 128, 1>(g, s);
+        case 64: return launch_bf16<CONV_WGRAD, 64, 128, 1>(g, s);
+        default: return launch_bf16<CONV_WGRAD, 32, 128, 1>(g, s);
     }
 }

@@ -1,5 +1,5 @@
 // Shared by the fp32 (conv.hip) and bf16-MFMA (conv_bf16.hip) 3x3 convolutions: the launch arguments, the activation
-// applied on load, the tap shifts and the finish kernels of split-K / tail-split launches (defined in conv.hip).
+// applied on load, and the bf16 launcher that conv.hip's entry points call with their plan's tile.
 #pragma once
 #include "gemm_tile.h"
 
@@ -44,18 +44,5 @@ __device__ __forceinline__ float4 slope4(float a, int c, int act_ch) {
     return make_float4(c < act_ch ? a : 1.f, c + 1 < act_ch ? a : 1.f, c + 2 < act_ch ? a : 1.f, c + 3 < act_ch ? a : 1.f);
 }
 
-static void fill_shifts(ConvArgs& g, int wp, int sign) {
-    for (int ky = 0; ky < 3; ++ky)
-        for (int kx = 0; kx < 3; ++kx) g.shift[ky * 3 + kx] = sign * ((ky - 1) * wp + (kx - 1));
-    g.wp = wp; g.sign = sign;
-}
-
-static bool conv_ok(const void* p) { return p != nullptr && vlg_aligned16(p); }
-
-// the epilogue operands of a finish kernel over the whole output (forward: bias, residual, row mask; data gradient: x_in,
-// row mask, slope, act_ch, epilogue flags)
-struct ConvFinish { const float* bias; const float* aux; const float* rowmask; const float* prelu; float* out; int act_ch, epi; };
-// Sum `splits` raw partial outputs (slab s at ws + s * stride, rows row0 .. g.M - 1 of the output) and apply the epilogue f
-// with conv_finish_kernel (CONV_FWD) or conv_finish_dgrad_kernel (CONV_DGRAD); g supplies M and ldc.
-int conv_launch_finish(int mode, const float* ws, int splits, int64_t stride, int64_t row0, const ConvArgs& g,
-                       const ConvFinish& f, hipStream_t s);
+// launch conv_bf16_kernel (conv_bf16.hip) for mode CONV_* on a BM x BN tile of the plan; g as conv.hip fills it
+int conv_bf16_launch(int mode, int bm, int bn, const ConvArgs& g, hipStream_t s);
