@@ -193,6 +193,14 @@ int vlg_attention_clip_fwd(const float* qkv, const float* valid, float* out, flo
                            int64_t B, int T, int N, int d, void* stream);
 int vlg_attention_clip_bwd(const float* qkv, const float* valid, const float* out, const float* dout, const float* lse,
                            float* delta, float* dqkv, int64_t B, int T, int N, int d, void* stream);
+/* bf16 storage (precision "bf16"): qkv, out, dout and dqkv bf16; valid, lse and delta fp32 in the layouts above.  Products
+ * on bf16 MFMA with fp32 accumulation; scores, softmax statistics, lse and delta fp32; P and dS rounded to bf16 only as
+ * MFMA operands; O, dQ, dK, dV rounded once on store.  Same shape contract and return codes as the fp32 entries. */
+int vlg_attention_clip_fwd_bf16(const vlg_bf16* qkv, const float* valid, vlg_bf16* out, float* lse,
+                                int64_t B, int T, int N, int d, void* stream);
+int vlg_attention_clip_bwd_bf16(const vlg_bf16* qkv, const float* valid, const vlg_bf16* out, const vlg_bf16* dout,
+                                const float* lse, float* delta, vlg_bf16* dqkv,
+                                int64_t B, int T, int N, int d, void* stream);
 
 /* ------------------------------------------------------------------ reductions */
 int vlg_reduce_slabs(const float* slabs, int64_t slab_stride, int n_slabs,

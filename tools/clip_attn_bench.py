@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """Development tool: the per-clip attention kernels (csrc/attention_clip.hip) alone at the metric shape.
-    python tools/clip_attn_bench.py [B] [T] [N] [d] [--valid]"""
+    python tools/clip_attn_bench.py [B] [T] [N] [d] [--valid] [--bf16]
+--bf16: the fp32 and the bf16-storage kernels on the same shape, timed alternately in one process (bf16 rates against the
+2.5 PF/s bf16 MFMA peak)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "video-layout-generation_amd")]
@@ -21,17 +23,29 @@ st = torch.cuda.current_stream().cuda_stream
 fwd = lambda: hip.call("vlg_attention_clip_fwd", P(qkv), P(valid), P(out), P(lse), B, T, N, d, st)
 bwd = lambda: hip.call("vlg_attention_clip_bwd", P(qkv), P(valid), P(out), P(dout), P(lse), P(delta), P(dqkv), B, T, N, d, st)
 fl = 4.0 * B * d * N * N * T * (T + 1) / 2.0
-for name, fn, work in (("fwd", fwd, fl), ("bwd", bwd, 2.5 * fl)):
+kernels = [("fwd", fwd, fl, 157.3), ("bwd", bwd, 2.5 * fl, 157.3)]
+if "--bf16" in sys.argv:
+    q16, g16 = qkv.bfloat16(), dout.bfloat16()
+    o16, dq16 = torch.empty(M, d, device=dev, dtype=torch.bfloat16), torch.empty(M, 3 * d, device=dev, dtype=torch.bfloat16)
+    fwd16 = lambda: hip.call("vlg_attention_clip_fwd_bf16", P(q16), P(valid), P(o16), P(lse), B, T, N, d, st)
+    bwd16 = lambda: hip.call("vlg_attention_clip_bwd_bf16", P(q16), P(valid), P(o16), P(g16), P(lse), P(delta), P(dq16),
+                             B, T, N, d, st)
+    kernels = [("fwd", fwd, fl, 157.3), ("fwd bf16", fwd16, fl, 2500.0), ("bwd", bwd, 2.5 * fl, 157.3),
+               ("bwd bf16", bwd16, 2.5 * fl, 2500.0)]
+for _, fn, _, _ in kernels:
     for _ in range(3):
         fn()
-    ts = []
-    for _ in range(5):
+ts = {name: [] for name, _, _, _ in kernels}
+for _ in range(5):                                   # rounds: every kernel once per round, so drift hits all alike
+    for name, fn, _, _ in kernels:
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s.record()
         for _ in range(5):
             fn()
         e.record()
         torch.cuda.synchronize()
-        ts.append(s.elapsed_time(e) / 5)
-    t = sorted(ts)[2]
-    print("clip attention %s  (B,T,N,d)=(%d,%d,%d,%d)%s: %.1f us  %.1f TFLOP/s algorithmic (%.3f of 157.3)" % (name, B, T, N, d, " +valid" if valid is not None else "", t * 1e3, work / t / 1e9, work / t / 1e9 / 157.3))
+        ts[name].append(s.elapsed_time(e) / 5)
+for name, _, work, peak in kernels:
+    t = sorted(ts[name])[2]
+    print("clip attention %s  (B,T,N,d)=(%d,%d,%d,%d)%s: %.1f us  %.1f TFLOP/s algorithmic (%.3f of %.1f)" % (
+        name, B, T, N, d, " +valid" if valid is not None else "", t * 1e3, work / t / 1e9, work / t / 1e9 / peak, peak))

@@ -70,12 +70,11 @@ class LayoutEngine:
         "fp32x3"    fp32 tensors and fp32-grade projections on the bf16 matrix cores: every operand split exactly into
                     three bf16 terms, six bf16 MFMAs per product block (csrc/gemm_split.hip).
         The residual stream and its gradient, layer-norm statistics, softmax, losses, weight gradients, Adam and the
-        master weights are fp32 in all three."""
+        master weights are fp32 in all three.  attention = "clip" follows the storage: its bf16 entry points under "bf16"
+        (bf16 MFMA, fp32 scores and softmax statistics), the fp32 kernels otherwise (bf16_mfma included)."""
         cfg.validate()
         if precision not in ("fp32", "bf16", "bf16_mfma", "fp32x3"):
             raise ValueError("precision must be fp32, fp32x3, bf16 or bf16_mfma")
-        if cfg.attention == "clip" and precision == "bf16":
-            raise ValueError("attention='clip' runs on fp32 tensors (precision fp32 | fp32x3 | bf16_mfma)")
         # attention = "clip": padded slots (batch['valid'] == 0) must not be attended to; padded_slots = False tells the engine
         # that its batches never hold any (fixed-N feeds), so the kernels skip the per-key validity masks
         self.padded_slots = bool(padded_slots)
@@ -378,8 +377,10 @@ class LayoutEngine:
         d, s = self.cfg.d, self._stream()
         if self.cfg.attention == "clip":
             fl = 4.0 * B * d * N * N * T * (T + 1) / 2.0            # visible (query, key) pairs x 2 products x 2 x head dim, all heads
-            self._timed("attn_clip_fwd", fl, "vlg_attention_clip_fwd", ptr(self.qkv[l]), ptr(batch["valid"]) if self.padded_slots else 0,
-                        ptr(self.att[l]), ptr(self.lse[l]), B, T, N, d, s, nbytes=16.0 * M * d)
+            e = self.qkv.element_size()                             # qkv read, out written; the fp32 lse is negligible
+            self._timed("attn_clip_fwd", fl, "vlg_attention_clip_fwd" + self._sfx, ptr(self.qkv[l]),
+                        ptr(batch["valid"]) if self.padded_slots else 0, ptr(self.att[l]), ptr(self.lse[l]), B, T, N, d, s,
+                        nbytes=4.0 * e * M * d)
             return
         self._timed("attn_fwd", 0.0, "vlg_attention_fwd" + self._sfx, ptr(self.qkv[l]), ptr(self.att[l]), B * N, T, d, s,
                     nbytes=4.0 * self.qkv.element_size() * M * d)
@@ -389,9 +390,10 @@ class LayoutEngine:
         if self.cfg.attention == "clip":
             fl = 2.5 * 4.0 * B * d * N * N * T * (T + 1) / 2.0       # ALGORITHMIC: 5 products against the forward's 2 (the two-kernel
                                                                      # backward recomputes S and dP: 7 are executed)
-            self._timed("attn_clip_bwd", fl, "vlg_attention_clip_bwd", ptr(self.qkv[l]), ptr(batch["valid"]) if self.padded_slots else 0,
-                        ptr(self.att[l]), ptr(self.dh), ptr(self.lse[l]), ptr(self.delta), ptr(self.dqkv), B, T, N, d, s,
-                        nbytes=28.0 * M * d)
+            e = self.qkv.element_size()                             # qkv, out, dout read, dqkv written (+ qkv, dout again)
+            self._timed("attn_clip_bwd", fl, "vlg_attention_clip_bwd" + self._sfx, ptr(self.qkv[l]),
+                        ptr(batch["valid"]) if self.padded_slots else 0, ptr(self.att[l]), ptr(self.dh), ptr(self.lse[l]),
+                        ptr(self.delta), ptr(self.dqkv), B, T, N, d, s, nbytes=7.0 * e * M * d)
             return
         self._timed("attn_bwd", 0.0, "vlg_attention_bwd" + self._sfx, ptr(self.qkv[l]), ptr(self.dh), ptr(self.dqkv), B * N, T, d, s,
                     nbytes=7.0 * self.qkv.element_size() * M * d)
