@@ -9,8 +9,20 @@ import os
 
 import torch
 
+from conftest import assert_close
 from oracle import layout_spec as O
 from vlg.spec import ADAM_BETA1, ADAM_BETA2, ADAM_EPS, ADAM_LR, LayoutConfig, param_layout, param_shapes
+
+
+def check_close(got, want, rtol=1e-4, atol=1e-5, what=""):
+    """conftest.assert_close after refusing non-finite values: a NaN passes its `err > tol` test, so an output element a
+    kernel never wrote (buffers start as NaN sentinels or torch.empty) or a NaN / inf it computed would otherwise pass.
+    Every GPU comparison goes through this; a comparison that legitimately holds NaN states the NaN positions itself."""
+    g = got.detach().cpu()
+    bad = ~torch.isfinite(g)
+    assert not bool(bad.any()), "%s: %d/%d elements not finite (never written, or NaN / inf computed)" % (
+        what, int(bad.sum()), bad.numel())
+    assert_close(g, want, rtol=rtol, atol=atol, what=what)
 
 
 class OracleEngine:

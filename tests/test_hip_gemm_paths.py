@@ -18,7 +18,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import assert_close
+from helpers import check_close
 from test_hip_ops import BF_OUT
 
 EPI_NONE, EPI_BIAS, EPI_GELU, EPI_RESID, EPI_DGELU, EPI_BF16 = 0, 1, 2, 4, 8, 16
@@ -33,16 +33,6 @@ SPARE_ROWS = 136                              # more than one 128-row tile below
 
 def _cdiv(a, b):
     return -(-a // b)
-
-
-def check_close(got, want, rtol=1e-4, atol=1e-5, what=""):
-    """conftest.assert_close after refusing non-finite values: a NaN passes its `err > tol` test, and every output here
-    starts as a NaN sentinel, so an element the kernel never wrote would otherwise pass."""
-    g = got.detach().cpu()
-    bad = ~torch.isfinite(g)
-    assert not bool(bad.any()), "%s: %d/%d elements not finite (never written, or NaN / inf computed)" % (
-        what, int(bad.sum()), bad.numel())
-    assert_close(g, want, rtol=rtol, atol=atol, what=what)
 
 
 # ------------------------------------------------------------------------------------------------ dispatch mirror

@@ -10,7 +10,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import GOLDEN, assert_close
+from conftest import GOLDEN
+from helpers import check_close
 from oracle import gridnet_spec as G
 
 pytestmark = pytest.mark.gpu
@@ -18,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 def rel_close(got, want, tol=1e-4, what=""):
     scale = max(float(want.abs().max()), 1e-12)
-    assert_close(got.cpu() / scale, want / scale, rtol=tol, atol=tol * 0.2, what=what)
+    check_close(got.cpu() / scale, want / scale, rtol=tol, atol=tol * 0.2, what=what)
 
 
 def kink_tolerant(got, want, what):
@@ -209,12 +210,12 @@ def test_upsample_matches_torch(dev):
     hip.call("vlg_upsample2x_fwd", ti.ptr, to.ptr, b, h, w, ti.cp, S)
     out = torch.empty(b, C, 2 * h, 2 * w, device=dev)
     hip.call("vlg_padded_to_nchw", to.ptr, out.data_ptr(), b, C, 2 * h, 2 * w, to.cp, S)
-    assert_close(out, y.detach(), rtol=1e-5, atol=1e-6, what="upsample fwd")
+    check_close(out, y.detach(), rtol=1e-5, atol=1e-6, what="upsample fwd")
     hip.call("vlg_nchw_to_padded", rd.data_ptr(), tg.ptr, b, C, 2 * h, 2 * w, tg.cp, -1, S)
     hip.call("vlg_upsample2x_bwd", tg.ptr, tgi.ptr, b, h, w, tgi.cp, 0, S)
     dxo = torch.empty(b, C, h, w, device=dev)
     hip.call("vlg_padded_to_nchw", tgi.ptr, dxo.data_ptr(), b, C, h, w, tgi.cp, S)
-    assert_close(dxo, x.grad, rtol=1e-5, atol=1e-5, what="upsample bwd")
+    check_close(dxo, x.grad, rtol=1e-5, atol=1e-5, what="upsample bwd")
 
 
 def test_fill_coords_matches_reference_addcoords(dev):

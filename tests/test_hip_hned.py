@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, assert_close
+from conftest import GOLDEN
+from helpers import check_close
 from oracle import hned_spec as HS
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +24,7 @@ def test_hned_matches_reference_outputs(dev, tag):
     assert net.reference_shapes() == {k: tuple(v) for k, v in HS.param_shapes().items()}
     net.load_state_dict(HS.test_params(0))
     out = net.forward(x.to(dev))
-    assert_close(out, torch.from_numpy(z[tag + "_out"]), rtol=1e-4, atol=1e-5, what="HED d1..d5, fuse")
+    check_close(out, torch.from_numpy(z[tag + "_out"]), rtol=1e-4, atol=1e-5, what="HED d1..d5, fuse")
 
 
 def test_hned_256_against_restatement(dev):
@@ -33,4 +34,4 @@ def test_hned_256_against_restatement(dev):
     net = HNEDHIP(1, 256, 256, dev)
     net.load_state_dict(p)
     want = torch.stack([o[:, 0] for o in HS.forward(p, x)])
-    assert_close(net.forward(x.to(dev)), want, rtol=1e-4, atol=1e-5, what="HED 256x256")
+    check_close(net.forward(x.to(dev)), want, rtol=1e-4, atol=1e-5, what="HED 256x256")

@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, assert_close
+from conftest import GOLDEN
+from helpers import check_close
 from oracle import image_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -105,7 +106,7 @@ def test_adam_matches_reference_golden(H, dev):
         g = torch.from_numpy(z["g%d" % s]).to(dev)
         H.call("vlg_adam_step", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), 16, s, 2e-4, 0.5, 0.999, 1e-8,
                1.0, S())
-        assert_close(p, torch.from_numpy(z["p%d" % s]), rtol=1e-6, atol=1e-7, what="adam golden step %d" % s)
+        check_close(p, torch.from_numpy(z["p%d" % s]), rtol=1e-6, atol=1e-7, what="adam golden step %d" % s)
 
 
 def test_flip_is_an_involution_and_losses_are_flip_invariant(H, dev):

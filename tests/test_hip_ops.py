@@ -10,7 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import assert_close
+from helpers import check_close
 from oracle import layout_spec as O
 
 pytestmark = pytest.mark.gpu
@@ -58,14 +58,14 @@ def test_clip_attention_fwd_bwd(H, dev, B, T, N, d, masked):
     lse = torch.full((B * heads * S,), float("nan"), device=dev)
     H.call("vlg_attention_clip_fwd", qd.data_ptr(), H.ptr(vd), out.data_ptr(), lse.data_ptr(), B, T, N, d, stream())
     got = out.view(B, N, T, d).permute(0, 2, 1, 3)
-    assert_close(got, want.detach(), rtol=1e-4, atol=2e-5, what="clip attention fwd")
+    check_close(got, want.detach(), rtol=1e-4, atol=2e-5, what="clip attention fwd")
     dqkv = torch.full((M, 3 * d), float("nan"), device=dev)
     delta = torch.full((B * heads * S,), float("nan"), device=dev)
     H.call("vlg_attention_clip_bwd", qd.data_ptr(), H.ptr(vd), out.data_ptr(), gd.data_ptr(), lse.data_ptr(), delta.data_ptr(),
            dqkv.data_ptr(), B, T, N, d, stream())
     gq = dqkv.view(B, N, T, 3 * d).permute(0, 2, 1, 3)
     scale = float(q.grad.abs().max())
-    assert_close(gq.cpu() / scale, q.grad / scale, rtol=1e-4, atol=2e-5, what="clip attention bwd (dq | dk | dv)")
+    check_close(gq.cpu() / scale, q.grad / scale, rtol=1e-4, atol=2e-5, what="clip attention bwd (dq | dk | dv)")
     # shapes the tiles cannot hold are refused, not mangled
     assert H.load().vlg_attention_clip_fwd(qd.data_ptr(), 0, out.data_ptr(), lse.data_ptr(), 1, 3, 5, 64, stream()) == 1001
 
@@ -92,7 +92,7 @@ def test_embed_fwd_bwd(H, dev, B, T, N, d):
            pd["box_w"].data_ptr(), pd["box_b"].data_ptr(), pd["time_emb"].data_ptr(), x.data_ptr(),
            B, T, N, d, vocab, stream())
     got = x.view(B, N, T, d).permute(0, 2, 1, 3)
-    assert_close(got, want, what="embed fwd")
+    check_close(got, want, what="embed fwd")
     # backward
     dx = gy.permute(0, 2, 1, 3).contiguous().view(B * N * T, d).to(dev)
     L = vocab * d + d * 4 + d + T * d
@@ -104,7 +104,7 @@ def test_embed_fwd_bwd(H, dev, B, T, N, d):
     g = reduce_slabs(H, slabs, L, ns, L, dev)
     o = 0
     for name, n in (("cls_emb", vocab * d), ("box_w", d * 4), ("box_b", d), ("time_emb", T * d)):
-        assert_close(g[o:o + n].view(p[name].shape), q[name].grad, rtol=1e-4, atol=1e-4, what="embed d" + name)
+        check_close(g[o:o + n].view(p[name].shape), q[name].grad, rtol=1e-4, atol=1e-4, what="embed d" + name)
         o += n
 
 
@@ -134,7 +134,7 @@ def test_embed_class_table_matches_reference_embedding(H, dev):
     H.call("vlg_embed_bwd", dx.data_ptr(), ids.data_ptr(), box.data_ptr(), slabs.data_ptr(), L, slabs.numel(), B, T, N, d, vocab,
            stream())
     g = reduce_slabs(H, slabs, L, ns, L, dev)
-    assert_close(g[:vocab * d].view(vocab, d), torch.from_numpy(z["dtable"]), rtol=1e-5, atol=1e-6, what="class-table gradient")
+    check_close(g[:vocab * d].view(vocab, d), torch.from_numpy(z["dtable"]), rtol=1e-5, atol=1e-6, what="class-table gradient")
 
 
 # ----------------------------------------------------------------------- layer-norm
@@ -153,8 +153,8 @@ def test_layernorm_fwd_bwd(H, dev, rows, d):
     rstd = torch.empty(rows, device=dev)
     H.call("vlg_layernorm_fwd", xd.data_ptr(), gd.data_ptr(), bd.data_ptr(), yd.data_ptr(), mean.data_ptr(),
            rstd.data_ptr(), rows, d, 1e-5, stream())
-    assert_close(yd, y, what="ln fwd")
-    assert_close(mean, x.detach().mean(-1), what="ln mean")
+    check_close(yd, y, what="ln fwd")
+    check_close(mean, x.detach().mean(-1), what="ln mean")
     ns = H.load().vlg_layernorm_bwd_slabs(rows)
     slabs = torch.empty(ns * 2 * d, device=dev)
     res = torch.randn(rows, d)
@@ -162,15 +162,15 @@ def test_layernorm_fwd_bwd(H, dev, rows, d):
     dyd = dy.to(dev)
     H.call("vlg_layernorm_bwd", dyd.data_ptr(), xd.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gd.data_ptr(),
            dres.data_ptr(), dres.data_ptr(), slabs.data_ptr(), 2 * d, slabs.numel(), rows, d, stream())      # in place
-    assert_close(dres, res + x.grad, rtol=1e-4, atol=2e-5, what="ln dx (+residual, in place)")
+    check_close(dres, res + x.grad, rtol=1e-4, atol=2e-5, what="ln dx (+residual, in place)")
     gb = reduce_slabs(H, slabs, 2 * d, ns, 2 * d, dev)
-    assert_close(gb[:d], g.grad, rtol=1e-4, atol=1e-4, what="ln dgamma")
-    assert_close(gb[d:], b.grad, rtol=1e-4, atol=1e-4, what="ln dbeta")
+    check_close(gb[:d], g.grad, rtol=1e-4, atol=1e-4, what="ln dgamma")
+    check_close(gb[d:], b.grad, rtol=1e-4, atol=1e-4, what="ln dbeta")
     # without residual
     dx2 = torch.empty(rows, d, device=dev)
     H.call("vlg_layernorm_bwd", dyd.data_ptr(), xd.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gd.data_ptr(),
            0, dx2.data_ptr(), slabs.data_ptr(), 2 * d, slabs.numel(), rows, d, stream())
-    assert_close(dx2, x.grad, rtol=1e-4, atol=2e-5, what="ln dx")
+    check_close(dx2, x.grad, rtol=1e-4, atol=2e-5, what="ln dx")
 
 
 # ----------------------------------------------------------------------------- GEMM
@@ -187,7 +187,7 @@ def test_linear_fwd_bias(H, dev, M, N, K):
     c = torch.full((M, N), float("nan"), device=dev)
     H.call("vlg_linear_fwd", ad.data_ptr(), K, wd.data_ptr(), K, bd.data_ptr(), c.data_ptr(), N, 0, 0, M, N, K,
            H.EPI_BIAS, stream())
-    assert_close(c, want, rtol=1e-4, atol=1e-5, what="linear fwd bias")
+    check_close(c, want, rtol=1e-4, atol=1e-5, what="linear fwd bias")
 
 
 @pytest.mark.parametrize("M,N,K", [(256, 256, 64), (300, 1024, 256)])
@@ -200,11 +200,11 @@ def test_linear_fwd_gelu_and_resid(H, dev, M, N, K):
     u = torch.empty(M, N, device=dev)
     H.call("vlg_linear_fwd", ad.data_ptr(), K, wd.data_ptr(), K, bd.data_ptr(), c.data_ptr(), N, 0, u.data_ptr(),
            M, N, K, H.EPI_BIAS | H.EPI_GELU, stream())
-    assert_close(u, pre.float(), what="ffn pre-activation")
-    assert_close(c, F.gelu(pre).float(), what="ffn gelu")
+    check_close(u, pre.float(), what="ffn pre-activation")
+    check_close(c, F.gelu(pre).float(), what="ffn gelu")
     H.call("vlg_linear_fwd", ad.data_ptr(), K, wd.data_ptr(), K, bd.data_ptr(), c.data_ptr(), N, rd.data_ptr(), 0,
            M, N, K, H.EPI_BIAS | H.EPI_RESID, stream())
-    assert_close(c, (pre + r.double()).float(), what="linear + residual")
+    check_close(c, (pre + r.double()).float(), what="linear + residual")
 
 
 @pytest.mark.parametrize("M,N,K", [(256, 256, 64), (300, 1024, 256), (520, 384, 96)])
@@ -222,8 +222,8 @@ def test_linear_gelu_grad_saved_and_mul(H, dev, M, N, K):
     dsave = torch.full((M, N), float("nan"), device=dev)
     H.call("vlg_linear_fwd", ad.data_ptr(), K, wd.data_ptr(), K, bd.data_ptr(), c.data_ptr(), N, 0, dsave.data_ptr(),
            M, N, K, H.EPI_BIAS | H.EPI_GELU | H.EPI_GELU_GRAD, stream())
-    assert_close(c, F.gelu(pre).float(), what="ffn gelu (grad saved)")
-    assert_close(dsave, uu.grad.float(), rtol=1e-4, atol=1e-5, what="saved gelu'")
+    check_close(c, F.gelu(pre).float(), what="ffn gelu (grad saved)")
+    check_close(dsave, uu.grad.float(), rtol=1e-4, atol=1e-5, what="saved gelu'")
     # data gradient of the second projection: dU = (dY . W2) * saved
     K2 = 128
     dy, w2 = torch.randn(M, K2), torch.randn(K2, N) / math.sqrt(K2)
@@ -232,15 +232,15 @@ def test_linear_gelu_grad_saved_and_mul(H, dev, M, N, K):
     H.call("vlg_linear_dgrad", dyd.data_ptr(), K2, w2d.data_ptr(), N, du.data_ptr(), N, dsave.data_ptr(), M, K2, N,
            H.EPI_MUL, stream())
     want = (dy.double() @ w2.double()) * uu.grad
-    assert_close(du, want.float(), rtol=1e-4, atol=1e-5, what="dgrad * saved gelu'")
+    check_close(du, want.float(), rtol=1e-4, atol=1e-5, what="dgrad * saved gelu'")
     # the bf16 MFMA kernel takes the same flags (fp32 tensors here: operands rounded to bf16 on their way to LDS)
     H.call("vlg_linear_fwd", ad.data_ptr(), K, wd.data_ptr(), K, bd.data_ptr(), c.data_ptr(), N, 0, dsave.data_ptr(),
            M, N, K, H.EPI_BIAS | H.EPI_GELU | H.EPI_GELU_GRAD | H.EPI_BF16, stream())
-    assert_close(c, F.gelu(pre).float(), rtol=2e-2, atol=2e-2, what="ffn gelu (grad saved, bf16 MFMA)")
-    assert_close(dsave, uu.grad.float(), rtol=2e-2, atol=2e-2, what="saved gelu' (bf16 MFMA)")
+    check_close(c, F.gelu(pre).float(), rtol=2e-2, atol=2e-2, what="ffn gelu (grad saved, bf16 MFMA)")
+    check_close(dsave, uu.grad.float(), rtol=2e-2, atol=2e-2, what="saved gelu' (bf16 MFMA)")
     H.call("vlg_linear_dgrad", dyd.data_ptr(), K2, w2d.data_ptr(), N, du.data_ptr(), N, dsave.data_ptr(), M, K2, N,
            H.EPI_MUL | H.EPI_BF16, stream())
-    assert_close(du, ((dy.double() @ w2.double()) * dsave.double().cpu()).float(), rtol=2e-2, atol=3e-2, what="dgrad * saved (bf16 MFMA)")
+    check_close(du, ((dy.double() @ w2.double()) * dsave.double().cpu()).float(), rtol=2e-2, atol=3e-2, what="dgrad * saved (bf16 MFMA)")
     # the split-bf16 fp32 mode refuses the flags instead of ignoring them
     lib = H.load()
     assert lib.vlg_linear_fwd(ad.data_ptr(), K, wd.data_ptr(), K, bd.data_ptr(), c.data_ptr(), N, 0, dsave.data_ptr(),
@@ -280,10 +280,10 @@ def test_linear_dgrad_wgrad_is_the_two_calls(H, dev, M, N, K, mul):
     want_dx = dy.double() @ w.double()
     if mul:
         want_dx = want_dx * aux.double()
-    assert_close(out[1][0], want_dx.float(), rtol=1e-4, atol=1e-4, what="paired dgrad")
+    check_close(out[1][0], want_dx.float(), rtol=1e-4, atol=1e-4, what="paired dgrad")
     g = out[1][1].cpu()
-    assert_close(g[:N * K].view(N, K), (dy.double().t() @ x.double()).float(), rtol=1e-4, atol=2e-3, what="paired wgrad")
-    assert_close(g[N * K:], dy.double().sum(0).float(), rtol=1e-4, atol=1e-3, what="paired bias gradient")
+    check_close(g[:N * K].view(N, K), (dy.double().t() @ x.double()).float(), rtol=1e-4, atol=2e-3, what="paired wgrad")
+    check_close(g[N * K:], dy.double().sum(0).float(), rtol=1e-4, atol=1e-3, what="paired bias gradient")
 
 
 @pytest.mark.parametrize("M,N,K,mul,dy16", [(4096, 256, 1024, True, False), (4096, 1024, 256, False, True), (2048, 256, 256, False, False),
@@ -328,20 +328,20 @@ def test_linear_chained_tiles(H, dev):
         ad, wd, bd = a.to(dev), w.to(dev), b.to(dev)
         c = torch.full((M, N), float("nan"), device=dev)
         H.call("vlg_linear_fwd", ad.data_ptr(), K, wd.data_ptr(), K, bd.data_ptr(), c.data_ptr(), N, 0, 0, M, N, K, H.EPI_BIAS, stream())
-        assert_close(c, pre.float(), rtol=1e-4, atol=1e-5, what="chained fwd bias")
+        check_close(c, pre.float(), rtol=1e-4, atol=1e-5, what="chained fwd bias")
         dsave = torch.full((M, N), float("nan"), device=dev)
         H.call("vlg_linear_fwd", ad.data_ptr(), K, wd.data_ptr(), K, bd.data_ptr(), c.data_ptr(), N, 0, dsave.data_ptr(), M, N, K,
                H.EPI_BIAS | H.EPI_GELU | H.EPI_GELU_GRAD, stream())
         uu = pre.clone().requires_grad_(True)
         F.gelu(uu).sum().backward()
-        assert_close(c, F.gelu(pre).float(), what="chained gelu")
-        assert_close(dsave, uu.grad.float(), rtol=1e-4, atol=1e-5, what="chained saved gelu'")
+        check_close(c, F.gelu(pre).float(), what="chained gelu")
+        check_close(dsave, uu.grad.float(), rtol=1e-4, atol=1e-5, what="chained saved gelu'")
         # data gradient into a wide output: dX[M, N] = dY[M, K] . W2[K, N], times the saved derivative
         dy, w2 = torch.randn(M, K), torch.randn(K, N) / math.sqrt(K)
         dyd, w2d = dy.to(dev), w2.to(dev)
         dx = torch.full((M, N), float("nan"), device=dev)
         H.call("vlg_linear_dgrad", dyd.data_ptr(), K, w2d.data_ptr(), N, dx.data_ptr(), N, dsave.data_ptr(), M, K, N, H.EPI_MUL, stream())
-        assert_close(dx, ((dy.double() @ w2.double()) * uu.grad).float(), rtol=1e-4, atol=1e-5, what="chained dgrad * saved")
+        check_close(dx, ((dy.double() @ w2.double()) * uu.grad).float(), rtol=1e-4, atol=1e-5, what="chained dgrad * saved")
 
 
 @pytest.mark.parametrize("M,N,K", [(256, 256, 1024), (300, 128, 512), (1000, 256, 96)])
@@ -356,17 +356,17 @@ def test_linear_gelu_on_load(H, dev, M, N, K):
     c = torch.full((M, N), float("nan"), device=dev)
     H.call("vlg_linear_fwd", ud.data_ptr(), K, wd.data_ptr(), K, bd.data_ptr(), c.data_ptr(), N, rd.data_ptr(), 0,
            M, N, K, H.EPI_BIAS | H.EPI_RESID | H.EPI_ACT_GELU, stream())
-    assert_close(c, (F.linear(g, w.double(), b.double()) + r.double()).float(), rtol=1e-4, atol=1e-5, what="gelu-on-load fwd")
+    check_close(c, (F.linear(g, w.double(), b.double()) + r.double()).float(), rtol=1e-4, atol=1e-5, what="gelu-on-load fwd")
     assert torch.equal(ud.cpu(), u)                                      # the stored pre-activation is untouched
-    ns = H.load().vlg_linear_wgrad_slabs(M, N, K)
+    ns = H.load().vlg_linear_wgrad_slabs_for(M, N, K, H.EPI_ACT_GELU)     # the flag's own split plan: no NaN slab left over
     stride = N * K + N
     slabs = torch.full((ns * stride,), float("nan"), device=dev)
     H.call("vlg_linear_wgrad", dyd.data_ptr(), N, ud.data_ptr(), K, slabs.data_ptr(), stride, slabs.numel(), M, N, K,
            H.EPI_ACT_GELU, stream())
     gr = reduce_slabs(H, slabs, stride, ns, stride, dev)
     sc = math.sqrt(M)
-    assert_close(gr[:N * K].view(N, K) / sc, (dy.double().t() @ g).float() / sc, rtol=1e-4, atol=1e-5, what="gelu-on-load wgrad")
-    assert_close(gr[N * K:] / sc, dy.double().sum(0).float() / sc, rtol=1e-4, atol=1e-5, what="bias grad")
+    check_close(gr[:N * K].view(N, K) / sc, (dy.double().t() @ g).float() / sc, rtol=1e-4, atol=1e-5, what="gelu-on-load wgrad")
+    check_close(gr[N * K:] / sc, dy.double().sum(0).float() / sc, rtol=1e-4, atol=1e-5, what="bias grad")
     # only the native fp32 path implements it: the other modes refuse instead of silently ignoring the flag
     rc = H.load().vlg_linear_fwd(ud.data_ptr(), K, wd.data_ptr(), K, bd.data_ptr(), c.data_ptr(), N, rd.data_ptr(), 0,
                                  M, N, K, H.EPI_BIAS | H.EPI_RESID | H.EPI_ACT_GELU | H.EPI_BF16, stream())
@@ -380,22 +380,22 @@ def test_linear_dgrad_wgrad(H, dev, M, N, K):
     dyd, wd, xd = dy.to(dev), w.to(dev), x.to(dev)
     dx = torch.empty(M, K, device=dev)
     H.call("vlg_linear_dgrad", dyd.data_ptr(), N, wd.data_ptr(), K, dx.data_ptr(), K, 0, M, N, K, H.EPI_NONE, stream())
-    assert_close(dx, (dy.double() @ w.double()).float(), rtol=1e-4, atol=1e-5, what="dgrad")
+    check_close(dx, (dy.double() @ w.double()).float(), rtol=1e-4, atol=1e-5, what="dgrad")
     u = torch.randn(M, K)
     ud = u.to(dev)
     H.call("vlg_linear_dgrad", dyd.data_ptr(), N, wd.data_ptr(), K, dx.data_ptr(), K, ud.data_ptr(), M, N, K,
            H.EPI_DGELU, stream())
     uu = u.double().requires_grad_(True)
     F.gelu(uu).backward(dy.double() @ w.double())
-    assert_close(dx, uu.grad.float(), rtol=1e-4, atol=1e-5, what="dgrad * gelu'")
+    check_close(dx, uu.grad.float(), rtol=1e-4, atol=1e-5, what="dgrad * gelu'")
     ns = H.load().vlg_linear_wgrad_slabs(M, N, K)
     stride = N * K + N
     slabs = torch.full((ns * stride,), float("nan"), device=dev)
     H.call("vlg_linear_wgrad", dyd.data_ptr(), N, xd.data_ptr(), K, slabs.data_ptr(), stride, slabs.numel(), M, N, K, 0, stream())
     g = reduce_slabs(H, slabs, stride, ns, stride, dev)
     sc = math.sqrt(M)
-    assert_close(g[:N * K].view(N, K) / sc, (dy.double().t() @ x.double()).float() / sc, rtol=1e-4, atol=1e-5, what="wgrad")
-    assert_close(g[N * K:] / sc, dy.double().sum(0).float() / sc, rtol=1e-4, atol=1e-5, what="bias grad")
+    check_close(g[:N * K].view(N, K) / sc, (dy.double().t() @ x.double()).float() / sc, rtol=1e-4, atol=1e-5, what="wgrad")
+    check_close(g[N * K:] / sc, dy.double().sum(0).float() / sc, rtol=1e-4, atol=1e-5, what="bias grad")
 
 
 # ------------------------------------------------------------------------ attention
@@ -411,11 +411,11 @@ def test_attention_fwd_bwd(H, dev, T, d, n_seq):
     qd = to_int(qkv.detach()).to(dev)
     o = torch.full((n_seq * T, d), float("nan"), device=dev)
     H.call("vlg_attention_fwd", qd.data_ptr(), o.data_ptr(), n_seq, T, d, stream())
-    assert_close(o, to_int(want.detach()), what="attention fwd")
+    check_close(o, to_int(want.detach()), what="attention fwd")
     dod = to_int(do).to(dev)
     dq = torch.full((n_seq * T, 3 * d), float("nan"), device=dev)
     H.call("vlg_attention_bwd", qd.data_ptr(), dod.data_ptr(), dq.data_ptr(), n_seq, T, d, stream())
-    assert_close(dq, to_int(qkv.grad), rtol=1e-4, atol=2e-5, what="attention bwd")
+    check_close(dq, to_int(qkv.grad), rtol=1e-4, atol=2e-5, what="attention bwd")
 
 
 # ----------------------------------------------------------------------------- loss
@@ -437,9 +437,9 @@ def test_layout_loss(H, dev, B, T, N, var):
     H.call("vlg_layout_loss", out.data_ptr(), 24, tc.data_ptr(), tb.data_ptr(), va.data_ptr(), dout.data_ptr(),
            loss.data_ptr(), scratch.data_ptr(), B, T, N, 20, O.SMOOTH_L1_BETA, O.IOU_EPS, O.W_REG, O.W_IOU, O.W_CE,
            stream())
-    assert_close(loss, torch.stack([x.detach() for x in parts]), rtol=1e-4, atol=1e-6, what="loss values")
+    check_close(loss, torch.stack([x.detach() for x in parts]), rtol=1e-4, atol=1e-6, what="loss values")
     want = torch.cat([to_int(logits.grad), to_int(raw.grad)], dim=1)
-    assert_close(dout, want, rtol=1e-4, atol=1e-7, what="loss grads")
+    check_close(dout, want, rtol=1e-4, atol=1e-7, what="loss grads")
 
 
 def test_layout_loss_all_masked(H, dev):
@@ -464,7 +464,7 @@ def test_reduce_slabs(H, dev):
     for n, L, stride in ((1, 8, 8), (7, 1000, 1024), (41, 4096, 4096)):
         s = torch.randn(n, stride)
         got = reduce_slabs(H, s.to(dev).flatten(), stride, n, L, dev)
-        assert_close(got, s[:, :L].double().sum(0).float(), rtol=1e-5, atol=1e-5, what="reduce_slabs")
+        check_close(got, s[:, :L].double().sum(0).float(), rtol=1e-5, atol=1e-5, what="reduce_slabs")
 
 
 def test_adam_matches_torch_optim(H, dev):
@@ -484,7 +484,7 @@ def test_adam_matches_torch_optim(H, dev):
         gd = (g * 4).to(dev)            # grad_scale 0.25 undoes the x4: models all-reduce SUM over 4 ranks
         H.call("vlg_adam_step", p.data_ptr(), gd.data_ptr(), m.data_ptr(), v.data_ptr(), n, step, 2e-4, 0.5, 0.999,
                1e-8, 0.25, stream())
-        assert_close(p, ref.detach(), rtol=1e-6, atol=1e-7, what="adam step %d" % step)
+        check_close(p, ref.detach(), rtol=1e-6, atol=1e-7, what="adam step %d" % step)
 
 
 def test_bad_arguments_raise(H, dev):
@@ -525,17 +525,17 @@ def test_layernorm_bf16_storage(H, dev, rows, d):
     mean, rstd = torch.empty(rows, device=dev), torch.empty(rows, device=dev)
     H.call("vlg_layernorm_fwd_bf16", xd.data_ptr(), gd.data_ptr(), bd.data_ptr(), yd.data_ptr(), mean.data_ptr(),
            rstd.data_ptr(), rows, d, 1e-5, stream())
-    assert_close(yd.float(), y.detach(), what="ln fwd -> bf16", **BF_OUT)
+    check_close(yd.float(), y.detach(), what="ln fwd -> bf16", **BF_OUT)
     ns = H.load().vlg_layernorm_bwd_slabs(rows)
     slabs = torch.empty(ns * 2 * d, device=dev)
     res = torch.randn(rows, d)
     dres, dyd = res.to(dev), dy.to(dev).to(BF)
     H.call("vlg_layernorm_bwd_bf16", dyd.data_ptr(), xd.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gd.data_ptr(),
            dres.data_ptr(), dres.data_ptr(), slabs.data_ptr(), 2 * d, slabs.numel(), rows, d, stream())
-    assert_close(dres, res + x.grad, rtol=1e-4, atol=2e-5, what="ln dx from bf16 dy")
+    check_close(dres, res + x.grad, rtol=1e-4, atol=2e-5, what="ln dx from bf16 dy")
     gb = reduce_slabs(H, slabs, 2 * d, ns, 2 * d, dev)
-    assert_close(gb[:d], g.grad, rtol=1e-4, atol=1e-4, what="ln dgamma from bf16 dy")
-    assert_close(gb[d:], b.grad, rtol=1e-4, atol=1e-4, what="ln dbeta from bf16 dy")
+    check_close(gb[:d], g.grad, rtol=1e-4, atol=1e-4, what="ln dgamma from bf16 dy")
+    check_close(gb[d:], b.grad, rtol=1e-4, atol=1e-4, what="ln dbeta from bf16 dy")
 
 
 @pytest.mark.parametrize("T,d,n_seq", [(4, 64, 5), (8, 128, 3), (16, 256, 6), (32, 128, 3)])
@@ -549,11 +549,11 @@ def test_attention_bf16_storage(H, dev, T, d, n_seq):
     qd = to_int(qkv.detach()).to(dev).to(BF)
     o = torch.zeros(n_seq * T, d, device=dev, dtype=BF)
     H.call("vlg_attention_fwd_bf16", qd.data_ptr(), o.data_ptr(), n_seq, T, d, stream())
-    assert_close(o.float(), to_int(want.detach()), what="attention fwd (bf16 storage)", **BF_OUT)
+    check_close(o.float(), to_int(want.detach()), what="attention fwd (bf16 storage)", **BF_OUT)
     dod = to_int(do).to(dev).to(BF)
     dq = torch.zeros(n_seq * T, 3 * d, device=dev, dtype=BF)
     H.call("vlg_attention_bwd_bf16", qd.data_ptr(), dod.data_ptr(), dq.data_ptr(), n_seq, T, d, stream())
-    assert_close(dq.float(), to_int(qkv.grad), rtol=2.0 ** -7, atol=1e-5, what="attention bwd (bf16 storage)")
+    check_close(dq.float(), to_int(qkv.grad), rtol=2.0 ** -7, atol=1e-5, what="attention bwd (bf16 storage)")
 
 
 @pytest.mark.parametrize("M,N,K", [(256, 128, 64), (200, 768, 256), (333, 256, 1024)])
@@ -572,17 +572,17 @@ def test_linear_bf16_storage(H, dev, M, N, K):
     c = torch.zeros(M, N, device=dev, dtype=BF)
     H.call("vlg_linear_fwd", ad.data_ptr(), K, wd.data_ptr(), K, bd.data_ptr(), c.data_ptr(), N, 0, 0, M, N, K,
            H.EPI_BIAS | FL | H.EPI_A_BF16 | WB | H.EPI_OUT_BF16, stream())
-    assert_close(c.float(), ref.float(), what="fwd bias (bf16 in/out)", **BF_OUT)
+    check_close(c.float(), ref.float(), what="fwd bias (bf16 in/out)", **BF_OUT)
     u = torch.zeros(M, N, device=dev, dtype=BF)
     H.call("vlg_linear_fwd", ad.data_ptr(), K, wd.data_ptr(), K, bd.data_ptr(), c.data_ptr(), N, 0, u.data_ptr(), M, N, K,
            H.EPI_BIAS | H.EPI_GELU | FL | H.EPI_A_BF16 | WB | H.EPI_OUT_BF16, stream())
-    assert_close(u.float(), ref.float(), what="fwd pre-activation (bf16)", **BF_OUT)
-    assert_close(c.float(), F.gelu(ref).float(), what="fwd gelu (bf16)", rtol=2.0 ** -7, atol=2e-6)
+    check_close(u.float(), ref.float(), what="fwd pre-activation (bf16)", **BF_OUT)
+    check_close(c.float(), F.gelu(ref).float(), what="fwd gelu (bf16)", rtol=2.0 ** -7, atol=2e-6)
     resid = torch.randn(M, N)
     rd, c32 = resid.to(dev), torch.zeros(M, N, device=dev)
     H.call("vlg_linear_fwd", ad.data_ptr(), K, wd.data_ptr(), K, bd.data_ptr(), c32.data_ptr(), N, rd.data_ptr(), 0, M, N, K,
            H.EPI_BIAS | H.EPI_RESID | FL | H.EPI_A_BF16 | WB, stream())
-    assert_close(c32, (ref + resid.double()).float(), rtol=1e-4, atol=1e-5, what="fwd bias+resid (bf16 A, fp32 out)")
+    check_close(c32, (ref + resid.double()).float(), rtol=1e-4, atol=1e-5, what="fwd bias+resid (bf16 A, fp32 out)")
     # data gradient: dY fp32 or bf16 -> dX bf16; with gelu' of a bf16 pre-activation
     dy = _bf(torch.randn(M, N))
     dref = dy.double() @ w.double()
@@ -590,7 +590,7 @@ def test_linear_bf16_storage(H, dev, M, N, K):
         dx = torch.zeros(M, K, device=dev, dtype=BF)
         H.call("vlg_linear_dgrad", dy_dev.data_ptr(), N, wd.data_ptr(), K, dx.data_ptr(), K, 0, M, N, K,
                FL | bits | WB | H.EPI_OUT_BF16, stream())
-        assert_close(dx.float(), dref.float(), what="dgrad -> bf16 (%s)" % tag, rtol=2.0 ** -7, atol=1e-5)
+        check_close(dx.float(), dref.float(), what="dgrad -> bf16 (%s)" % tag, rtol=2.0 ** -7, atol=1e-5)
     pre = _bf(torch.randn(M, K))
     pd = pre.to(dev).to(BF)
     dx = torch.zeros(M, K, device=dev, dtype=BF)
@@ -598,7 +598,7 @@ def test_linear_bf16_storage(H, dev, M, N, K):
            H.EPI_DGELU | FL | WB | H.EPI_OUT_BF16, stream())
     uu = pre.double().requires_grad_(True)
     F.gelu(uu).backward(dref)
-    assert_close(dx.float(), uu.grad.float(), what="dgrad * gelu' (bf16 aux/out)", rtol=2.0 ** -7, atol=1e-5)
+    check_close(dx.float(), uu.grad.float(), what="dgrad * gelu' (bf16 aux/out)", rtol=2.0 ** -7, atol=1e-5)
     # weight gradient: (fp32 | bf16) dY with bf16 X -> fp32 slabs
     x = _bf(torch.randn(M, K))
     xd = x.to(dev).to(BF)
@@ -610,9 +610,9 @@ def test_linear_bf16_storage(H, dev, M, N, K):
         H.call("vlg_linear_wgrad", dy_dev.data_ptr(), N, xd.data_ptr(), K, slabs.data_ptr(), stride, slabs.numel(), M, N, K,
                FL | bits | H.EPI_B_BF16, stream())
         g = reduce_slabs(H, slabs, stride, ns, stride, dev)
-        assert_close(g[:N * K].view(N, K) / sc, (dy.double().t() @ x.double()).float() / sc, rtol=1e-4, atol=1e-5,
+        check_close(g[:N * K].view(N, K) / sc, (dy.double().t() @ x.double()).float() / sc, rtol=1e-4, atol=1e-5,
                      what="wgrad (%s, bf16 X)" % tag)
-        assert_close(g[N * K:] / sc, dy.double().sum(0).float() / sc, rtol=1e-4, atol=1e-5, what="bias grad (%s)" % tag)
+        check_close(g[N * K:] / sc, dy.double().sum(0).float() / sc, rtol=1e-4, atol=1e-5, what="bias grad (%s)" % tag)
     # storage flags without the bf16 MFMA flag, or a combination no step uses, are refused
     with pytest.raises(H.HipError):
         H.call("vlg_linear_fwd", ad.data_ptr(), K, wd.data_ptr(), K, bd.data_ptr(), c.data_ptr(), N, 0, 0, M, N, K,
@@ -654,20 +654,20 @@ def test_linear_split3_is_fp32_grade(H, dev, M, N, K):
         c = torch.zeros(M, N, device=dev)
         H.call("vlg_linear_fwd", ad.data_ptr(), K, wd.data_ptr(), K, bd.data_ptr(), c.data_ptr(), N, 0, 0, M, N, K,
                H.EPI_BIAS | fl, stream())
-        assert_close(c, ref.float(), rtol=1e-4, atol=1e-5, what="fwd bias (%s)" % tag)
+        check_close(c, ref.float(), rtol=1e-4, atol=1e-5, what="fwd bias (%s)" % tag)
         err[tag] = float((c.cpu().double() - ref).abs().max())
     assert err["split"] <= 4 * err["native"] + 1e-7, err
     if N > 32:
         u, c = torch.zeros(M, N, device=dev), torch.zeros(M, N, device=dev)
         H.call("vlg_linear_fwd", ad.data_ptr(), K, wd.data_ptr(), K, bd.data_ptr(), c.data_ptr(), N, 0, u.data_ptr(), M, N, K,
                H.EPI_BIAS | H.EPI_GELU | S3, stream())
-        assert_close(u, ref.float(), rtol=1e-4, atol=1e-5, what="split fwd pre-activation")
-        assert_close(c, F.gelu(ref).float(), rtol=1e-4, atol=1e-5, what="split fwd gelu")
+        check_close(u, ref.float(), rtol=1e-4, atol=1e-5, what="split fwd pre-activation")
+        check_close(c, F.gelu(ref).float(), rtol=1e-4, atol=1e-5, what="split fwd gelu")
         resid = torch.randn(M, N)
         rd = resid.to(dev)
         H.call("vlg_linear_fwd", ad.data_ptr(), K, wd.data_ptr(), K, bd.data_ptr(), c.data_ptr(), N, rd.data_ptr(), 0, M, N, K,
                H.EPI_BIAS | H.EPI_RESID | S3, stream())
-        assert_close(c, (ref + resid.double()).float(), rtol=1e-4, atol=1e-5, what="split fwd bias+resid")
+        check_close(c, (ref + resid.double()).float(), rtol=1e-4, atol=1e-5, what="split fwd bias+resid")
     if N % 8:
         return
     dy = torch.randn(M, N)
@@ -675,7 +675,7 @@ def test_linear_split3_is_fp32_grade(H, dev, M, N, K):
     dref = dy.double() @ w.double()
     dx = torch.zeros(M, K, device=dev)
     H.call("vlg_linear_dgrad", dyd.data_ptr(), N, wd.data_ptr(), K, dx.data_ptr(), K, 0, M, N, K, S3, stream())
-    assert_close(dx, dref.float(), rtol=1e-4, atol=1e-5, what="split dgrad")
+    check_close(dx, dref.float(), rtol=1e-4, atol=1e-5, what="split dgrad")
     if N > 32:
         pre = torch.randn(M, K)
         pd = pre.to(dev)
@@ -683,7 +683,7 @@ def test_linear_split3_is_fp32_grade(H, dev, M, N, K):
                H.EPI_DGELU | S3, stream())
         uu = pre.double().requires_grad_(True)
         F.gelu(uu).backward(dref)
-        assert_close(dx, uu.grad.float(), rtol=1e-4, atol=1e-5, what="split dgrad * gelu'")
+        check_close(dx, uu.grad.float(), rtol=1e-4, atol=1e-5, what="split dgrad * gelu'")
     x = torch.randn(M, K)
     xd = x.to(dev)
     ns = H.load().vlg_linear_wgrad_slabs_for(M, N, K, S3)
@@ -692,8 +692,8 @@ def test_linear_split3_is_fp32_grade(H, dev, M, N, K):
     H.call("vlg_linear_wgrad", dyd.data_ptr(), N, xd.data_ptr(), K, slabs.data_ptr(), stride, slabs.numel(), M, N, K, S3, stream())
     g = reduce_slabs(H, slabs, stride, ns, stride, dev)
     sc = math.sqrt(M)
-    assert_close(g[:N * K].view(N, K) / sc, (dy.double().t() @ x.double()).float() / sc, rtol=1e-4, atol=1e-5, what="split wgrad")
-    assert_close(g[N * K:] / sc, dy.double().sum(0).float() / sc, rtol=1e-4, atol=1e-5, what="split bias grad")
+    check_close(g[:N * K].view(N, K) / sc, (dy.double().t() @ x.double()).float() / sc, rtol=1e-4, atol=1e-5, what="split wgrad")
+    check_close(g[N * K:] / sc, dy.double().sum(0).float() / sc, rtol=1e-4, atol=1e-5, what="split bias grad")
     with pytest.raises(H.HipError):                                  # the split is an fp32-tensor mode
         H.call("vlg_linear_dgrad", dyd.data_ptr(), N, wd.data_ptr(), K, dx.data_ptr(), K, 0, M, N, K, S3 | H.EPI_BF16, stream())
 

@@ -7,7 +7,7 @@ section 0); tolerance 1e-4 relative with a small absolute floor, written per che
 import pytest
 import torch
 
-from conftest import assert_close
+from helpers import check_close
 from oracle import layout_spec as O
 
 pytestmark = pytest.mark.gpu
@@ -48,14 +48,14 @@ def test_step_matches_oracle(dev, kw, variable_n, precision):
     batch = O.synthetic_batch(cfg.B, cfg.T, cfg.N, seed=7, variable_n=variable_n, min_valid=3)
     parts, grads = O.loss_and_grads(p, batch, cfg.n_layers)
     loss = eng.forward_backward(to_dev(batch, dev))
-    assert_close(loss, torch.tensor(parts), rtol=1e-4, atol=1e-6, what="loss parts")
+    check_close(loss, torch.tensor(parts), rtol=1e-4, atol=1e-6, what="loss parts")
     logits, box_raw = O.forward(p, batch["slot_class"], batch["slot_box"], cfg.n_layers)
     gl, gb = eng.outputs_btn()
-    assert_close(gl, logits, rtol=1e-4, atol=1e-4, what="logits")
-    assert_close(gb, box_raw, rtol=1e-4, atol=1e-4, what="box outputs")
+    check_close(gl, logits, rtol=1e-4, atol=1e-4, what="logits")
+    check_close(gb, box_raw, rtol=1e-4, atol=1e-4, what="box outputs")
     for name, g in eng.named_grads().items():
         scale = max(float(grads[name].abs().max()), 1e-6)
-        assert_close(g / scale, grads[name] / scale, rtol=1e-4, atol=2e-5, what="grad " + name)
+        check_close(g / scale, grads[name] / scale, rtol=1e-4, atol=2e-5, what="grad " + name)
 
 
 @pytest.mark.parametrize("kw", [dict(B=4, T=4, N=8, d=64, n_layers=2), dict(B=2, T=16, N=12, d=256, n_layers=2),
@@ -73,14 +73,14 @@ def test_step_with_per_clip_attention_matches_oracle(dev, kw, variable_n):
     batch = O.synthetic_batch(cfg.B, cfg.T, cfg.N, seed=11, variable_n=variable_n, min_valid=3)
     parts, grads = O.loss_and_grads(p, batch, cfg.n_layers, attention="clip")
     loss = eng.forward_backward(to_dev(batch, dev))
-    assert_close(loss, torch.tensor(parts), rtol=1e-4, atol=1e-6, what="loss parts (clip attention)")
+    check_close(loss, torch.tensor(parts), rtol=1e-4, atol=1e-6, what="loss parts (clip attention)")
     logits, box_raw = O.forward(p, batch["slot_class"], batch["slot_box"], cfg.n_layers, attention="clip", valid=batch["valid"])
     gl, gb = eng.outputs_btn()
-    assert_close(gl, logits, rtol=1e-4, atol=1e-4, what="logits (clip attention)")
-    assert_close(gb, box_raw, rtol=1e-4, atol=1e-4, what="box outputs (clip attention)")
+    check_close(gl, logits, rtol=1e-4, atol=1e-4, what="logits (clip attention)")
+    check_close(gb, box_raw, rtol=1e-4, atol=1e-4, what="box outputs (clip attention)")
     for name, g in eng.named_grads().items():
         scale = max(float(grads[name].abs().max()), 1e-6)
-        assert_close(g / scale, grads[name] / scale, rtol=1e-4, atol=2e-5, what="grad %s (clip attention)" % name)
+        check_close(g / scale, grads[name] / scale, rtol=1e-4, atol=2e-5, what="grad %s (clip attention)" % name)
     # bitwise reproducible (no atomics anywhere in the two backward kernels), eager and replayed from a hipGraph
     g1 = eng.grads.clone()
     eng.forward_backward(to_dev(batch, dev))
@@ -112,7 +112,7 @@ def test_three_adam_steps_track_oracle(dev):
     for name, t in eng.named_params().items():
         sel = signal[name]
         checked += int(sel.sum())
-        assert_close(t.cpu()[sel], p[name][sel], rtol=1e-4, atol=1e-6, what="param " + name)
+        check_close(t.cpu()[sel], p[name][sel], rtol=1e-4, atol=1e-6, what="param " + name)
         # and nothing, signal or not, moved by more than 3 steps of lr (+ rounding)
         assert float((t.cpu() - p[name]).abs().max()) <= 2 * 3 * ADAM_LR * 1.01
     assert checked > 0.5 * eng.n_params
@@ -142,10 +142,10 @@ def test_full_size_properties(dev, shape):
     pb = {k: v[perm.to(dev)].contiguous() for k, v in batch.items()}
     l2 = eng.forward_backward(pb).clone()
     o2 = eng.out.view(cfg.B, -1)[torch.argsort(perm).to(dev)]
-    assert_close(o2, out0.view(cfg.B, -1), rtol=0, atol=0, what="per-clip outputs under permutation")
-    assert_close(l2, l0, rtol=1e-5, atol=1e-6, what="loss under permutation")
+    check_close(o2, out0.view(cfg.B, -1), rtol=0, atol=0, what="per-clip outputs under permutation")
+    check_close(l2, l0, rtol=1e-5, atol=1e-6, what="loss under permutation")
     gs = float(g0.abs().max())
-    assert_close(eng.grads / gs, g0 / gs, rtol=1e-4, atol=1e-5, what="grads under permutation")
+    check_close(eng.grads / gs, g0 / gs, rtol=1e-4, atol=1e-5, what="grads under permutation")
     # training makes progress
     first = float(l0[0])
     for _ in range(20):
@@ -184,18 +184,18 @@ def test_full_size_step_matches_fp64_oracle(dev, kw, precision, variable_n):
     parts, grads = O.loss_and_grads(p64, b64, cfg.n_layers)
     with torch.no_grad():
         logits, box_raw = O.forward(p64, b64["slot_class"], b64["slot_box"], cfg.n_layers)
-    # (a NaN passes assert_close's `err > tol` test: refuse non-finite results first)
+    # (a NaN passes conftest's `err > tol` test: check_close refuses non-finite results too)
     for what, t in [("loss parts", loss), ("logits", gl), ("box outputs", gb)] + [("grad " + n, g) for n, g in got.items()]:
         assert bool(torch.isfinite(t).all()), "%s: not finite" % what
-    assert_close(loss, torch.tensor(parts, dtype=torch.float64), rtol=1e-4, atol=1e-6, what="loss parts")
-    assert_close(gl, logits, rtol=1e-4, atol=1e-4, what="logits")
-    assert_close(gb, box_raw, rtol=1e-4, atol=1e-4, what="box outputs")
+    check_close(loss, torch.tensor(parts, dtype=torch.float64), rtol=1e-4, atol=1e-6, what="loss parts")
+    check_close(gl, logits, rtol=1e-4, atol=1e-4, what="logits")
+    check_close(gb, box_raw, rtol=1e-4, atol=1e-4, what="box outputs")
     worst = {}
     for name, g in got.items():
         w = grads[name]
         scale = max(float(w.abs().max()), 1e-6)
         worst[name] = float((g.double() - w).abs().max()) / scale
-        assert_close(g / scale, w / scale, rtol=1e-4, atol=2e-5, what="grad " + name)
+        check_close(g / scale, w / scale, rtol=1e-4, atol=2e-5, what="grad " + name)
     print("\nworst relative gradient error vs fp64 (%s, %s%s): %s" % (
         kw, precision, ", variable_n" if variable_n else "",
         ", ".join("%s %.2e" % (k, v) for k, v in sorted(worst.items(), key=lambda kv: -kv[1]))))
@@ -271,7 +271,7 @@ def test_bf16_mode_at_full_size(dev, shape):
     pb = {k: v[perm.to(dev)].contiguous() for k, v in batch.items()}
     eng.forward_backward(pb)
     o2 = eng.out.view(cfg.B, -1)[torch.argsort(perm).to(dev)]
-    assert_close(o2, out0.view(cfg.B, -1), rtol=0, atol=0, what="per-clip outputs under permutation (bf16)")
+    check_close(o2, out0.view(cfg.B, -1), rtol=0, atol=0, what="per-clip outputs under permutation (bf16)")
     first = float(l0[0])
     for _ in range(10):
         eng.train_step(batch)
@@ -288,10 +288,10 @@ def test_smallest_and_ragged_shapes_match_oracle(dev):
         batch = O.synthetic_batch(cfg.B, cfg.T, cfg.N, seed=5, variable_n=cfg.N > 2, min_valid=1)
         parts, grads = O.loss_and_grads(p, batch, cfg.n_layers)
         loss = eng.forward_backward(to_dev(batch, dev))
-        assert_close(loss, torch.tensor(parts), rtol=1e-4, atol=1e-6, what="loss %s" % (kw,))
+        check_close(loss, torch.tensor(parts), rtol=1e-4, atol=1e-6, what="loss %s" % (kw,))
         for name, g in eng.named_grads().items():
             scale = max(float(grads[name].abs().max()), 1e-6)
-            assert_close(g / scale, grads[name] / scale, rtol=1e-4, atol=2e-5, what="grad %s %s" % (name, kw))
+            check_close(g / scale, grads[name] / scale, rtol=1e-4, atol=2e-5, what="grad %s %s" % (name, kw))
 
 
 def test_largest_baseline_config_runs(dev):
@@ -334,11 +334,11 @@ def test_captured_step_replays_bitwise(dev, precision):
         lh = host.train_step(b).clone()
         lg = run(b).clone()
         assert torch.equal(le, lg), (le, lg)
-        assert_close(lh, le, rtol=1e-6, atol=1e-6, what="loss, host vs device step counter")
+        check_close(lh, le, rtol=1e-6, atol=1e-6, what="loss, host vs device step counter")
     assert torch.equal(graphed.params, eager.params) and torch.equal(graphed.exp_avg_sq, eager.exp_avg_sq)
     assert graphed.step_count == eager.step_count == 4
     assert int(graphed.adam_state.view(torch.int32)[2]) == 4
-    assert_close(host.params, eager.params, rtol=1e-5, atol=1e-7, what="params, host vs device step counter")
+    check_close(host.params, eager.params, rtol=1e-5, atol=1e-7, what="params, host vs device step counter")
     if precision == "bf16":
         assert torch.equal(graphed.params_bf16, graphed.params.to(torch.bfloat16))
 

@@ -6,8 +6,7 @@ import random
 import pytest
 import torch
 
-from conftest import assert_close
-from helpers import reference_args
+from helpers import check_close, reference_args
 from oracle import layout_spec as O
 
 pytestmark = pytest.mark.gpu
@@ -72,7 +71,7 @@ def test_bf16_clip_step_at_metric_shape(dev):
     pb = {k: v[perm.to(dev)].contiguous() for k, v in batch.items()}
     eng.forward_backward(pb)
     o2 = eng.out.view(cfg.B, -1)[torch.argsort(perm).to(dev)]
-    assert_close(o2, out0.view(cfg.B, -1), rtol=0, atol=0, what="per-clip outputs under permutation (bf16 + clip)")
+    check_close(o2, out0.view(cfg.B, -1), rtol=0, atol=0, what="per-clip outputs under permutation (bf16 + clip)")
     first = float(l0[0])
     for _ in range(10):
         eng.train_step(batch)

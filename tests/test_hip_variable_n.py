@@ -6,8 +6,7 @@ import random
 import pytest
 import torch
 
-from conftest import assert_close
-from helpers import reference_args
+from helpers import check_close, reference_args
 from oracle import layout_spec as O
 
 pytestmark = pytest.mark.gpu
@@ -40,11 +39,11 @@ def test_bucketed_variable_n_training(tmp_path, monkeypatch, attention):
         loss = tr.engine.forward_backward(dev_batch)
         if checked < 3:                                   # oracle comparison on the first few buckets (initial weights)
             parts, grads = O.loss_and_grads(p, batch, tr.cfg.n_layers, attention=attention)
-            assert_close(loss, torch.tensor(parts), rtol=1e-4, atol=1e-6, what="loss N=%d" % n)
+            check_close(loss, torch.tensor(parts), rtol=1e-4, atol=1e-6, what="loss N=%d" % n)
             for name in ("cls_emb", "l0.qkv_w", "l1.ff2_w", "head_w"):
                 g, w = tr.engine.named_grads()[name], grads[name]
                 s = max(float(w.abs().max()), 1e-6)
-                assert_close(g / s, w / s, rtol=1e-4, atol=2e-5, what="grad %s N=%d" % (name, n))
+                check_close(g / s, w / s, rtol=1e-4, atol=2e-5, what="grad %s N=%d" % (name, n))
             checked += 1
         # padded slots: zero gradient at the head outputs
         B, T = batch["slot_class"].shape[:2]

@@ -145,6 +145,11 @@ __global__ __launch_bounds__(GO_BLOCK) void add_rows_kernel(float* __restrict__ 
     }
 }
 
+// NaN-keeping max and ReLU, as torch computes them: a NaN operand gives NaN, where fmaxf (IEEE maxNum) would return the
+// other operand.  Finite operands take the fmaxf path, so every finite result is bit for bit what fmaxf gives.
+__device__ __forceinline__ float max_nan(float a, float b) { return (a != a || b != b) ? a + b : fmaxf(a, b); }
+__device__ __forceinline__ float relu_nan(float v) { return v != v ? v : fmaxf(v, 0.f); }
+
 // ---------------------------------------------------------------------------- HED helpers
 // (frozen edge detector, reference src/models/hned.py:9-105; forward only)
 // MaxPool2d(2,2) on padded NHWC, hned.py:20,28,38,48.  ReLU commutes with max, so the pool runs on the
@@ -161,8 +166,8 @@ __global__ __launch_bounds__(GO_BLOCK) void maxpool2x2_kernel(const float* __res
         const float* p = in + ((n * (H + 2) + 2 * y + 1) * (int64_t)(W + 2) + 2 * x + 1) * cp + c;
         const float4 a = ld4(p), bq = ld4(p + cp), cq = ld4(p + (int64_t)(W + 2) * cp), d = ld4(p + (int64_t)(W + 3) * cp);
         float4 m;
-        m.x = fmaxf(fmaxf(a.x, bq.x), fmaxf(cq.x, d.x)); m.y = fmaxf(fmaxf(a.y, bq.y), fmaxf(cq.y, d.y));
-        m.z = fmaxf(fmaxf(a.z, bq.z), fmaxf(cq.z, d.z)); m.w = fmaxf(fmaxf(a.w, bq.w), fmaxf(cq.w, d.w));
+        m.x = max_nan(max_nan(a.x, bq.x), max_nan(cq.x, d.x)); m.y = max_nan(max_nan(a.y, bq.y), max_nan(cq.y, d.y));
+        m.z = max_nan(max_nan(a.z, bq.z), max_nan(cq.z, d.z)); m.w = max_nan(max_nan(a.w, bq.w), max_nan(cq.w, d.w));
         st4(out + ((n * (h + 2) + y + 1) * (int64_t)(w + 2) + x + 1) * cp + c, m);
     }
 }
@@ -180,7 +185,7 @@ __global__ __launch_bounds__(GO_BLOCK) void score1x1_kernel(const float* __restr
         const int64_t n = i / ((int64_t)W * H);
         const float* p = in + ((n * (H + 2) + y + 1) * (int64_t)(W + 2) + x + 1) * cp;
         float s = 0.f;
-        for (int c = lane; c < C; c += 64) s += fmaxf(p[c], 0.f) * w[c];
+        for (int c = lane; c < C; c += 64) s += relu_nan(p[c]) * w[c];
         s = wave_sum(s);
         if (lane == 0) out[i] = s + bias[0];
     }
@@ -222,7 +227,8 @@ __global__ __launch_bounds__(GO_BLOCK) void hed_head_kernel(const float* __restr
 }
 
 // backward of the 2x2 max-pool: the gradient of a pooled pixel goes to the first maximum of its window in
-// row-major order (torch's tie rule); thread per (input pixel, float4 of channels), gather form
+// row-major order, or to its last NaN if it holds one (torch's rule: val > max || isnan(val)); thread per
+// (input pixel, float4 of channels), gather form
 __global__ __launch_bounds__(GO_BLOCK) void maxpool2x2_bwd_kernel(const float* __restrict__ in, const float* __restrict__ dout,
                                                                  float* __restrict__ din, int b, int h, int w, int cp) {
     const int H = 2 * h, W = 2 * w, c4n = cp >> 2;
@@ -249,7 +255,7 @@ __global__ __launch_bounds__(GO_BLOCK) void maxpool2x2_bwd_kernel(const float* _
 #pragma unroll
             for (int k = 1; k < 4; ++k) {
                 const float t = (&v[k].x)[e];
-                if (t > bv) { bv = t; best = k; }
+                if (t > bv || t != t) { bv = t; best = k; }
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) (&o[k].x)[e] = (k == best) ? gp[e] : 0.f;
@@ -273,7 +279,7 @@ __global__ __launch_bounds__(GO_BLOCK) void l1_relu_padded_kernel(const float* _
         float* gp = &g.x;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float d = fmaxf(xp[e], 0.f) - fmaxf(yp[e], 0.f);
+            const float d = relu_nan(xp[e]) - relu_nan(yp[e]);
             acc += fabsf(d);
             gp[e] = xp[e] > 0.f ? (d > 0.f ? gscale : (d < 0.f ? -gscale : 0.f)) : 0.f;
         }

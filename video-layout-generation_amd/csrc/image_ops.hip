@@ -168,14 +168,20 @@ __global__ __launch_bounds__(IMG_BLOCK) void ssim_kernel(const float* __restrict
     const int h0 = (tl / tiles_w) * ST, w0 = (tl % tiles_w) * ST;
     const float* xp = x + plane * (int64_t)H * W;
     const float* yp = y + plane * (int64_t)H * W;
+    // torch's loss is NaN once a window holds a NaN or inf pixel (torch.clamp keeps the NaN that fminf / fmaxf below
+    // would drop).  Every pixel of the image lies in some window, so a non-finite pixel a tile loads (halo included)
+    // makes the whole loss NaN: flagged here, on the loads, so the window arithmetic stays as it is for finite input.
+    int nonfinite = 0;
     for (int e = threadIdx.x; e < (ST + 4) * (ST + 4); e += IMG_BLOCK) {
         const int r = e / (ST + 4), c = e - r * (ST + 4);
         const int hh = h0 - 2 + r, ww = w0 - 2 + c;
         const bool in = hh >= 0 && hh < H && ww >= 0 && ww < W;
-        xs[r][c] = in ? xp[(int64_t)hh * W + ww] : 0.f;
-        ys[r][c] = in ? yp[(int64_t)hh * W + ww] : 0.f;
+        const float xv = in ? xp[(int64_t)hh * W + ww] : 0.f, yv = in ? yp[(int64_t)hh * W + ww] : 0.f;
+        xs[r][c] = xv;
+        ys[r][c] = yv;
+        nonfinite |= !isfinite(xv) || !isfinite(yv);
     }
-    __syncthreads();
+    nonfinite = __syncthreads_or(nonfinite);
     float acc = 0.f;
     for (int e = threadIdx.x; e < (ST + 2) * (ST + 2); e += IMG_BLOCK) {
         const int r = e / (ST + 2), c = e - r * (ST + 2);
@@ -227,7 +233,7 @@ __global__ __launch_bounds__(IMG_BLOCK) void ssim_kernel(const float* __restrict
         }
     }
     acc = block_sum(acc, red);
-    if (threadIdx.x == 0) scratch[4 + blockIdx.x] = acc;
+    if (threadIdx.x == 0) scratch[4 + blockIdx.x] = nonfinite ? __builtin_nanf("") : acc;
 }
 
 // sums an arbitrary number of per-block partials (SSIM launches one block per tile)
@@ -361,7 +367,8 @@ extern "C" int vlg_prep_input(const float* e1, const float* seg1, const float* f
 }
 
 // ---- autoregressive rollout (reference src/trainer.py:453-476)
-// seg_next = torch.argmax(seg_next, dim=1).unsqueeze_(1).float()      trainer.py:467   (first maximum wins, as torch)
+// seg_next = torch.argmax(seg_next, dim=1).unsqueeze_(1).float()      trainer.py:467   (first maximum wins, as torch;
+// a NaN counts as the maximum, so the first NaN wins over everything)
 __global__ __launch_bounds__(IMG_BLOCK) void argmax_nchw_kernel(const float* __restrict__ logits, float* __restrict__ out,
                                                                int64_t n, int C, int64_t hw) {
     for (int64_t i = (int64_t)blockIdx.x * IMG_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * IMG_BLOCK) {
@@ -371,7 +378,7 @@ __global__ __launch_bounds__(IMG_BLOCK) void argmax_nchw_kernel(const float* __r
         int arg = 0;
         for (int c = 1; c < C; ++c) {
             const float v = p[c * hw];
-            if (v > best) { best = v; arg = c; }
+            if (v > best || (v != v && best == best)) { best = v; arg = c; }
         }
         out[i] = (float)arg;
     }
