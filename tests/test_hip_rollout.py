@@ -151,13 +151,43 @@ def test_layout_rollout_values_and_entry(tmp_path, monkeypatch, dev, attention):
     monkeypatch.delenv("VLG_MODEL", raising=False)
     monkeypatch.setenv("VLG_ATTENTION", attention)
     from trainer import Trainer
-    cfgk = dict(batch_size=3, epochs=1, print_freq=1, n_frames=8, n_slots=8, d_model=64, n_layers=2, train_clips=6, val_clips=3)
-    tr = Trainer(reference_args(tmp_path / "exp", **cfgk))
+    tr = Trainer(reference_args(tmp_path / "exp", **LAYOUT_CFG))
     batch = next(iter(tr.val_loader))
-    cls0, box0 = batch["slot_class"].cpu(), batch["slot_box"].cpu()
-    steps = 8
+    _check_layout_rollout(tr, batch["slot_class"].cpu(), batch["slot_box"].cpu(), attention)
+    # layout mode has no pixel inputs: the main.py:64-67 entry logs an error and returns, as the reference's does for
+    # unusable inputs (trainer.py:436-438) - no traceback
+    assert tr.eval_generate_sequence("a.png", "b.png", "c.png", "d.png") is None
+
+
+def test_layout_rollout_clip_masks_padded_slots_at_fixed_n(tmp_path, monkeypatch, dev):
+    """A fixed-N Trainer builds its engine without validity masks (its training batches hold no padded slot), but a
+    rollout window can hold the reserved class id: under VLG_ATTENTION=clip those slots must not be attended to as keys,
+    as O.forward(..., valid=cls < n_classes) has it."""
+    (tmp_path / "src").mkdir()
+    monkeypatch.chdir(tmp_path / "src")
+    monkeypatch.delenv("VLG_MODEL", raising=False)
+    monkeypatch.delenv("VLG_VARIABLE_N", raising=False)
+    monkeypatch.setenv("VLG_ATTENTION", "clip")
+    from trainer import Trainer
+    tr = Trainer(reference_args(tmp_path / "exp", **LAYOUT_CFG))
+    assert tr.cfg.attention == "clip" and not tr.engine.padded_slots
+    batch = next(iter(tr.val_loader))
+    cls0, box0 = batch["slot_class"].cpu().clone(), batch["slot_box"].cpu()
+    cls0[:, :, 5:] = tr.cfg.n_classes                   # the last three of eight slots padded in every frame
+    cls0[1, :3, 1] = tr.cfg.n_classes                   # and one slot of one clip in its first three frames only
+    _check_layout_rollout(tr, cls0, box0, "clip")
+
+
+LAYOUT_CFG = dict(batch_size=3, epochs=1, print_freq=1, n_frames=8, n_slots=8, d_model=64, n_layers=2, train_clips=6,
+                  val_clips=3)
+
+
+def _check_layout_rollout(tr, cls0, box0, attention, steps=8):
+    """generate_sequence's predictions vs the CPU restatement, teacher-forced on the HIP rollout's own window: class ids
+    wherever the top-2 margin is clear, boxes within 1e-4."""
+    B, T, N = cls0.shape
     out_c, out_b = tr.generate_sequence(cls0, box0, steps=steps)
-    assert out_c.shape == (3, steps, 8) and out_b.shape == (3, steps, 8, 4)
+    assert out_c.shape == (B, steps, N) and out_b.shape == (B, steps, N, 4)
     params = {k: v.cpu() for k, v in tr.engine.named_params().items()}
     cls, box = cls0.clone(), box0.clone()
     with torch.no_grad():
@@ -172,6 +202,3 @@ def test_layout_rollout_values_and_entry(tmp_path, monkeypatch, dev, attention):
             assert float((out_b[:, i] - want_b).abs().max()) <= 1e-4, i
             cls = torch.cat([cls[:, 1:], out_c[:, i][:, None]], dim=1)            # slide the window on the HIP predictions
             box = torch.cat([box[:, 1:], out_b[:, i][:, None]], dim=1)
-    # layout mode has no pixel inputs: the main.py:64-67 entry logs an error and returns, as the reference's does for
-    # unusable inputs (trainer.py:436-438) - no traceback
-    assert tr.eval_generate_sequence("a.png", "b.png", "c.png", "d.png") is None

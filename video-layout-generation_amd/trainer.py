@@ -493,9 +493,13 @@ class Trainer:
         dummy = {"tgt_class": torch.zeros_like(cls), "tgt_box": torch.zeros_like(box)}
         for _ in range(steps):
             # valid: padded slots carry the reserved class id (vlg/data.py) - with attention = "clip" they must not be attended
-            # to; the loss the forward also evaluates against the dummy targets is not used
+            # to; the loss the forward also evaluates against the dummy targets is not used.  An engine built for fixed-N
+            # training skips the masks (padded_slots False): it is told to mask a window that holds a padded slot
             valid = (cls < self.cfg.n_classes).to(torch.float32).contiguous()
-            self.engine.forward(dict(dummy, slot_class=cls.contiguous(), slot_box=box.contiguous(), valid=valid))
+            kw = {}
+            if not getattr(self.engine, "padded_slots", True) and bool((valid == 0).any()):
+                kw["padded_slots"] = True
+            self.engine.forward(dict(dummy, slot_class=cls.contiguous(), slot_box=box.contiguous(), valid=valid), **kw)
             logits, raw = self.engine.outputs_btn()
             nc = torch.argmax(logits[:, -1], dim=-1)                 # (B,N), as trainer.py:467
             nb = torch.sigmoid(raw[:, -1])

@@ -78,6 +78,7 @@ class LayoutEngine:
         # attention = "clip": padded slots (batch['valid'] == 0) must not be attended to; padded_slots = False tells the engine
         # that its batches never hold any (fixed-N feeds), so the kernels skip the per-key validity masks
         self.padded_slots = bool(padded_slots)
+        self._masked = self.padded_slots             # this forward's choice; its backward follows it
         self.precision = precision
         self.gemm_flags = {"fp32": 0, "fp32x3": hip.EPI_SPLIT3}.get(precision, hip.EPI_BF16)
         self.bf16_store = precision == "bf16"
@@ -379,7 +380,7 @@ class LayoutEngine:
             fl = 4.0 * B * d * N * N * T * (T + 1) / 2.0            # visible (query, key) pairs x 2 products x 2 x head dim, all heads
             e = self.qkv.element_size()                             # qkv read, out written; the fp32 lse is negligible
             self._timed("attn_clip_fwd", fl, "vlg_attention_clip_fwd" + self._sfx, ptr(self.qkv[l]),
-                        ptr(batch["valid"]) if self.padded_slots else 0, ptr(self.att[l]), ptr(self.lse[l]), B, T, N, d, s,
+                        ptr(batch["valid"]) if self._masked else 0, ptr(self.att[l]), ptr(self.lse[l]), B, T, N, d, s,
                         nbytes=4.0 * e * M * d)
             return
         self._timed("attn_fwd", 0.0, "vlg_attention_fwd" + self._sfx, ptr(self.qkv[l]), ptr(self.att[l]), B * N, T, d, s,
@@ -392,7 +393,7 @@ class LayoutEngine:
                                                                      # backward recomputes S and dP: 7 are executed)
             e = self.qkv.element_size()                             # qkv, out, dout read, dqkv written (+ qkv, dout again)
             self._timed("attn_clip_bwd", fl, "vlg_attention_clip_bwd" + self._sfx, ptr(self.qkv[l]),
-                        ptr(batch["valid"]) if self.padded_slots else 0, ptr(self.att[l]), ptr(self.dh), ptr(self.lse[l]),
+                        ptr(batch["valid"]) if self._masked else 0, ptr(self.att[l]), ptr(self.dh), ptr(self.lse[l]),
                         ptr(self.delta), ptr(self.dqkv), B, T, N, d, s, nbytes=7.0 * e * M * d)
             return
         self._timed("attn_bwd", 0.0, "vlg_attention_bwd" + self._sfx, ptr(self.qkv[l]), ptr(self.dh), ptr(self.dqkv), B * N, T, d, s,
@@ -431,11 +432,13 @@ class LayoutEngine:
         return B, T, N, M
 
     # --------------------------------------------------------------------- forward
-    def forward(self, batch: Dict[str, torch.Tensor]) -> torch.Tensor:
+    def forward(self, batch: Dict[str, torch.Tensor], padded_slots: Optional[bool] = None) -> torch.Tensor:
         """Forward + fused loss (the loss kernel also leaves d(total)/d(out) in self.dout).
-        Returns the device tensor {total, smooth_l1, iou, ce}."""
+        Returns the device tensor {total, smooth_l1, iou, ce}.  padded_slots overrides the engine's setting for this
+        forward and the backward that follows it: a rollout window can hold padded slots where training batches never do."""
         cfg, d, ff = self.cfg, self.cfg.d, self.cfg.d_ff
         B, T, N, M = self._check_batch(batch)
+        self._masked = self.padded_slots if padded_slots is None else bool(padded_slots)
         self._shape = (B, T, N, M)
         s = self._stream()
         self._timed("embed_fwd", 0.0, "vlg_embed_fwd", ptr(batch["slot_class"]), ptr(batch["slot_box"]), ptr(self.p("cls_emb")),
