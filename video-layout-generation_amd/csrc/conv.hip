@@ -341,7 +341,9 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void conv_gemm_kernel(const ConvAr
 #pragma unroll
                 for (int i = 0; i < TA::NV; ++i) xa[i] = __builtin_amdgcn_raw_buffer_load_b128(ua, va, oa + i * a_is, 0);
 #pragma unroll
-                for (int i = 0; i < TB::NV; ++i) xb[i] = __builtin_amdgcn_raw_buffer_load_b128(ub, vb, ob + i * b_is, 0);
+                for (int i = 0; i < TB::NV; ++i)                // (the data gradient's 128 x 96 tile: no constant row step, gemm_tile.h)
+                    xb[i] = __builtin_amdgcn_raw_buffer_load_b128(ub, TB::ROWSTEP ? vb : TB::voff_bytes(ldb, tid + GEMM_THREADS * i),
+                                                                  ob + (TB::ROWSTEP ? i * b_is : 0), 0);
                 ++l_t;                                          // (selects, not branches: the iteration stays one basic block)
                 const bool wrap_c = l_ci + BK >= g.cin, wrap_x = wrap_c && l_kx == 2;
                 l_ci = wrap_c ? 0 : l_ci + BK;
@@ -1023,7 +1025,9 @@ static ConvPlan conv_plan(int prec, int mode, int64_t rows, int cin_p, int cout,
     } else if (prec == CONV_BF16) {
         p.t = bf16_tile(rows, n_cols);                         // (no tail split)
     } else {
-        const bool tail_ok = ws == WS_ALIGNED && !tables && !da_slab && !prelu;
+        // (n_valid == n_cols: the finish kernel sums whole rows of n_cols lanes, the tail tiles write only the n_valid
+        // computed ones - with a padded cout it would add unwritten workspace into the output's padding lanes)
+        const bool tail_ok = ws == WS_ALIGNED && !tables && !da_slab && !prelu && n_valid == n_cols;
         p.t = conv_tile(rows, n_cols, n_valid, tail_ok ? kc : 0);
         if (tail_ok) {
             const ConvTail tl = conv_tail_plan(rows, p.t, n_valid, kc, n_cols);

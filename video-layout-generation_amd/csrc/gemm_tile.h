@@ -88,6 +88,9 @@ struct Tile {
     // per-thread part of every address is a loop constant and the rest is a scalar or an instruction immediate.
     static constexpr int ISTEP = NT / PER_ROW;                          // memory rows between a thread's consecutive float4
     static constexpr int SSTEP = KC ? ISTEP * LDK : NT * 4;             // the same step in the LDS tile, floats
+    // ... which holds only where the block's threads cover whole memory rows.  A 96-row MC tile has 24 float4 per memory row:
+    // NT = 256 float4 further on is 10 rows AND 16 columns away, so there float4 i is addressed by voff_bytes(ld, tid + NT * i)
+    static constexpr bool ROWSTEP = NT % PER_ROW == 0;
     __device__ static __forceinline__ int voff_bytes(int ld, int tid) { return ((tid / PER_ROW) * ld + ((tid % PER_ROW) << 2)) * 4; }
     __device__ static __forceinline__ int soff(int tid) { return KC ? (tid / PER_ROW) * LDK + ((tid % PER_ROW) << 2) : (tid << 2); }
     __device__ static __forceinline__ int roff(int row, int h) { return KC ? row * LDK + 4 * h : 4 * h * BR + row; }
