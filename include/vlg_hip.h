@@ -143,8 +143,11 @@ int vlg_linear_wgrad(const void* dY, int ldy, const void* X, int ldx,
 /* vlg_linear_wgrad and vlg_linear_dgrad of ONE projection (same dY) as one call: accepts exactly what the two calls accept
  * (the weight gradient takes the mode and the dY / X storage bits of `epilogue`), and results are bit for bit those of the
  * two calls.  Native fp32 tensors and the bf16-storage step (bf16 W / X / dX) with epilogue VLG_EPI_NONE | VLG_EPI_MUL can
- * run as ONE launch whose blocks are dealt both problems at once (the plan depends on the shape and flags alone: csrc/gemm.hip);
- * everything else runs as the two launches.  Replaces the two autograd nodes of one nn.Linear backward. */
+ * run as ONE launch whose blocks are dealt both problems at once; everything else runs as the two launches.  Which it is,
+ * and on which tiles, is part of the call's plan (gemm_plan in csrc/gemm.hip, a function of shape, flags and leading
+ * dimensions alone; vlg_linear_plan below reports it).  Like every vlg_linear_* call it is checked and planned completely
+ * before its first launch: a call that is refused - for either product - has enqueued nothing, riders included.
+ * Replaces the two autograd nodes of one nn.Linear backward. */
 int vlg_linear_dgrad_wgrad(const void* dY, int ldy, const void* W, int ldw, void* dX, int ldx, const void* aux_in,
                            const void* X, int ldxx, float* slabs, int64_t slab_stride, int64_t slab_capacity,
                            int64_t M, int N, int K, int epilogue,
@@ -152,6 +155,33 @@ int vlg_linear_dgrad_wgrad(const void* dY, int ldy, const void* W, int ldw, void
                               gradient bucket's partial sums): reduced by extra blocks of the same launch where the products are
                               fused, by its own launch otherwise; rows as vlg_reduce_slabs_table requires, 1 <= rider_rows
                               <= 4096 */, int rider_rows, void* stream);
+/* The plan of a vlg_linear_* call: a pure host-side planner like the slab-count queries (no GPU, no launch, no state), and
+ * the same function the entry points launch from.  (M, N, K, flags) as the call takes them; the leading dimensions in the
+ * call's own order: fwd (lda, ldw, ldc), dgrad (ldy, ldw, ldx), wgrad (ldy, ldx, unused), pair (ldy, ldw, ldx) and ldxx
+ * (unused by the others).  Returns 0 and fills *plan, or the error the call returns on shape, flag and leading-dimension
+ * grounds (pointers, slab stride and capacity are taken to be fine; *plan is zeroed). */
+#define VLG_CALL_FWD   0
+#define VLG_CALL_DGRAD 1
+#define VLG_CALL_WGRAD 2
+#define VLG_CALL_PAIR  3   /* vlg_linear_dgrad_wgrad: p[0] = the data gradient, p[1] = the weight gradient */
+#define VLG_GEMM_F32   0   /* kernel family: native fp32 MFMA (csrc/gemm.hip) */
+#define VLG_GEMM_BF16  1   /* bf16 MFMA (csrc/gemm_bf16.hip) */
+#define VLG_GEMM_F32X3 2   /* fp32 as three bf16 terms (csrc/gemm_split.hip) */
+typedef struct vlg_gemm_problem {
+    int bm, bn, bk;            /* block tile of the output and contraction depth per LDS tile */
+    int run;                   /* consecutive N tiles one block computes */
+    int splits;                /* ranges of the contraction extent = slabs of a weight gradient */
+    int blocks;                /* blocks of the launch that work on this problem */
+    int64_t rows_per_split;    /* contraction rows per range */
+} vlg_gemm_problem;
+typedef struct vlg_gemm_plan {
+    int family;                /* VLG_GEMM_* */
+    int launches;              /* GEMM launches: 1, or 2 for a pair that runs as its two single calls (weight gradient first) */
+    int problems;              /* entries of p: 1, or 2 for VLG_CALL_PAIR */
+    int fused;                 /* 1 = a pair as one launch of the pair kernel, on the tiles p names */
+    vlg_gemm_problem p[2];
+} vlg_gemm_plan;
+int vlg_linear_plan(int call, int64_t M, int N, int K, int flags, int lda, int ldb, int ldc, int ldxx, vlg_gemm_plan* plan);
 
 
 /* ------------------------------------------------------------------- attention

@@ -40,6 +40,11 @@ def test_binding_covers_header_and_types_resolve():
     assert lib.vlg_embed_bwd_slabs() > 0
     assert 1 <= lib.vlg_linear_wgrad_slabs(32768, 768, 256) <= 128
     assert lib.vlg_linear_wgrad_slabs(128, 64, 64) == 1
+    plan = (ctypes.c_int64 * 12)()                                                            # sizeof(vlg_gemm_plan) = 80
+    assert lib.vlg_linear_plan(2, 32768, 768, 256, 0, 768, 256, 0, 0, plan) == 0            # the weight gradient's plan
+    ints = (ctypes.c_int * 24).from_buffer(plan)                                              # family, launches, problems, fused, p[0] ...
+    assert list(ints[:4]) == [0, 1, 1, 0] and ints[8] == lib.vlg_linear_wgrad_slabs(32768, 768, 256)
+    assert lib.vlg_linear_plan(2, 32768, 770, 256, 0, 770, 256, 0, 0, plan) == 1001          # N not a multiple of 4
     assert lib.vlg_layout_loss_scratch() > 4 and lib.vlg_image_loss_scratch() > 4
 
 

@@ -2,9 +2,9 @@
 
 The dispatcher chooses tile size, contraction depth (BK), chained N tiles, the fast or guarded main loop per block, the
 paired launch and its rider blocks from the call's shape alone, so a path is reached by choosing a shape.  CASES names
-the path each shape is meant to reach; `plan` below restates the dispatch rules in Python (with the gemm.hip lines it
-mirrors) and test_mirror_names_the_path / test_mirror_split_counts_match_the_library keep the table and the mirror
-honest on the host.  The GPU tests then run each case with every output inside a larger buffer filled with a sentinel
+the path each shape is meant to reach; `mirror_plan` below restates the planner (gemm_plan) in Python, function by
+function, and test_mirror_names_the_path / test_mirror_matches_the_library_plan keep the table and the mirror honest on
+the host: the second compares every field the library's own plan query reports with the mirror's.  The GPU tests then run each case with every output inside a larger buffer filled with a sentinel
 bit pattern (leading dimension >= N + 4, spare rows below the last one, slab padding and spare slab capacity), compare
 the results with an fp64 CPU reference computed from the same fp32 (or bf16-representable) inputs, and assert that no
 padding bit changed and that every output element was written (the sentinel is a NaN, which conftest.assert_close
@@ -12,6 +12,7 @@ would let through: check_close refuses any non-finite value first).  Bars: 1e-4 
 test_hip_ops.BF_OUT (one bf16 rounding) for bf16 outputs; native fp32 products must also stay within 4x of torch-CPU
 fp32's own error against fp64.
 """
+import ctypes
 import math
 
 import pytest
@@ -36,16 +37,25 @@ def _cdiv(a, b):
 
 
 # ------------------------------------------------------------------------------------------------ dispatch mirror
-def wants_small(M, N, splits):
-    """gemm.hip:719-724 - 64x64 tiles while the 128x128 grid has fewer than 512 blocks."""
-    return _cdiv(M, 128) * _cdiv(N, 128) * splits < 512
+# An independent restatement of gemm_plan (csrc/gemm.hip) and its helpers, named by the function each piece mirrors.
+# mirror_plan returns exactly the fields vlg_linear_plan reports; describe() turns such fields - the mirror's or the
+# library's - into the path label the case table uses.
+F32, BF16_MFMA, F32X3 = 0, 1, 2                          # VLG_GEMM_*
+CALLS = {"fwd": 0, "dgrad": 1, "wgrad": 2, "pair": 3}    # VLG_CALL_*
+STORAGE = EPI_A_BF16 | EPI_B_BF16 | EPI_OUT_BF16
 
 
-def gemm_run(M, N, Kc, lda, ldb, ldc, a_kc, b_kc, splits=1, slots=512):
-    """gemm.hip:694-707 (BM = BN = 128, BK = 32): N tiles chained per block when every block takes the fast path."""
-    if splits != 1 or M % 128 or N % 128 or Kc % 64:
+def wants_small(M, N):
+    """gemm_wants_small - 64x64 tiles while the 128x128 grid has fewer than 512 blocks."""
+    return _cdiv(M, 128) * _cdiv(N, 128) < 512
+
+
+def gemm_run(M, N, Kc, lda, ldb, ldc, b_kc, slots=512):
+    """gemm_run (BM = BN = 128, BK = 32, A contraction-contiguous): N tiles chained per block when every block takes
+    the fast path."""
+    if M % 128 or N % 128 or Kc % 64:
         return 1
-    span_a = 127 * lda + Kc if a_kc else Kc * lda + 128
+    span_a = 127 * lda + Kc
     span_b = 255 * ldb + Kc if b_kc else Kc * ldb + 256
     if span_a >= 1 << 28 or span_b >= 1 << 28 or 127 * ldc + 128 >= 1 << 28:
         return 1
@@ -58,7 +68,7 @@ def gemm_run(M, N, Kc, lda, ldb, ldc, a_kc, b_kc, splits=1, slots=512):
 
 
 def wgrad_plan(M, N, K, flags):
-    """gemm.hip:884-911 -> (splits, rows per split, small)."""
+    """wgrad_split -> (splits, rows per split, small)."""
     native = (flags & (EPI_BF16 | EPI_SPLIT3 | EPI_ACT_GELU)) == 0
     bm = 32 if N <= 32 else 128
     tiles = _cdiv(N, bm) * _cdiv(K, 128)
@@ -84,7 +94,7 @@ def wgrad_plan(M, N, K, flags):
 
 
 def body_kinds(BM, BN, BK, fast_kernel, M, N, Kc, lda, ldb, ldc, a_kc, b_kc, splits=1, per=None, run=1):
-    """gemm.hip:111-126 (tile and K range of a block), 425 (`interior`), 429-440 (`fits`, fast or guarded main loop).
+    """gemm_f32_body: tile and K range of a block, `interior`, `fits`, fast or guarded main loop.
     Returns the set of main loops the blocks take: fast / guarded (fast-path kernels), general / guarded (the others),
     plus "unfit" when some block misses the fast path only for its 32-bit byte offsets."""
     per = Kc if per is None else per
@@ -111,105 +121,128 @@ def body_kinds(BM, BN, BK, fast_kernel, M, N, Kc, lda, ldb, ldc, a_kc, b_kc, spl
     return "+".join(k for k in ("fast", "general", "guarded", "unfit") if k in kinds)
 
 
-def _f32_launch(BM, BN, M, N, Kc, lda, ldb, ldc, a_kc, b_kc, heavy=False, can_run=True, fast=True, splits=1, per=None):
-    """gemm.hip:726-755 launch_gemm for one instantiation -> label."""
-    bk, run = 32, 1
-    if BM == 128 and BN == 128:
-        run32 = gemm_run(M, N, Kc, lda, ldb, ldc, a_kc, b_kc, splits) if can_run else 1
-        if heavy and run32 == 1:
+def _family(flags):
+    return BF16_MFMA if flags & EPI_BF16 else F32X3 if flags & EPI_SPLIT3 else F32
+
+
+def _terms(call, M, N, K, ldc):
+    """The product in the kernel's terms (fwd_args, dgrad_args, wgrad_args): C[gM, gN] over gK, leading dimension of C."""
+    return {"fwd": (M, N, K, ldc), "dgrad": (M, K, N, ldc), "wgrad": (N, K, M, K)}[call]
+
+
+def mirror_problem(call, M, N, K, flags, lda, ldb, ldc):
+    """gemm_problem -> (bm, bn, bk, run, splits, blocks, rows per split) of one single call."""
+    fwd, wgrad = call == "fwd", call == "wgrad"
+    native = _family(flags) == F32
+    act = call != "dgrad" and bool(flags & EPI_ACT_GELU)         # GELU on load: no small tiles, no chaining, no fast path
+    epi = 0 if wgrad else flags & (EPI_BIAS | EPI_GELU | EPI_RESID | EPI_DGELU | EPI_GELU_GRAD | EPI_MUL)
+    gM, gN, gK, gldc = _terms(call, M, N, K, ldc)
+    bm = bn = 128
+    bk = {F32: 32, BF16_MFMA: 64, F32X3: 16}[_family(flags)]
+    run, splits, per = 1, 1, gK
+    if wgrad:
+        splits, per, small = wgrad_plan(M, N, K, flags)
+        bm, bn = (64, 64) if small else (32 if N <= 32 else 128, 128)
+    elif fwd and N <= 32 and (not native or (epi == EPI_BIAS and not act)):
+        bn = 32
+    elif native and not act and wants_small(gM, gN):
+        bm = bn = 64
+    if native and bm == 128 and bn == 128:
+        run32 = 1 if wgrad or act else gemm_run(gM, gN, gK, lda, ldb, gldc, fwd)
+        if epi & (EPI_GELU | EPI_DGELU) and run32 == 1:          # heavy epilogue: three blocks per CU, unless the tiles chain
             bk = 16
         else:
             run = run32
-    fast = fast and BM == BN and BM in (64, 128)
-    kinds = body_kinds(BM, BN, bk, fast, M, N, Kc, lda, ldb, ldc, a_kc, b_kc, splits, per, run)
-    lab = "%dx%d BK%d" % (BM, BN, bk)
-    if run > 1:
-        lab += " run%d" % run
-    if splits > 1:
-        lab += " splits%d" % splits
-    return lab + " " + kinds
+    return (bm, bn, bk, run, splits, _cdiv(gM, bm) * (_cdiv(gN, bn) // run) * splits, per)
 
 
-def plan_fwd(M, N, K, flags, lda, ldw, ldc):
-    """gemm.hip:774-819."""
-    if flags & EPI_SPLIT3:
-        return "gemm_split_kernel %s" % ("128x32" if N <= 32 else "128x128")
-    if flags & EPI_BF16:
-        return "gemm_bf16_kernel %s" % ("128x32" if N <= 32 else "128x128")
-    if flags & EPI_ACT_GELU:                             # GELU on load: no small tiles, no chaining, no fast path
-        return "gemm_f32_kernel " + _f32_launch(128, 128, M, N, K, lda, ldw, ldc, True, True, can_run=False, fast=False)
-    if N <= 32:
-        return "gemm_f32_kernel " + _f32_launch(128, 32, M, N, K, lda, ldw, ldc, True, True)
-    if wants_small(M, N, 1):
-        return "gemm_f32_kernel " + _f32_launch(64, 64, M, N, K, lda, ldw, ldc, True, True)
-    return "gemm_f32_kernel " + _f32_launch(128, 128, M, N, K, lda, ldw, ldc, True, True, heavy=bool(flags & EPI_GELU))
-
-
-def plan_dgrad(M, N, K, flags, ldy, ldw, ldx):
-    """gemm.hip:857-877 with dgrad_args (C[M,K] = dY[M,N] . W[N,K]: contraction over N)."""
-    if flags & EPI_SPLIT3:
-        return "gemm_split_kernel 128x128"
-    if flags & EPI_BF16:
-        return "gemm_bf16_kernel 128x128"
-    if wants_small(M, K, 1):
-        return "gemm_f32_kernel " + _f32_launch(64, 64, M, K, N, ldy, ldw, ldx, True, False)
-    return "gemm_f32_kernel " + _f32_launch(128, 128, M, K, N, ldy, ldw, ldx, True, False, heavy=bool(flags & EPI_DGELU))
-
-
-def plan_wgrad(M, N, K, flags, ldy, ldx):
-    """gemm.hip:927-942 with wgrad_args (slab[N,K] = dY^T . X: contraction over the M tokens, split per wgrad_plan)."""
-    splits, per, small = wgrad_plan(M, N, K, flags)
-    sp = " splits%d" % splits if splits > 1 else ""
-    if flags & EPI_BF16:
-        return "gemm_bf16_kernel %s%s" % ("32x128" if N <= 32 else "128x128", sp)
-    if flags & EPI_SPLIT3:
-        return "gemm_split_kernel %s%s" % ("32x128" if N <= 32 else "128x128", sp)
-    args = (N, K, M, ldy, ldx, K, False, False)
-    if flags & EPI_ACT_GELU:
-        return "gemm_f32_kernel " + _f32_launch(128, 128, *args, can_run=False, fast=False, splits=splits, per=per)
-    if small:
-        return "gemm_f32_kernel " + _f32_launch(64, 64, *args, can_run=False, splits=splits, per=per)
-    if N <= 32:
-        return "gemm_f32_kernel " + _f32_launch(32, 128, *args, can_run=False, splits=splits, per=per)
-    return "gemm_f32_kernel " + _f32_launch(128, 128, *args, can_run=False, splits=splits, per=per)
-
-
-def plan_pair(M, N, K, flags, ldy, ldw, ldx, ldxx):
-    """gemm.hip:967-1010 (and gemm_bf16.hip:266-272): one fused launch or the two single calls."""
-    st = flags & (EPI_A_BF16 | EPI_B_BF16 | EPI_OUT_BF16)
-    epi = flags & ~(EPI_BF16 | EPI_A_BF16 | EPI_B_BF16 | EPI_OUT_BF16)
+def mirror_plan(call, M, N, K, flags, lda, ldb, ldc, ldxx=0):
+    """gemm_plan -> (family, launches, problems, fused, problem[, problem]) as vlg_linear_plan reports them."""
+    if call != "pair":
+        return (_family(flags), 1, 1, 0, mirror_problem(call, M, N, K, flags, lda, ldb, ldc))
+    st = flags & STORAGE
+    epi = flags & ~(EPI_BF16 | STORAGE)
     wflags = flags & (EPI_BF16 | EPI_SPLIT3 | EPI_A_BF16 | EPI_B_BF16)
-    splits, per, small = wgrad_plan(M, N, K, wflags)
+    small = wgrad_plan(M, N, K, wflags)[2]
     mul = epi == EPI_MUL
     bf16_pair = bool(flags & EPI_BF16) and (st & ~EPI_A_BF16) == (EPI_B_BF16 | EPI_OUT_BF16)
     native = not (flags & EPI_BF16) and st == 0
-    small_d = wants_small(M, K, 1)
-    fusable = (epi == EPI_NONE or mul) and N > 32 and K > 32 and \
+    small_d = wants_small(M, K)
+    fused = (epi == EPI_NONE or mul) and N > 32 and K > 32 and \
         ((not (mul and st & EPI_A_BF16)) if bf16_pair else (native and small == small_d))
-    if not fusable:
-        return "two calls | w %s | d %s" % (plan_wgrad(M, N, K, wflags, ldy, ldxx), plan_dgrad(M, N, K, flags, ldy, ldw, ldx))
-    if bf16_pair:
-        return "gemm16_pair_kernel splits%d" % splits
-    bt = 64 if small_d else 128
-    run = gemm_run(M, K, N, ldy, ldw, ldx, True, False) if bt == 128 else 1
-    d = body_kinds(bt, bt, 32, True, M, K, N, ldy, ldw, ldx, True, False, run=run)
-    w = body_kinds(bt, bt, 32, True, N, K, M, ldy, ldxx, K, False, False, splits, per)
-    return "gemm_pair_kernel %d | d%s %s | w splits%d %s" % (bt, " run%d" % run if run > 1 else "", d, splits, w)
+    d = mirror_problem("dgrad", M, N, K, flags, lda, ldb, ldc)
+    w = mirror_problem("wgrad", M, N, K, wflags, lda, ldxx, K)
+    return (_family(flags), 1 if fused else 2, 2, int(fused), d, w)
+
+
+def _describe_problem(call, family, prob, M, N, K, flags, lda, ldb, ldc):
+    bm, bn, bk, run, splits, _, per = prob
+    sp = " splits%d" % splits if splits > 1 else ""
+    if family != F32:
+        return "%s %dx%d%s" % ("gemm_bf16_kernel" if family == BF16_MFMA else "gemm_split_kernel", bm, bn, sp)
+    gM, gN, gK, gldc = _terms(call, M, N, K, ldc)
+    fast = bm == bn and bm in (64, 128) and not (call != "dgrad" and flags & EPI_ACT_GELU)
+    kinds = body_kinds(bm, bn, bk, fast, gM, gN, gK, lda, ldb, gldc, call != "wgrad", call == "fwd", splits, per, run)
+    return "gemm_f32_kernel %dx%d BK%d%s%s %s" % (bm, bn, bk, " run%d" % run if run > 1 else "", sp, kinds)
+
+
+def describe(fields, call, M, N, K, flags, lda, ldb, ldc, ldxx=0):
+    """The path label of a plan (the mirror's or the library's fields): kernel, tile, depth, chaining, splits, and the
+    main loops its blocks take."""
+    family, launches, problems, fused = fields[:4]
+    if call != "pair":
+        return _describe_problem(call, family, fields[4], M, N, K, flags, lda, ldb, ldc)
+    wflags = flags & (EPI_BF16 | EPI_SPLIT3 | EPI_A_BF16 | EPI_B_BF16)
+    d, w = fields[4], fields[5]
+    if not fused:
+        return "two calls | w %s | d %s" % (_describe_problem("wgrad", family, w, M, N, K, wflags, lda, ldxx, K),
+                                            _describe_problem("dgrad", family, d, M, N, K, flags, lda, ldb, ldc))
+    if family == BF16_MFMA:
+        return "gemm16_pair_kernel splits%d" % w[4]
+    bt = d[0]
+    assert (d[0], d[1], d[2], w[0], w[1], w[2], w[3]) == (bt, bt, 32, bt, bt, 32, 1)
+    dk = body_kinds(bt, bt, 32, True, M, K, N, lda, ldb, ldc, True, False, run=d[3])
+    wk = body_kinds(bt, bt, 32, True, N, K, M, lda, ldxx, K, False, False, w[4], w[6])
+    return "gemm_pair_kernel %d | d%s %s | w splits%d %s" % (bt, " run%d" % d[3] if d[3] > 1 else "", dk, w[4], wk)
 
 
 def _ld(n):
     return _cdiv(n + 4, 8) * 8                 # >= n + 4 and a multiple of 8 (bf16 outputs need it)
 
 
+def launch_lds(call, N, K):
+    """Leading dimensions the GPU tests launch a case with, in vlg_linear_plan's order (lda, ldb, ldc, ldxx)."""
+    return {"fwd": (K, K, _ld(N), 0), "dgrad": (N, K, _ld(K), 0), "wgrad": (N, K, 0, 0), "pair": (N, K, _ld(K), K)}[call]
+
+
 def plan(call, M, N, K, flags):
     """The mirror's name of the path a case reaches, with the leading dimensions the GPU tests use."""
-    if call == "fwd":
-        return plan_fwd(M, N, K, flags, K, K, _ld(N))
-    if call == "dgrad":
-        return plan_dgrad(M, N, K, flags, N, K, _ld(K))
-    if call == "wgrad":
-        return plan_wgrad(M, N, K, flags, N, K)
-    return plan_pair(M, N, K, flags, N, K, _ld(K), K)
+    lds = launch_lds(call, N, K)
+    return describe(mirror_plan(call, M, N, K, flags, *lds), call, M, N, K, flags, *lds)
+
+
+class _Problem(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("bm", "bn", "bk", "run", "splits", "blocks")] + [("rows_per_split", ctypes.c_int64)]
+
+
+class _Plan(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("family", "launches", "problems", "fused")] + [("p", _Problem * 2)]
+
+
+def library_plan(lib, call, M, N, K, flags, lda, ldb, ldc, ldxx=0):
+    """vlg_linear_plan -> (return code, fields in mirror_plan's layout)."""
+    out = _Plan()
+    rc = lib.vlg_linear_plan(CALLS[call], M, N, K, flags, lda, ldb, ldc, ldxx, ctypes.byref(out))
+    probs = tuple((p.bm, p.bn, p.bk, p.run, p.splits, p.blocks, p.rows_per_split) for p in out.p[:out.problems])
+    return rc, (out.family, out.launches, out.problems, out.fused) + probs
+
+
+def library_path(lib, call, M, N, K, flags):
+    """The path the LIBRARY's plan names for the leading dimensions the GPU tests launch with."""
+    lds = launch_lds(call, N, K)
+    rc, fields = library_plan(lib, call, M, N, K, flags, *lds)
+    assert rc == 0, (call, M, N, K, flags, rc)
+    return describe(fields, call, M, N, K, flags, *lds)
 
 
 # ------------------------------------------------------------------------------------------------ the case table
@@ -274,19 +307,108 @@ def test_mirror_names_the_path(case):
     assert plan(call, M, N, K, flags) == path
 
 
-def test_mirror_split_counts_match_the_library():
-    """Host only (no launch): the mirror's weight-gradient split count is the library's, for every case and a grid of
-    shapes around the plan's thresholds, so the mirror cannot drift from csrc/gemm.hip silently."""
+# Sweep of test_mirror_matches_the_library_plan.  Extents are multiples of 8 (the bf16 and fp32x3 kernels' slots).  M crosses:
+# 512 blocks of gemm_wants_small at N or K = 256 (32 640 / 32 768 / 32 896), the weight-gradient rule's 385 at N = K = 256
+# (24 576 / 24 832), M % 128 (1 000, 4 000, 33 000), and the `tiles_m * tiles_n / r >= 512` steps of gemm_run (16 256 /
+# 16 384 x 1 536, 32 768 x 768 | 1 024, 65 536).  N crosses N <= 32 and N % 128, K crosses Kc % 64.
+SWEEP_M = (128, 1000, 4000, 4096, 8192, 16256, 16384, 24576, 24832, 32640, 32768, 32896, 33000, 65536)
+SWEEP_N = (24, 32, 40, 200, 256, 520, 768, 1024, 1536)
+SWEEP_K = (64, 136, 192, 256, 264, 768)
+IO3, IO6, IO7 = EPI_A_BF16 | EPI_B_BF16, EPI_B_BF16 | EPI_OUT_BF16, STORAGE
+GG = EPI_BIAS | EPI_GELU | EPI_GELU_GRAD
+SWEEP_FLAGS = {        # plain and heavy epilogues; native fp32, fp32x3, bf16 with io 0 and the storage combinations the step uses
+    "fwd": [EPI_BIAS, EPI_BIAS | EPI_GELU, GG, EPI_BIAS | EPI_RESID, EPI_BIAS | EPI_RESID | EPI_ACT_GELU,
+            EPI_SPLIT3 | EPI_BIAS, EPI_SPLIT3 | EPI_BIAS | EPI_GELU, EPI_SPLIT3 | EPI_BIAS | EPI_RESID,
+            EPI_BF16 | EPI_BIAS, EPI_BF16 | EPI_BIAS | EPI_GELU, EPI_BF16 | GG, EPI_BF16 | EPI_BIAS | EPI_RESID,
+            EPI_BF16 | IO3 | EPI_BIAS, EPI_BF16 | IO7 | EPI_BIAS, EPI_BF16 | IO7 | EPI_BIAS | EPI_GELU, EPI_BF16 | IO7 | GG,
+            EPI_BF16 | IO3 | EPI_BIAS | EPI_RESID],
+    "dgrad": [EPI_NONE, EPI_DGELU, EPI_MUL, EPI_SPLIT3, EPI_SPLIT3 | EPI_DGELU, EPI_BF16, EPI_BF16 | EPI_DGELU,
+              EPI_BF16 | EPI_MUL, EPI_BF16 | IO6, EPI_BF16 | IO6 | EPI_DGELU, EPI_BF16 | IO6 | EPI_MUL, EPI_BF16 | IO7],
+    "wgrad": [0, EPI_ACT_GELU, EPI_SPLIT3, EPI_BF16, EPI_BF16 | EPI_B_BF16, EPI_BF16 | IO3],
+    "pair": [EPI_NONE, EPI_MUL, EPI_DGELU, EPI_SPLIT3, EPI_BF16, EPI_BF16 | IO6, EPI_BF16 | IO7, EPI_BF16 | IO6 | EPI_MUL],
+}
+# leading dimensions on both sides of the 2^28-element spans of gemm_run: 127 * lda + Kc, 255 * ldb + Kc (forward) or
+# Kc * ldb + 256 (data gradient), 127 * ldc + 128
+LD_A = (2113648, 2113672)            # 127 * ld + 768 < 2^28 <= 127 * ld + 64
+LD_C = (2113656, 2113664)            # 127 * ld + 128 < 2^28 <= ...
+
+
+def _sweep_lds(call, M, N, K):
+    """Leading-dimension sets of one shape: tight, padded, and - where the shape could chain - around each 2^28 span."""
+    a, bb, c, xx = launch_lds(call, N, K)
+    tight = {"fwd": (K, K, N, 0), "dgrad": (N, K, K, 0), "wgrad": (N, K, 0, 0), "pair": (N, K, K, K)}[call]
+    out = [tight, (a + 8, bb + 8, c, xx + 8 if xx else 0)]
+    if call != "wgrad" and M % 128 == 0 and M >= 16384:
+        gK = K if call == "fwd" else N
+        ld_b = ((1 << 28) // 255 // 8 * 8 - 8, (1 << 28) // 255 // 8 * 8 + 8) if call == "fwd" else \
+            (((1 << 28) - 256) // gK // 8 * 8 - 8, ((1 << 28) - 256) // gK // 8 * 8 + 8)
+        out += [(v, bb, c, xx) for v in LD_A] + [(a, v, c, xx) for v in ld_b] + [(a, bb, v, xx) for v in LD_C]
+    return out
+
+
+def _accepted(call, N, flags):
+    """Combinations with a kernel (the table of gemm_plan): the narrow forward exists with the BIAS epilogue only outside the
+    native family, GELU on load needs wide products."""
+    epi = flags & ~(EPI_BF16 | EPI_SPLIT3 | STORAGE)
+    if flags & EPI_ACT_GELU and N <= 32:
+        return False
+    return not (call == "fwd" and N <= 32 and flags & (EPI_BF16 | EPI_SPLIT3) and epi != EPI_BIAS)
+
+
+def test_mirror_matches_the_library_plan():
+    """Host only (no launch): every field vlg_linear_plan reports - family, launches, fused, and per problem tile, BK, run,
+    splits, blocks, rows per split - is the mirror's, for every case of the tables at the leading dimensions it launches
+    with and over a sweep that crosses each threshold of the planner, so neither the mirror nor a case's path can drift
+    from csrc/gemm.hip silently.  The slab-count queries read the same plan."""
     from vlg import hip
     lib = hip.load()
-    shapes = [(c[2], c[3], c[4], c[5] & (EPI_BF16 | EPI_SPLIT3 | EPI_ACT_GELU)) for c in ALL_CASES if c[1] in ("wgrad", "pair")]
-    for M in (128, 1000, 4000, 4096, 8192, 16384, 33000, 65536):
-        for N in (24, 32, 200, 256, 520, 768, 1024):
-            for K in (64, 136, 256, 264, 768):
-                for fl in (0, EPI_BF16, EPI_SPLIT3, EPI_ACT_GELU):
-                    shapes.append((M, N, K, fl))
-    for M, N, K, fl in shapes:
-        assert wgrad_plan(M, N, K, fl)[0] == lib.vlg_linear_wgrad_slabs_for(M, N, K, fl), (M, N, K, fl)
+    n = 0
+    todo = [(c[1], c[2], c[3], c[4], c[5], launch_lds(c[1], c[3], c[4])) for c in ALL_CASES]
+    todo += [("pair", M, N, K, fl, launch_lds("pair", N, K)) for _, M, N, K, fl, _ in RIDER_CALLS]
+    for call, flag_list in SWEEP_FLAGS.items():
+        for M in SWEEP_M:
+            for N in SWEEP_N:
+                for K in SWEEP_K:
+                    for lds in _sweep_lds(call, M, N, K):
+                        todo += [(call, M, N, K, fl, lds) for fl in flag_list if _accepted(call, N, fl)]
+    for call, M, N, K, fl, lds in todo:
+        rc, got = library_plan(lib, call, M, N, K, fl, *lds)
+        assert rc == 0, (call, M, N, K, fl, lds, rc)
+        assert got == mirror_plan(call, M, N, K, fl, *lds), (call, M, N, K, fl, lds)
+        w = got[-1] if call in ("wgrad", "pair") else None
+        if w is not None:
+            wfl = fl & (EPI_BF16 | EPI_SPLIT3 | EPI_A_BF16 | EPI_B_BF16) if call == "pair" else fl
+            assert lib.vlg_linear_wgrad_slabs_for(M, N, K, wfl) == w[4], (call, M, N, K, fl)
+            if wfl == 0:
+                assert lib.vlg_linear_wgrad_slabs(M, N, K) == w[4]
+        n += 1
+    assert n > SWEEP_MIN_PLANS, n
+    # every threshold was crossed: both sides appear among the compared plans
+    seen = {(call, lib_fields[4][:4]) for call, lib_fields in
+            ((c, library_plan(lib, c, M, N, K, fl, *lds)[1]) for c, M, N, K, fl, lds in todo)}
+    for want in (("fwd", (64, 64, 32, 1)), ("fwd", (128, 128, 32, 1)), ("fwd", (128, 128, 16, 1)), ("fwd", (128, 32, 32, 1)),
+                 ("fwd", (128, 128, 32, 3)), ("fwd", (128, 128, 32, 4)), ("fwd", (128, 128, 32, 12)), ("dgrad", (128, 128, 16, 1)),
+                 ("dgrad", (128, 128, 32, 2)), ("wgrad", (64, 64, 32, 1)), ("wgrad", (32, 128, 32, 1)), ("wgrad", (128, 128, 32, 1)),
+                 ("fwd", (128, 128, 64, 1)), ("fwd", (128, 128, 16, 1)), ("pair", (64, 64, 32, 1)), ("pair", (128, 128, 32, 3))):
+        assert want in seen, want
+
+
+# compared plans of the sweep above (a count of the table, asserted so that a shrinking sweep is noticed)
+SWEEP_MIN_PLANS = 100000
+
+
+# A chained shape on both sides of each 32-bit span: run > 1 just under 2^28 elements, 1 at or above
+@pytest.mark.parametrize("call,which", [("fwd", 0), ("fwd", 1), ("fwd", 2), ("dgrad", 0), ("dgrad", 1), ("dgrad", 2)])
+def test_chaining_stops_at_the_32_bit_spans(call, which):
+    from vlg import hip
+    lib = hip.load()
+    M, N, K = (16384, 1536, 192) if call == "fwd" else (16384, 192, 1536)
+    lds = [lst for lst in _sweep_lds(call, M, N, K)[2:]]
+    under, over = lds[2 * which], lds[2 * which + 1]
+    for ld, run in ((under, 3), (over, 1)):
+        rc, got = library_plan(lib, call, M, N, K, EPI_BIAS if call == "fwd" else EPI_NONE, *ld)
+        assert rc == 0 and got[4][3] == run, (ld, got)
+        assert got == mirror_plan(call, M, N, K, EPI_BIAS if call == "fwd" else EPI_NONE, *ld)
 
 
 # ------------------------------------------------------------------------------------------------ GPU helpers
@@ -551,6 +673,7 @@ RUNNERS = {"fwd": run_fwd, "dgrad": run_dgrad, "wgrad": run_wgrad, "pair": run_p
 def test_gemm_path_against_fp64(H, dev, case):
     _, call, M, N, K, flags, path = case
     assert plan(call, M, N, K, flags) == path
+    assert library_path(H.load(), call, M, N, K, flags) == path
     RUNNERS[call](H, dev, M, N, K, flags)
 
 
@@ -562,6 +685,7 @@ def test_wgrad_32bit_offset_fallback(H, dev):
     _, _, M, N, K, flags, path = FALLBACK
     assert plan("wgrad", M, N, K, flags) == path
     lib = H.load()
+    assert library_path(lib, "wgrad", M, N, K, flags) == path
     ns = lib.vlg_linear_wgrad_slabs_for(M, N, K, 0)
     assert ns == 1
     gen = torch.Generator(device=dev)
@@ -620,6 +744,7 @@ def test_rider_reductions(H, dev, rc):
     those of the same call without riders."""
     _, M, N, K, flags, kind = rc
     assert plan("pair", M, N, K, flags).startswith(kind)
+    assert library_path(H.load(), "pair", M, N, K, flags).startswith(kind)
     slabs, dst, offs, table = _rider_table(dev)
     (dy, w, x, aux), d, out_t = pair_inputs(M, N, K, flags, dev, 41)
     dx0, gs0 = call_pair(H, dev, d, M, N, K, flags, out_t, fused=True)

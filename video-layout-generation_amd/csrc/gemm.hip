@@ -627,312 +627,375 @@ __global__ __launch_bounds__(GEMM_THREADS, BT == 64 ? 4 : 2) void gemm_pair_kern
     }
 }
 
-// The library keeps NO mutable process-wide state (include/vlg_hip.h).  The development switches below exist only in the
-// diagnostic build (`make diag` -> libvlg_hip_diag.so, -DVLG_DIAG; loaded by tools/diag, tools/ab through VLG_HIP_LIB); in
-// the product build they are constants (VLG_TUNE, common.h) and the vlg_debug_set_* entry points do not exist.
+// ---- host side.  The library keeps NO mutable process-wide state (include/vlg_hip.h).  The development switches below
+// exist only in the diagnostic build (`make diag` -> libvlg_hip_diag.so, -DVLG_DIAG; loaded by tools/diag, tools/ab through
+// VLG_HIP_LIB); in the product build they are constants (VLG_TUNE, common.h) and the vlg_debug_set_* entry points do not
+// exist.  They are inputs of the planner (gemm_plan) and of nothing else.
 #ifdef VLG_DIAG
 // a device buffer of 2 * blocks uint64 set through vlg_debug_set_clock_probe (NULL = off)
 static unsigned long long* vlg_gemm_clock_probe = nullptr;
 extern "C" void vlg_debug_set_clock_probe(unsigned long long* p) { vlg_gemm_clock_probe = p; }
-#else
-static constexpr unsigned long long* vlg_gemm_clock_probe = nullptr;
-#endif
-
-// Contraction depth per tile.  Measured on MI355X at the metric shape (tools/kernel_bench.py):
-// BK = 32 (2 blocks / CU) is 3-5 % faster for plain epilogues, BK = 16 (41 KB LDS, 4 blocks / CU)
-// is 8-11 % faster when the epilogue is heavy (GELU / dGELU: two extra 134 MB streams), because more
-// resident blocks de-synchronise the store bursts from the other blocks' MFMA phases.
-// VLG_GEMM_BK=16|32 (or vlg_debug_set_gemm_bk) forces one value for A/B runs.
-#ifdef VLG_DIAG
+// VLG_GEMM_BK=16|32 (or vlg_debug_set_gemm_bk) forces one contraction depth for A/B runs
 static int vlg_gemm_bk_forced = -1;
 extern "C" void vlg_debug_set_gemm_bk(int bk) { vlg_gemm_bk_forced = (bk == 16 || bk == 32) ? bk : 0; }
-#endif
-static int gemm_bk_override() {
-#ifdef VLG_DIAG
-    if (vlg_gemm_bk_forced >= 0) return vlg_gemm_bk_forced;
-#endif
-    return VLG_TUNE("VLG_GEMM_BK", 0);
-}
-
-// Consecutive N tiles per block (GemmArgs::run) for a launch that would otherwise take several rounds of blocks: the
-// largest divisor of the N tile count that still leaves one block per slot.  Only where EVERY block takes the fast path
-// (no edge tiles, an even number of K tiles, 32-bit spans): a block that does not computes one tile only.
-#ifdef VLG_DIAG
-static int vlg_gemm_run_forced = -1;
 // run: 0 = never chain, -1 = the library's choice, > 0 = that many
+static int vlg_gemm_run_forced = -1;
 extern "C" void vlg_debug_set_gemm_run(int run) { vlg_gemm_run_forced = run < 0 ? -1 : run; }
 #else
-static constexpr int vlg_gemm_run_forced = -1;
+static constexpr unsigned long long* vlg_gemm_clock_probe = nullptr;
+static constexpr int vlg_gemm_bk_forced = -1, vlg_gemm_run_forced = -1;
 #endif
-template <int BM, int BN, int BK, bool A_KC, bool B_KC>
-static int gemm_run(const GemmArgs& g, int slots) {
-    if (BM != 128 || BN != 128 || g.splits != 1) return 1;
-    if (g.M % BM != 0 || g.N % BN != 0 || g.Kc % (2 * BK) != 0) return 1;
-    const int64_t span_a = A_KC ? (int64_t)(BM - 1) * g.lda + g.Kc : g.Kc * g.lda + BM;
-    const int64_t span_b = B_KC ? (int64_t)(2 * BN - 1) * g.ldb + g.Kc : g.Kc * g.ldb + 2 * BN;
-    if (span_a >= (1ll << 28) || span_b >= (1ll << 28) || (int64_t)(BM - 1) * g.ldc + BN >= (1ll << 28)) return 1;
-    if (vlg_gemm_run_forced == 0) return 1;
-    int best = 1;
-    for (int r = 2; r <= g.tiles_n; ++r)
-        if (g.tiles_n % r == 0 && (int64_t)g.tiles_m * (g.tiles_n / r) >= slots) best = r;
-    if (vlg_gemm_run_forced > 0 && g.tiles_n % vlg_gemm_run_forced == 0) best = vlg_gemm_run_forced;
-    return best;
+static int gemm_bk_override() { return vlg_gemm_bk_forced >= 0 ? vlg_gemm_bk_forced : VLG_TUNE("VLG_GEMM_BK", 0); }
+
+// The instantiated native-fp32 kernels.  The call fixes the operand layouts: forward A.W^T reads both operands
+// contraction-contiguous, the data gradient dY.W reads W contraction-major, the weight gradient dY^T.X reads both
+// contraction-major and sums the columns of dY.  128x128 tiles come at both contraction depths.
+template <int CALL, int EPI, int BM, int BN, int BK>
+constexpr GemmKernelRow f32_row() {
+    return {CALL, EPI, 0, BM, BN, BK, gemm_f32_kernel<BM, BN, BK, CALL != VLG_CALL_WGRAD, CALL == VLG_CALL_FWD, EPI, CALL == VLG_CALL_WGRAD>};
+}
+#define EPI_GELU_GRAD (VLG_EPI_BIAS | VLG_EPI_GELU | VLG_EPI_GELU_GRAD)
+#define EPI_ACT_FWD (VLG_EPI_BIAS | VLG_EPI_RESID | GEMM_A_GELU)      /* A = gelu(stored pre-activation): the FFN's second projection */
+static const GemmKernelRow gemm_f32_kernels[] = {
+    f32_row<VLG_CALL_FWD, EPI_ACT_FWD, 128, 128, 16>(), f32_row<VLG_CALL_FWD, EPI_ACT_FWD, 128, 128, 32>(),
+    f32_row<VLG_CALL_FWD, VLG_EPI_BIAS, 128, 32, 32>(), f32_row<VLG_CALL_FWD, VLG_EPI_BIAS, 64, 64, 32>(),
+    f32_row<VLG_CALL_FWD, VLG_EPI_BIAS, 128, 128, 16>(), f32_row<VLG_CALL_FWD, VLG_EPI_BIAS, 128, 128, 32>(),
+    f32_row<VLG_CALL_FWD, VLG_EPI_BIAS | VLG_EPI_GELU, 64, 64, 32>(),
+    f32_row<VLG_CALL_FWD, VLG_EPI_BIAS | VLG_EPI_GELU, 128, 128, 16>(), f32_row<VLG_CALL_FWD, VLG_EPI_BIAS | VLG_EPI_GELU, 128, 128, 32>(),
+    f32_row<VLG_CALL_FWD, EPI_GELU_GRAD, 64, 64, 32>(),
+    f32_row<VLG_CALL_FWD, EPI_GELU_GRAD, 128, 128, 16>(), f32_row<VLG_CALL_FWD, EPI_GELU_GRAD, 128, 128, 32>(),
+    f32_row<VLG_CALL_FWD, VLG_EPI_BIAS | VLG_EPI_RESID, 64, 64, 32>(),
+    f32_row<VLG_CALL_FWD, VLG_EPI_BIAS | VLG_EPI_RESID, 128, 128, 16>(), f32_row<VLG_CALL_FWD, VLG_EPI_BIAS | VLG_EPI_RESID, 128, 128, 32>(),
+    f32_row<VLG_CALL_DGRAD, VLG_EPI_NONE, 64, 64, 32>(),
+    f32_row<VLG_CALL_DGRAD, VLG_EPI_NONE, 128, 128, 16>(), f32_row<VLG_CALL_DGRAD, VLG_EPI_NONE, 128, 128, 32>(),
+    f32_row<VLG_CALL_DGRAD, VLG_EPI_DGELU, 64, 64, 32>(),
+    f32_row<VLG_CALL_DGRAD, VLG_EPI_DGELU, 128, 128, 16>(), f32_row<VLG_CALL_DGRAD, VLG_EPI_DGELU, 128, 128, 32>(),
+    f32_row<VLG_CALL_DGRAD, VLG_EPI_MUL, 64, 64, 32>(),
+    f32_row<VLG_CALL_DGRAD, VLG_EPI_MUL, 128, 128, 16>(), f32_row<VLG_CALL_DGRAD, VLG_EPI_MUL, 128, 128, 32>(),
+    // (X = gelu(stored pre-activation): weight gradient of the FFN's second projection)
+    f32_row<VLG_CALL_WGRAD, GEMM_B_GELU, 128, 128, 16>(), f32_row<VLG_CALL_WGRAD, GEMM_B_GELU, 128, 128, 32>(),
+    f32_row<VLG_CALL_WGRAD, VLG_EPI_NONE, 64, 64, 32>(), f32_row<VLG_CALL_WGRAD, VLG_EPI_NONE, 32, 128, 32>(),
+    f32_row<VLG_CALL_WGRAD, VLG_EPI_NONE, 128, 128, 16>(), f32_row<VLG_CALL_WGRAD, VLG_EPI_NONE, 128, 128, 32>(),
+};
+static GemmPairKernel gemm_f32_pair_kernel(int bt, int epi_d) {
+    if (bt == 64) return epi_d == VLG_EPI_MUL ? gemm_pair_kernel<64, VLG_EPI_MUL> : gemm_pair_kernel<64, VLG_EPI_NONE>;
+    return epi_d == VLG_EPI_MUL ? gemm_pair_kernel<128, VLG_EPI_MUL> : gemm_pair_kernel<128, VLG_EPI_NONE>;
 }
 
-// 64x64 tiles (four 32x32 waves, four blocks per CU) for launches whose 128x128 tiles would leave CUs without a block: the
-// per-GPU share of a GLOBAL batch (reference src/trainer.py:148: 32 // 8 = 4 clips, M = 4 096 tokens) gives the N = 256
-// products 64 tiles for 256 CUs.  VLG_GEMM_SMALL=0 keeps 128x128 everywhere (A/B runs).
-static bool gemm_small_tiles() { return VLG_TUNE("VLG_GEMM_SMALL", 1) != 0; }
-// Measured (tools/shard_bench.py, interleaved repeated runs on one box): 64x64 tiles pay while the 128x128 tiles would not fill
-// the 512 block slots of the chip (2 per CU) - four resident 64x64 blocks overlap one block's prologue / epilogue with the
-// others' MFMAs: B = 4: 1.75 -> 1.05 ms, B = 8: 1.79 -> 1.76, B = 16: 3.11 -> 3.05.  A launch of exactly 512 blocks (the d x d
-// products of the headline step) is FASTER on 128x128 tiles (their higher arithmetic intensity: K = 4096 asymptote 150 vs 140
-// TFLOP/s; the step 5.55 vs 5.63 ms with a threshold of 1 025 - a first single-run sweep had suggested the opposite).
-// 128x128 block count under which 64x64 tiles are taken
-static int gemm_small_below() { return VLG_TUNE("VLG_GEMM_SMALL_BELOW", 512); }
-// the same for the weight-gradient plan: under 3/4 of the 512 slots of the 128x128 plan (B = 32 keeps that plan: 504-512 blocks)
-static int gemm_small_below_wgrad() { return VLG_TUNE("VLG_GEMM_SMALL_BELOW_WGRAD", 385); }
-static bool gemm_wants_small(int64_t M, int N, int splits) {
-    return gemm_small_tiles() && ((M + 127) / 128) * (int64_t)((N + 127) / 128) * splits < gemm_small_below();
-}
+// ================================================================================================ the planner
+// gemm_plan() is the ONE place that decides how a vlg_linear_* call runs: kernel family, tile, contraction depth, chained N
+// tiles, the weight gradient's split, one fused launch or two for a pair - and whether the call has a kernel at all.  It
+// is a function of the call's shape, flags and leading dimensions (and, in the diagnostic build, of the switches above):
+// the entry points launch what it returns, vlg_linear_plan and the slab-count queries report it.
 
-template <int BM, int BN, bool A_KC, bool B_KC, int EPI, bool COLSUM>
-static int launch_gemm(GemmArgs g, hipStream_t s) {
-    if constexpr (BM == 128 && BN == 128 && !COLSUM && (EPI & (GEMM_A_GELU | GEMM_B_GELU)) == 0) {
-        if (gemm_wants_small(g.M, g.N, g.splits)) return launch_gemm<64, 64, A_KC, B_KC, EPI, COLSUM>(g, s);
-    }
-    g.tiles_m = (int)((g.M + BM - 1) / BM);
-    g.tiles_n = (g.N + BN - 1) / BN;
-    g.run = 1;
-    g.clock_probe = vlg_gemm_clock_probe;
-    const dim3 block(GEMM_THREADS);
-    constexpr bool CAN_RUN = BM == 128 && BN == 128 && !COLSUM && (EPI & (GEMM_A_GELU | GEMM_B_GELU)) == 0;
-    if constexpr (BM == 128 && BN == 128) {
-        const int forced = gemm_bk_override();
-        const bool heavy_epilogue = (EPI & (VLG_EPI_GELU | VLG_EPI_DGELU)) != 0;
-        int run32 = 1;
-        if constexpr (CAN_RUN) run32 = gemm_run<BM, BN, 32, A_KC, B_KC>(g, 512);
-        // heavy epilogues: three blocks per CU (BK = 16) hide more of the store phase - unless the tiles chain (run > 1)
-        if (forced == 16 || (forced != 32 && heavy_epilogue && run32 == 1)) {
-            const int64_t blocks = (int64_t)g.tiles_m * (g.tiles_n / g.run) * g.splits;
-            if (blocks < 1 || blocks > 0x7fffffff) return VLG_ERR_SHAPE;
-            hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, 16, A_KC, B_KC, EPI, COLSUM>), dim3((unsigned)blocks), block, 0, s, g);
-            return vlg_last_error();
-        }
-        g.run = run32;
-    }
-    const int64_t blocks = (int64_t)g.tiles_m * (g.tiles_n / g.run) * g.splits;
-    if (blocks < 1 || blocks > 0x7fffffff) return VLG_ERR_SHAPE;
-    hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, 32, A_KC, B_KC, EPI, COLSUM>), dim3((unsigned)blocks), block, 0, s, g);
-    return vlg_last_error();
-}
-
-// bf16-MFMA kernels with bf16 LDS tiles (gemm_bf16.hip)
-int vlg_gemm16_fwd(GemmArgs g, int epilogue, int io, hipStream_t s);
-int vlg_gemm16_dgrad(GemmArgs g, int epilogue, int io, hipStream_t s);
-int vlg_gemm16_wgrad(GemmArgs g, int io, hipStream_t s);
-int vlg_gemm16_pair(GemmArgs gd, GemmArgs gw, int epilogue, bool dy_bf16, const int64_t* rider, int rider_rows, int rider_bpr, hipStream_t s);
-// fp32 operands split into three bf16 terms, six bf16 MFMAs per product block (gemm_split.hip)
-int vlg_gemm_split_fwd(GemmArgs g, int epilogue, hipStream_t s);
-int vlg_gemm_split_dgrad(GemmArgs g, int epilogue, hipStream_t s);
-int vlg_gemm_split_wgrad(GemmArgs g, hipStream_t s);
-// storage bits of the epilogue / flags word -> IO template value (bit 0 A, bit 1 B, bit 2 C + aux)
+// storage bits of the flags word -> IO template value (bit 0 A, bit 1 B, bit 2 C + aux)
 static int gemm_io_bits(int flags) {
     return ((flags & VLG_EPI_A_BF16) ? 1 : 0) | ((flags & VLG_EPI_B_BF16) ? 2 : 0) | ((flags & VLG_EPI_OUT_BF16) ? 4 : 0);
 }
 #define VLG_EPI_STORAGE (VLG_EPI_A_BF16 | VLG_EPI_B_BF16 | VLG_EPI_OUT_BF16)
 
-static bool gemm_ptr_ok(const void* p, int ld) { return vlg_aligned16(p) && (ld & 3) == 0; }
+// What the caller's buffers add to the checks of a call, so that the planner applies every check in the one order the
+// entry points have always applied them.  The plan queries pass none: every buffer is taken to be fine.
+struct GemmBufs {
+    bool ab_ok = true;            // fwd, dgrad: both operands 16-byte aligned and the output non-NULL
+    bool wg_ok = true;            // wgrad: dY and X 16-byte aligned, slabs non-NULL
+    bool bias = true, aux_in = true, aux_out = true;      // present
+    bool out16_ok = true;         // bf16 outputs: C (and aux_out) 16-byte aligned
+    bool slabs = false;           // wgrad: the caller's slab stride and capacity, to be checked
+    int64_t slab_stride = 0, slab_capacity = 0;
+};
 
-extern "C" int vlg_linear_fwd(const void* A, int lda, const void* W, int ldw, const float* bias,
-                              void* C, int ldc, const void* aux_in, void* aux_out,
-                              int64_t M, int N, int K, int epilogue, void* stream) {
-    if (M < 1 || N < 1 || K < 4 || (K & 3) || lda < K || ldw < K || ldc < N) return VLG_ERR_SHAPE;
-    if (!gemm_ptr_ok(A, lda) || !gemm_ptr_ok(W, ldw) || !C) return VLG_ERR_ALIGN;
-    GemmArgs g{};
-    g.A = A; g.B = W; g.C = C; g.bias = bias; g.aux_in = aux_in; g.aux_out = aux_out;
-    g.M = M; g.N = N; g.Kc = K; g.lda = lda; g.ldb = ldw; g.ldc = ldc;
-    g.splits = 1; g.kc_per_split = K; g.slab_stride = 0; g.colsum_off = 0;
-    hipStream_t s = (hipStream_t)stream;
-    const bool bf16 = (epilogue & VLG_EPI_BF16) != 0, split3 = (epilogue & VLG_EPI_SPLIT3) != 0;
-    const int io = gemm_io_bits(epilogue);
-    epilogue &= ~(VLG_EPI_BF16 | VLG_EPI_STORAGE | VLG_EPI_SPLIT3);
-    if (split3 && (bf16 || io != 0)) return VLG_ERR_SHAPE;
-    if ((epilogue & VLG_EPI_BIAS) && !bias) return VLG_ERR_SHAPE;
-    if ((epilogue & (VLG_EPI_RESID | VLG_EPI_DGELU)) && !aux_in) return VLG_ERR_SHAPE;
-    if ((epilogue & VLG_EPI_GELU) && !aux_out) return VLG_ERR_SHAPE;
-    if ((epilogue & VLG_EPI_MUL) != 0) return VLG_ERR_SHAPE;                                          // a dgrad epilogue
-    if ((epilogue & VLG_EPI_GELU_GRAD) && (split3 || epilogue != (VLG_EPI_BIAS | VLG_EPI_GELU | VLG_EPI_GELU_GRAD)))
-        return VLG_ERR_SHAPE;                                                                         // native fp32 and bf16 paths
-    const bool narrow = N <= 32;
-    const bool act_gelu = (epilogue & VLG_EPI_ACT_GELU) != 0;
-    epilogue &= ~VLG_EPI_ACT_GELU;
-    if (act_gelu && (bf16 || split3)) return VLG_ERR_SHAPE;      // native fp32 path only
-    if (io != 0 && !bf16) return VLG_ERR_SHAPE;      // bf16 activation storage exists for the bf16 MFMA mode only
-    if (((io & 1) && (lda & 7)) || ((io & 2) && (ldw & 7))) return VLG_ERR_ALIGN;
-    if (bf16) return vlg_gemm16_fwd(g, epilogue, io, s);
-    if (split3) return vlg_gemm_split_fwd(g, epilogue, s);
-    if (act_gelu) {                                   // A = gelu(stored pre-activation): the FFN's second projection
-        if (epilogue != (VLG_EPI_BIAS | VLG_EPI_RESID) || narrow) return VLG_ERR_SHAPE;
-        return launch_gemm<128, 128, true, true, VLG_EPI_BIAS | VLG_EPI_RESID | GEMM_A_GELU, false>(g, s);
-    }
-    switch (epilogue) {
-        case VLG_EPI_BIAS:
-            return narrow ? launch_gemm<128, 32, true, true, VLG_EPI_BIAS, false>(g, s)
-                          : launch_gemm<128, 128, true, true, VLG_EPI_BIAS, false>(g, s);
-        case VLG_EPI_BIAS | VLG_EPI_GELU:
-            return launch_gemm<128, 128, true, true, VLG_EPI_BIAS | VLG_EPI_GELU, false>(g, s);
-        case VLG_EPI_BIAS | VLG_EPI_GELU | VLG_EPI_GELU_GRAD:
-            return launch_gemm<128, 128, true, true, VLG_EPI_BIAS | VLG_EPI_GELU | VLG_EPI_GELU_GRAD, false>(g, s);
-        case VLG_EPI_BIAS | VLG_EPI_RESID:
-            return launch_gemm<128, 128, true, true, VLG_EPI_BIAS | VLG_EPI_RESID, false>(g, s);
-        default:
-            return VLG_ERR_SHAPE;
-    }
+// 64x64 tiles (four 32x32 waves, four blocks per CU) for launches whose 128x128 tiles would leave CUs without a block: the
+// per-GPU share of a GLOBAL batch (reference src/trainer.py:148: 32 // 8 = 4 clips, M = 4 096 tokens) gives the N = 256
+// products 64 tiles for 256 CUs.  VLG_GEMM_SMALL=0 keeps 128x128 everywhere (A/B runs).
+// Measured (tools/shard_bench.py, interleaved repeated runs on one box): 64x64 tiles pay while the 128x128 tiles would not fill
+// the 512 block slots of the chip (2 per CU) - four resident 64x64 blocks overlap one block's prologue / epilogue with the
+// others' MFMAs: B = 4: 1.75 -> 1.05 ms, B = 8: 1.79 -> 1.76, B = 16: 3.11 -> 3.05.  A launch of exactly 512 blocks (the d x d
+// products of the headline step) is FASTER on 128x128 tiles (their higher arithmetic intensity: K = 4096 asymptote 150 vs 140
+// TFLOP/s; the step 5.55 vs 5.63 ms with a threshold of 1 025 - a first single-run sweep had suggested the opposite).
+static bool gemm_small_tiles() { return VLG_TUNE("VLG_GEMM_SMALL", 1) != 0; }
+static bool gemm_wants_small(int64_t M, int N) {
+    return gemm_small_tiles() && ((M + 127) / 128) * (int64_t)((N + 127) / 128) < VLG_TUNE("VLG_GEMM_SMALL_BELOW", 512);
 }
 
-// Argument checks of the two backward calls, shared with vlg_linear_dgrad_wgrad: the pair accepts exactly what the two single
-// calls accept.  0 = valid.  (The bf16 and split kernels add the 8-element granularity of their slots.)
-static int check_dgrad(const void* dY, int ldy, const void* W, int ldw, const void* dX, int ldx, const void* aux_in,
-                       int64_t M, int N, int K, int flags) {
-    if (M < 1 || N < 4 || (N & 3) || K < 4 || (K & 3) || ldy < N || ldw < K || ldx < K) return VLG_ERR_SHAPE;
-    if (!gemm_ptr_ok(dY, ldy) || !gemm_ptr_ok(W, ldw) || !dX) return VLG_ERR_ALIGN;
-    const bool bf16 = (flags & VLG_EPI_BF16) != 0, split3 = (flags & VLG_EPI_SPLIT3) != 0;
-    const int io = gemm_io_bits(flags);
-    const int epi = flags & ~(VLG_EPI_BF16 | VLG_EPI_STORAGE | VLG_EPI_SPLIT3);
-    if (split3 && (bf16 || io != 0)) return VLG_ERR_SHAPE;
-    if (io != 0 && !bf16) return VLG_ERR_SHAPE;
-    if (((io & 1) && (ldy & 7)) || ((io & 2) && (ldw & 7))) return VLG_ERR_ALIGN;
-    if ((epi == VLG_EPI_DGELU || epi == VLG_EPI_MUL) && !aux_in) return VLG_ERR_SHAPE;
-    if (epi == VLG_EPI_MUL && split3) return VLG_ERR_SHAPE;                                           // native fp32 and bf16 paths
-    return 0;
-}
-static int check_wgrad(const void* dY, int ldy, const void* X, int ldx, const float* slabs, int64_t slab_stride,
-                       int64_t M, int N, int K, int flags) {
-    if (M < 1 || N < 4 || (N & 3) || K < 4 || (K & 3) || ldy < N || ldx < K) return VLG_ERR_SHAPE;
-    if (slab_stride < (int64_t)N * K + N) return VLG_ERR_SHAPE;
-    if (!gemm_ptr_ok(dY, ldy) || !gemm_ptr_ok(X, ldx) || !slabs) return VLG_ERR_ALIGN;
-    const int io = gemm_io_bits(flags);
-    if (io != 0 && !(flags & VLG_EPI_BF16)) return VLG_ERR_SHAPE;
-    if (((io & 1) && (ldy & 7)) || ((io & 2) && (ldx & 7))) return VLG_ERR_ALIGN;
-    return 0;
+// Consecutive N tiles per block (GemmArgs::run) of a 128x128, BK = 32 launch that would otherwise take several rounds of
+// blocks: the largest divisor of the N tile count that still leaves one block per slot (512 = 256 CUs x 2).  Only where
+// EVERY block takes the fast path (no edge tiles, an even number of K tiles, 32-bit spans): a block that does not
+// computes one tile only.  A is contraction-contiguous in every launch that may chain (forward, data gradient).
+// (The span test restates `fits` of gemm_f32_body for BM = BN = 128 and a contraction-contiguous A: sharing one helper
+// with the kernel changed its register allocation, and the device code is to stay as it is.)
+static int gemm_run(int64_t M, int N, int64_t Kc, int lda, int ldb, int ldc, bool b_kc) {
+    if (M % 128 != 0 || N % 128 != 0 || Kc % 64 != 0 || vlg_gemm_run_forced == 0) return 1;
+    const int64_t span_a = (int64_t)127 * lda + Kc, span_b = b_kc ? (int64_t)255 * ldb + Kc : Kc * ldb + 256;
+    if (span_a >= (1ll << 28) || span_b >= (1ll << 28) || (int64_t)127 * ldc + 128 >= (1ll << 28)) return 1;
+    const int64_t tiles_m = M / 128;
+    const int tiles_n = N / 128;
+    int best = 1;
+    for (int r = 2; r <= tiles_n; ++r)
+        if (tiles_n % r == 0 && tiles_m * (tiles_n / r) >= 512) best = r;
+    if (vlg_gemm_run_forced > 0 && tiles_n % vlg_gemm_run_forced == 0) best = vlg_gemm_run_forced;
+    return best;
 }
 
-// dX[M,K] = dY[M,N] . W[N,K]  : contraction over N, W is contraction-major
-static GemmArgs dgrad_args(const void* dY, int ldy, const void* W, int ldw, void* dX, int ldx, const void* aux_in, int64_t M, int N, int K) {
-    GemmArgs g{};
-    g.A = dY; g.B = W; g.C = dX; g.aux_in = aux_in;
-    g.M = M; g.N = K; g.Kc = N; g.lda = ldy; g.ldb = ldw; g.ldc = ldx;
-    g.splits = 1; g.kc_per_split = N;
-    return g;
-}
-
-extern "C" int vlg_linear_dgrad(const void* dY, int ldy, const void* W, int ldw, void* dX, int ldx,
-                                const void* aux_in, int64_t M, int N, int K, int epilogue, void* stream) {
-    if (const int rc = check_dgrad(dY, ldy, W, ldw, dX, ldx, aux_in, M, N, K, epilogue)) return rc;
-    const GemmArgs g = dgrad_args(dY, ldy, W, ldw, dX, ldx, aux_in, M, N, K);
-    hipStream_t s = (hipStream_t)stream;
-    const bool bf16 = (epilogue & VLG_EPI_BF16) != 0, split3 = (epilogue & VLG_EPI_SPLIT3) != 0;
-    const int io = gemm_io_bits(epilogue);
-    epilogue &= ~(VLG_EPI_BF16 | VLG_EPI_STORAGE | VLG_EPI_SPLIT3);
-    if (bf16) return vlg_gemm16_dgrad(g, epilogue, io, s);
-    if (split3) return vlg_gemm_split_dgrad(g, epilogue, s);
-    switch (epilogue) {
-        case VLG_EPI_NONE:
-            return launch_gemm<128, 128, true, false, VLG_EPI_NONE, false>(g, s);
-        case VLG_EPI_DGELU:
-            return launch_gemm<128, 128, true, false, VLG_EPI_DGELU, false>(g, s);
-        case VLG_EPI_MUL:
-            return launch_gemm<128, 128, true, false, VLG_EPI_MUL, false>(g, s);
-        default:
-            return VLG_ERR_SHAPE;
-    }
-}
-
-// Split plan for the weight gradient: enough blocks to fill 256 CUs x 2 blocks, each split a multiple of BK token rows.
+// Split of the weight gradient over the tokens: enough blocks to fill 256 CUs x 2 blocks, each split a multiple of 64 token rows.
 // small (native fp32 kernel only: flags without the bf16 / split / GELU-on-load bits): 64x64 tiles, four resident blocks per
 // CU, token ranges down to 128 rows - taken when the 128x128 plan would leave CUs without a block (few tokens: the
-// strong-scaling shard).  The ONE plan of every weight-gradient launch and of the slab-count queries (M >= 1).
-struct WgradPlan { int splits; int64_t per; bool small; };
-static WgradPlan wgrad_plan(int64_t M, int N, int K, int flags) {
-    const bool native = (flags & (VLG_EPI_BF16 | VLG_EPI_SPLIT3 | VLG_EPI_ACT_GELU)) == 0;
-    WgradPlan r{1, 0, false};
+// strong-scaling shard): under 3/4 of the 512 slots (B = 32 keeps the 128x128 plan: 504-512 blocks).
+static void wgrad_split(GemmProblem& p, int64_t M, int N, int K, bool native) {
     const int bm = N <= 32 ? 32 : 128;
     int64_t tiles = ((N + bm - 1) / bm) * (int64_t)((K + 127) / 128);
     int64_t want = 512 / tiles;                      // blocks <= 512 = 256 CUs x 2 resident blocks: one full wave, no tail
     int64_t max_splits = (M + 255) / 256;
-    if (native && bm == 128 && gemm_small_tiles() && tiles * (want < max_splits ? (want < 1 ? 1 : want) : max_splits) < gemm_small_below_wgrad()) {
-        r.small = true;
+    const bool small = native && bm == 128 && gemm_small_tiles() &&
+                       tiles * (want < max_splits ? (want < 1 ? 1 : want) : max_splits) < VLG_TUNE("VLG_GEMM_SMALL_BELOW_WGRAD", 385);
+    if (small) {
         tiles = ((N + 63) / 64) * (int64_t)((K + 63) / 64);
         want = VLG_TUNE("VLG_WGRAD_SMALL_SLOTS", 1024) / tiles;
         max_splits = (M + 127) / 128;
     }
     if (want > max_splits) want = max_splits;
     if (want < 1) want = 1;
-    if (r.small) {
+    if (small) {
         // equal token ranges where a slightly smaller count allows them (a ragged last range costs a whole block round)
         for (int64_t c = want; c >= 1 && 4 * c >= 3 * want; --c)
             if (M % (c * 64) == 0) { want = c; break; }
     }
-    int64_t p = (M + want - 1) / want;
-    const int kt = 64;                               // whole K tiles, and an even number of the fp32 kernel's 32-row tiles (its
-                                                     // loop runs them in pairs: an odd count costs one iteration on zeros)
-    p = (p + kt - 1) / kt * kt;
-    r.per = p;
-    r.splits = (int)((M + p - 1) / p);
-    return r;
+    // whole K tiles, and an even number of the fp32 kernel's 32-row tiles (its loop runs them in pairs: an odd count costs
+    // one iteration on zeros)
+    p.per = ((M + want - 1) / want + 63) / 64 * 64;
+    p.splits = (int)((M + p.per - 1) / p.per);
+    p.bm = small ? 64 : bm;
+    p.bn = small ? 64 : 128;
 }
 
-extern "C" int vlg_linear_wgrad_slabs_for(int64_t M, int N, int K, int flags) { return wgrad_plan(M, N, K, flags).splits; }
-extern "C" int vlg_linear_wgrad_slabs(int64_t M, int N, int K) { return vlg_linear_wgrad_slabs_for(M, N, K, 0); }
-
-// slab[s][n*K + k] = sum_{m in split s} dY[m,n] X[m,k] ;  slab[s][N*K + n] = sum_m dY[m,n]
-static GemmArgs wgrad_args(const void* dY, int ldy, const void* X, int ldx, float* slabs, int64_t slab_stride, int64_t M, int N, int K,
-                           const WgradPlan& plan) {
-    GemmArgs g{};
-    g.A = dY; g.B = X; g.C = slabs;
-    g.M = N; g.N = K; g.Kc = M; g.lda = ldy; g.ldb = ldx; g.ldc = K;
-    g.splits = plan.splits; g.kc_per_split = plan.per;
-    g.slab_stride = slab_stride; g.colsum_off = (int64_t)N * K;
-    return g;
-}
-
-extern "C" int vlg_linear_wgrad(const void* dY, int ldy, const void* X, int ldx, float* slabs,
-                                int64_t slab_stride, int64_t slab_capacity, int64_t M, int N, int K, int flags, void* stream) {
-    if (const int rc = check_wgrad(dY, ldy, X, ldx, slabs, slab_stride, M, N, K, flags)) return rc;
-    const WgradPlan plan = wgrad_plan(M, N, K, flags);
-    if (slab_capacity < (int64_t)plan.splits * slab_stride) return VLG_ERR_SHAPE;   // the caller's buffer must hold every slab
-    const GemmArgs g = wgrad_args(dY, ldy, X, ldx, slabs, slab_stride, M, N, K, plan);
-    hipStream_t s = (hipStream_t)stream;
+// Argument checks of the three single calls, up to the choice of a kernel; the pair accepts exactly what its two single calls accept.
+static int check_fwd(int64_t M, int N, int K, int flags, int lda, int ldw, int ldc, const GemmBufs& b) {
+    if (M < 1 || N < 1 || K < 4 || (K & 3) || lda < K || ldw < K || ldc < N) return VLG_ERR_SHAPE;
+    if (!b.ab_ok || (lda & 3) || (ldw & 3)) return VLG_ERR_ALIGN;
+    const bool bf16 = (flags & VLG_EPI_BF16) != 0, split3 = (flags & VLG_EPI_SPLIT3) != 0, act_gelu = (flags & VLG_EPI_ACT_GELU) != 0;
     const int io = gemm_io_bits(flags);
-    if (flags & VLG_EPI_BF16) return (flags & VLG_EPI_ACT_GELU) ? VLG_ERR_SHAPE : vlg_gemm16_wgrad(g, io, s);
-    if (flags & VLG_EPI_SPLIT3) return (io == 0 && !(flags & VLG_EPI_ACT_GELU)) ? vlg_gemm_split_wgrad(g, s) : VLG_ERR_SHAPE;
-    if (flags & VLG_EPI_ACT_GELU)                     // X = gelu(stored pre-activation): weight gradient of the FFN's second projection
-        return N <= 32 ? VLG_ERR_SHAPE : launch_gemm<128, 128, false, false, GEMM_B_GELU, true>(g, s);
-    if (plan.small) return launch_gemm<64, 64, false, false, VLG_EPI_NONE, true>(g, s);
-    return N <= 32 ? launch_gemm<32, 128, false, false, VLG_EPI_NONE, true>(g, s)
-                   : launch_gemm<128, 128, false, false, VLG_EPI_NONE, true>(g, s);
+    const int epi = flags & ~(VLG_EPI_BF16 | VLG_EPI_STORAGE | VLG_EPI_SPLIT3);
+    if (split3 && (bf16 || io != 0)) return VLG_ERR_SHAPE;
+    if (((epi & VLG_EPI_BIAS) && !b.bias) || ((epi & (VLG_EPI_RESID | VLG_EPI_DGELU)) && !b.aux_in) || ((epi & VLG_EPI_GELU) && !b.aux_out))
+        return VLG_ERR_SHAPE;
+    if ((epi & VLG_EPI_MUL) != 0) return VLG_ERR_SHAPE;                                               // a dgrad epilogue
+    if ((epi & VLG_EPI_GELU_GRAD) && (split3 || epi != EPI_GELU_GRAD)) return VLG_ERR_SHAPE;          // native fp32 and bf16 paths
+    if (act_gelu && (bf16 || split3)) return VLG_ERR_SHAPE;                                           // native fp32 path only
+    if (io != 0 && !bf16) return VLG_ERR_SHAPE;      // bf16 activation storage exists for the bf16 MFMA mode only
+    if (((io & 1) && (lda & 7)) || ((io & 2) && (ldw & 7))) return VLG_ERR_ALIGN;
+    return 0;
+}
+static int check_dgrad(int64_t M, int N, int K, int flags, int ldy, int ldw, int ldx, const GemmBufs& b) {
+    if (M < 1 || N < 4 || (N & 3) || K < 4 || (K & 3) || ldy < N || ldw < K || ldx < K) return VLG_ERR_SHAPE;
+    if (!b.ab_ok || (ldy & 3) || (ldw & 3)) return VLG_ERR_ALIGN;
+    const bool bf16 = (flags & VLG_EPI_BF16) != 0, split3 = (flags & VLG_EPI_SPLIT3) != 0;
+    const int io = gemm_io_bits(flags);
+    const int epi = flags & ~(VLG_EPI_BF16 | VLG_EPI_STORAGE | VLG_EPI_SPLIT3);
+    if (split3 && (bf16 || io != 0)) return VLG_ERR_SHAPE;
+    if (io != 0 && !bf16) return VLG_ERR_SHAPE;
+    if (((io & 1) && (ldy & 7)) || ((io & 2) && (ldw & 7))) return VLG_ERR_ALIGN;
+    if ((epi == VLG_EPI_DGELU || epi == VLG_EPI_MUL) && !b.aux_in) return VLG_ERR_SHAPE;
+    if (epi == VLG_EPI_MUL && split3) return VLG_ERR_SHAPE;                                           // native fp32 and bf16 paths
+    return 0;
+}
+static int check_wgrad(int64_t M, int N, int K, int flags, int ldy, int ldx, const GemmBufs& b) {
+    if (M < 1 || N < 4 || (N & 3) || K < 4 || (K & 3) || ldy < N || ldx < K) return VLG_ERR_SHAPE;
+    if (b.slabs && b.slab_stride < (int64_t)N * K + N) return VLG_ERR_SHAPE;
+    if (!b.wg_ok || (ldy & 3) || (ldx & 3)) return VLG_ERR_ALIGN;
+    const int io = gemm_io_bits(flags);
+    if (io != 0 && !(flags & VLG_EPI_BF16)) return VLG_ERR_SHAPE;
+    if (((io & 1) && (ldy & 7)) || ((io & 2) && (ldx & 7))) return VLG_ERR_ALIGN;
+    return 0;
 }
 
-// ---- data gradient + weight gradient of one projection in ONE launch (gemm_pair_kernel)
+// One single call's kernel: family, tile, depth, chaining, split, instantiation, grid.  Every field is filled whatever the
+// result (M, N, K >= 1); the result is 0 or the refusal.  bk_forced: 0 = the library's choice.
+static int gemm_problem(GemmProblem& p, int call, int64_t M, int N, int K, int flags, int lda, int ldb, int ldc, int bk_forced, const GemmBufs& b) {
+    const bool fwd = call == VLG_CALL_FWD, wgrad = call == VLG_CALL_WGRAD;
+    const bool act = !(call == VLG_CALL_DGRAD) && (flags & VLG_EPI_ACT_GELU) != 0, narrow = N <= 32;
+    p = GemmProblem{};
+    p.call = call;
+    p.family = (flags & VLG_EPI_BF16) ? VLG_GEMM_BF16 : (flags & VLG_EPI_SPLIT3) ? VLG_GEMM_F32X3 : VLG_GEMM_F32;
+    const bool native = p.family == VLG_GEMM_F32;
+    p.io = gemm_io_bits(flags);
+    // (a weight gradient has no epilogue and ignores the bits; the data gradient knows no GELU on load and finds no kernel for the bit)
+    p.epi = wgrad ? (act && native ? GEMM_B_GELU : 0)
+                  : (flags & ~(VLG_EPI_BF16 | VLG_EPI_STORAGE | VLG_EPI_SPLIT3 | (fwd ? VLG_EPI_ACT_GELU : 0))) | (act && native ? GEMM_A_GELU : 0);
+    // the product in the kernel's terms: C[gM, gN] = A . B over gK
+    const int64_t gM = wgrad ? N : M, gK = fwd ? K : wgrad ? M : N;
+    const int gN = fwd ? N : K;
+    p.bm = 128; p.bn = 128; p.run = 1; p.splits = 1; p.per = gK;
+    p.bk = native ? 32 : p.family == VLG_GEMM_BF16 ? 64 : 16;
+    // tiles.  32 wide for the narrow side of the head's products (N <= 32), where that kernel exists; the native kernels
+    // without bias-gradient sums and GELU on load have 64x64 twins (the weight gradient's come with its split)
+    if (wgrad) wgrad_split(p, M, N, K, native && !act);
+    else if (fwd && narrow && (!native || p.epi == VLG_EPI_BIAS)) p.bn = 32;
+    else if (native && !act && gemm_wants_small(gM, gN)) p.bm = p.bn = 64;
+    // contraction depth and chaining of the native 128x128 kernels.  Measured on MI355X at the metric shape
+    // (tools/kernel_bench.py): BK = 32 (2 blocks / CU) is 3-5 % faster for plain epilogues, BK = 16 (41 KB LDS, 3 blocks /
+    // CU) is 8-11 % faster when the epilogue is heavy (GELU / dGELU: two extra 134 MB streams), because more resident
+    // blocks de-synchronise the store bursts from the other blocks' MFMA phases - unless the tiles chain (run > 1).
+    if (native && p.bm == 128 && p.bn == 128) {
+        const bool heavy = (p.epi & (VLG_EPI_GELU | VLG_EPI_DGELU)) != 0;
+        const int run32 = (wgrad || act) ? 1 : gemm_run(gM, gN, gK, lda, ldb, ldc, fwd);
+        if (bk_forced == 16 || (bk_forced != 32 && heavy && run32 == 1)) p.bk = 16;
+        else p.run = run32;
+    }
+    p.kernel = native ? gemm_find_kernel(gemm_f32_kernels, sizeof(gemm_f32_kernels) / sizeof(gemm_f32_kernels[0]), p)
+                      : p.family == VLG_GEMM_BF16 ? vlg_gemm16_kernel(p) : vlg_gemm_split_kernel(p);
+    p.blocks = ((gM + p.bm - 1) / p.bm) * (((gN + p.bn - 1) / p.bn) / p.run) * p.splits;
+
+    // the caller's slab buffer must hold every slab
+    if (wgrad && b.slabs && b.slab_capacity < (int64_t)p.splits * b.slab_stride) return VLG_ERR_SHAPE;
+    if (!wgrad && p.family == VLG_GEMM_BF16 && (p.io & 4) && ((ldc & 7) || !b.out16_ok)) return VLG_ERR_ALIGN;
+    // bf16 LDS tiles are filled in 8-element slots: every memory-contiguous extent of the two operands in whole slots
+    if (!native && (fwd ? (K & 7) : ((N | K) & 7)) != 0) return VLG_ERR_SHAPE;
+    if (act && (!native || narrow)) return VLG_ERR_SHAPE;
+    if (!p.kernel || p.blocks < 1 || p.blocks > 0x7fffffff) return VLG_ERR_SHAPE;
+    return 0;
+}
+
+// ---- data gradient + weight gradient of one projection in ONE launch (gemm_pair_kernel, gemm16_pair_kernel)
 // VLG_GEMM_PAIR (diagnostic build): 0 = always two launches, 1 = one launch only where both problems take the 64x64 tiles (few
 // tokens: neither fills the chip alone), 2 (default) = also on 128x128 tiles.  Measured at the metric shape (interleaved
 // repeated runs, one box): 5.553 -> 5.500 ms per step (-1.0 %, three of three pairs of runs) - each launch pays one ramp
 // and one drain for two problems, and the second problem's blocks fill the slots the first one's stragglers leave.
-static int gemm_pair_mode() { return VLG_TUNE("VLG_GEMM_PAIR", 2); }
 #define VLG_RIDER_BPR 128          /* blocks per table row: what vlg_reduce_slabs_table launches get from the engine */
-template <int BT, int EPI_D>
-static int launch_pair(GemmArgs gd, GemmArgs gw, const int64_t* rider, int rider_rows, hipStream_t s) {
-    gd.tiles_m = (int)((gd.M + BT - 1) / BT); gd.tiles_n = (gd.N + BT - 1) / BT; gd.run = 1; gd.clock_probe = nullptr;
-    gw.tiles_m = (int)((gw.M + BT - 1) / BT); gw.tiles_n = (gw.N + BT - 1) / BT; gw.run = 1; gw.clock_probe = nullptr;
-    if constexpr (BT == 128) gd.run = gemm_run<128, 128, 32, true, false>(gd, 512);
-    const int64_t nd = (int64_t)gd.tiles_m * (gd.tiles_n / gd.run), nw = (int64_t)gw.tiles_m * gw.tiles_n * gw.splits;
-    const int64_t nd_pad = (nd + 7) / 8 * 8;
-    const int64_t nr = rider ? (int64_t)rider_rows * VLG_RIDER_BPR : 0;
-    if (nd < 1 || nw < 1 || nd_pad + nw + nr > 0x7fffffff) return VLG_ERR_SHAPE;
-    hipLaunchKernelGGL((gemm_pair_kernel<BT, EPI_D>), dim3((unsigned)(nd_pad + nw + nr)), dim3(GEMM_THREADS), 0, s, gd, gw, (int)nd, (int)nd_pad,
-                       (int)nw, rider, VLG_RIDER_BPR);
+
+// call: VLG_CALL_*; (M, N, K) and the leading dimensions as the entry point of that call takes them: (lda, ldb, ldc) =
+// fwd (lda, ldw, ldc), dgrad (ldy, ldw, ldx), wgrad (ldy, ldx, -), pair (ldy, ldw, ldx) + ldxx.  O(N tiles) arithmetic.
+static GemmPlan gemm_plan(int call, int64_t M, int N, int K, int flags, int lda, int ldb, int ldc, int ldxx = 0, const GemmBufs& b = GemmBufs{}) {
+    GemmPlan r{};
+    r.n = call == VLG_CALL_PAIR ? 2 : 1;
+    r.err = VLG_ERR_SHAPE;
+    if (call < VLG_CALL_FWD || call > VLG_CALL_PAIR || M < 1 || N < 1 || K < 1) return r;
+    auto first = [](int e0, int e1) { return e0 ? e0 : e1; };
+    if (call != VLG_CALL_PAIR) {
+        const int e = call == VLG_CALL_FWD ? check_fwd(M, N, K, flags, lda, ldb, ldc, b)
+                    : call == VLG_CALL_DGRAD ? check_dgrad(M, N, K, flags, lda, ldb, ldc, b) : check_wgrad(M, N, K, flags, lda, ldb, b);
+        r.err = first(e, gemm_problem(r.p[0], call, M, N, K, flags, lda, ldb, call == VLG_CALL_WGRAD ? K : ldc, gemm_bk_override(), b));
+        return r;
+    }
+    // the weight gradient's flags (bf16 storage: A = the shared dY, B = W of the data gradient AND X of the weight gradient)
+    const int wflags = flags & (VLG_EPI_BF16 | VLG_EPI_SPLIT3 | VLG_EPI_A_BF16 | VLG_EPI_B_BF16);
+    const int e = first(check_wgrad(M, N, K, wflags, lda, ldxx, b), check_dgrad(M, N, K, flags, lda, ldb, ldc, b));
+    GemmProblem &d = r.p[0], &w = r.p[1];
+    int ew = gemm_problem(w, VLG_CALL_WGRAD, M, N, K, wflags, lda, ldxx, K, gemm_bk_override(), b);
+    int ed = gemm_problem(d, VLG_CALL_DGRAD, M, N, K, flags, lda, ldb, ldc, gemm_bk_override(), b);
+    // fusable into one launch: the data gradient's epilogue is NONE or MUL and both products are wide, and
+    //   native fp32: both problems on the same tiles (64x64 at few tokens, 128x128 elsewhere - VLG_GEMM_PAIR >= 2)
+    //   bf16 storage (bf16 W / X / dX, dY bf16 or fp32; VLG_GEMM_PAIR >= 2): the bf16-tile pair kernel at every shape - but
+    //   not MUL with a bf16 dY, which the single data gradient has no kernel for
+    const int st_bits = flags & VLG_EPI_STORAGE;
+    const bool a16 = (st_bits & VLG_EPI_A_BF16) != 0, mul = d.epi == VLG_EPI_MUL;
+    const bool bf16_pair = (flags & VLG_EPI_BF16) && (st_bits & ~VLG_EPI_A_BF16) == (VLG_EPI_B_BF16 | VLG_EPI_OUT_BF16);
+    const bool native = d.family == VLG_GEMM_F32 && w.family == VLG_GEMM_F32;
+    const int mode = VLG_TUNE("VLG_GEMM_PAIR", 2);
+    r.fused = (d.epi == VLG_EPI_NONE || mul) && N > 32 && K > 32 &&
+              (bf16_pair ? (mode > 1 && !(mul && a16)) : (native && mode > 0 && w.bm == d.bm && (d.bm == 64 || mode > 1)));
+    if (r.fused) {
+        // the pair kernels are built at the families' one depth (native: BK = 32); a misaligned bf16 dX is a shape error here
+        ew = gemm_problem(w, VLG_CALL_WGRAD, M, N, K, wflags, lda, ldxx, K, 32, b);
+        ed = gemm_problem(d, VLG_CALL_DGRAD, M, N, K, flags, lda, ldb, ldc, 32, b) ? VLG_ERR_SHAPE : 0;
+        r.pair = bf16_pair ? vlg_gemm16_pair_kernel(d.epi, a16) : gemm_f32_pair_kernel(d.bm, d.epi);
+        // (the data gradient's blocks are padded to a multiple of 8: a block's number mod 8 still names its XCD for the second problem)
+        if ((d.blocks + 7) / 8 * 8 + w.blocks > 0x7fffffff) ed = VLG_ERR_SHAPE;
+    }
+    r.err = first(e, first(ew, ed));
+    return r;
+}
+
+extern "C" int vlg_linear_plan(int call, int64_t M, int N, int K, int flags, int lda, int ldb, int ldc, int ldxx, vlg_gemm_plan* out) {
+    const GemmPlan r = gemm_plan(call, M, N, K, flags, lda, ldb, ldc, ldxx);
+    if (!out) return VLG_ERR_ALIGN;
+    *out = vlg_gemm_plan{};
+    if (r.err) return r.err;
+    out->family = r.p[0].family; out->problems = r.n; out->fused = r.fused ? 1 : 0; out->launches = r.n == 2 && !r.fused ? 2 : 1;
+    for (int i = 0; i < r.n; ++i) {
+        const GemmProblem& p = r.p[i];
+        out->p[i] = vlg_gemm_problem{p.bm, p.bn, p.bk, p.run, p.splits, (int)p.blocks, p.per};
+    }
+    return 0;
+}
+// (every M >= 1, N >= 1, K >= 1: the split follows from the extents and the mode bits, also where the call itself is refused)
+extern "C" int vlg_linear_wgrad_slabs_for(int64_t M, int N, int K, int flags) { return gemm_plan(VLG_CALL_WGRAD, M, N, K, flags, N, K, K).p[0].splits; }
+extern "C" int vlg_linear_wgrad_slabs(int64_t M, int N, int K) { return vlg_linear_wgrad_slabs_for(M, N, K, 0); }
+
+// ================================================================================================ the launches
+// One launch of one problem, whatever the family: host-only arguments, grid and kernel come from the plan.
+static int gemm_launch(GemmArgs g, const GemmProblem& p, hipStream_t s) {
+    gemm_apply_plan(g, p, p.family == VLG_GEMM_F32 ? vlg_gemm_clock_probe : nullptr);
+    hipLaunchKernelGGL(p.kernel, dim3((unsigned)p.blocks), dim3(GEMM_THREADS), 0, s, g);
     return vlg_last_error();
+}
+// A fused pair: blocks [0, nd_pad) the data gradient, [nd_pad, nd_pad + nw) the weight gradient, then the rider rows.
+static int gemm_launch_pair(GemmArgs gd, GemmArgs gw, const GemmPlan& plan, const int64_t* rider, int rider_rows, hipStream_t s) {
+    gemm_apply_plan(gd, plan.p[0], nullptr);
+    gemm_apply_plan(gw, plan.p[1], nullptr);
+    const int64_t nd = plan.p[0].blocks, nw = plan.p[1].blocks, nd_pad = (nd + 7) / 8 * 8;
+    const int64_t nr = rider ? (int64_t)rider_rows * VLG_RIDER_BPR : 0;
+    if (nd_pad + nw + nr > 0x7fffffff) return VLG_ERR_SHAPE;
+    hipLaunchKernelGGL(plan.pair, dim3((unsigned)(nd_pad + nw + nr)), dim3(GEMM_THREADS), 0, s, gd, gw, (int)nd, (int)nd_pad, (int)nw, rider,
+                       VLG_RIDER_BPR);
+    return vlg_last_error();
+}
+
+// C[M,N] = A[M,K] . W[N,K]^T
+static GemmArgs fwd_args(const void* A, int lda, const void* W, int ldw, const float* bias, void* C, int ldc, const void* aux_in,
+                         void* aux_out, int64_t M, int N, int K) {
+    GemmArgs g{};
+    g.A = A; g.B = W; g.C = C; g.bias = bias; g.aux_in = aux_in; g.aux_out = aux_out;
+    g.M = M; g.N = N; g.Kc = K; g.lda = lda; g.ldb = ldw; g.ldc = ldc;
+    return g;
+}
+// dX[M,K] = dY[M,N] . W[N,K]  : contraction over N, W is contraction-major
+static GemmArgs dgrad_args(const void* dY, int ldy, const void* W, int ldw, void* dX, int ldx, const void* aux_in, int64_t M, int N, int K) {
+    GemmArgs g{};
+    g.A = dY; g.B = W; g.C = dX; g.aux_in = aux_in;
+    g.M = M; g.N = K; g.Kc = N; g.lda = ldy; g.ldb = ldw; g.ldc = ldx;
+    return g;
+}
+// slab[s][n*K + k] = sum_{m in split s} dY[m,n] X[m,k] ;  slab[s][N*K + n] = sum_m dY[m,n]
+static GemmArgs wgrad_args(const void* dY, int ldy, const void* X, int ldx, float* slabs, int64_t slab_stride, int64_t M, int N, int K) {
+    GemmArgs g{};
+    g.A = dY; g.B = X; g.C = slabs;
+    g.M = N; g.N = K; g.Kc = M; g.lda = ldy; g.ldb = ldx; g.ldc = K;
+    g.slab_stride = slab_stride; g.colsum_off = (int64_t)N * K;
+    return g;
+}
+
+// Every entry point: the buffers' facts, the plan (all checks), then - only for an accepted call - the launches.
+extern "C" int vlg_linear_fwd(const void* A, int lda, const void* W, int ldw, const float* bias,
+                              void* C, int ldc, const void* aux_in, void* aux_out,
+                              int64_t M, int N, int K, int epilogue, void* stream) {
+    GemmBufs b;
+    b.ab_ok = vlg_aligned16(A) && vlg_aligned16(W) && C;
+    b.bias = bias; b.aux_in = aux_in; b.aux_out = aux_out;
+    b.out16_ok = vlg_aligned16(C) && vlg_aligned16(aux_out);
+    const GemmPlan plan = gemm_plan(VLG_CALL_FWD, M, N, K, epilogue, lda, ldw, ldc, 0, b);
+    if (plan.err) return plan.err;
+    return gemm_launch(fwd_args(A, lda, W, ldw, bias, C, ldc, aux_in, aux_out, M, N, K), plan.p[0], (hipStream_t)stream);
+}
+
+extern "C" int vlg_linear_dgrad(const void* dY, int ldy, const void* W, int ldw, void* dX, int ldx,
+                                const void* aux_in, int64_t M, int N, int K, int epilogue, void* stream) {
+    GemmBufs b;
+    b.ab_ok = vlg_aligned16(dY) && vlg_aligned16(W) && dX;
+    b.aux_in = aux_in;
+    b.out16_ok = vlg_aligned16(dX);
+    const GemmPlan plan = gemm_plan(VLG_CALL_DGRAD, M, N, K, epilogue, ldy, ldw, ldx, 0, b);
+    if (plan.err) return plan.err;
+    return gemm_launch(dgrad_args(dY, ldy, W, ldw, dX, ldx, aux_in, M, N, K), plan.p[0], (hipStream_t)stream);
+}
+
+extern "C" int vlg_linear_wgrad(const void* dY, int ldy, const void* X, int ldx, float* slabs,
+                                int64_t slab_stride, int64_t slab_capacity, int64_t M, int N, int K, int flags, void* stream) {
+    GemmBufs b;
+    b.wg_ok = vlg_aligned16(dY) && vlg_aligned16(X) && slabs;
+    b.slabs = true; b.slab_stride = slab_stride; b.slab_capacity = slab_capacity;
+    const GemmPlan plan = gemm_plan(VLG_CALL_WGRAD, M, N, K, flags, ldy, ldx, 0, 0, b);
+    if (plan.err) return plan.err;
+    return gemm_launch(wgrad_args(dY, ldy, X, ldx, slabs, slab_stride, M, N, K), plan.p[0], (hipStream_t)stream);
 }
 
 extern "C" int vlg_reduce_slabs_table(const int64_t* table, int n_rows, int blocks_per_row, void* stream);
@@ -946,38 +1009,21 @@ extern "C" int vlg_linear_dgrad_wgrad(const void* dY, int ldy, const void* W, in
     // a slab-reduction table (vlg_reduce_slabs_table) over OTHER buffers than this call writes, reduced by extra blocks of the
     // same launch where the two products are fused, by a launch of their own otherwise - same sums either way.
     if (rider_table != nullptr && (rider_rows < 1 || rider_rows > 4096)) return VLG_ERR_SHAPE;
-    // the weight gradient's flags (bf16 storage: A = the shared dY, B = W of the data gradient AND X of the weight gradient)
-    const int wflags = epilogue & (VLG_EPI_BF16 | VLG_EPI_SPLIT3 | VLG_EPI_A_BF16 | VLG_EPI_B_BF16);
-    if (const int rc = check_wgrad(dY, ldy, X, ldxx, slabs, slab_stride, M, N, K, wflags)) return rc;
-    if (const int rc = check_dgrad(dY, ldy, W, ldw, dX, ldx, aux_in, M, N, K, epilogue)) return rc;
-    const WgradPlan plan = wgrad_plan(M, N, K, wflags);
-    if (slab_capacity < (int64_t)plan.splits * slab_stride) return VLG_ERR_SHAPE;
-
-    // fusable into one launch: the data gradient's epilogue is NONE or MUL and both products are wide, and
-    //   native fp32: both problems on the same tiles (64x64 at few tokens, 128x128 elsewhere - VLG_GEMM_PAIR >= 2)
-    //   bf16 storage (bf16 W / X / dX, dY bf16 or fp32; VLG_GEMM_PAIR >= 2): the bf16-tile pair kernel at every shape - but
-    //   not MUL with a bf16 dY, which the single data gradient has no kernel for
-    const int epi = epilogue & ~(VLG_EPI_BF16 | VLG_EPI_STORAGE);
-    const int st_bits = epilogue & VLG_EPI_STORAGE;
-    const bool a16 = (st_bits & VLG_EPI_A_BF16) != 0, mul = epi == VLG_EPI_MUL;
-    const bool bf16_pair = (epilogue & VLG_EPI_BF16) && (st_bits & ~VLG_EPI_A_BF16) == (VLG_EPI_B_BF16 | VLG_EPI_OUT_BF16);
-    const bool native = (epilogue & VLG_EPI_BF16) == 0 && st_bits == 0;
-    const bool small_d = gemm_wants_small(M, K, 1);
-    const int mode = gemm_pair_mode();
-    const bool fusable = (epi == VLG_EPI_NONE || mul) && N > 32 && K > 32 &&
-                         (bf16_pair ? (mode > 1 && !(mul && a16))
-                                    : (native && mode > 0 && plan.small == small_d && (small_d || mode > 1)));
-    if (!fusable) {
-        if (rider_table != nullptr) {
-            if (const int rc = vlg_reduce_slabs_table(rider_table, rider_rows, VLG_RIDER_BPR, stream)) return rc;
-        }
-        if (const int rc = vlg_linear_wgrad(dY, ldy, X, ldxx, slabs, slab_stride, slab_capacity, M, N, K, wflags, stream)) return rc;
-        return vlg_linear_dgrad(dY, ldy, W, ldw, dX, ldx, aux_in, M, N, K, epilogue, stream);
-    }
+    GemmBufs b;
+    b.wg_ok = vlg_aligned16(dY) && vlg_aligned16(X) && slabs;
+    b.ab_ok = vlg_aligned16(dY) && vlg_aligned16(W) && dX;
+    b.aux_in = aux_in;
+    b.out16_ok = vlg_aligned16(dX);
+    b.slabs = true; b.slab_stride = slab_stride; b.slab_capacity = slab_capacity;
+    const GemmPlan plan = gemm_plan(VLG_CALL_PAIR, M, N, K, epilogue, ldy, ldw, ldx, ldxx, b);
+    if (plan.err) return plan.err;
     const GemmArgs gd = dgrad_args(dY, ldy, W, ldw, dX, ldx, aux_in, M, N, K);
-    const GemmArgs gw = wgrad_args(dY, ldy, X, ldxx, slabs, slab_stride, M, N, K, plan);
+    const GemmArgs gw = wgrad_args(dY, ldy, X, ldxx, slabs, slab_stride, M, N, K);
     hipStream_t s = (hipStream_t)stream;
-    if (bf16_pair) return vlg_gemm16_pair(gd, gw, epi, a16, rider_table, rider_rows, VLG_RIDER_BPR, s);
-    if (small_d) return mul ? launch_pair<64, VLG_EPI_MUL>(gd, gw, rider_table, rider_rows, s) : launch_pair<64, VLG_EPI_NONE>(gd, gw, rider_table, rider_rows, s);
-    return mul ? launch_pair<128, VLG_EPI_MUL>(gd, gw, rider_table, rider_rows, s) : launch_pair<128, VLG_EPI_NONE>(gd, gw, rider_table, rider_rows, s);
+    if (plan.fused) return gemm_launch_pair(gd, gw, plan, rider_table, rider_rows, s);
+    if (rider_table != nullptr) {
+        if (const int rc = vlg_reduce_slabs_table(rider_table, rider_rows, VLG_RIDER_BPR, stream)) return rc;
+    }
+    if (const int rc = gemm_launch(gw, plan.p[1], s)) return rc;
+    return gemm_launch(gd, plan.p[0], s);
 }

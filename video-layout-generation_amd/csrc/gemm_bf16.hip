@@ -250,99 +250,35 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm16_pair_kernel(const Gemm
         reduce_table_row(rider, rb / rider_bpr, rb % rider_bpr, rider_bpr, reinterpret_cast<float4(*)[16]>(smem));
     }
 }
-template <int EPI_D, bool A16>
-static int launch16_pair(GemmArgs gd, GemmArgs gw, const int64_t* rider, int rider_rows, int rider_bpr, hipStream_t s) {
-    gd.tiles_m = (int)((gd.M + 127) / 128); gd.tiles_n = (gd.N + 127) / 128; gd.clock_probe = nullptr; gd.run = 1;
-    gw.tiles_m = (int)((gw.M + 127) / 128); gw.tiles_n = (gw.N + 127) / 128; gw.clock_probe = nullptr; gw.run = 1;
-    const int64_t nd = (int64_t)gd.tiles_m * gd.tiles_n, nw = (int64_t)gw.tiles_m * gw.tiles_n * gw.splits;
-    const int64_t nd_pad = (nd + 7) / 8 * 8;
-    const int64_t nr = rider ? (int64_t)rider_rows * rider_bpr : 0;
-    if (nd < 1 || nw < 1 || nd_pad + nw + nr > 0x7fffffff) return VLG_ERR_SHAPE;
-    hipLaunchKernelGGL((gemm16_pair_kernel<EPI_D, A16>), dim3((unsigned)(nd_pad + nw + nr)), dim3(GEMM_THREADS), 0, s, gd, gw, (int)nd, (int)nd_pad,
-                       (int)nw, rider, rider_bpr);
-    return vlg_last_error();
+// ---- host side: the instantiated kernels, one row each (gemm_tile.h); gemm_plan (gemm.hip) takes a call's kernel from here
+// and gemm.hip launches it.  Everything fp32 in HBM (io 0, the "bf16_mfma" mode) and the combinations the bf16-storage
+// step launches (bf16 activations AND bf16 shadow weights); the pair: W / X / dX bf16, the shared dY bf16 or fp32 (a
+// residual-stream gradient).
+GemmPairKernel vlg_gemm16_pair_kernel(int epi_d, bool dy_bf16) {
+    if (epi_d == VLG_EPI_NONE) return dy_bf16 ? gemm16_pair_kernel<VLG_EPI_NONE, true> : gemm16_pair_kernel<VLG_EPI_NONE, false>;
+    if (epi_d == VLG_EPI_MUL) return dy_bf16 ? gemm16_pair_kernel<VLG_EPI_MUL, true> : gemm16_pair_kernel<VLG_EPI_MUL, false>;
+    return nullptr;
 }
-// bf16-storage pair (W / X / dX bf16): dy_bf16 = the shared dY is bf16 (else fp32: a residual-stream gradient)
-int vlg_gemm16_pair(GemmArgs gd, GemmArgs gw, int epilogue, bool dy_bf16, const int64_t* rider, int rider_rows, int rider_bpr, hipStream_t s) {
-    if ((gd.ldc & 7) || !vlg_aligned16(gd.C) || (gd.Kc & 7) || (gd.N & 7) || (gw.M & 7) || (gw.N & 7) || gw.M <= 32) return VLG_ERR_SHAPE;
-#define PAIR16(EPI, A16) launch16_pair<EPI, A16>(gd, gw, rider, rider_rows, rider_bpr, s)
-    if (epilogue == VLG_EPI_NONE) return dy_bf16 ? PAIR16(VLG_EPI_NONE, true) : PAIR16(VLG_EPI_NONE, false);
-    if (epilogue == VLG_EPI_MUL) return dy_bf16 ? PAIR16(VLG_EPI_MUL, true) : PAIR16(VLG_EPI_MUL, false);
-#undef PAIR16
-    return VLG_ERR_SHAPE;
+template <int CALL, int EPI, int IO, int BM, int BN>
+constexpr GemmKernelRow bf16_row() {
+    return {CALL, EPI, IO, BM, BN, 64, gemm_bf16_kernel<BM, BN, CALL != VLG_CALL_WGRAD, CALL == VLG_CALL_FWD, EPI, CALL == VLG_CALL_WGRAD, IO>};
 }
-template <int BM, int BN, bool A_KC, bool B_KC, int EPI, bool COLSUM, int IO>
-static int launch16(GemmArgs g, hipStream_t s) {
-    g.tiles_m = (int)((g.M + BM - 1) / BM);
-    g.tiles_n = (g.N + BN - 1) / BN;
-    const int64_t blocks = (int64_t)g.tiles_m * g.tiles_n * g.splits;
-    if (blocks < 1 || blocks > 0x7fffffff) return VLG_ERR_SHAPE;
-    g.clock_probe = nullptr;
-    hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, A_KC, B_KC, EPI, COLSUM, IO>), dim3((unsigned)blocks), dim3(GEMM_THREADS), 0, s, g);
-    return vlg_last_error();
-}
-
-// Entry points for gemm.hip's C ABI functions.  `io` = storage bits (see gemm_bf16_kernel); shapes were validated by the
-// caller, this layer adds the 8-element granularity of the bf16 slots.  Instantiated: everything fp32 (io 0, the
-// "bf16_mfma" mode) and the combinations the bf16-storage step launches (bf16 activations AND bf16 shadow weights).
-int vlg_gemm16_fwd(GemmArgs g, int epilogue, int io, hipStream_t s) {
-    if ((io & 4) && ((g.ldc & 7) || !vlg_aligned16(g.C) || (g.aux_out && !vlg_aligned16(g.aux_out)))) return VLG_ERR_ALIGN;
-    if (g.Kc & 7) return VLG_ERR_SHAPE;
-    const bool narrow = g.N <= 32;
-#define FWD(EPI, IO) (narrow ? launch16<128, 32, true, true, EPI, false, IO>(g, s) : launch16<128, 128, true, true, EPI, false, IO>(g, s))
-    if (epilogue == VLG_EPI_BIAS) {
-        switch (io) { case 0: return FWD(VLG_EPI_BIAS, 0); case 3: return FWD(VLG_EPI_BIAS, 3); case 7: return FWD(VLG_EPI_BIAS, 7); default: return VLG_ERR_SHAPE; }
-    }
-#undef FWD
-    if (narrow) return VLG_ERR_SHAPE;
-    if (epilogue == (VLG_EPI_BIAS | VLG_EPI_GELU)) {
-        if (io == 0) return launch16<128, 128, true, true, VLG_EPI_BIAS | VLG_EPI_GELU, false, 0>(g, s);
-        if (io == 7) return launch16<128, 128, true, true, VLG_EPI_BIAS | VLG_EPI_GELU, false, 7>(g, s);
-        return VLG_ERR_SHAPE;
-    }
-    if (epilogue == (VLG_EPI_BIAS | VLG_EPI_GELU | VLG_EPI_GELU_GRAD)) {
-        if (io == 0) return launch16<128, 128, true, true, VLG_EPI_BIAS | VLG_EPI_GELU | VLG_EPI_GELU_GRAD, false, 0>(g, s);
-        if (io == 7) return launch16<128, 128, true, true, VLG_EPI_BIAS | VLG_EPI_GELU | VLG_EPI_GELU_GRAD, false, 7>(g, s);
-        return VLG_ERR_SHAPE;
-    }
-    if (epilogue == (VLG_EPI_BIAS | VLG_EPI_RESID)) {
-        if (io == 0) return launch16<128, 128, true, true, VLG_EPI_BIAS | VLG_EPI_RESID, false, 0>(g, s);
-        if (io == 3) return launch16<128, 128, true, true, VLG_EPI_BIAS | VLG_EPI_RESID, false, 3>(g, s);
-        return VLG_ERR_SHAPE;
-    }
-    return VLG_ERR_SHAPE;
-}
-
-int vlg_gemm16_dgrad(GemmArgs g, int epilogue, int io, hipStream_t s) {
-    // contraction over N (g.Kc), W rows are K-contiguous: both extents in 8-element slots
-    if ((io & 4) && ((g.ldc & 7) || !vlg_aligned16(g.C))) return VLG_ERR_ALIGN;
-    if ((g.Kc & 7) || (g.N & 7)) return VLG_ERR_SHAPE;
-    if (epilogue == VLG_EPI_NONE) {
-        switch (io) {
-            case 0: return launch16<128, 128, true, false, VLG_EPI_NONE, false, 0>(g, s);
-            case 6: return launch16<128, 128, true, false, VLG_EPI_NONE, false, 6>(g, s);
-            case 7: return launch16<128, 128, true, false, VLG_EPI_NONE, false, 7>(g, s);
-            default: return VLG_ERR_SHAPE;
-        }
-    }
-    if (epilogue == VLG_EPI_DGELU) {
-        if (io == 0) return launch16<128, 128, true, false, VLG_EPI_DGELU, false, 0>(g, s);
-        if (io == 6) return launch16<128, 128, true, false, VLG_EPI_DGELU, false, 6>(g, s);
-        return VLG_ERR_SHAPE;
-    }
-    if (epilogue == VLG_EPI_MUL) {
-        if (io == 0) return launch16<128, 128, true, false, VLG_EPI_MUL, false, 0>(g, s);
-        if (io == 6) return launch16<128, 128, true, false, VLG_EPI_MUL, false, 6>(g, s);
-        return VLG_ERR_SHAPE;
-    }
-    return VLG_ERR_SHAPE;
-}
-
-int vlg_gemm16_wgrad(GemmArgs g, int io, hipStream_t s) {
-    // A = dY [tokens][N] and B = X [tokens][K] are both contraction-major: row extents in 8-element slots
-    if ((g.M & 7) || (g.N & 7)) return VLG_ERR_SHAPE;
-    const bool narrow = g.M <= 32;
-#define WG(IO) (narrow ? launch16<32, 128, false, false, VLG_EPI_NONE, true, IO>(g, s) : launch16<128, 128, false, false, VLG_EPI_NONE, true, IO>(g, s))
-    switch (io) { case 0: return WG(0); case 2: return WG(2); case 3: return WG(3); default: return VLG_ERR_SHAPE; }
-#undef WG
+#define EPI_GELU_GRAD (VLG_EPI_BIAS | VLG_EPI_GELU | VLG_EPI_GELU_GRAD)
+static const GemmKernelRow gemm_bf16_kernels[] = {
+    bf16_row<VLG_CALL_FWD, VLG_EPI_BIAS, 0, 128, 32>(), bf16_row<VLG_CALL_FWD, VLG_EPI_BIAS, 0, 128, 128>(),
+    bf16_row<VLG_CALL_FWD, VLG_EPI_BIAS, 3, 128, 32>(), bf16_row<VLG_CALL_FWD, VLG_EPI_BIAS, 3, 128, 128>(),
+    bf16_row<VLG_CALL_FWD, VLG_EPI_BIAS, 7, 128, 32>(), bf16_row<VLG_CALL_FWD, VLG_EPI_BIAS, 7, 128, 128>(),
+    bf16_row<VLG_CALL_FWD, VLG_EPI_BIAS | VLG_EPI_GELU, 0, 128, 128>(), bf16_row<VLG_CALL_FWD, VLG_EPI_BIAS | VLG_EPI_GELU, 7, 128, 128>(),
+    bf16_row<VLG_CALL_FWD, EPI_GELU_GRAD, 0, 128, 128>(), bf16_row<VLG_CALL_FWD, EPI_GELU_GRAD, 7, 128, 128>(),
+    bf16_row<VLG_CALL_FWD, VLG_EPI_BIAS | VLG_EPI_RESID, 0, 128, 128>(), bf16_row<VLG_CALL_FWD, VLG_EPI_BIAS | VLG_EPI_RESID, 3, 128, 128>(),
+    bf16_row<VLG_CALL_DGRAD, VLG_EPI_NONE, 0, 128, 128>(), bf16_row<VLG_CALL_DGRAD, VLG_EPI_NONE, 6, 128, 128>(),
+    bf16_row<VLG_CALL_DGRAD, VLG_EPI_NONE, 7, 128, 128>(),
+    bf16_row<VLG_CALL_DGRAD, VLG_EPI_DGELU, 0, 128, 128>(), bf16_row<VLG_CALL_DGRAD, VLG_EPI_DGELU, 6, 128, 128>(),
+    bf16_row<VLG_CALL_DGRAD, VLG_EPI_MUL, 0, 128, 128>(), bf16_row<VLG_CALL_DGRAD, VLG_EPI_MUL, 6, 128, 128>(),
+    bf16_row<VLG_CALL_WGRAD, VLG_EPI_NONE, 0, 32, 128>(), bf16_row<VLG_CALL_WGRAD, VLG_EPI_NONE, 0, 128, 128>(),
+    bf16_row<VLG_CALL_WGRAD, VLG_EPI_NONE, 2, 32, 128>(), bf16_row<VLG_CALL_WGRAD, VLG_EPI_NONE, 2, 128, 128>(),
+    bf16_row<VLG_CALL_WGRAD, VLG_EPI_NONE, 3, 32, 128>(), bf16_row<VLG_CALL_WGRAD, VLG_EPI_NONE, 3, 128, 128>(),
+};
+GemmKernel vlg_gemm16_kernel(const GemmProblem& p) {
+    return gemm_find_kernel(gemm_bf16_kernels, sizeof(gemm_bf16_kernels) / sizeof(gemm_bf16_kernels[0]), p);
 }

@@ -238,36 +238,18 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_split_kernel(const GemmA
     }
 }
 
-template <int BM, int BN, bool A_KC, bool B_KC, int EPI, bool COLSUM>
-static int launch_split(GemmArgs g, hipStream_t s) {
-    g.tiles_m = (int)((g.M + BM - 1) / BM);
-    g.tiles_n = (g.N + BN - 1) / BN;
-    const int64_t blocks = (int64_t)g.tiles_m * g.tiles_n * g.splits;
-    if (blocks < 1 || blocks > 0x7fffffff) return VLG_ERR_SHAPE;
-    g.clock_probe = nullptr;
-    hipLaunchKernelGGL((gemm_split_kernel<BM, BN, A_KC, B_KC, EPI, COLSUM>), dim3((unsigned)blocks), dim3(GEMM_THREADS), 0, s, g);
-    return vlg_last_error();
+// ---- host side: the instantiated kernels, one row each (gemm_tile.h); gemm_plan (gemm.hip) takes a call's kernel from here
+// and gemm.hip launches it
+template <int CALL, int EPI, int BM, int BN>
+constexpr GemmKernelRow split_row() {
+    return {CALL, EPI, 0, BM, BN, 16, gemm_split_kernel<BM, BN, CALL != VLG_CALL_WGRAD, CALL == VLG_CALL_FWD, EPI, CALL == VLG_CALL_WGRAD>};
 }
-
-// Entry points for gemm.hip's C ABI functions (shapes validated there; this layer adds the 8-element slot granularity).
-int vlg_gemm_split_fwd(GemmArgs g, int epilogue, hipStream_t s) {
-    if (g.Kc & 7) return VLG_ERR_SHAPE;
-    const bool narrow = g.N <= 32;
-    if (epilogue == VLG_EPI_BIAS)
-        return narrow ? launch_split<128, 32, true, true, VLG_EPI_BIAS, false>(g, s) : launch_split<128, 128, true, true, VLG_EPI_BIAS, false>(g, s);
-    if (narrow) return VLG_ERR_SHAPE;
-    if (epilogue == (VLG_EPI_BIAS | VLG_EPI_GELU)) return launch_split<128, 128, true, true, VLG_EPI_BIAS | VLG_EPI_GELU, false>(g, s);
-    if (epilogue == (VLG_EPI_BIAS | VLG_EPI_RESID)) return launch_split<128, 128, true, true, VLG_EPI_BIAS | VLG_EPI_RESID, false>(g, s);
-    return VLG_ERR_SHAPE;
-}
-int vlg_gemm_split_dgrad(GemmArgs g, int epilogue, hipStream_t s) {
-    if ((g.Kc & 7) || (g.N & 7)) return VLG_ERR_SHAPE;
-    if (epilogue == VLG_EPI_NONE) return launch_split<128, 128, true, false, VLG_EPI_NONE, false>(g, s);
-    if (epilogue == VLG_EPI_DGELU) return launch_split<128, 128, true, false, VLG_EPI_DGELU, false>(g, s);
-    return VLG_ERR_SHAPE;
-}
-int vlg_gemm_split_wgrad(GemmArgs g, hipStream_t s) {
-    if ((g.M & 7) || (g.N & 7)) return VLG_ERR_SHAPE;
-    return g.M <= 32 ? launch_split<32, 128, false, false, VLG_EPI_NONE, true>(g, s)
-                     : launch_split<128, 128, false, false, VLG_EPI_NONE, true>(g, s);
+static const GemmKernelRow gemm_split_kernels[] = {
+    split_row<VLG_CALL_FWD, VLG_EPI_BIAS, 128, 32>(), split_row<VLG_CALL_FWD, VLG_EPI_BIAS, 128, 128>(),
+    split_row<VLG_CALL_FWD, VLG_EPI_BIAS | VLG_EPI_GELU, 128, 128>(), split_row<VLG_CALL_FWD, VLG_EPI_BIAS | VLG_EPI_RESID, 128, 128>(),
+    split_row<VLG_CALL_DGRAD, VLG_EPI_NONE, 128, 128>(), split_row<VLG_CALL_DGRAD, VLG_EPI_DGELU, 128, 128>(),
+    split_row<VLG_CALL_WGRAD, VLG_EPI_NONE, 32, 128>(), split_row<VLG_CALL_WGRAD, VLG_EPI_NONE, 128, 128>(),
+};
+GemmKernel vlg_gemm_split_kernel(const GemmProblem& p) {
+    return gemm_find_kernel(gemm_split_kernels, sizeof(gemm_split_kernels) / sizeof(gemm_split_kernels[0]), p);
 }

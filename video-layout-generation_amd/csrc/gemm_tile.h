@@ -21,6 +21,46 @@ struct GemmArgs {
     unsigned long long* clock_probe;   // diagnostic only (VLG_GEMM_CLOCK_PROBE): {shader ticks, 100 MHz ticks} per block
 };
 
+// ---- host side: the plan of a projection-GEMM call (gemm_plan, gemm.hip) and what the three kernel files share to run it
+typedef void (*GemmKernel)(const GemmArgs);
+typedef void (*GemmPairKernel)(const GemmArgs, const GemmArgs, const int, const int, const int, const int64_t*, const int);
+// One kernel's share of a call: call = VLG_CALL_FWD | _DGRAD | _WGRAD, family = VLG_GEMM_F32 | _BF16 | _F32X3
+struct GemmProblem {
+    int call, family;
+    int epi, io;             // the kernel's template values: epilogue (+ gemm.hip's GELU-on-load bits), storage bits
+    int bm, bn, bk, run, splits;
+    int64_t per;             // contraction rows per split
+    int64_t blocks;          // grid of the launch (a fused pair: this problem's share of it)
+    GemmKernel kernel;       // NULL = no kernel for this combination
+};
+struct GemmPlan {
+    int err;                 // 0, or what the call returns instead of launching anything
+    int n;                   // problems: p[0]; a pair: p[0] the data gradient, p[1] the weight gradient
+    bool fused;              // a pair as ONE launch of `pair` (else the two single launches, weight gradient first)
+    GemmProblem p[2];
+    GemmPairKernel pair;
+};
+// The instantiated kernels of a file, one row each: the plan takes its kernel from these tables, so a combination without
+// a row is refused by the planner and the set of kernels is the set of rows.
+struct GemmKernelRow { int call, epi, io, bm, bn, bk; GemmKernel kernel; };
+static inline GemmKernel gemm_find_kernel(const GemmKernelRow* rows, int n, const GemmProblem& p) {
+    for (int i = 0; i < n; ++i) {
+        const GemmKernelRow& r = rows[i];
+        if (r.call == p.call && r.epi == p.epi && r.io == p.io && r.bm == p.bm && r.bn == p.bn && r.bk == p.bk) return r.kernel;
+    }
+    return nullptr;
+}
+GemmKernel vlg_gemm16_kernel(const GemmProblem& p);             // gemm_bf16.hip
+GemmPairKernel vlg_gemm16_pair_kernel(int epi_d, bool dy_bf16);
+GemmKernel vlg_gemm_split_kernel(const GemmProblem& p);         // gemm_split.hip
+// the host-only fields of GemmArgs: filled HERE, from the plan, for every launch of every family
+static inline void gemm_apply_plan(GemmArgs& g, const GemmProblem& p, unsigned long long* clock_probe) {
+    g.tiles_m = (int)((g.M + p.bm - 1) / p.bm);
+    g.tiles_n = (g.N + p.bn - 1) / p.bn;
+    g.run = p.run; g.splits = p.splits; g.kc_per_split = p.per;
+    g.clock_probe = clock_probe;
+}
+
 // Pin the staging interleave of one chunk, placed right behind its N_MFMA MFMAs: one LDS write (then one global load)
 // behind each MFMA, so the matrix pipe keeps issuing while the tile is staged (hipcc left alone emits the writes as one blob).
 template <int N_MFMA, int N_ST, int N_LD>

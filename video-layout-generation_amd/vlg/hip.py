@@ -40,6 +40,7 @@ SIGNATURES = {
     "vlg_linear_dgrad_wgrad": (I, [P, I, P, I, P, I, P, P, I, P, L, L, L, I, I, I, P, I, P]),
     "vlg_linear_wgrad_slabs_for": (I, [L, I, I, I]),
     "vlg_linear_wgrad": (I, [P, I, P, I, P, L, L, L, I, I, I, P]),
+    "vlg_linear_plan": (I, [I, L, I, I, I, I, I, I, I, P]),      # host-side planner; fills a vlg_gemm_plan
     "vlg_attention_fwd": (I, [P, P, L, I, I, P]),
     "vlg_attention_bwd": (I, [P, P, P, L, I, I, P]),
     "vlg_attention_fwd_bf16": (I, [P, P, L, I, I, P]),
