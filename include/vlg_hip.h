@@ -267,6 +267,40 @@ int vlg_adam_step_bf16(float* param, const float* grad, float* exp_avg, float* e
                        int64_t n, int step, float lr, float beta1, float beta2, float eps,
                        float grad_scale, void* stream);
 
+/* The guarded step: global-norm gradient clipping, a step that is skipped when the gradient holds inf or NaN, and a
+ * learning rate that lives in device memory - all decided on the device by three stream-ordered launches, so the step
+ * needs no host synchronisation and a captured graph replays it unchanged:
+ *     vlg_grad_sumsq -> vlg_optim_control -> vlg_adam_step_ctl
+ * They share `ctl`, a 16-float, 16-byte-aligned device record (ints are stored in the same 4-byte slots): */
+#define VLG_CTL_STEP_SIZE  0   /* float  lr / (1 - beta1^step) of the step about to be applied          */
+#define VLG_CTL_SQRT_BC2   1   /* float  sqrt(1 - beta2^step)                                            */
+#define VLG_CTL_STEP       2   /* int    steps applied so far (slots 0-2 = the state of vlg_adam_step_graph) */
+#define VLG_CTL_APPLY      3   /* int    1: this step updates; 0: the gradient was not finite, nothing is touched */
+#define VLG_CTL_GRAD_MULT  4   /* float  what Adam multiplies the gradient by: grad_scale * clip coefficient */
+#define VLG_CTL_GRAD_NORM  5   /* float  grad_scale * ||grad||_2 (the norm of the mean gradient under data parallelism) */
+#define VLG_CTL_LR         6   /* float  learning rate: an INPUT, written by the host, only read by the kernels */
+#define VLG_CTL_SKIPPED    7   /* int    running count of skipped steps                                  */
+#define VLG_CTL_CLIP_COEF  8   /* float  min(1, max_norm / (norm + 1e-6)); 1 without clipping           */
+#define VLG_CTL_FLOATS     16  /* slots 9-15 are reserved and stay as the host left them                 */
+/* partials[b] = sum of grad[i]^2 over the elements block b visits, b < vlg_grad_sumsq_blocks(n) (a pure host planner,
+ * 1 <= blocks <= 2048, non-decreasing in n); later elements of `partials` are not written.  fp64 accumulation, fixed
+ * summation order (bitwise reproducible), no atomics; an inf or NaN element gives an inf or NaN partial.
+ * n >= 4, n % 4 == 0 (VLG_ERR_SHAPE); 16-byte-aligned pointers (VLG_ERR_ALIGN). */
+int vlg_grad_sumsq_blocks(int64_t n);
+int vlg_grad_sumsq(const float* grad, int64_t n, float* partials, void* stream);
+/* One block: norm = grad_scale * sqrt(sum of the partials, in double, fixed order) -> VLG_CTL_GRAD_NORM.  Finite norm:
+ * APPLY = 1, STEP += 1, the two bias-correction factors from STEP and VLG_CTL_LR in double (as vlg_adam_step computes
+ * them on the host), GRAD_MULT = grad_scale * min(1, max_norm / (norm + 1e-6)) - torch.nn.utils.clip_grad_norm_'s rule;
+ * max_norm <= 0 = no clipping, GRAD_MULT = grad_scale exactly.  Otherwise APPLY = 0, SKIPPED += 1 and STEP, the factors,
+ * GRAD_MULT and CLIP_COEF keep their values.  1 <= n_partials <= 2048. */
+int vlg_optim_control(float* ctl, const float* partials, int n_partials, float grad_scale, float max_norm,
+                      float beta1, float beta2, void* stream);
+/* vlg_adam_step / vlg_adam_step_bf16 (shadow may be NULL) with step_size, sqrt_bc2 and the gradient multiplier read
+ * from ctl: bitwise their result when GRAD_MULT == grad_scale.  With APPLY == 0 no element of param, the moments or
+ * the shadow is read or written.  May be called on slices of the buffers, like the other Adam entry points. */
+int vlg_adam_step_ctl(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, vlg_bf16* shadow,
+                      int64_t n, const float* ctl, float beta1, float beta2, float eps, void* stream);
+
 /* ---------------------------------------------------- reference-real image ops
  * Pixel-space ops of the reference step that exist verbatim in the reference.
  *   vlg_ce_nchw        nn.CrossEntropyLoss('mean') on (b,C,H,W) logits / (b,H,W) int64

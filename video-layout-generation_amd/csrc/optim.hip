@@ -9,6 +9,17 @@
 //                    parameter (reference src/trainer.py:83,258 - Adam(lr, betas=(beta1,0.999)),
 //                    no weight decay, no amsgrad).  One launch per step instead of one per tensor.
 //                    Algorithmic bytes: 16 B read + 12 B written per parameter.
+//                    Algorithmic bytes: 16 B read + 12 B written per parameter.
+// The guarded step (global-norm clipping, skip of a non-finite gradient, learning rate in device memory) is three
+// launches around one 16-float device record `ctl` (layout: include/vlg_hip.h), so it needs no host synchronisation and
+// survives hipGraph replay:
+// vlg_grad_sumsq   : per-block partial sums of grad[i]^2, accumulated in fp64 per lane (the kernel is HBM-bound: four
+//                    fp64 FMAs per 16 bytes are far below the vector rate) and combined in a fixed order - bitwise
+//                    reproducible; inf / NaN pass through.  Algorithmic bytes: 4 B read per parameter.
+// vlg_optim_control: one block sums the partials in double and decides the step: norm, clip coefficient, apply flag,
+//                    step counter and bias-correction factors (as adam_state_kernel computes them).
+// vlg_adam_step_ctl: adam_kernel's arithmetic with {step_size, sqrt_bc2, gradient multiplier} read from ctl; when the
+//                    apply flag is 0 every block returns before it touches memory.
 #include "common.h"
 #include "reduce_body.h"
 #include <math.h>
@@ -59,6 +70,26 @@ __global__ __launch_bounds__(256) void reduce_slabs_tall_kernel(const float* __r
     }
 }
 
+// The update of four consecutive parameters: the one statement of Adam's arithmetic, shared by every Adam kernel here
+// (so the guarded step is bitwise the plain one whenever its gradient multiplier equals grad_scale).
+__device__ __forceinline__ void adam_update4(float* __restrict__ param, const float* __restrict__ grad, float* __restrict__ m,
+                                             float* __restrict__ v, bf16_t* __restrict__ shadow, int64_t e, float omb1,
+                                             float beta2, float omb2, float eps, float step_size, float sqrt_bc2,
+                                             float grad_scale) {
+    float4 p = ld4(param + e * 4), g = ld4(grad + e * 4), mm = ld4(m + e * 4), vv = ld4(v + e * 4);
+    float* pp = &p.x; float* gp = &g.x; float* mp = &mm.x; float* vp = &vv.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float gk = gp[k] * grad_scale;
+        mp[k] = mp[k] + omb1 * (gk - mp[k]);            // exp_avg.lerp_(grad, 1-beta1)
+        vp[k] = vp[k] * beta2 + omb2 * gk * gk;
+        const float denom = sqrtf(vp[k]) / sqrt_bc2 + eps;
+        pp[k] -= step_size * (mp[k] / denom);
+    }
+    st4(param + e * 4, p); st4(m + e * 4, mm); st4(v + e * 4, vv);
+    if (shadow != nullptr) st4(shadow + e * 4, p);         // bf16 copy of the updated weights for the bf16-MFMA projections
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ param, const float* __restrict__ grad,
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n4,
                                                    float beta1, float beta2, float eps, float step_size,
@@ -70,18 +101,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ param, co
     const float omb1 = 1.f - beta1, omb2 = 1.f - beta2;
     (void)beta1;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4; e += (int64_t)gridDim.x * blockDim.x) {
-        float4 p = ld4(param + e * 4), g = ld4(grad + e * 4), mm = ld4(m + e * 4), vv = ld4(v + e * 4);
-        float* pp = &p.x; float* gp = &g.x; float* mp = &mm.x; float* vp = &vv.x;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float gk = gp[k] * grad_scale;
-            mp[k] = mp[k] + omb1 * (gk - mp[k]);            // exp_avg.lerp_(grad, 1-beta1)
-            vp[k] = vp[k] * beta2 + omb2 * gk * gk;
-            const float denom = sqrtf(vp[k]) / sqrt_bc2 + eps;
-            pp[k] -= step_size * (mp[k] / denom);
-        }
-        st4(param + e * 4, p); st4(m + e * 4, mm); st4(v + e * 4, vv);
-        if (shadow != nullptr) st4(shadow + e * 4, p);         // bf16 copy of the updated weights for the bf16-MFMA projections
+        adam_update4(param, grad, m, v, shadow, e, omb1, beta2, omb2, eps, step_size, sqrt_bc2, grad_scale);
     }
 }
 
@@ -192,5 +212,119 @@ extern "C" int vlg_adam_step_graph(float* param, const float* grad, float* exp_a
     hipLaunchKernelGGL(adam_state_kernel, dim3(1), dim3(1), 0, s, state, lr, beta1, beta2, advance);
     hipLaunchKernelGGL(adam_kernel, dim3(stream_blocks(n / 4)), dim3(256), 0, s, param, grad, exp_avg, exp_avg_sq, n / 4,
                        beta1, beta2, eps, 0.f, 1.f, grad_scale, reinterpret_cast<bf16_t*>(shadow), (const float*)state);
+    return vlg_last_error();
+}
+
+// ---- guarded step: gradient norm, control record, Adam driven by the record
+#define VLG_SUMSQ_MAX_BLOCKS 2048
+
+extern "C" int vlg_grad_sumsq_blocks(int64_t n) {
+    int64_t b = (n / 4 + 255) / 256;
+    if (b > VLG_SUMSQ_MAX_BLOCKS) b = VLG_SUMSQ_MAX_BLOCKS;
+    if (b < 1) b = 1;
+    return (int)b;
+}
+
+__device__ __forceinline__ double sumsq4(double acc, float4 g) {
+    const double x = g.x, y = g.y, z = g.z, w = g.w;         // squares of fp32 values are exact in fp64
+    return acc + ((x * x + y * y) + (z * z + w * w));
+}
+
+// sum over the block in a fixed order (lane tree, then the waves in order); result valid in thread 0
+__device__ __forceinline__ double block_sum_f64(double v, double* smem) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = (blockDim.x + 63) >> 6;
+    if (l == 0) smem[w] = v;
+    __syncthreads();
+    double r = 0.0;
+    if (threadIdx.x == 0)
+        for (int i = 0; i < nw; ++i) r += smem[i];
+    return r;
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ grad, int64_t n4,
+                                                         float* __restrict__ partials) {
+    __shared__ double red[4];
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    double a0 = 0.0, a1 = 0.0;
+    for (; e + stride < n4; e += 2 * stride) {               // 2 independent loads in flight per lane
+        const float4 g0 = ld4(grad + e * 4), g1 = ld4(grad + (e + stride) * 4);
+        a0 = sumsq4(a0, g0);
+        a1 = sumsq4(a1, g1);
+    }
+    if (e < n4) a0 = sumsq4(a0, ld4(grad + e * 4));
+    const double s = block_sum_f64(a0 + a1, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = (float)s;   // beyond fp32 range -> inf: the step is skipped, not wrong
+}
+
+extern "C" int vlg_grad_sumsq(const float* grad, int64_t n, float* partials, void* stream) {
+    if (n < 4 || (n & 3) || !partials) return VLG_ERR_SHAPE;
+    if (!vlg_aligned16(grad) || !vlg_aligned16(partials)) return VLG_ERR_ALIGN;
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)vlg_grad_sumsq_blocks(n)), dim3(256), 0, (hipStream_t)stream,
+                       grad, n / 4, partials);
+    return vlg_last_error();
+}
+
+// ctl: the record include/vlg_hip.h documents (VLG_CTL_*).  One block; thread 0 decides.
+__global__ __launch_bounds__(256) void optim_control_kernel(float* __restrict__ ctl, const float* __restrict__ partials,
+                                                            int n_partials, float grad_scale, float max_norm,
+                                                            float beta1, float beta2) {
+    __shared__ double red[4];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n_partials; i += 256) acc += (double)partials[i];
+    const double sum = block_sum_f64(acc, red);
+    if (threadIdx.x != 0) return;
+    int* ictl = reinterpret_cast<int*>(ctl);
+    const double norm = (double)grad_scale * sqrt(sum);
+    const float norm_f = (float)norm;
+    ctl[VLG_CTL_GRAD_NORM] = norm_f;
+    if (!isfinite(norm_f)) {                                 // inf or NaN anywhere in the gradient: leave the state alone
+        ictl[VLG_CTL_APPLY] = 0;
+        ictl[VLG_CTL_SKIPPED] = ictl[VLG_CTL_SKIPPED] + 1;
+        return;
+    }
+    const int step = ictl[VLG_CTL_STEP] + 1;
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    double coef = 1.0;
+    if (max_norm > 0.f) coef = fmin(1.0, (double)max_norm / (norm + 1e-6));     // torch.nn.utils.clip_grad_norm_
+    ctl[VLG_CTL_STEP_SIZE] = (float)((double)ctl[VLG_CTL_LR] / bc1);
+    ctl[VLG_CTL_SQRT_BC2] = (float)sqrt(bc2);
+    ictl[VLG_CTL_STEP] = step;
+    ictl[VLG_CTL_APPLY] = 1;
+    ctl[VLG_CTL_GRAD_MULT] = max_norm > 0.f ? (float)((double)grad_scale * coef) : grad_scale;
+    ctl[VLG_CTL_CLIP_COEF] = (float)coef;
+}
+
+extern "C" int vlg_optim_control(float* ctl, const float* partials, int n_partials, float grad_scale, float max_norm,
+                                 float beta1, float beta2, void* stream) {
+    if (!ctl || !partials || n_partials < 1 || n_partials > VLG_SUMSQ_MAX_BLOCKS) return VLG_ERR_SHAPE;
+    if (!vlg_aligned16(ctl)) return VLG_ERR_ALIGN;
+    hipLaunchKernelGGL(optim_control_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ctl, partials, n_partials,
+                       grad_scale, max_norm, beta1, beta2);
+    return vlg_last_error();
+}
+
+__global__ __launch_bounds__(256) void adam_ctl_kernel(float* __restrict__ param, const float* __restrict__ grad,
+                                                       float* __restrict__ m, float* __restrict__ v, int64_t n4,
+                                                       float beta1, float beta2, float eps, bf16_t* __restrict__ shadow,
+                                                       const float* __restrict__ ctl) {
+    // a branch, not a multiplication by zero: 0 * inf would write NaN into the moments
+    if (reinterpret_cast<const int*>(ctl)[VLG_CTL_APPLY] == 0) return;
+    const float step_size = ctl[VLG_CTL_STEP_SIZE], sqrt_bc2 = ctl[VLG_CTL_SQRT_BC2], grad_mult = ctl[VLG_CTL_GRAD_MULT];
+    const float omb1 = 1.f - beta1, omb2 = 1.f - beta2;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4; e += (int64_t)gridDim.x * blockDim.x)
+        adam_update4(param, grad, m, v, shadow, e, omb1, beta2, omb2, eps, step_size, sqrt_bc2, grad_mult);
+}
+
+extern "C" int vlg_adam_step_ctl(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, vlg_bf16* shadow,
+                                 int64_t n, const float* ctl, float beta1, float beta2, float eps, void* stream) {
+    if (n < 4 || (n & 3) || !ctl) return VLG_ERR_SHAPE;
+    if (!vlg_aligned16(param) || !vlg_aligned16(grad) || !vlg_aligned16(exp_avg) || !vlg_aligned16(exp_avg_sq) ||
+        !vlg_aligned16(ctl) || (shadow && !vlg_aligned8(shadow))) return VLG_ERR_ALIGN;
+    hipLaunchKernelGGL(adam_ctl_kernel, dim3(stream_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, param, grad,
+                       exp_avg, exp_avg_sq, n / 4, beta1, beta2, eps, reinterpret_cast<bf16_t*>(shadow), ctl);
     return vlg_last_error();
 }

@@ -23,6 +23,12 @@ VLG_WITH_HED / VLG_WITH_VGG = 1 add the frozen edge net and the VGG19 term, VLG_
 src/trainer.py:193-258) on synthetic frame triplets of VLG_IMG_SIZE (256) pixels; the default (layout) is the
 token step BASELINE.json's metric is quoted on.
 
+Optimiser knobs (all off by default; vlg/optim_guard.py): args.clip_grad / VLG_CLIP_GRAD = global-norm gradient clipping
+at that norm (0 = off), args.skip_nonfinite / VLG_SKIP_NONFINITE = 1 skips a step whose gradient holds inf or NaN,
+VLG_LR_DECAY = 1 honours --lr_decay_step / --lr_decay_gamma (epochs; the reference parses them and never applies them, so
+they stay ignored unless asked for).  Any of them switches the engine to its guarded step; the train log line then also
+shows the gradient norm and the number of skipped steps.
+
 Repairs of reference defects, all stated: gradients are overwritten each
 step (A-5 zero_grad), the train log line uses the `loss` key (A-6), one checkpoint schema
 {'epoch','arch','gridnet','optimizer'} for save/--ckpt/--resume (A-1,A-8,A-9), `.model` exists
@@ -43,6 +49,7 @@ import torch.distributed as dist
 
 from vlg.data import BATCH_KEYS, BucketedClipLoader, ClipLoader, synthetic_clips, to_device
 from vlg.dp import GradReducer, bucket_ranges
+from vlg.optim_guard import decayed_lr
 from vlg.spec import ADAM_BETA1, ADAM_LR, SEED, LayoutConfig
 
 
@@ -94,6 +101,23 @@ def _knob(args, name: str, env: str, default: int) -> int:
     return int(v) if v is not None else int(os.environ.get(env, default))
 
 
+def _knob_float(args, name: str, env: str, default: float) -> float:
+    v = getattr(args, name, None)
+    return float(v) if v is not None else float(os.environ.get(env, default))
+
+
+def optim_knobs(args) -> Dict[str, object]:
+    """{clip_grad, skip_nonfinite, lr_decay} from args / environment (module docstring); all off by default."""
+    return {"clip_grad": max(_knob_float(args, "clip_grad", "VLG_CLIP_GRAD", 0.0), 0.0),
+            "skip_nonfinite": bool(_knob(args, "skip_nonfinite", "VLG_SKIP_NONFINITE", 0)),
+            "lr_decay": os.environ.get("VLG_LR_DECAY", "0") == "1"}
+
+
+def epoch_lr(args, epoch: int) -> float:
+    """Learning rate of 0-based `epoch` under VLG_LR_DECAY=1: args.lr * lr_decay_gamma ** (epoch // lr_decay_step)."""
+    return decayed_lr(float(getattr(args, "lr", ADAM_LR)), epoch, int(args.lr_decay_step), float(args.lr_decay_gamma))
+
+
 def layout_config(args) -> LayoutConfig:
     """Per-GPU batch = batch_size // gpus, as reference src/trainer.py:148 sizes its loaders."""
     gpus = max(int(getattr(args, "gpus", 1) or 1), 1)
@@ -108,6 +132,7 @@ def get_layout_engine(args, cfg: Optional[LayoutConfig] = None, engine_factory: 
     """Model + optimiser state in one object (counterpart of get_gridnet, reference src/trainer.py:81-94:
     build on args.rank's device, Adam(lr=args.lr, betas=(args.beta1, 0.999)), optional --ckpt load)."""
     cfg = cfg or layout_config(args)
+    knobs = optim_knobs(args)
     if engine_factory is None:
         from vlg.engine import LayoutEngine          # HIP only; raises without a GPU / without the .so
         device = torch.device("cuda", int(args.rank))
@@ -115,9 +140,12 @@ def get_layout_engine(args, cfg: Optional[LayoutConfig] = None, engine_factory: 
         engine = LayoutEngine(cfg, device, seed=int(getattr(args, "seed", SEED)),
                               lr=float(getattr(args, "lr", ADAM_LR)), beta1=float(getattr(args, "beta1", ADAM_BETA1)),
                               precision=precision,
-                              padded_slots=bool(_knob(args, "variable_n", "VLG_VARIABLE_N", 0)))   # fixed-N feeds hold no padded slots
+                              padded_slots=bool(_knob(args, "variable_n", "VLG_VARIABLE_N", 0)),   # fixed-N feeds hold no padded slots
+                              clip_grad=knobs["clip_grad"], skip_nonfinite=knobs["skip_nonfinite"])
     else:
         engine = engine_factory(cfg, args)
+    if knobs["lr_decay"]:                            # guarded from the start, so a checkpoint's lr and skip count are resumed
+        engine.set_lr(float(getattr(args, "lr", ADAM_LR)))
     ckpt_path = getattr(args, "ckpt", None)
     if ckpt_path is not None:
         args.logger.info("Loading from ckpt %s" % ckpt_path)
@@ -180,12 +208,15 @@ class _ImageModel:
         precision = str(getattr(args, "precision", None) or os.environ.get("VLG_PRECISION", "fp32"))
         if precision == "bf16_mfma":
             precision = "bf16"
+        knobs = optim_knobs(args)
         if precision == "fp32x3":
             args.logger.warning("VLG_PRECISION=fp32x3 has no convolution form: the pixel model runs its convolutions in fp32")
             precision = "fp32"
         self.engine = ImageEngine(batch, size, size, self.device, arch=arch, lr=float(getattr(args, "lr", ADAM_LR)),
                                   beta1=float(getattr(args, "beta1", ADAM_BETA1)), with_hed=with_hed, with_vgg=with_vgg,
-                                  precision=precision)
+                                  precision=precision, clip_grad=knobs["clip_grad"], skip_nonfinite=knobs["skip_nonfinite"])
+        if knobs["lr_decay"]:
+            self.engine.set_lr(float(getattr(args, "lr", ADAM_LR)))
         for net, env in ((self.engine.hed, "VLG_HED_CKPT"), (self.engine.vgg, "VLG_VGG_CKPT")):
             if net is not None:
                 _load_frozen(net, env, args)
@@ -225,6 +256,12 @@ class _ImageModel:
 
     def load_optimizer(self, st):
         self.engine.load_optimizer(st)
+
+    def set_lr(self, lr: float):
+        self.engine.set_lr(lr)
+
+    def optimizer_stats(self):
+        return self.engine.optimizer_stats()
 
     def train_step(self, batch, flip: bool, reducer=None):
         return self.engine.train_step(batch, flip, reducer).reshape(1)
@@ -303,6 +340,8 @@ class Trainer:
                                            bucket_ranges(self.engine.layout, self.engine.n_params, self.cfg.n_layers))
         self.device = self.engine.device
         self.gridnet = self.model = _ModelHandle(self.engine)   # reference attr `gridnet`; main.py:65 wants `.model`
+        self.optim = optim_knobs(args)
+        self.guarded = self.optim["clip_grad"] > 0.0 or self.optim["skip_nonfinite"] or self.optim["lr_decay"]
         self.global_step = 0
         self.epoch = 0
         if getattr(args, "resume", None) is not None:           # reference src/trainer.py:138-139
@@ -344,6 +383,8 @@ class Trainer:
         """0-based in, 1-based stored, samplers reseeded (reference src/trainer.py:158-162)."""
         self.args.logger.info("Start of epoch %d" % (epoch + 1))
         self.epoch = epoch + 1
+        if self.optim["lr_decay"]:
+            self.engine.set_lr(epoch_lr(self.args, epoch))
         self.train_loader.set_epoch(epoch)
         self.val_loader.set_epoch(epoch)
 
@@ -383,14 +424,20 @@ class Trainer:
                 # the token step, the last one of the pixel step): logged value = cross-rank mean, as sync() gave the
                 # reference (trainer.py:256), without a collective of its own
                 value = float(loss[0].item()) / (self.world if self.reducer is not None else 1)
+                # guarded step: its device record is read here only, next to the loss (one 64-byte copy)
+                stats = self.engine.optimizer_stats() if self.guarded else None
                 comp_time = time() - end
                 self.args.logger.info(
                     "Epoch [{epoch:d}/{tot_epoch:d}][{cur_batch:d}/{tot_batch:d}] "
                     "load [{load_time:.3f}s] comp [{comp_time:.3f}s] "
                     "loss [{loss:.4f}]".format(epoch=self.epoch, tot_epoch=int(self.args.epochs), cur_batch=i + 1,
                                                tot_batch=n_batches, load_time=load_time, comp_time=comp_time,
-                                               loss=value))
+                                               loss=value)
+                    + (" grad_norm [{grad_norm:.4g}] skipped [{skipped_steps:d}]".format(**stats) if stats else ""))
                 self.writer.add_scalar("train/gen loss GAN", value, self.global_step)   # tag: trainer.py:281
+                if stats:
+                    self.writer.add_scalar("train/grad_norm", stats["grad_norm"], self.global_step)
+                    self.writer.add_scalar("train/lr", stats["lr"], self.global_step)
             end = time()
 
     # ---------------------------------------------------------------------- validate
@@ -450,7 +497,8 @@ class Trainer:
         shutil.copy("%s/%03d.pth" % (prefix, self.epoch), "%s/latest.pth" % prefix)
 
     def load_checkpoint(self, resume):
-        """--resume (reference src/trainer.py:404-414): arch must match; restores epoch, weights, Adam state."""
+        """--resume (reference src/trainer.py:404-414): arch must match; restores epoch, weights, Adam state - and, when an
+        optimiser knob is on (guarded engine), the learning rate and the skipped-step count the entry records."""
         self.args.logger.info("Resuming checkpoint %s" % resume)
         ckpt = torch.load(resume, map_location=torch.device("cpu"), weights_only=True)
         assert ckpt["arch"] == self.args.arch, ("Architecture mismatch: ckpt %s, config %s"

@@ -22,6 +22,7 @@ from typing import Dict, Optional
 import torch
 
 from . import hip
+from .optim_guard import OptimControl
 from .hip import (EPI_A_BF16, EPI_B_BF16, EPI_BIAS, EPI_DGELU, EPI_GELU, EPI_NONE, EPI_OUT_BF16, EPI_RESID,
                   call, ptr)
 from .spec import (ADAM_BETA1, ADAM_BETA2, ADAM_EPS, ADAM_LR, BOX_DIM, IOU_EPS, LN_EPS, LOSS_W_CE,
@@ -60,8 +61,13 @@ class LayoutEngine:
     """Owns parameters, optimiser state and workspace; runs forward/backward/Adam."""
 
     def __init__(self, cfg: LayoutConfig, device: torch.device, seed: int = 1024,
-                 lr: float = ADAM_LR, beta1: float = ADAM_BETA1, precision: str = "fp32", padded_slots: bool = True):
-        """precision:
+                 lr: float = ADAM_LR, beta1: float = ADAM_BETA1, precision: str = "fp32", padded_slots: bool = True,
+                 clip_grad: float = 0.0, skip_nonfinite: bool = False):
+        """clip_grad > 0 clips the gradient to that global L2 norm (torch.nn.utils.clip_grad_norm_'s rule); skip_nonfinite
+        leaves parameters, moments and step count untouched when the gradient holds inf or NaN.  Either one - or a call
+        of set_lr - turns on the GUARDED optimiser step (vlg/optim_guard.py), eager and captured alike; with both off and
+        set_lr never called, the step's launches are exactly those of an engine without these options.
+        precision:
         "fp32"      exact-fp32 MFMA projections, every tensor fp32 (parity 1e-4);
         "bf16"      BASELINE.json configs[2]: bf16 MFMA projections (fp32 accumulate) AND the activations that only
                     feed projections / attention (normalised inputs, q k v, attention output, FFN hidden and their
@@ -105,12 +111,17 @@ class LayoutEngine:
         self.exp_avg_sq = torch.zeros(self.n_params, **f32)
         self.step_count = 0
         self.adam_state = None                       # device-side {step_size, sqrt_bc2, step} once a step is captured in a hipGraph
+        self.clip_grad, self.skip_nonfinite = max(float(clip_grad), 0.0), bool(skip_nonfinite)
+        self.guard: Optional[OptimControl] = None    # guarded step: the optimiser's scalars live in its device record
+        self._captured_plain = False                 # a captured graph holds the plain Adam launches (lr by value)
         # bf16 mode: a bf16 copy of the weights feeds the projections (the Adam kernel refreshes it with every update)
         self.params_bf16 = torch.zeros(self.n_params, dtype=torch.bfloat16, device=device) if self.bf16_store else None
         self.load_params(init_params(cfg, seed))
         self._alloc_workspace(cfg.tokens)
         self.loss_out = self.grads_ext[self.n_params:]   # {total, smooth_l1, iou, ce}
         self.timer = None                            # optional KernelTimer (bench.py roofline leg)
+        if self.clip_grad > 0.0 or self.skip_nonfinite:
+            self._enable_guard()
 
     # ------------------------------------------------------------------ parameters
     def view(self, flat: torch.Tensor, name: str) -> torch.Tensor:
@@ -127,6 +138,47 @@ class LayoutEngine:
     def _sync_device_step(self) -> None:
         if self.adam_state is not None:
             self.adam_state.view(torch.int32)[2] = int(self.step_count)
+        if self.guard is not None:
+            self.guard.set_counts(self.step_count)
+
+    # ------------------------------------------------------------------ guarded optimiser step
+    @property
+    def guarded(self) -> bool:
+        return self.guard is not None
+
+    def _enable_guard(self) -> None:
+        if self.guard is None:
+            if self._captured_plain:
+                raise RuntimeError("a step was captured with the plain optimiser (learning rate by value): build the engine "
+                                   "with clip_grad / skip_nonfinite, or call set_lr, BEFORE capture_train_step")
+            self.guard = OptimControl(self.n_params, self.device, self.lr, self.beta1, self.clip_grad, self.step_count)
+
+    def set_lr(self, lr: float) -> None:
+        """New learning rate from the next step on: one 4-byte write into the device record the guarded step reads, legal
+        between replays of a captured step (no recapture).  Turns the guarded step on."""
+        self.lr = float(lr)
+        self._enable_guard()
+        self.guard.set_lr(self.lr)
+
+    def optimizer_stats(self) -> Dict[str, float]:
+        """{grad_norm, clip_coef, applied_steps, skipped_steps, lr} of the guarded step: one 64-byte device-to-host copy
+        (it waits for the stream - call it where the loss is read anyway)."""
+        if self.guard is None:
+            raise RuntimeError("optimizer_stats() needs the guarded step (clip_grad, skip_nonfinite or set_lr)")
+        st = self.guard.read()
+        self.step_count = st["applied_steps"]        # the device count is the authority: skipped steps do not advance it
+        return st
+
+    def _applied_steps(self) -> int:
+        return self.optimizer_stats()["applied_steps"] if self.guard is not None else int(self.step_count)
+
+    def optimizer_update(self, grad_scale: float = 1.0) -> None:
+        """The stage after backward (and after every gradient bucket has arrived): squared-norm partials of `grads`
+        -> control record -> Adam over the whole buffer.  The 4 loss floats behind the parameters are not part of the
+        norm.  grad_scale = 1 / world turns the summed gradient into the mean: the norm is that of the mean gradient."""
+        self._enable_guard()
+        shadow = self.params_bf16
+        self.guard.update(self.params, self.grads, self.exp_avg, self.exp_avg_sq, shadow, grad_scale, self._stream())
 
     def _refresh_shadow(self) -> None:
         if self.params_bf16 is not None:
@@ -148,7 +200,7 @@ class LayoutEngine:
 
     def state_dict(self) -> Dict[str, object]:
         return {"params": self.params.detach().cpu().clone(), "exp_avg": self.exp_avg.cpu().clone(),
-                "exp_avg_sq": self.exp_avg_sq.cpu().clone(), "step": self.step_count,
+                "exp_avg_sq": self.exp_avg_sq.cpu().clone(), "step": self._applied_steps(),
                 "layout": {k: (o, tuple(s)) for k, (o, s) in self.layout.items()}}
 
     def load_state_dict(self, sd: Dict[str, object]) -> None:
@@ -163,8 +215,9 @@ class LayoutEngine:
 
     def optimizer_state(self) -> Dict[str, object]:
         """Adam state for the checkpoint's 'optimizer' entry (flat tensors, CPU)."""
+        skipped = self.optimizer_stats()["skipped_steps"] if self.guard is not None else 0     # (refreshes step_count)
         return {"exp_avg": self.exp_avg.cpu().clone(), "exp_avg_sq": self.exp_avg_sq.cpu().clone(),
-                "step": int(self.step_count), "lr": self.lr, "beta1": self.beta1}
+                "step": int(self.step_count), "lr": self.lr, "beta1": self.beta1, "skipped": skipped}
 
     def load_optimizer(self, st: Dict[str, object]) -> None:
         if st["exp_avg"].numel() != self.n_params:
@@ -173,6 +226,10 @@ class LayoutEngine:
         self.exp_avg_sq.copy_(st["exp_avg_sq"])
         self.step_count = int(st["step"])
         self._sync_device_step()
+        if self.guard is not None:                   # a guarded run resumes its learning rate and skip count ("lr" and
+            self.guard.set_counts(self.step_count, int(st.get("skipped", 0)))   # "skipped" are absent from older entries)
+            if st.get("lr") is not None:
+                self.set_lr(float(st["lr"]))
 
     # ------------------------------------------------------------------- workspace
     def _alloc_workspace(self, tokens: int) -> None:
@@ -586,9 +643,16 @@ class LayoutEngine:
 
     def train_step(self, batch: Dict[str, torch.Tensor], reducer=None) -> torch.Tensor:
         """forward -> loss -> backward (+ overlapped gradient all-reduce) -> Adam, as one call.
-        Returns the loss scalars (summed over ranks when a reducer is attached)."""
+        Returns the loss scalars (summed over ranks when a reducer is attached).
+        Guarded step: the norm needs every gradient, so with a reducer it waits for ALL buckets and then runs one
+        squared-norm pass and one Adam over the whole buffer - the split Adam below, which updates everything but the
+        embeddings while their bucket is still in flight, is given up in that mode (and only there)."""
         loss = self.forward_backward(batch, reducer)
-        if reducer is not None:
+        if self.guard is not None:
+            if reducer is not None:
+                reducer.wait()
+            self.optimizer_update(reducer.grad_scale if reducer is not None else 1.0)
+        elif reducer is not None:
             # the embedding bucket is the last to be produced, so its all-reduce would be fully exposed: update
             # everything else while it is in flight, then the embedding range
             split = self.layout["l0.ln1_g"][0]
@@ -605,6 +669,11 @@ class LayoutEngine:
         """torch.optim.Adam(lr, betas=(beta1, 0.999)) on the flat buffer (reference src/trainer.py:83,258), or on its
         [lo, hi) slice (both multiples of 4); `advance` = False keeps the step count (second slice of one step)."""
         hi = self.n_params if hi is None else hi
+        if self.guard is not None:
+            if lo != 0 or hi != self.n_params or not advance:
+                raise ValueError("the guarded step updates the whole buffer at once (its norm needs every gradient)")
+            self.optimizer_update(grad_scale)
+            return
         if advance:
             self.step_count += 1
         o = 4 * lo
@@ -637,20 +706,24 @@ class LayoutEngine:
         data-parallel hooks are not captured) and return `run(batch) -> loss scalars`: it copies the batch into the
         graph's static input buffers and replays ~110 kernel launches with one host call.  Everything the step
         touches is preallocated and no launch argument changes between steps (the Adam step counter moves to the
-        device), so replay is bitwise identical to the eager step."""
+        device), so replay is bitwise identical to the eager step.  A guarded engine captures its guarded step: clipping,
+        the skip and set_lr keep working across replays."""
         self._check_batch(example_batch)
-        self.use_device_step_counter()
+        if self.guard is None:
+            self.use_device_step_counter()
+            self._captured_plain = True
+        counter = self.adam_state if self.guard is None else self.guard.ctl      # the optimiser's device-side scalars
         static = {k: example_batch[k].clone() for k in ("slot_class", "slot_box", "tgt_class", "tgt_box", "valid")}
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
-        keep = (self.params.clone(), self.exp_avg.clone(), self.exp_avg_sq.clone(), self.adam_state.clone(), self.step_count)
+        keep = (self.params.clone(), self.exp_avg.clone(), self.exp_avg_sq.clone(), counter.clone(), self.step_count)
         with torch.cuda.stream(side):            # warm-up on a side stream, as stream capture requires
             self.train_step(static)
         torch.cuda.current_stream(self.device).wait_stream(side)
         torch.cuda.synchronize(self.device)
         # undo the warm-up step: capture must not change the training trajectory
         self.params.copy_(keep[0]); self.exp_avg.copy_(keep[1]); self.exp_avg_sq.copy_(keep[2])
-        self.adam_state.copy_(keep[3]); self.step_count = keep[4]
+        counter.copy_(keep[3]); self.step_count = keep[4]
         self._refresh_shadow()
         timer, self.timer = self.timer, None     # events are not capturable work
         graph = torch.cuda.CUDAGraph()
@@ -658,7 +731,7 @@ class LayoutEngine:
             self.train_step(static)
         self.timer = timer
         self.params.copy_(keep[0]); self.exp_avg.copy_(keep[1]); self.exp_avg_sq.copy_(keep[2])
-        self.adam_state.copy_(keep[3]); self.step_count = keep[4]
+        counter.copy_(keep[3]); self.step_count = keep[4]
         self._refresh_shadow()
 
         def run(batch: Dict[str, torch.Tensor]) -> torch.Tensor:
@@ -666,7 +739,8 @@ class LayoutEngine:
                 if batch[k] is not t:
                     t.copy_(batch[k], non_blocking=True)
             graph.replay()
-            self.step_count += 1
+            if self.guard is None:                   # (guarded: the device record counts, optimizer_stats() reads it)
+                self.step_count += 1
             return self.loss_out
         run.graph, run.static_batch = graph, static
         return run

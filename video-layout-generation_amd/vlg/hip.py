@@ -57,6 +57,10 @@ SIGNATURES = {
     "vlg_adam_step": (I, [P, P, P, P, L, I, F, F, F, F, F, P]),
     "vlg_adam_step_graph": (I, [P, P, P, P, P, L, P, I, F, F, F, F, F, P]),
     "vlg_adam_step_bf16": (I, [P, P, P, P, P, L, I, F, F, F, F, F, P]),
+    "vlg_grad_sumsq_blocks": (I, [L]),
+    "vlg_grad_sumsq": (I, [P, L, P, P]),
+    "vlg_optim_control": (I, [P, P, I, F, F, F, F, P]),
+    "vlg_adam_step_ctl": (I, [P, P, P, P, P, L, P, F, F, F, P]),
     "vlg_image_loss_scratch": (I, []),
     "vlg_ce_nchw": (I, [P, P, P, P, P, I, I, L, F, P]),
     "vlg_l1_mean": (I, [P, P, P, P, P, L, F, P]),

@@ -28,6 +28,7 @@ import torch
 from . import hip
 from .gridnet import GridNetHIP, reference_param_order
 from .hip import call, ptr
+from .optim_guard import OptimControl
 from .spec import ADAM_BETA1, ADAM_BETA2, ADAM_EPS, ADAM_LR, IMG_MEAN, IMG_STD, OUT_MEAN, OUT_STD
 
 IMAGE_KEYS = ("frame1", "seg1", "frame2", "seg2", "frame3", "seg3", "e1", "e2")
@@ -37,8 +38,10 @@ W_L1, W_STYLE, W_CE = 40.0, 20.0, 10.0          # reference src/trainer.py:248-2
 class ImageEngine:
     def __init__(self, batch: int, H: int, W: int, device, arch: str = "CoordGridNet", lr: float = ADAM_LR,
                  beta1: float = ADAM_BETA1, filters=(32, 64, 96), with_hed: bool = False, with_vgg: bool = False,
-                 precision: str = "fp32"):
-        """precision: "fp32" (the reference's) or "bf16" - the 3x3 convolutions of GridNet, HED and VGG on bf16-rounded
+                 precision: str = "fp32", clip_grad: float = 0.0, skip_nonfinite: bool = False):
+        """clip_grad / skip_nonfinite: the guarded optimiser step, as LayoutEngine's (vlg/optim_guard.py): global-norm
+        clipping and a step that a non-finite gradient skips; set_lr turns it on too.  Off, the step is unchanged.
+        precision: "fp32" (the reference's) or "bf16" - the 3x3 convolutions of GridNet, HED and VGG on bf16-rounded
         GEMM operands with fp32 accumulation (csrc/conv_bf16.hip); tensors, losses, gradients and Adam stay fp32."""
         if arch not in ("GridNet", "CoordGridNet"):
             raise ValueError("arch must be GridNet or CoordGridNet (reference src/main.py:101-102)")
@@ -58,6 +61,10 @@ class ImageEngine:
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=device)
         self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=device)
         self.step_count = 0
+        self.clip_grad, self.skip_nonfinite = max(float(clip_grad), 0.0), bool(skip_nonfinite)
+        self.guard: Optional[OptimControl] = None
+        if self.clip_grad > 0.0 or self.skip_nonfinite:
+            self._enable_guard()
         f32 = dict(dtype=torch.float32, device=device)
         self.x10 = torch.empty(batch, 10, H, W, **f32)
         self.f3 = torch.empty(batch, 3, H, W, **f32)
@@ -84,6 +91,37 @@ class ImageEngine:
     def state_dict(self):
         return self.net.state_dict()
 
+    # ------------------------------------------------------------------ guarded optimiser step
+    @property
+    def guarded(self) -> bool:
+        return self.guard is not None
+
+    def _enable_guard(self) -> None:
+        if self.guard is None:
+            self.guard = OptimControl(self.net.params.numel(), self.device, self.lr, self.beta1, self.clip_grad, self.step_count)
+
+    def set_lr(self, lr: float) -> None:
+        """New learning rate from the next step on (one 4-byte write into the guarded step's device record)."""
+        self.lr = float(lr)
+        self._enable_guard()
+        self.guard.set_lr(self.lr)
+
+    def optimizer_stats(self) -> Dict[str, float]:
+        """{grad_norm, clip_coef, applied_steps, skipped_steps, lr}: one 64-byte device-to-host copy."""
+        if self.guard is None:
+            raise RuntimeError("optimizer_stats() needs the guarded step (clip_grad, skip_nonfinite or set_lr)")
+        st = self.guard.read()
+        self.step_count = st["applied_steps"]        # the device count is the authority: skipped steps do not advance it
+        return st
+
+    def optimizer_update(self, grad_scale: float = 1.0) -> None:
+        """Squared-norm partials of net.grads -> control record -> Adam, after backward and every gradient bucket.  The
+        norm runs over the flat kernel layout: its padded lanes (channel padding, the 3 spare floats of a PReLU slope)
+        are never written by backward and stay zero, so it is the norm of the reference's tensors; the 8 loss floats
+        behind the parameters are not part of it."""
+        self._enable_guard()
+        self.guard.update(self.net.params, self.net.grads, self.exp_avg, self.exp_avg_sq, None, grad_scale, self._stream())
+
     # ------------------------------------------------------------------ optimiser state (checkpoints)
     def optimizer_state(self) -> Dict[str, object]:
         """Adam state in torch.optim.Adam.state_dict() form - {'state': {i: {'step','exp_avg','exp_avg_sq'}},
@@ -91,6 +129,7 @@ class ImageEngine:
         shapes - i.e. what reference src/trainer.py:91-92 loads into its own optimizer ('optimizer' entry of --ckpt)."""
         order = reference_param_order(self.net.coord)
         state = {}
+        skipped = self.optimizer_stats()["skipped_steps"] if self.guard is not None else 0     # (refreshes step_count)
         if self.step_count > 0:                      # torch keeps no per-parameter state before the first step
             m, v = self.net.unpack(self.exp_avg), self.net.unpack(self.exp_avg_sq)
             state = {i: {"step": torch.tensor(float(self.step_count)), "exp_avg": m[k], "exp_avg_sq": v[k]}
@@ -98,11 +137,21 @@ class ImageEngine:
         group = {"lr": self.lr, "betas": (self.beta1, ADAM_BETA2), "eps": ADAM_EPS, "weight_decay": 0, "amsgrad": False,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
                  "params": list(range(len(order)))}
-        return {"state": state, "param_groups": [group]}
+        return {"state": state, "param_groups": [group], "skipped": skipped}
 
     def load_optimizer(self, st: Dict[str, object]) -> None:
         """Accepts a torch.optim.Adam state_dict over the reference model's parameters (reference trainer.py:92) - mapped
-        parameter by parameter into the kernels' flat layout - or the flat {'exp_avg','exp_avg_sq','step'} form."""
+        parameter by parameter into the kernels' flat layout - or the flat {'exp_avg','exp_avg_sq','step'} form.  A guarded
+        engine also resumes the learning rate and the skipped-step count where the entry records them."""
+        self._load_optimizer(st)
+        if self.guard is not None:
+            groups = st.get("param_groups") or [{}]
+            lr = groups[0].get("lr") if "param_groups" in st else st.get("lr")
+            self.guard.set_counts(self.step_count, int(st.get("skipped", 0)))
+            if lr is not None:
+                self.set_lr(float(lr))
+
+    def _load_optimizer(self, st: Dict[str, object]) -> None:
         n = self.net.params.numel()
         if "state" in st and "param_groups" in st:
             order = reference_param_order(self.net.coord)
@@ -176,6 +225,9 @@ class ImageEngine:
         self.net.backward(self.dseg, self.dtmp, reducer)
 
     def adam_step(self, grad_scale: float = 1.0) -> None:
+        if self.guard is not None:
+            self.optimizer_update(grad_scale)
+            return
         self.step_count += 1
         call("vlg_adam_step", ptr(self.net.params), ptr(self.net.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq),
              self.net.params.numel(), self.step_count, self.lr, self.beta1, ADAM_BETA2, ADAM_EPS, grad_scale, self._stream())
