@@ -436,6 +436,88 @@ def test_image_engine_norm_is_that_of_the_tensors_and_skips(dev):
     assert eng.optimizer_stats()["applied_steps"] == 2 and not torch.equal(eng.net.params, keep[0])
 
 
+# ------------------------------------------------------------- one optimiser object: three forms, both engines, resumed
+RESUME_CFG = dict(B=1, T=16, N=9, d=64, n_layers=2)          # the smallest two-layer config of test_hip_step's edge shapes
+RESUME_LR = 7e-5
+
+
+class _LayoutCase:
+    def __init__(self, dev):
+        self.dev = dev
+        self.batches = [to_dev(O.synthetic_batch(RESUME_CFG["B"], RESUME_CFG["T"], RESUME_CFG["N"], seed=50 + i), dev) for i in range(3)]
+
+    def engine(self, **kw):
+        from vlg.engine import LayoutEngine
+        from vlg.spec import LayoutConfig
+        return LayoutEngine(LayoutConfig(**RESUME_CFG), self.dev, seed=1024, **kw)
+
+    params = staticmethod(lambda eng: eng.params)
+    copy_params = staticmethod(lambda src, dst: dst.load_params(src.named_params()))
+    recorded_lr = staticmethod(lambda st: st["lr"])
+
+
+class _ImageCase:
+    FILT = (8, 16, 24)
+
+    def __init__(self, dev):
+        from vlg.image_engine import synthetic_frames
+        self.dev = dev
+        self.batches = [{k: v.to(dev) for k, v in synthetic_frames(1, 32, 32, seed=60 + i).items()} for i in range(3)]
+
+    def engine(self, **kw):
+        from oracle import gridnet_spec as G
+        from vlg.image_engine import ImageEngine
+        eng = ImageEngine(1, 32, 32, self.dev, arch="CoordGridNet", filters=self.FILT, **kw)
+        eng.load_state_dict(G.test_params(G.param_shapes(10, self.FILT, coord=True), seed=1))
+        return eng
+
+    params = staticmethod(lambda eng: eng.net.params)
+    copy_params = staticmethod(lambda src, dst: dst.load_state_dict(src.state_dict()))
+    recorded_lr = staticmethod(lambda st: st["param_groups"][0]["lr"])
+
+
+@pytest.mark.parametrize("mode", ["plain", "device_counter", "guarded"])
+@pytest.mark.parametrize("case", [_LayoutCase, _ImageCase], ids=["layout", "image"])
+def test_resumed_optimiser_continues_bitwise_in_every_form(dev, case, mode):
+    """two steps, optimizer_state() + parameters into a fresh engine of the same form, one more step on both: parameters,
+    both moments and the step count are bitwise those of the uninterrupted engine; a guarded engine takes the recorded lr"""
+    c = case(dev)
+
+    def make():
+        eng = c.engine(**(dict(clip_grad=1.0) if mode == "guarded" else {}))
+        if mode == "device_counter":
+            eng.use_device_step_counter()
+        assert eng.guarded == (mode == "guarded") and (eng.adam_state is not None) == (mode == "device_counter")
+        return eng
+
+    def steps(eng):
+        counts = [eng.optimizer_stats()["applied_steps"]] if eng.guarded else [eng.step_count]
+        if eng.adam_state is not None:
+            counts.append(int(eng.adam_state.view(torch.int32)[2]))
+        return counts
+
+    whole = make()
+    for b in c.batches[:2]:
+        whole.train_step(b)
+    if mode == "guarded":
+        whole.set_lr(RESUME_LR)                       # the fresh engine is built with the default: it must take the recorded one
+    st = whole.optimizer_state()
+    assert steps(whole) == [2] * len(steps(whole))
+    resumed = make()
+    c.copy_params(whole, resumed)
+    resumed.load_optimizer(st)
+    assert steps(resumed) == steps(whole) and torch.equal(resumed.exp_avg_sq, whole.exp_avg_sq)
+    if mode == "guarded":
+        assert c.recorded_lr(st) == RESUME_LR
+        assert resumed.optimizer_stats()["lr"] == float(np.float32(RESUME_LR)) and resumed.lr == RESUME_LR
+    for eng in (whole, resumed):
+        eng.train_step(c.batches[2])
+    assert steps(resumed) == steps(whole) == [3] * len(steps(whole))
+    assert torch.equal(c.params(resumed), c.params(whole)) and bool(torch.isfinite(c.params(whole)).all())
+    assert torch.equal(resumed.exp_avg, whole.exp_avg) and torch.equal(resumed.exp_avg_sq, whole.exp_avg_sq)
+    assert bool(whole.exp_avg.any()) and not torch.equal(c.params(whole), c.params(make()))
+
+
 # ------------------------------------------------------------------------------------- two ranks on one device
 DP_CFG = dict(B=2, T=4, N=4, d=64, n_layers=1)
 

@@ -1,4 +1,4 @@
-"""Cost of the guarded optimiser step (clip_grad + skip_nonfinite, vlg/optim_guard.py) against the default step: whole-step
+"""Cost of the guarded optimiser step (clip_grad + skip_nonfinite, vlg/optim.py) against the default step: whole-step
 time of two engines in ONE process, rounds interleaved A B A B on the same box, fp32 and bf16, at the metric shape
 (32,16,64) d=256 L=4 and at the 4-clip shard.  Prints one line per (shape, precision): medians and their difference."""
 import os, sys, time

@@ -23,7 +23,7 @@ VLG_WITH_HED / VLG_WITH_VGG = 1 add the frozen edge net and the VGG19 term, VLG_
 src/trainer.py:193-258) on synthetic frame triplets of VLG_IMG_SIZE (256) pixels; the default (layout) is the
 token step BASELINE.json's metric is quoted on.
 
-Optimiser knobs (all off by default; vlg/optim_guard.py): args.clip_grad / VLG_CLIP_GRAD = global-norm gradient clipping
+Optimiser knobs (all off by default; vlg/optim.py): args.clip_grad / VLG_CLIP_GRAD = global-norm gradient clipping
 at that norm (0 = off), args.skip_nonfinite / VLG_SKIP_NONFINITE = 1 skips a step whose gradient holds inf or NaN,
 VLG_LR_DECAY = 1 honours --lr_decay_step / --lr_decay_gamma (epochs; the reference parses them and never applies them, so
 they stay ignored unless asked for).  Any of them switches the engine to its guarded step; the train log line then also
@@ -49,7 +49,7 @@ import torch.distributed as dist
 
 from vlg.data import BATCH_KEYS, BucketedClipLoader, ClipLoader, synthetic_clips, to_device
 from vlg.dp import GradReducer, bucket_ranges
-from vlg.optim_guard import decayed_lr
+from vlg.optim import decayed_lr
 from vlg.spec import ADAM_BETA1, ADAM_LR, SEED, LayoutConfig
 
 

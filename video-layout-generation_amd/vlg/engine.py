@@ -22,7 +22,8 @@ from typing import Dict, Optional
 import torch
 
 from . import hip
-from .optim_guard import OptimControl
+from .optim import AdamSurface, FlatAdam
+from .slabs import SlabBuckets
 from .hip import (EPI_A_BF16, EPI_B_BF16, EPI_BIAS, EPI_DGELU, EPI_GELU, EPI_NONE, EPI_OUT_BF16, EPI_RESID,
                   call, ptr)
 from .spec import (ADAM_BETA1, ADAM_BETA2, ADAM_EPS, ADAM_LR, BOX_DIM, IOU_EPS, LN_EPS, LOSS_W_CE,
@@ -57,7 +58,7 @@ def init_params(cfg: LayoutConfig, seed: int) -> Dict[str, torch.Tensor]:
     return out
 
 
-class LayoutEngine:
+class LayoutEngine(AdamSurface):
     """Owns parameters, optimiser state and workspace; runs forward/backward/Adam."""
 
     def __init__(self, cfg: LayoutConfig, device: torch.device, seed: int = 1024,
@@ -65,7 +66,7 @@ class LayoutEngine:
                  clip_grad: float = 0.0, skip_nonfinite: bool = False):
         """clip_grad > 0 clips the gradient to that global L2 norm (torch.nn.utils.clip_grad_norm_'s rule); skip_nonfinite
         leaves parameters, moments and step count untouched when the gradient holds inf or NaN.  Either one - or a call
-        of set_lr - turns on the GUARDED optimiser step (vlg/optim_guard.py), eager and captured alike; with both off and
+        of set_lr - turns on the GUARDED optimiser step (vlg/optim.py), eager and captured alike; with both off and
         set_lr never called, the step's launches are exactly those of an engine without these options.
         precision:
         "fp32"      exact-fp32 MFMA projections, every tensor fp32 (parity 1e-4);
@@ -99,7 +100,6 @@ class LayoutEngine:
         if device.type != "cuda":
             raise hip.HipError("LayoutEngine needs a HIP device (got %s); there is no CPU path" % device)
         self.cfg, self.device = cfg, device
-        self.lr, self.beta1 = float(lr), float(beta1)
         self.layout, self.n_params = param_layout(cfg)
         f32 = dict(dtype=torch.float32, device=device)
         self.params = torch.zeros(self.n_params, **f32)
@@ -107,21 +107,14 @@ class LayoutEngine:
         # first gradient bucket of the data-parallel all-reduce (vlg/dp.py)
         self.grads_ext = torch.zeros(self.n_params + 4, **f32)
         self.grads = self.grads_ext[:self.n_params]
-        self.exp_avg = torch.zeros(self.n_params, **f32)
-        self.exp_avg_sq = torch.zeros(self.n_params, **f32)
-        self.step_count = 0
-        self.adam_state = None                       # device-side {step_size, sqrt_bc2, step} once a step is captured in a hipGraph
-        self.clip_grad, self.skip_nonfinite = max(float(clip_grad), 0.0), bool(skip_nonfinite)
-        self.guard: Optional[OptimControl] = None    # guarded step: the optimiser's scalars live in its device record
-        self._captured_plain = False                 # a captured graph holds the plain Adam launches (lr by value)
         # bf16 mode: a bf16 copy of the weights feeds the projections (the Adam kernel refreshes it with every update)
         self.params_bf16 = torch.zeros(self.n_params, dtype=torch.bfloat16, device=device) if self.bf16_store else None
+        self.optim = FlatAdam(self.n_params, device, lr, beta1, clip_grad, skip_nonfinite, shadow=self.params_bf16)
         self.load_params(init_params(cfg, seed))
+        self._wgrad_plans: Dict[tuple, tuple] = {}
         self._alloc_workspace(cfg.tokens)
         self.loss_out = self.grads_ext[self.n_params:]   # {total, smooth_l1, iou, ce}
         self.timer = None                            # optional KernelTimer (bench.py roofline leg)
-        if self.clip_grad > 0.0 or self.skip_nonfinite:
-            self._enable_guard()
 
     # ------------------------------------------------------------------ parameters
     def view(self, flat: torch.Tensor, name: str) -> torch.Tensor:
@@ -134,51 +127,6 @@ class LayoutEngine:
     def pw(self, name: str) -> torch.Tensor:
         """weight operand of a projection: the fp32 master, or its bf16 shadow in the bf16 mode"""
         return self.view(self.params_bf16 if self.bf16_store else self.params, name)
-
-    def _sync_device_step(self) -> None:
-        if self.adam_state is not None:
-            self.adam_state.view(torch.int32)[2] = int(self.step_count)
-        if self.guard is not None:
-            self.guard.set_counts(self.step_count)
-
-    # ------------------------------------------------------------------ guarded optimiser step
-    @property
-    def guarded(self) -> bool:
-        return self.guard is not None
-
-    def _enable_guard(self) -> None:
-        if self.guard is None:
-            if self._captured_plain:
-                raise RuntimeError("a step was captured with the plain optimiser (learning rate by value): build the engine "
-                                   "with clip_grad / skip_nonfinite, or call set_lr, BEFORE capture_train_step")
-            self.guard = OptimControl(self.n_params, self.device, self.lr, self.beta1, self.clip_grad, self.step_count)
-
-    def set_lr(self, lr: float) -> None:
-        """New learning rate from the next step on: one 4-byte write into the device record the guarded step reads, legal
-        between replays of a captured step (no recapture).  Turns the guarded step on."""
-        self.lr = float(lr)
-        self._enable_guard()
-        self.guard.set_lr(self.lr)
-
-    def optimizer_stats(self) -> Dict[str, float]:
-        """{grad_norm, clip_coef, applied_steps, skipped_steps, lr} of the guarded step: one 64-byte device-to-host copy
-        (it waits for the stream - call it where the loss is read anyway)."""
-        if self.guard is None:
-            raise RuntimeError("optimizer_stats() needs the guarded step (clip_grad, skip_nonfinite or set_lr)")
-        st = self.guard.read()
-        self.step_count = st["applied_steps"]        # the device count is the authority: skipped steps do not advance it
-        return st
-
-    def _applied_steps(self) -> int:
-        return self.optimizer_stats()["applied_steps"] if self.guard is not None else int(self.step_count)
-
-    def optimizer_update(self, grad_scale: float = 1.0) -> None:
-        """The stage after backward (and after every gradient bucket has arrived): squared-norm partials of `grads`
-        -> control record -> Adam over the whole buffer.  The 4 loss floats behind the parameters are not part of the
-        norm.  grad_scale = 1 / world turns the summed gradient into the mean: the norm is that of the mean gradient."""
-        self._enable_guard()
-        shadow = self.params_bf16
-        self.guard.update(self.params, self.grads, self.exp_avg, self.exp_avg_sq, shadow, grad_scale, self._stream())
 
     def _refresh_shadow(self) -> None:
         if self.params_bf16 is not None:
@@ -200,7 +148,7 @@ class LayoutEngine:
 
     def state_dict(self) -> Dict[str, object]:
         return {"params": self.params.detach().cpu().clone(), "exp_avg": self.exp_avg.cpu().clone(),
-                "exp_avg_sq": self.exp_avg_sq.cpu().clone(), "step": self._applied_steps(),
+                "exp_avg_sq": self.exp_avg_sq.cpu().clone(), "step": self.optim.applied_steps(),
                 "layout": {k: (o, tuple(s)) for k, (o, s) in self.layout.items()}}
 
     def load_state_dict(self, sd: Dict[str, object]) -> None:
@@ -210,26 +158,14 @@ class LayoutEngine:
         self._refresh_shadow()
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
-        self.step_count = int(sd["step"])
-        self._sync_device_step()
+        self.optim.set_step(int(sd["step"]))
 
     def optimizer_state(self) -> Dict[str, object]:
         """Adam state for the checkpoint's 'optimizer' entry (flat tensors, CPU)."""
-        skipped = self.optimizer_stats()["skipped_steps"] if self.guard is not None else 0     # (refreshes step_count)
-        return {"exp_avg": self.exp_avg.cpu().clone(), "exp_avg_sq": self.exp_avg_sq.cpu().clone(),
-                "step": int(self.step_count), "lr": self.lr, "beta1": self.beta1, "skipped": skipped}
+        return self.optim.flat_state()
 
     def load_optimizer(self, st: Dict[str, object]) -> None:
-        if st["exp_avg"].numel() != self.n_params:
-            raise ValueError("optimizer state has %d elements, model has %d" % (st["exp_avg"].numel(), self.n_params))
-        self.exp_avg.copy_(st["exp_avg"])
-        self.exp_avg_sq.copy_(st["exp_avg_sq"])
-        self.step_count = int(st["step"])
-        self._sync_device_step()
-        if self.guard is not None:                   # a guarded run resumes its learning rate and skip count ("lr" and
-            self.guard.set_counts(self.step_count, int(st.get("skipped", 0)))   # "skipped" are absent from older entries)
-            if st.get("lr") is not None:
-                self.set_lr(float(st["lr"]))
+        self.optim.load_flat_state(st)
 
     # ------------------------------------------------------------------- workspace
     def _alloc_workspace(self, tokens: int) -> None:
@@ -262,110 +198,37 @@ class LayoutEngine:
         # partial-sum ("slab") arenas: floats needed by the embedding, a layer-norm, and each weight-gradient shape
         emb_len = self.layout["l0.ln1_g"][0]
         need = [lib.vlg_embed_bwd_slabs() * emb_len, lib.vlg_layernorm_bwd_slabs(M) * 2 * d]
-        for (n, k) in ((3 * d, d), (d, d), (ff, d), (d, ff), (cfg.n_out, d)):
-            need.append(lib.vlg_linear_wgrad_slabs_for(M, n, k, self.gemm_flags) * (n * k + n))
-        # option: backward can run the weight gradients on a second HIP stream, concurrently with the data-gradient chain
-        # (see backward).  Measured -1.7 % step time at the metric shape (6.12 -> 6.02 ms): a 512-block launch takes every
-        # CU slot, so the other stream's kernel only overlaps its tail.  OFF by default: with two kernels sharing the chip
-        # a kernel's own duration no longer says anything about that kernel (bench.py's per-kernel roofline).
+        for (dy, x, n, k) in ((self.dqkv, self.h1, 3 * d, d), (self.dx, self.att, d, d), (self.du, self.h2, ff, d),
+                              (self.dx, self.gl, d, ff), (self.dout, self.xf, cfg.n_out, d)):      # as backward launches them
+            need.append(self._wgrad_plan(dy, x, M, n, k)[1] * (n * k + n))
+        # two streams (see backward): -1.7 % step time at the metric shape; OFF: sharing the chip, a kernel's duration says nothing
         self.side = torch.cuda.Stream(device=self.device)
         self.overlap_wgrad = os.environ.get("VLG_OVERLAP_WGRAD", "0") == "1"
-        # Single-stream backward (the default): the partial-sum producers of one bucket (a layer: four weight gradients + two
-        # layer-norms) write side by side into ONE arena and ONE table-driven launch (vlg_reduce_slabs_table, the form the
-        # GridNet path uses) reduces them all when the bucket is complete: 27 launches of ~5.5 us -> 6 per step.
-        self.group_reduce = not self.overlap_wgrad
-        # a projection's data gradient and weight gradient through one call (vlg_linear_dgrad_wgrad: one launch where the
-        # library can fuse them), single stream
+        self.group_reduce = not self.overlap_wgrad       # 27 reduction launches of ~5.5 us -> 6 per step
         self.pair_backward = (not self.overlap_wgrad and self.precision in ("fp32", "bf16")
                               and os.environ.get("VLG_PAIR_BACKWARD", "1") == "1")
-        self.ride_reduces = False
-        if self.group_reduce:
-            pad = lambda v: (v + 3) // 4 * 4
-            layer = sum(pad(v) for v in need[2:6]) + 2 * pad(need[1])
-            head = pad(need[6]) + pad(need[1])
-            # TWO arenas: a finished bucket's table may be reduced by rider blocks of the NEXT paired launch (which writes its
-            # own partial sums into the other arena) instead of by a launch of its own - _join_reduces(defer=True)
-            self.garenas = [torch.empty(max(layer, head, pad(need[0])), **f32) for _ in range(2)]
-            self._gsel = 0
-            self._goff = 0
-            self._grows: list = []
-            self._gtables: Dict[tuple, torch.Tensor] = {}
-            self._pending = None                     # (table rows, callback) of a bucket waiting for its ride
-            self.ride_reduces = self.pair_backward and os.environ.get("VLG_RIDE_REDUCE", "1") == "1"
+        # a finished bucket's table may be reduced by rider blocks of the NEXT paired launch instead of by a launch of its own
+        self.ride_reduces = self.group_reduce and self.pair_backward and os.environ.get("VLG_RIDE_REDUCE", "1") == "1"
+        if self.group_reduce:       # buckets (vlg/slabs.py): a layer, the head, the embeddings
+            self.buckets = self.wbuckets = SlabBuckets([need[2:6] + [need[1]] * 2, [need[6], need[1]], [need[0]]], self.device, True,
+                                                       self.ride_reduces)
         else:   # one arena per producer family, each reduced right behind its producer (before the next one writes)
-            self.slabs = torch.empty(max(need[:2]), **f32)          # layer-norm, embedding (main stream)
-            self.slabs_w = torch.empty(max(need[2:]), **f32)        # weight gradients (the side stream in a two-stream backward)
+            self.buckets = SlabBuckets([need[:2]], self.device, False, False)       # layer-norm, embedding (main stream)
+            self.wbuckets = SlabBuckets([need[2:]], self.device, False, False)      # weight gradients (the side stream)
 
     # --------------------------------------------------------------------- helpers
     @staticmethod
     def _stream() -> int:
         return torch.cuda.current_stream().cuda_stream
 
-    def _arena(self, kind: str, need: int = 0) -> torch.Tensor:
-        """the slab arena the next partial-sum producer writes (`need` floats).  Grouped reductions: the next free range of the
-        bucket's arena.  Otherwise one arena per producer family ("w": weight gradients, "s": layer-norm / embedding), whose
-        previous contents were reduced on the same stream right behind their producer."""
-        if self.group_reduce:
-            garena = self.garenas[self._gsel]
-            off = self._goff
-            if off + need > garena.numel():
-                raise RuntimeError("partial-sum arena of %d floats is too small for %d more" % (garena.numel(), need))
-            self._goff = off + (need + 3) // 4 * 4
-            self._gcur = garena.data_ptr() + 4 * off
-            return garena[off:off + need]
-        return self.slabs_w if kind == "w" else self.slabs
-
-    def _reduce(self, kind: str, stride: int, n_slabs: int, dst_off: int, dst_len: int) -> None:
-        """sum the slabs the producer just launched on the current stream wrote into its arena -> grads[dst_off : +dst_len]:
-        a row of the bucket's table (grouped), or a launch of its own right behind the producer"""
-        dst = self.grads.data_ptr() + 4 * dst_off
-        if self.group_reduce:
-            self._grows.append((self._gcur, stride, n_slabs, dst, dst_len))
-            return
-        call("vlg_reduce_slabs", ptr(self.slabs_w if kind == "w" else self.slabs), stride, n_slabs, dst, dst_len, self._stream())
-
-    def _table(self, rows: tuple) -> torch.Tensor:
-        table = self._gtables.get(rows)
-        if table is None:
-            table = torch.tensor([v for row in rows for v in row], dtype=torch.int64, device=self.device)
-            self._gtables[rows] = table
-        return table
-
-    def _join_reduces(self, defer: bool = False, then=None) -> None:
-        """grouped reductions: the bucket that is complete now (a table of {slabs, stride, count, destination, length} rows in
-        device memory, built once per batch geometry) is reduced by ONE launch on the current stream - or, with defer=True
-        and a paired launch to follow, handed to that launch as rider blocks (vlg_linear_dgrad_wgrad: the next producers then
-        write the other arena).  `then` (e.g. reducer.ready of the bucket) runs once the reduction has been enqueued.  A
-        bucket still waiting when another one completes travels in the same table."""
-        if not self.group_reduce:
-            if then is not None:
-                then()
-            return
-        rows = tuple(self._grows)
-        self._grows = []
-        self._goff = 0
-        if defer and self.ride_reduces and rows and self._pending is None:
-            self._pending = (rows, then)
-            self._gsel ^= 1
-            return
-        waiting, self._pending = self._pending, None
-        if waiting is not None:
-            rows = waiting[0] + rows
-        if rows:
-            call("vlg_reduce_slabs_table", ptr(self._table(rows)), len(rows), 128, self._stream())
-        if waiting is not None and waiting[1] is not None:
-            waiting[1]()
-        if then is not None:
-            then()
-
-    def _take_rider(self):
-        """(table pointer, rows, callback) of the bucket waiting for a ride, for the paired launch about to be enqueued"""
-        if not self.group_reduce or self._pending is None:
-            self._rider_bytes = 0.0
-            return 0, 0, None
-        (rows, then), self._pending = self._pending, None
-        self._rider_bytes = 4.0 * sum((n_slabs + 1) * length for (_, _, n_slabs, _, length) in rows)   # slabs read + sums written
-        return ptr(self._table(rows)), len(rows), then
+    def _wgrad_plan(self, dy, x, M: int, N: int, K: int) -> tuple:
+        """(flags word, partial sums written) of the weight gradient dy^T . x, alone or as the weight-gradient half of a paired call"""
+        key = (M, N, K, dy.dtype, x.dtype)
+        plan = self._wgrad_plans.get(key)             # (the library's plan depends on these alone; asked once per shape)
+        if plan is None:
+            flags = self.gemm_flags | self._storage_bits(dy, x)
+            plan = self._wgrad_plans[key] = (flags, hip.load().vlg_linear_wgrad_slabs_for(M, N, K, flags))
+        return plan
 
     def _timed(self, family: str, flops: float, name: str, *args, nbytes: float = 0.0) -> None:
         """Launch through the C ABI; when a timer is attached, bracket the launch with events on
@@ -397,39 +260,36 @@ class LayoutEngine:
                     ptr(aux_in), M, N, K, flags, self._stream(), nbytes=nb)
 
     def _wgrad(self, dy, x, wname, M, N, K):
-        """grad[w | b] = (dy^T . x | colsum dy): split partials -> slab arena -> flat gradient.  Runs on the CURRENT stream
-        (backward makes that the side stream)."""
-        lib = hip.load()
+        """grad[w | b] = (dy^T . x | colsum dy): split partials -> slab arena -> flat gradient, on the CURRENT stream."""
         stride = N * K + N
-        flags = self.gemm_flags | self._storage_bits(dy, x)
-        n_slabs = lib.vlg_linear_wgrad_slabs_for(M, N, K, flags)
-        arena = self._arena("w", n_slabs * stride)
+        flags, n_slabs = self._wgrad_plan(dy, x, M, N, K)
+        arena = self.wbuckets.reserve(n_slabs * stride)
         s = self._stream()
         self._timed("gemm_wgrad" if N > 32 else "gemm_head", 2.0 * M * N * K, "vlg_linear_wgrad", ptr(dy), N, ptr(x),
                     K, ptr(arena), stride, arena.numel(), M, N, K, flags, s,
                     nbytes=dy.element_size() * M * N + x.element_size() * M * K + 4.0 * n_slabs * stride)
-        self._reduce("w", stride, n_slabs, self.layout[wname][0], stride)
+        self.wbuckets.add(arena, stride, n_slabs, self.grads.data_ptr() + 4 * self.layout[wname][0], stride, s)
 
     def _dgrad_wgrad(self, dy, w, dx, x, wname, M, N, K, epi=EPI_NONE, aux_in=None):
         """backward of one projection y = x W^T + b given dy: grad[w | b] (slab partials -> flat gradient) AND dx = dy . W
         (x aux_in with EPI_MUL) through ONE C-ABI call, which the library runs as one launch where neither product fills
         the chip alone (few tokens per GPU; vlg_linear_dgrad_wgrad).  Same results, bit for bit, as _wgrad then _dgrad."""
-        lib = hip.load()
         stride = N * K + N
-        n_slabs = lib.vlg_linear_wgrad_slabs_for(M, N, K, self.gemm_flags)
-        arena = self._arena("w", n_slabs * stride)
+        n_slabs = self._wgrad_plan(dy, x, M, N, K)[1]
+        arena = self.wbuckets.reserve(n_slabs * stride)
         nb = (dy.element_size() * M * N * 2 + w.element_size() * N * K + dx.element_size() * M * K * (1 + (aux_in is not None)) +
               x.element_size() * M * K + 4.0 * n_slabs * stride)
         bits = self._storage_bits(dy, w, dx)       # bf16 mode: A = the shared dY, B = W (data gradient) AND X (weight gradient), OUT = dX
         if (x.dtype == torch.bfloat16) != (w.dtype == torch.bfloat16):
             raise ValueError("paired backward: X and W must have the same storage type")
-        rider, rider_rows, then = self._take_rider()       # a finished bucket's reduction rides in this launch (its bytes count)
+        rider, rider_rows, then, rider_bytes = self.buckets.take_rider()    # a finished bucket's reduction rides in this launch
+        s = self._stream()
         self._timed("gemm_pair", 4.0 * M * N * K, "vlg_linear_dgrad_wgrad", ptr(dy), N, ptr(w), K, ptr(dx), K, ptr(aux_in),
                     ptr(x), K, ptr(arena), stride, arena.numel(), M, N, K, epi | self.gemm_flags | bits, rider, rider_rows,
-                    self._stream(), nbytes=nb + self._rider_bytes)
+                    s, nbytes=nb + rider_bytes)
         if then is not None:
             then()
-        self._reduce("w", stride, n_slabs, self.layout[wname][0], stride)
+        self.wbuckets.add(arena, stride, n_slabs, self.grads.data_ptr() + 4 * self.layout[wname][0], stride, s)
 
     def _attn_fwd(self, l: int, batch, B, T, N, M) -> None:
         d, s = self.cfg.d, self._stream()
@@ -464,14 +324,13 @@ class LayoutEngine:
 
     def _ln_bwd(self, dy, x, stat, gname, dres, dx_out, M):
         d = self.cfg.d
-        lib = hip.load()
-        n_slabs = lib.vlg_layernorm_bwd_slabs(M)
-        arena = self._arena("s", n_slabs * 2 * d)
+        n_slabs = hip.load().vlg_layernorm_bwd_slabs(M)
+        arena = self.buckets.reserve(n_slabs * 2 * d)
         s = self._stream()
         self._timed("ln_bwd", 0.0, "vlg_layernorm_bwd_bf16" if dy.dtype == torch.bfloat16 else "vlg_layernorm_bwd", ptr(dy), ptr(x), ptr(stat[0]),
                     ptr(stat[1]), ptr(self.p(gname)), ptr(dres), ptr(dx_out), ptr(arena), 2 * d, arena.numel(), M, d, s,
                     nbytes=(dy.element_size() + 4.0 + 4.0 + (4.0 if dres is not None else 0.0)) * M * d)
-        self._reduce("s", 2 * d, n_slabs, self.layout[gname][0], 2 * d)
+        self.buckets.add(arena, 2 * d, n_slabs, self.grads.data_ptr() + 4 * self.layout[gname][0], 2 * d, s)
 
     def _check_batch(self, batch) -> tuple:
         sc = batch["slot_class"]
@@ -529,13 +388,13 @@ class LayoutEngine:
         (vlg.dp.GradReducer) is told as soon as each contiguous gradient bucket is complete so its
         all-reduce overlaps the rest of backward.
 
-        Two HIP streams.  The data-gradient chain (dgrad GEMMs, attention / layer-norm backward) stays on the caller's
-        stream; every weight gradient (+ its slab reduction) is launched on `self.side` as soon as its dY exists and runs
-        CONCURRENTLY with the chain.  Each GEMM launch leaves the matrix pipes idle while its blocks load their first tiles
-        and drain their stores (all blocks of a launch do that in step: 10-25 % of a K = 256 launch), and the
-        bandwidth-bound kernels of the chain leave them idle altogether; blocks of the other stream's kernel fill those
-        gaps.  Ordering is by events: a side kernel waits for the producer of its dY, and the chain waits before it
-        overwrites a buffer a side kernel still reads (du, dqkv, dx) and before a bucket is handed to the reducer."""
+        Default: ONE stream.  Each projection's data and weight gradient go through one paired call (`pair_backward`), one
+        table-driven launch reduces the partial sums of a bucket - the head, a layer, the embeddings (`group_reduce`) - and a
+        finished bucket's reduction rides in the next paired launch instead (`ride_reduces`, vlg/slabs.py).
+        Option, VLG_OVERLAP_WGRAD=1: two HIP streams.  The data-gradient chain stays on the caller's stream; every weight gradient
+        (+ its slab reduction) is launched on `self.side` as soon as its dY exists and runs CONCURRENTLY with the chain, filling the
+        gaps its launches leave in the matrix pipes.  Ordering is by events: a side kernel waits for the producer of its dY, and the
+        chain waits before it overwrites a buffer a side kernel still reads (du, dqkv, dx) and before a bucket goes to the reducer."""
         cfg, d, ff = self.cfg, self.cfg.d, self.cfg.d_ff
         B, T, N, M = self._shape
         main = torch.cuda.current_stream(self.device)
@@ -573,18 +432,14 @@ class LayoutEngine:
                 main.wait_event(e)
                 last_read.clear()
 
-        if self.group_reduce:
-            # every step uses the arenas in the same order: the reduction tables (device memory, cached by their rows) are
-            # the same from step to step - also what a captured hipGraph needs.  A backward that raised half way leaves
-            # nothing behind for this one.
-            self._gsel, self._goff, self._grows, self._pending = 0, 0, [], None
+        self.buckets.reset()         # a backward that raised half way leaves nothing behind for this one
         on_side(("dout",), lambda: self._wgrad(self.dout, self.xf, "head_w", M, cfg.n_out, d))
         self._dgrad(self.dout, self.pw("head_w"), self.dh, M, cfg.n_out, d)
         self._ln_bwd(self.dh, self.x[L], self.stats[2 * L], "lnf_g", None, self.dx, M)
         ready = (lambda tag: (lambda: reducer.ready(tag))) if reducer is not None else (lambda tag: None)
         if reducer is not None or self.group_reduce:
             join()
-            self._join_reduces(defer=self.pair_backward, then=ready("head"))      # (paired: rides in the last layer's first launch)
+            self.buckets.close(s, defer=self.pair_backward, then=ready("head"))      # (paired: rides in the last layer's first launch)
         for l in reversed(range(L)):
             pre = "l%d." % l
             if self.pair_backward:
@@ -596,7 +451,7 @@ class LayoutEngine:
                 self._dgrad_wgrad(self.dqkv, self.pw(pre + "qkv_w"), self.dh, self.h1[l], pre + "qkv_w", M, 3 * d, d)
                 self._ln_bwd(self.dh, self.x[l], self.stats[2 * l], pre + "ln1_g", self.dx, self.dx, M)
                 # the layer's bucket rides in the next layer's first paired launch (layer 0: in the embedding bucket's table)
-                self._join_reduces(defer=True, then=ready("l%d" % l))
+                self.buckets.close(s, defer=True, then=ready("l%d" % l))
                 continue
             # FFN:  x_out = xmid + W2 gelu(W1 h2 + b1) + b2
             on_side(("dx",), lambda: self._wgrad(self.dx, self.gl[l], pre + "ff2_w", M, d, ff))
@@ -617,7 +472,7 @@ class LayoutEngine:
             self._ln_bwd(self.dh, self.x[l], self.stats[2 * l], pre + "ln1_g", self.dx, self.dx, M)
             if reducer is not None or self.group_reduce:
                 join()
-                self._join_reduces()
+                self.buckets.close(s)
             if reducer is not None:
                 reducer.ready("l%d" % l)
         join()
@@ -625,16 +480,15 @@ class LayoutEngine:
 
     def _backward_tail(self, batch, B, T, N, M, reducer) -> None:
         cfg, d = self.cfg, self.cfg.d
-        lib = hip.load()
         s = self._stream()
         emb_len = self.layout["l0.ln1_g"][0]
-        n_slabs = lib.vlg_embed_bwd_slabs_for(B, T, N, d, cfg.vocab)          # by shape: few clips write (and reduce) few slabs
-        arena = self._arena("s", n_slabs * emb_len)
+        n_slabs = hip.load().vlg_embed_bwd_slabs_for(B, T, N, d, cfg.vocab)          # by shape: few clips write (and reduce) few slabs
+        arena = self.buckets.reserve(n_slabs * emb_len)
         self._timed("embed_bwd", 0.0, "vlg_embed_bwd", ptr(self.dx), ptr(batch["slot_class"]), ptr(batch["slot_box"]), ptr(arena),
                     emb_len, arena.numel(), B, T, N, d, cfg.vocab, s, nbytes=4.0 * M * d + 24.0 * M)
-        self._reduce("s", emb_len, n_slabs, 0, emb_len)
+        self.buckets.add(arena, emb_len, n_slabs, self.grads.data_ptr(), emb_len, s)
         # (flushes a bucket still waiting for a ride in the same table: the gradient buffer is complete for whoever runs next)
-        self._join_reduces(then=(lambda: reducer.ready("embed")) if reducer is not None else None)
+        self.buckets.close(s, then=(lambda: reducer.ready("embed")) if reducer is not None else None)
 
     def forward_backward(self, batch: Dict[str, torch.Tensor], reducer=None) -> torch.Tensor:
         loss = self.forward(batch)
@@ -648,7 +502,7 @@ class LayoutEngine:
         squared-norm pass and one Adam over the whole buffer - the split Adam below, which updates everything but the
         embeddings while their bucket is still in flight, is given up in that mode (and only there)."""
         loss = self.forward_backward(batch, reducer)
-        if self.guard is not None:
+        if self.optim.guard is not None:
             if reducer is not None:
                 reducer.wait()
             self.optimizer_update(reducer.grad_scale if reducer is not None else 1.0)
@@ -668,39 +522,15 @@ class LayoutEngine:
     def adam_step(self, grad_scale: float = 1.0, lo: int = 0, hi: Optional[int] = None, advance: bool = True) -> None:
         """torch.optim.Adam(lr, betas=(beta1, 0.999)) on the flat buffer (reference src/trainer.py:83,258), or on its
         [lo, hi) slice (both multiples of 4); `advance` = False keeps the step count (second slice of one step)."""
-        hi = self.n_params if hi is None else hi
-        if self.guard is not None:
-            if lo != 0 or hi != self.n_params or not advance:
-                raise ValueError("the guarded step updates the whole buffer at once (its norm needs every gradient)")
-            self.optimizer_update(grad_scale)
-            return
-        if advance:
-            self.step_count += 1
-        o = 4 * lo
-        shadow = self.params_bf16.data_ptr() + o // 2 if self.params_bf16 is not None else 0
-        if self.adam_state is not None:          # captured / capturable step: the counter and its factors live on the device
-            call("vlg_adam_step_graph", self.params.data_ptr() + o, self.grads.data_ptr() + o, self.exp_avg.data_ptr() + o,
-                 self.exp_avg_sq.data_ptr() + o, shadow, hi - lo, ptr(self.adam_state), 1 if advance else 0, self.lr,
-                 self.beta1, ADAM_BETA2, ADAM_EPS, grad_scale, self._stream())
-            return
-        if self.params_bf16 is not None:
-            call("vlg_adam_step_bf16", self.params.data_ptr() + o, self.grads.data_ptr() + o, self.exp_avg.data_ptr() + o,
-                 self.exp_avg_sq.data_ptr() + o, shadow, hi - lo, self.step_count, self.lr,
-                 self.beta1, ADAM_BETA2, ADAM_EPS, grad_scale, self._stream())
-            return
-        self._timed("adam", 0.0, "vlg_adam_step", self.params.data_ptr() + o, self.grads.data_ptr() + o, self.exp_avg.data_ptr() + o,
-                    self.exp_avg_sq.data_ptr() + o, hi - lo, self.step_count, self.lr, self.beta1, ADAM_BETA2, ADAM_EPS,
-                    grad_scale, self._stream(), nbytes=28.0 * (hi - lo))
+        launch = call if self.timer is None else (
+            lambda name, *a: self._timed("adam", 0.0, name, *a, nbytes=28.0 * ((self.n_params if hi is None else hi) - lo)))
+        self.optim.step(self.params, self.grads, grad_scale, lo, hi, advance, self._stream(), launch)
+
+    def optimizer_update(self, grad_scale: float = 1.0) -> None:
+        """The guarded stage after backward and every gradient bucket; the 4 loss floats behind the parameters are not in the norm."""
+        self.optim.update_guarded(self.params, self.grads, grad_scale, self._stream())
 
     # ------------------------------------------------------------------- hipGraph
-    def use_device_step_counter(self) -> None:
-        """Move Adam's step counter (and the bias-correction factors derived from it) to device memory, the form a
-        captured step needs; the host count `step_count` keeps mirroring it."""
-        if self.adam_state is None:
-            st = torch.zeros(4, dtype=torch.float32, device=self.device)
-            st.view(torch.int32)[2] = int(self.step_count)
-            self.adam_state = st
-
     def capture_train_step(self, example_batch: Dict[str, torch.Tensor]):
         """Capture forward -> loss -> backward -> Adam for this batch SHAPE in one hipGraph (single process: the
         data-parallel hooks are not captured) and return `run(batch) -> loss scalars`: it copies the batch into the
@@ -709,30 +539,28 @@ class LayoutEngine:
         device), so replay is bitwise identical to the eager step.  A guarded engine captures its guarded step: clipping,
         the skip and set_lr keep working across replays."""
         self._check_batch(example_batch)
-        if self.guard is None:
-            self.use_device_step_counter()
-            self._captured_plain = True
-        counter = self.adam_state if self.guard is None else self.guard.ctl      # the optimiser's device-side scalars
+        counter = self.optim.begin_capture()     # the optimiser's device-side scalars
         static = {k: example_batch[k].clone() for k in ("slot_class", "slot_box", "tgt_class", "tgt_box", "valid")}
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         keep = (self.params.clone(), self.exp_avg.clone(), self.exp_avg_sq.clone(), counter.clone(), self.step_count)
+        def restore():
+            self.params.copy_(keep[0]); self.exp_avg.copy_(keep[1]); self.exp_avg_sq.copy_(keep[2])
+            counter.copy_(keep[3]); self.step_count = keep[4]
+            self._refresh_shadow()
+
         with torch.cuda.stream(side):            # warm-up on a side stream, as stream capture requires
             self.train_step(static)
         torch.cuda.current_stream(self.device).wait_stream(side)
         torch.cuda.synchronize(self.device)
         # undo the warm-up step: capture must not change the training trajectory
-        self.params.copy_(keep[0]); self.exp_avg.copy_(keep[1]); self.exp_avg_sq.copy_(keep[2])
-        counter.copy_(keep[3]); self.step_count = keep[4]
-        self._refresh_shadow()
+        restore()
         timer, self.timer = self.timer, None     # events are not capturable work
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=side):
             self.train_step(static)
         self.timer = timer
-        self.params.copy_(keep[0]); self.exp_avg.copy_(keep[1]); self.exp_avg_sq.copy_(keep[2])
-        counter.copy_(keep[3]); self.step_count = keep[4]
-        self._refresh_shadow()
+        restore()
 
         def run(batch: Dict[str, torch.Tensor]) -> torch.Tensor:
             for k, t in static.items():

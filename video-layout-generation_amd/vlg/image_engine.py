@@ -28,24 +28,25 @@ import torch
 from . import hip
 from .gridnet import GridNetHIP, reference_param_order
 from .hip import call, ptr
-from .optim_guard import OptimControl
+from .optim import AdamSurface, FlatAdam
 from .spec import ADAM_BETA1, ADAM_BETA2, ADAM_EPS, ADAM_LR, IMG_MEAN, IMG_STD, OUT_MEAN, OUT_STD
 
 IMAGE_KEYS = ("frame1", "seg1", "frame2", "seg2", "frame3", "seg3", "e1", "e2")
 W_L1, W_STYLE, W_CE = 40.0, 20.0, 10.0          # reference src/trainer.py:248-250
 
 
-class ImageEngine:
+class ImageEngine(AdamSurface):
     def __init__(self, batch: int, H: int, W: int, device, arch: str = "CoordGridNet", lr: float = ADAM_LR,
                  beta1: float = ADAM_BETA1, filters=(32, 64, 96), with_hed: bool = False, with_vgg: bool = False,
                  precision: str = "fp32", clip_grad: float = 0.0, skip_nonfinite: bool = False):
-        """clip_grad / skip_nonfinite: the guarded optimiser step, as LayoutEngine's (vlg/optim_guard.py): global-norm
-        clipping and a step that a non-finite gradient skips; set_lr turns it on too.  Off, the step is unchanged.
+        """clip_grad / skip_nonfinite: the guarded optimiser step, as LayoutEngine's (vlg/optim.py, one FlatAdam each): global-norm
+        clipping and a step that a non-finite gradient skips; set_lr turns it on too.  Off, the step is unchanged.  As there, the
+        guard cannot be turned on after a capture with the plain optimiser - this engine has no capture, so nothing sets that latch.
         precision: "fp32" (the reference's) or "bf16" - the 3x3 convolutions of GridNet, HED and VGG on bf16-rounded
         GEMM operands with fp32 accumulation (csrc/conv_bf16.hip); tensors, losses, gradients and Adam stay fp32."""
         if arch not in ("GridNet", "CoordGridNet"):
             raise ValueError("arch must be GridNet or CoordGridNet (reference src/main.py:101-102)")
-        self.device, self.lr, self.beta1 = device, float(lr), float(beta1)
+        self.device = device
         self.b, self.H, self.W = batch, H, W
         self.precision = precision
         self.net = GridNetHIP(10, batch, H, W, device, coord=(arch == "CoordGridNet"), filters=filters, precision=precision)
@@ -57,14 +58,7 @@ class ImageEngine:
         if with_hed:
             from .hned import HNEDHIP
             self.hed = HNEDHIP(batch, H, W, device, precision=precision)
-        n = self.net.params.numel()
-        self.exp_avg = torch.zeros(n, dtype=torch.float32, device=device)
-        self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=device)
-        self.step_count = 0
-        self.clip_grad, self.skip_nonfinite = max(float(clip_grad), 0.0), bool(skip_nonfinite)
-        self.guard: Optional[OptimControl] = None
-        if self.clip_grad > 0.0 or self.skip_nonfinite:
-            self._enable_guard()
+        self.optim = FlatAdam(self.net.params.numel(), device, lr, beta1, clip_grad, skip_nonfinite)   # exp_avg, step_count, guard ...
         f32 = dict(dtype=torch.float32, device=device)
         self.x10 = torch.empty(batch, 10, H, W, **f32)
         self.f3 = torch.empty(batch, 3, H, W, **f32)
@@ -91,37 +85,6 @@ class ImageEngine:
     def state_dict(self):
         return self.net.state_dict()
 
-    # ------------------------------------------------------------------ guarded optimiser step
-    @property
-    def guarded(self) -> bool:
-        return self.guard is not None
-
-    def _enable_guard(self) -> None:
-        if self.guard is None:
-            self.guard = OptimControl(self.net.params.numel(), self.device, self.lr, self.beta1, self.clip_grad, self.step_count)
-
-    def set_lr(self, lr: float) -> None:
-        """New learning rate from the next step on (one 4-byte write into the guarded step's device record)."""
-        self.lr = float(lr)
-        self._enable_guard()
-        self.guard.set_lr(self.lr)
-
-    def optimizer_stats(self) -> Dict[str, float]:
-        """{grad_norm, clip_coef, applied_steps, skipped_steps, lr}: one 64-byte device-to-host copy."""
-        if self.guard is None:
-            raise RuntimeError("optimizer_stats() needs the guarded step (clip_grad, skip_nonfinite or set_lr)")
-        st = self.guard.read()
-        self.step_count = st["applied_steps"]        # the device count is the authority: skipped steps do not advance it
-        return st
-
-    def optimizer_update(self, grad_scale: float = 1.0) -> None:
-        """Squared-norm partials of net.grads -> control record -> Adam, after backward and every gradient bucket.  The
-        norm runs over the flat kernel layout: its padded lanes (channel padding, the 3 spare floats of a PReLU slope)
-        are never written by backward and stay zero, so it is the norm of the reference's tensors; the 8 loss floats
-        behind the parameters are not part of it."""
-        self._enable_guard()
-        self.guard.update(self.net.params, self.net.grads, self.exp_avg, self.exp_avg_sq, None, grad_scale, self._stream())
-
     # ------------------------------------------------------------------ optimiser state (checkpoints)
     def optimizer_state(self) -> Dict[str, object]:
         """Adam state in torch.optim.Adam.state_dict() form - {'state': {i: {'step','exp_avg','exp_avg_sq'}},
@@ -143,42 +106,28 @@ class ImageEngine:
         """Accepts a torch.optim.Adam state_dict over the reference model's parameters (reference trainer.py:92) - mapped
         parameter by parameter into the kernels' flat layout - or the flat {'exp_avg','exp_avg_sq','step'} form.  A guarded
         engine also resumes the learning rate and the skipped-step count where the entry records them."""
-        self._load_optimizer(st)
-        if self.guard is not None:
-            groups = st.get("param_groups") or [{}]
-            lr = groups[0].get("lr") if "param_groups" in st else st.get("lr")
-            self.guard.set_counts(self.step_count, int(st.get("skipped", 0)))
-            if lr is not None:
-                self.set_lr(float(lr))
-
-    def _load_optimizer(self, st: Dict[str, object]) -> None:
-        n = self.net.params.numel()
         if "state" in st and "param_groups" in st:
             order = reference_param_order(self.net.coord)
             ids = [i for g in st["param_groups"] for i in g["params"]]
             if len(ids) != len(order):
                 raise ValueError("optimizer state covers %d parameters, %s has %d"
                                  % (len(ids), "CoordGridNet" if self.net.coord else "GridNet", len(order)))
-            state = st["state"]
-            if len(state) == 0:
-                self.exp_avg.zero_(); self.exp_avg_sq.zero_(); self.step_count = 0
-                return
+            state, n = st["state"], self.net.params.numel()
             missing = [i for i in ids if i not in state]
-            if missing:
+            if state and missing:
                 raise ValueError("optimizer state lacks entries for parameter ids %s" % missing[:4])
-            steps = {int(float(state[i]["step"])) for i in ids}
+            steps = {int(float(state[i]["step"])) for i in ids} if state else {0}    # (torch keeps no state before the first step)
             if len(steps) != 1:
                 raise ValueError("per-parameter step counts differ (%s): one flat Adam step cannot represent that" % sorted(steps)[:4])
-            self.net.pack({k: state[i]["exp_avg"] for i, k in zip(ids, order)}, self.exp_avg)
-            self.net.pack({k: state[i]["exp_avg_sq"] for i, k in zip(ids, order)}, self.exp_avg_sq)
-            self.step_count = steps.pop()
-            return
+            st = {"exp_avg": torch.zeros(n), "exp_avg_sq": torch.zeros(n), "step": steps.pop(), "skipped": st.get("skipped", 0),
+                  "lr": st["param_groups"][0].get("lr")}
+            if state:
+                self.net.pack({name: state[i]["exp_avg"] for i, name in zip(ids, order)}, st["exp_avg"])
+                self.net.pack({name: state[i]["exp_avg_sq"] for i, name in zip(ids, order)}, st["exp_avg_sq"])
         for k in ("exp_avg", "exp_avg_sq", "step"):
             if k not in st:
                 raise ValueError("optimizer state is neither a torch.optim.Adam state_dict nor the flat form (no %r)" % k)
-        if st["exp_avg"].numel() != n or st["exp_avg_sq"].numel() != n:
-            raise ValueError("optimizer state has %d elements, model has %d" % (st["exp_avg"].numel(), n))
-        self.exp_avg.copy_(st["exp_avg"]); self.exp_avg_sq.copy_(st["exp_avg_sq"]); self.step_count = int(st["step"])
+        self.optim.load_flat_state(st)
 
     def forward(self, batch: Dict[str, torch.Tensor], flip: bool = False, want_grads: bool = True) -> torch.Tensor:
         """Forward + losses (+ d loss / d outputs).  Returns the device scalar-array {l1, gd, ssim, ce}."""
@@ -224,13 +173,16 @@ class ImageEngine:
         call("vlg_affine_nchw", ptr(self.dimg), ptr(self.dtmp), b, 3, H * W, self._zero, self._istd, s)   # d/d img_raw
         self.net.backward(self.dseg, self.dtmp, reducer)
 
-    def adam_step(self, grad_scale: float = 1.0) -> None:
-        if self.guard is not None:
-            self.optimizer_update(grad_scale)
-            return
-        self.step_count += 1
-        call("vlg_adam_step", ptr(self.net.params), ptr(self.net.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq),
-             self.net.params.numel(), self.step_count, self.lr, self.beta1, ADAM_BETA2, ADAM_EPS, grad_scale, self._stream())
+    def adam_step(self, grad_scale: float = 1.0, lo: int = 0, hi: Optional[int] = None, advance: bool = True) -> None:
+        """Adam on the flat parameter buffer, LayoutEngine.adam_step's signature."""
+        self.optim.step(self.net.params, self.net.grads, grad_scale, lo, hi, advance, self._stream())
+
+    def optimizer_update(self, grad_scale: float = 1.0) -> None:
+        """The guarded stage after backward and every gradient bucket (FlatAdam.update_guarded).  The norm runs over the
+        flat kernel layout: its padded lanes (channel padding, the 3 spare floats of a PReLU slope) are never written by
+        backward and stay zero, so it is the norm of the reference's tensors; the 8 loss floats behind the parameters
+        are not part of it."""
+        self.optim.update_guarded(self.net.params, self.net.grads, grad_scale, self._stream())
 
     def train_step(self, batch, flip: bool = False, reducer=None) -> torch.Tensor:
         """forward -> losses -> backward (+ bucketed gradient all-reduce overlapped with it) -> Adam.  Returns the total
