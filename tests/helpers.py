@@ -25,6 +25,22 @@ def check_close(got, want, rtol=1e-4, atol=1e-5, what=""):
     assert_close(g, want, rtol=rtol, atol=atol, what=what)
 
 
+def vs_cpu32(got, want64, cpu32, what, floor_rel=2.0 ** -20, bf16=False):
+    """Every element finite and max |got - fp64| <= 4 x max |torch-CPU fp32 - fp64| + floor_rel x max |fp64|; a bf16
+    output may in addition be off by one bf16 rounding of its value (2^-8 |fp64|, elementwise)."""
+    got = got.detach().cpu().double()
+    bad = ~torch.isfinite(got)
+    assert not bool(bad.any()), "%s: %d/%d elements not finite" % (what, int(bad.sum()), bad.numel())
+    e_cpu = float((cpu32.double() - want64).abs().max())
+    err = (got - want64).abs()
+    if bf16:
+        err = err - 2.0 ** -8 * want64.abs()
+    e_gpu = float(err.max())
+    floor = floor_rel * float(want64.abs().max())
+    assert e_gpu <= 4 * e_cpu + floor, "%s: |err| vs fp64 %.3e > 4 x torch-CPU fp32's %.3e + floor %.3e" % (
+        what, e_gpu, e_cpu, floor)
+
+
 class OracleEngine:
     def __init__(self, cfg: LayoutConfig, seed: int = 1024, lr: float = ADAM_LR, beta1: float = ADAM_BETA1):
         self.cfg, self.device = cfg, torch.device("cpu")

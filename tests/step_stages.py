@@ -1,0 +1,482 @@
+"""Stage references of the layout-token step: one pure function per launch of LayoutEngine.forward / .backward (tensors
+in, tensors out, generic in dtype), the schedule of launches the engine makes, and `emulate`, which chains the stage
+functions along that schedule.  Plain module: test infrastructure only, no fixtures, nothing collected.
+
+Every stage computes from the values its launch READS, in the dtype it is given: float64 gives the wanted value, float32
+the yardstick of helpers.vs_cpu32.  The storage contract of the precision modes ("Layout step: storage
+contract of the reduced-precision modes") enters as arguments and is read from vlg/engine.py and the kernels' headers, not from results:
+
+  bf16       h1, qkv, att, h2, u, gl, xf, dh, du, dqkv are bf16 in memory, projection weights come from params_bf16;
+             x, xmid, out, dout, dx, stats, lse, delta are fp32; fp32 accumulation; one round-to-nearest-even on store;
+             an fp32 operand of a projection (dx, dout as dY) is rounded to bf16 on its way to the matrix cores, the
+             bias-gradient column sums take it unrounded (csrc/gemm_tile16.h colsum_add)
+  bf16_mfma  every tensor fp32, both operands of every projection rounded to bf16 on load
+  fp32 / fp32x3  no rounding
+  saved u    gelu_grad_saved: u = gelu'(pre) from the fp32 pre-activation, then stored; else u = pre, gelu' on load
+  clip+bf16  scores, softmax statistics, lse fp32; P (forward: exp2(s - running max) per 32-key tile, backward:
+             exp2(s - lse)) and dS rounded to bf16 as matrix operands only; delta = <dO, O> on the stored values
+
+Stage outputs are returned UNROUNDED: the comparison allows a bf16 output its one rounding (vs_cpu32 bf16=True) and
+`emulate` rounds when it stores.  Rows of every (M, .) tensor are in the engine's order m = (b*N + n)*T + t.
+"""
+import math
+
+import torch
+import torch.nn.functional as F
+
+from oracle import layout_spec as O
+
+BF = torch.bfloat16
+EPI_NONE, EPI_BIAS, EPI_GELU, EPI_RESID, EPI_DGELU, EPI_BF16 = 0, 1, 2, 4, 8, 16
+EPI_A_BF16, EPI_B_BF16, EPI_OUT_BF16, EPI_SPLIT3 = 32, 64, 128, 256
+EPI_GELU_GRAD, EPI_MUL = 1024, 2048
+
+PRECISIONS = ("fp32", "fp32x3", "bf16", "bf16_mfma")
+BF16_BUFFERS = ("h1", "qkv", "att", "h2", "u", "gl", "xf", "dh", "du", "dqkv")      # bf16 in memory under "bf16"
+BACKWARD_BUFFERS = ("dx", "dh", "du", "dqkv", "dout", "delta")                        # reused by the backward: snapshot per launch
+LOG2E = 1.0 / math.log(2.0)
+
+
+class Contract:
+    """What a precision mode stores and rounds (see the module docstring)."""
+
+    def __init__(self, precision, attention="slot", masked=True, gelu_grad_saved=None, paired=None):
+        assert precision in PRECISIONS
+        self.precision, self.attention = precision, attention
+        self.store_bf16 = precision == "bf16"
+        self.round_operands = precision in ("bf16", "bf16_mfma")
+        self.gemm_flags = {"fp32": 0, "fp32x3": EPI_SPLIT3}.get(precision, EPI_BF16)
+        self.gelu_grad_saved = precision != "fp32x3" if gelu_grad_saved is None else gelu_grad_saved
+        assert not (self.gelu_grad_saved and precision == "fp32x3")
+        self.paired = precision in ("fp32", "bf16") if paired is None else paired
+        self.masked = masked and attention == "clip"                 # per-key validity masks (padded_slots)
+        self.sfx = "_bf16" if self.store_bf16 else ""
+
+    def dtype(self, buf):
+        return BF if self.store_bf16 and buf.split("[")[0] in BF16_BUFFERS else torch.float32
+
+    def bits(self, a=None, b=None, out=None):
+        """storage bits of a projection call from the CONTRACT's dtypes; b = True for a weight / X operand of the mode"""
+        is16 = lambda n: n is not None and (self.store_bf16 if n is True else self.dtype(n) == BF)
+        return (EPI_A_BF16 if is16(a) else 0) | (EPI_B_BF16 if is16(b) else 0) | (EPI_OUT_BF16 if is16(out) else 0)
+
+    def weight(self, name):
+        return ("pb:" if self.store_bf16 else "p:") + name
+
+
+class Raw:
+    """an output a mutation stores as it is, storage type included (emulate)"""
+
+    def __init__(self, t):
+        self.t = t
+
+
+def bf(x):
+    """round to nearest even to bf16, kept in x's dtype"""
+    return x.to(BF).to(x.dtype)
+
+
+def ident(x):
+    return x
+
+
+def gelu_grad(x):
+    return 0.5 * (1 + torch.erf(x / math.sqrt(2))) + x * torch.exp(-0.5 * x * x) / math.sqrt(2 * math.pi)
+
+
+def to_rows(t):
+    """(B,T,N,C) -> (M,C) in the engine's row order (b, n, t)"""
+    B, T, N = t.shape[:3]
+    return t.permute(0, 2, 1, *range(3, t.dim())).reshape(B * N * T, *t.shape[3:])
+
+
+def from_rows(t, B, T, N):
+    return t.reshape(B, N, T, *t.shape[1:]).permute(0, 2, 1, *range(3, t.dim() + 2))
+
+
+# ------------------------------------------------------------------------------------------------ forward stages
+def embed_fwd(cls_emb, box_w, box_b, time_emb, slot_class, slot_box):
+    p = {"cls_emb": cls_emb, "box_w": box_w, "box_b": box_b, "time_emb": time_emb}
+    return to_rows(O.embed(p, slot_class, slot_box.to(cls_emb.dtype)))
+
+
+def ln_fwd(x, g, b):
+    """-> (y, mean, rstd): the two-pass statistics of csrc/layernorm.hip"""
+    mean = x.mean(-1, keepdim=True)
+    xc = x - mean
+    rstd = 1.0 / torch.sqrt((xc * xc).mean(-1, keepdim=True) + O.LN_EPS)
+    return xc * rstd * g + b, mean.squeeze(-1), rstd.squeeze(-1)
+
+
+def linear_fwd(a, w, b, rnd=ident, resid=None, gelu=None):
+    """c = rnd(a) rnd(w)^T + b (+ resid); gelu = "pre": (gelu(pre), pre), "grad": (gelu(pre), gelu'(pre)) -> (c, aux_out)"""
+    pre = rnd(a) @ rnd(w).t() + b
+    if gelu is not None:
+        return F.gelu(pre), (gelu_grad(pre) if gelu == "grad" else pre)
+    return (pre + resid if resid is not None else pre), None
+
+
+def slot_attention_fwd(qkv, T):
+    """causal along T per (clip, slot, head): rows are (sequence, frame)"""
+    n_seq, d3 = qkv.shape[0] // T, qkv.shape[1]
+    o = O.temporal_attention(qkv.view(n_seq, T, d3).transpose(0, 1)[None], d3 // 192)          # (1, T, n_seq, d)
+    return o[0].transpose(0, 1).reshape(n_seq * T, d3 // 3)
+
+
+def _clip_heads(t, B, T, N):
+    """(M, H*64) rows -> (B, H, S, 64), tokens frame-major s = t*N + n"""
+    x = from_rows(t, B, T, N).reshape(B, T * N, -1, 64)
+    return x.permute(0, 2, 1, 3)
+
+
+def _clip_rows(t, B, T, N):
+    """(B, H, S, 64) -> (M, H*64) rows"""
+    return to_rows(t.permute(0, 2, 1, 3).reshape(B, T, N, -1))
+
+
+def _clip_allowed(valid, B, T, N):
+    S = T * N
+    frame = torch.arange(S) // N
+    allowed = (frame[None, :] <= frame[:, None])[None, None]
+    if valid is not None:
+        allowed = allowed & (valid.reshape(B, 1, 1, S) > 0)
+    return allowed | torch.eye(S, dtype=torch.bool)[None, None]
+
+
+def clip_attention_fwd(qkv, valid, B, T, N, rnd=ident, detail=None):
+    """-> (out rows, lse (B*H*S,) in the log2 domain).  The walk of csrc/attention_clip.hip: 32-key tiles in frame-major
+    order, a running maximum per query, P = exp2(s - running max) (rounded by `rnd` only as the operand of P.V, the row sum
+    takes it unrounded), O rescaled when the maximum moves, one division by the row sum at the end.  `detail`, a dict,
+    receives what operand_flip_slack needs: every tile's P before rounding and its weight in the final output."""
+    d = qkv.shape[1] // 3
+    q, k, v = (_clip_heads(t, B, T, N) for t in qkv.split(d, dim=-1))
+    s = (q @ k.transpose(-1, -2)) * (LOG2E / 8.0)
+    s = s.masked_fill(~_clip_allowed(valid, B, T, N), float("-inf"))
+    S = T * N
+    m = torch.full(s.shape[:-1], float("-inf"), dtype=s.dtype)
+    l = torch.zeros_like(m)
+    o = torch.zeros_like(q)
+    tiles = []
+    for j in range(0, S, 32):
+        st = s[..., j:j + 32]
+        m_new = torch.maximum(m, st.amax(-1))
+        m_use = torch.where(torch.isinf(m_new), torch.zeros_like(m_new), m_new)
+        alpha = torch.exp2(m - m_use)
+        p = torch.exp2(st - m_use[..., None])
+        l = l * alpha + p.sum(-1)
+        o = o * alpha[..., None] + rnd(p) @ v[..., j:j + 32, :]
+        m = m_new
+        tiles.append((p, m_use))
+    if detail is not None:
+        detail.update(p=torch.cat([t for t, _ in tiles], -1), v=v,        # weight of a tile's P in out: the later rescales / l
+                      w=torch.cat([(torch.exp2(mu - m) / l)[..., None].expand_as(t) for t, mu in tiles], -1))
+    return _clip_rows(o / l[..., None], B, T, N), (m + torch.log2(l)).reshape(-1)
+
+
+def loss_fwd(out, tgt_class, tgt_box, valid, B, T, N, n_classes=20):
+    """-> (the four loss scalars, dout rows) by oracle.losses and its autograd"""
+    o = from_rows(out, B, T, N).detach().clone().requires_grad_(True)
+    parts = O.losses(o[..., :n_classes], o[..., n_classes:], tgt_class, tgt_box.to(out.dtype), valid.to(out.dtype))
+    parts[0].backward()
+    return torch.stack([p.detach() for p in parts]), to_rows(o.grad)
+
+
+# ------------------------------------------------------------------------------------------------ backward stages
+def linear_dgrad(dy, w, rnd=ident, aux=None, mode=None):
+    """dx = rnd(dy) rnd(w), times aux ("mul": the saved gelu') or gelu'(aux) ("dgelu": the saved pre-activation)"""
+    dx = rnd(dy) @ rnd(w)
+    if mode == "mul":
+        dx = dx * aux
+    elif mode == "dgelu":
+        dx = dx * gelu_grad(aux)
+    return dx
+
+
+def linear_wgrad(dy, x, rnd=ident):
+    """-> (dW = rnd(dy)^T rnd(x), db = column sums of dy as stored)"""
+    return rnd(dy).t() @ rnd(x), dy.sum(0)
+
+
+def ln_bwd(dy, x, mean, rstd, g, dres=None):
+    """-> (dx (+ dres), dgamma, dbeta) from the SAVED statistics"""
+    xh = (x - mean[:, None]) * rstd[:, None]
+    a = dy * g
+    dx = rstd[:, None] * (a - a.mean(-1, keepdim=True) - xh * (a * xh).mean(-1, keepdim=True))
+    return (dx + dres if dres is not None else dx), (dy * xh).sum(0), dy.sum(0)
+
+
+def slot_attention_bwd(qkv, do, T):
+    q = qkv.detach().clone().requires_grad_(True)
+    slot_attention_fwd(q, T).backward(do)
+    return q.grad
+
+
+def clip_attention_bwd(qkv, do, out, lse, valid, B, T, N, rnd=ident, detail=None):
+    """-> (dqkv rows, delta (B*H*S,)).  As the two backward kernels: P = exp2(s - lse) from the SAVED lse, delta = <dO, O> on
+    the stored values, dS = P (dP - delta) / 8; `rnd` rounds P and dS only as matrix operands."""
+    d = qkv.shape[1] // 3
+    q, k, v = (_clip_heads(t, B, T, N) for t in qkv.split(d, dim=-1))
+    g, o = _clip_heads(do, B, T, N), _clip_heads(out, B, T, N)
+    s = (q @ k.transpose(-1, -2)) * (LOG2E / 8.0)
+    p = torch.exp2(s - lse.view(s.shape[:-1])[..., None])
+    p = torch.where(_clip_allowed(valid, B, T, N), p, torch.zeros_like(p))
+    delta = (g * o).sum(-1)
+    ds = p * (g @ v.transpose(-1, -2) - delta[..., None]) * 0.125
+    dq, dk, dv = rnd(ds) @ k, rnd(ds).transpose(-1, -2) @ q, rnd(p).transpose(-1, -2) @ g
+    if detail is not None:
+        detail.update(p=p, ds=ds, q=q, k=k, g=g)
+    return torch.cat([_clip_rows(t, B, T, N) for t in (dq, dk, dv)], dim=1), delta.reshape(-1)
+
+
+def flip_step(x64, x32):
+    """How far the bf16 rounding of an on-chip matrix operand (P, dS of the bf16 per-clip attention) can land from the
+    rounding of its fp64 value, elementwise.  An fp64 reference cannot decide a rounding whose argument carries fp32 noise:
+    an element that vs_cpu32's own rule - 4 x torch-CPU fp32's error plus 2^-20 of the value, here per element - cannot
+    place on one side of a rounding boundary may round either way.  Zero for every other element (all but ~1 in 3 000)."""
+    band = 4.0 * (x32.double() - x64).abs() + 2.0 ** -20 * x64.abs()
+    return (bf(x64 + band) - bf(x64 - band)).abs()
+
+
+def operand_flip_slack(kind, d64, d32, B, T, N):
+    """{output: elementwise slack (rows)} of a bf16 per-clip attention launch from the `detail` of its float64 and float32
+    evaluations: what the elements of flip_step can move each output by."""
+    sp = flip_step(d64["p"], d32["p"])
+    if kind == "clip_fwd":
+        return {"att": _clip_rows((sp * d64["w"]) @ d64["v"].abs(), B, T, N)}
+    sd = flip_step(d64["ds"], d32["ds"])
+    parts = (sd @ d64["k"].abs(), sd.transpose(-1, -2) @ d64["q"].abs(), sp.transpose(-1, -2) @ d64["g"].abs())
+    return {"dqkv": torch.cat([_clip_rows(t, B, T, N) for t in parts], dim=1)}
+
+
+def embed_bwd(dx, slot_class, slot_box, vocab, B, T, N):
+    """-> gradients of cls_emb, box_w, box_b, time_emb"""
+    ids, box = to_rows(slot_class[..., None])[:, 0], to_rows(slot_box).to(dx.dtype)
+    return {"cls_emb": torch.zeros(vocab, dx.shape[1], dtype=dx.dtype).index_add_(0, ids, dx), "box_w": dx.t() @ box,
+            "box_b": dx.sum(0), "time_emb": dx.view(B * N, T, -1).sum(0)}
+
+
+# ------------------------------------------------------------------------------------------------ the schedule
+def schedule(cfg, c):
+    """The launches of one forward_backward in order, as vlg/engine.py makes them under contract `c`.  Each entry: stage
+    (a name for messages), family, entry (C-ABI name), ops (names of the pointer arguments in order; None = NULL, "arena"
+    = a slab arena, "*" = not pinned), flags (projection calls), kind + the operand names the stage function takes."""
+    L, d, ff = cfg.n_layers, cfg.d, cfg.d_ff
+    clip = c.attention == "clip"
+    valid = "batch:valid" if c.masked else None
+    P = lambda n: "p:" + n
+    out = []
+
+    def ln_f(stage, x, gname, y, i):
+        out.append(dict(stage=stage, kind="ln_fwd", family="ln_fwd", entry="vlg_layernorm_fwd" + c.sfx, x=x, g=gname, y=y, stat=i,
+                        ops=(x, P(gname), P(gname[:-1] + "b"), y, "stats[%d].mean" % i, "stats[%d].rstd" % i)))
+
+    def lin(stage, a, wname, cbuf, epi, aux_in=None, aux_out=None):
+        flags = epi | c.gemm_flags | c.bits(a, True, cbuf)
+        out.append(dict(stage=stage, kind="linear_fwd", family="gemm_head" if wname == "head_w" else "gemm_fwd", entry="vlg_linear_fwd",
+                        a=a, w=wname, c=cbuf, epi=epi, aux_in=aux_in, aux_out=aux_out, flags=flags,
+                        ops=(a, c.weight(wname), P(wname[:-1] + "b"), cbuf, aux_in, aux_out)))
+
+    out.append(dict(stage="embedding", kind="embed_fwd", family="embed_fwd", entry="vlg_embed_fwd",
+                    ops=("batch:slot_class", "batch:slot_box", P("cls_emb"), P("box_w"), P("box_b"), P("time_emb"), "x[0]")))
+    epi_ff1 = EPI_BIAS | EPI_GELU | (EPI_GELU_GRAD if c.gelu_grad_saved else 0)
+    for l in range(L):
+        pre = "l%d." % l
+        x, h1, qkv, att, xmid, h2, u, gl = ("%s[%d]" % (n, l) for n in ("x", "h1", "qkv", "att", "xmid", "h2", "u", "gl"))
+        ln_f(pre + "ln1", x, pre + "ln1_g", h1, 2 * l)
+        lin(pre + "qkv", h1, pre + "qkv_w", qkv, EPI_BIAS)
+        if clip:
+            out.append(dict(stage=pre + "attention", kind="clip_fwd", family="attn_clip_fwd", entry="vlg_attention_clip_fwd" + c.sfx,
+                            l=l, ops=(qkv, valid, att, "lse[%d]" % l)))
+        else:
+            out.append(dict(stage=pre + "attention", kind="slot_fwd", family="attn_fwd", entry="vlg_attention_fwd" + c.sfx, l=l,
+                            ops=(qkv, att)))
+        lin(pre + "proj", att, pre + "proj_w", xmid, EPI_BIAS | EPI_RESID, aux_in=x)
+        ln_f(pre + "ln2", xmid, pre + "ln2_g", h2, 2 * l + 1)
+        lin(pre + "ff1", h2, pre + "ff1_w", gl, epi_ff1, aux_out=u)
+        lin(pre + "ff2", gl, pre + "ff2_w", "x[%d]" % (l + 1), EPI_BIAS | EPI_RESID, aux_in=xmid)
+    ln_f("lnf", "x[%d]" % L, "lnf_g", "xf", 2 * L)
+    lin("head", "xf", "head_w", "out", EPI_BIAS)
+    out.append(dict(stage="loss", kind="loss", family="loss", entry="vlg_layout_loss",
+                    ops=("out", "batch:tgt_class", "batch:tgt_box", "batch:valid", "dout", "loss_out", "loss_scratch")))
+
+    # ---- backward
+    def wg(stage, dy, x, wname):
+        out.append(dict(stage=stage + " wgrad", kind="wgrad", family="gemm_head" if wname == "head_w" else "gemm_wgrad",
+                        entry="vlg_linear_wgrad", dy=dy, x=x, w=wname, flags=c.gemm_flags | c.bits(dy, x), ops=(dy, x, "arena")))
+
+    def dg(stage, dy, wname, dx, epi=EPI_NONE, aux_in=None):
+        out.append(dict(stage=stage + " dgrad", kind="dgrad", family="gemm_dgrad", entry="vlg_linear_dgrad", dy=dy, w=wname, dx=dx,
+                        epi=epi, aux_in=aux_in, flags=epi | c.gemm_flags | c.bits(dy, True, dx), ops=(dy, c.weight(wname), dx, aux_in)))
+
+    def pair(stage, dy, wname, dx, x, epi=EPI_NONE, aux_in=None):
+        if not c.paired:
+            wg(stage, dy, x, wname)
+            dg(stage, dy, wname, dx, epi, aux_in)
+            return
+        out.append(dict(stage=stage + " dgrad+wgrad", kind="pair", family="gemm_pair", entry="vlg_linear_dgrad_wgrad", dy=dy, w=wname,
+                        dx=dx, x=x, epi=epi, aux_in=aux_in, flags=epi | c.gemm_flags | c.bits(dy, True, dx),
+                        ops=(dy, c.weight(wname), dx, aux_in, x, "arena", "*")))
+
+    def ln_b(stage, dy, x, i, gname, dres):
+        out.append(dict(stage=stage + " bwd", kind="ln_bwd", family="ln_bwd", entry="vlg_layernorm_bwd" + c.sfx, dy=dy, x=x, stat=i,
+                        g=gname, dres=dres, ops=(dy, x, "stats[%d].mean" % i, "stats[%d].rstd" % i, P(gname), dres, "dx", "arena")))
+
+    epi_dff2 = EPI_MUL if c.gelu_grad_saved else EPI_DGELU
+    wg("head", "dout", "xf", "head_w")
+    dg("head", "dout", "head_w", "dh")
+    ln_b("lnf", "dh", "x[%d]" % L, 2 * L, "lnf_g", None)
+    for l in reversed(range(L)):
+        pre = "l%d." % l
+        x, h1, qkv, att, xmid, h2, u, gl = ("%s[%d]" % (n, l) for n in ("x", "h1", "qkv", "att", "xmid", "h2", "u", "gl"))
+        pair(pre + "ff2", "dx", pre + "ff2_w", "du", gl, epi_dff2, aux_in=u)
+        pair(pre + "ff1", "du", pre + "ff1_w", "dh", h2)
+        ln_b(pre + "ln2", "dh", xmid, 2 * l + 1, pre + "ln2_g", "dx")
+        if c.paired:
+            pair(pre + "proj", "dx", pre + "proj_w", "dh", att)
+        else:
+            wg(pre + "proj", "dx", att, pre + "proj_w")
+            dg(pre + "proj", "dx", pre + "proj_w", "dh")
+        if clip:
+            out.append(dict(stage=pre + "attention bwd", kind="clip_bwd", family="attn_clip_bwd", entry="vlg_attention_clip_bwd" + c.sfx,
+                            l=l, ops=(qkv, valid, att, "dh", "lse[%d]" % l, "delta", "dqkv")))
+        else:
+            out.append(dict(stage=pre + "attention bwd", kind="slot_bwd", family="attn_bwd", entry="vlg_attention_bwd" + c.sfx, l=l,
+                            ops=(qkv, "dh", "dqkv")))
+        pair(pre + "qkv", "dqkv", pre + "qkv_w", "dh", h1)
+        ln_b(pre + "ln1", "dh", x, 2 * l, pre + "ln1_g", "dx")
+    out.append(dict(stage="embedding bwd", kind="embed_bwd", family="embed_bwd", entry="vlg_embed_bwd",
+                    ops=("dx", "batch:slot_class", "batch:slot_box", "arena")))
+    return out
+
+
+def epi_modes(epi):
+    """(forward gelu mode, data-gradient mode) of an epilogue word"""
+    gelu = None if not epi & EPI_GELU else "grad" if epi & EPI_GELU_GRAD else "pre"
+    return gelu, ("mul" if epi & EPI_MUL else "dgelu" if epi & EPI_DGELU else None)
+
+
+# ------------------------------------------------------------------------------------------------ the chain
+def run_stage(e, cfg, c, batch, val, detail=None):
+    """One schedule entry on the values `val(name)` hands out (already in the dtype to compute in; None -> None) ->
+    (outputs {buffer name: unrounded tensor}, parameter gradients {name: tensor} this launch is the source of).
+    `detail`: see clip_attention_fwd."""
+    B, T, N = batch["slot_class"].shape
+    rnd = bf if c.round_operands else ident
+    arnd = bf if c.store_bf16 else ident                     # P and dS of the per-clip attention
+    valid = batch["valid"] if c.masked else None
+    k = e["kind"]
+    o, g = {}, {}
+
+    def wgrad(dy):
+        g[e["w"]], g[e["w"][:-1] + "b"] = linear_wgrad(dy, val(e["x"]), rnd)
+
+    def dgrad(dy):
+        return linear_dgrad(dy, val(c.weight(e["w"])), rnd, val(e["aux_in"]), epi_modes(e["epi"])[1])
+
+    if k == "embed_fwd":
+        o["x[0]"] = embed_fwd(val("p:cls_emb"), val("p:box_w"), val("p:box_b"), val("p:time_emb"), batch["slot_class"], batch["slot_box"])
+    elif k == "ln_fwd":
+        o[e["y"]], o["stats[%d].mean" % e["stat"]], o["stats[%d].rstd" % e["stat"]] = ln_fwd(
+            val(e["x"]), val("p:" + e["g"]), val("p:" + e["g"][:-1] + "b"))
+    elif k == "linear_fwd":
+        o[e["c"]], aux = linear_fwd(val(e["a"]), val(c.weight(e["w"])), val("p:" + e["w"][:-1] + "b"), rnd,
+                                    val(e["aux_in"]) if e["epi"] & EPI_RESID else None, epi_modes(e["epi"])[0])
+        if aux is not None:
+            o[e["aux_out"]] = aux
+    elif k == "slot_fwd":
+        o["att[%d]" % e["l"]] = slot_attention_fwd(val("qkv[%d]" % e["l"]), T)
+    elif k == "clip_fwd":
+        o["att[%d]" % e["l"]], o["lse[%d]" % e["l"]] = clip_attention_fwd(val("qkv[%d]" % e["l"]), valid, B, T, N, arnd, detail)
+    elif k == "loss":
+        o["loss_out"], o["dout"] = loss_fwd(val("out"), batch["tgt_class"], batch["tgt_box"], batch["valid"], B, T, N, cfg.n_classes)
+    elif k == "wgrad":
+        wgrad(val(e["dy"]))
+    elif k == "dgrad":
+        o[e["dx"]] = dgrad(val(e["dy"]))
+    elif k == "pair":
+        dy = val(e["dy"])
+        wgrad(dy)
+        o[e["dx"]] = dgrad(dy)
+    elif k == "ln_bwd":
+        i = e["stat"]
+        o["dx"], g[e["g"]], g[e["g"][:-1] + "b"] = ln_bwd(val(e["dy"]), val(e["x"]), val("stats[%d].mean" % i), val("stats[%d].rstd" % i),
+                                                          val("p:" + e["g"]), val(e["dres"]))
+    elif k == "slot_bwd":
+        o["dqkv"] = slot_attention_bwd(val("qkv[%d]" % e["l"]), val("dh"), T)
+    elif k == "clip_bwd":
+        l = e["l"]
+        o["dqkv"], o["delta"] = clip_attention_bwd(val("qkv[%d]" % l), val("dh"), val("att[%d]" % l), val("lse[%d]" % l), valid,
+                                                   B, T, N, arnd, detail)
+    elif k == "embed_bwd":
+        g.update(embed_bwd(val("dx"), batch["slot_class"], batch["slot_box"], cfg.vocab, B, T, N))
+    else:
+        raise KeyError(k)
+    return o, g
+
+
+def emulate(cfg, c, params, batch, dtype, mutate=None):
+    """Chain the stage functions along schedule(cfg, c) in `dtype`, storing every buffer as the contract says (bf16
+    buffers as torch.bfloat16 tensors, everything else in `dtype`) -> (records, state) in the record format of
+    step_trace.trace: a record = dict(family, name, flags, ops, after = {backward buffer: clone}); state = every
+    forward buffer, "grads" {name: tensor} and "loss".  In float64 this is the emulated oracle of the mode.
+    `mutate(entry, val, outputs, grads, record)` may change what a launch leaves behind before it is stored (the checker's
+    own test); an output wrapped in Raw is stored as it is."""
+    st = {"p:" + k: v.to(dtype) for k, v in params.items()}
+    st.update({"pb:" + k: v.to(BF) for k, v in params.items()})
+    grads = {}
+    val = lambda n: None if n is None else st[n].to(dtype)
+    records = []
+    for e in schedule(cfg, c):
+        o, g = run_stage(e, cfg, c, batch, val)
+        rec = dict(family=e["family"], name=e["entry"], flags=e.get("flags"), ops=e["ops"])
+        if mutate is not None:
+            mutate(e, val, o, g, rec)
+        for n, t in o.items():
+            st[n] = t.t if isinstance(t, Raw) else t.to(BF if c.dtype(n) == BF else dtype)
+        grads.update(g)
+        rec["after"] = {n: st[n].clone() for n in BACKWARD_BUFFERS if n in st}
+        records.append(rec)
+    st["grads"], st["loss"] = grads, st["loss_out"]
+    return records, st
+
+
+def emulated_oracle(cfg, precision, params, batch, attention="slot", masked=True):
+    """Loss scalars and gradients of the mode, chained end to end in float64 with its storage roundings."""
+    _, st = emulate(cfg, Contract(precision, attention, masked), params, batch, torch.float64)
+    return st["loss"], st["grads"]
+
+
+# ------------------------------------------------------------------------------------------------ end-to-end bars
+_DISTANCES = {}
+
+
+def mode_distance(kw, precision, attention="slot", variable_n=False, seed=7):
+    """How far a reduced-precision mode is from the fp32 specification, measured on the CPU alone: oracle.layout_spec
+    (fp32, as the step tests run it) against the float64 emulation of the mode on the same parameters and batch ->
+    (relative distance of the total loss, {gradient tensor: relative L2 distance}).  Tensors whose gradient is
+    analytically zero (key bias) are left out, by the rule of the step tests (norm below 1e-6 of the largest)."""
+    key = (tuple(sorted(kw.items())), precision, attention, variable_n, seed)
+    if key not in _DISTANCES:
+        from vlg.spec import LayoutConfig, param_shapes
+        cfg = LayoutConfig(attention=attention, **kw)
+        params = O.init_params(param_shapes(cfg), seed=1024)
+        batch = O.synthetic_batch(cfg.B, cfg.T, cfg.N, seed=seed, variable_n=variable_n, min_valid=3)
+        parts, grads = O.loss_and_grads(params, batch, cfg.n_layers, attention=attention)
+        loss, emu = emulated_oracle(cfg, precision, params, batch, attention, masked=variable_n)
+        gmax = max(float(v.norm()) for v in grads.values())
+        dist = {n: float((w.double() - emu[n]).norm() / emu[n].norm()) for n, w in grads.items() if float(w.norm()) >= 1e-6 * gmax}
+        _DISTANCES[key] = (abs(parts[0] - float(loss[0])) / abs(float(loss[0])), dist)
+    return _DISTANCES[key]
+
+
+def end_to_end_bars(kw, precision, attention="slot", variable_n=False, seed=7, margin=4.0, old_loss=2e-2, old_grad=5e-2):
+    """The end-to-end bars of a reduced-precision mode: `margin` x mode_distance per quantity (the emulation's own
+    fp32-against-fp64 noise is about a third of the signal, hence 4), never above the bars they replace ->
+    (loss bar, {tensor: bar}, {tensor base name: largest bar over the layers} for deeper models of the same width)."""
+    dl, dg = mode_distance(kw, precision, attention, variable_n, seed)
+    bars = {n: min(old_grad, margin * v) for n, v in dg.items()}
+    by_base = {}
+    for n, v in bars.items():
+        b = n.split(".")[-1]
+        by_base[b] = max(by_base.get(b, 0.0), v)
+    return min(old_loss, margin * dl), bars, by_base

@@ -21,6 +21,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from helpers import vs_cpu32
 from oracle import layout_spec as O
 from test_hip_clip_attention_bf16 import lse_want
 from test_hip_pixel_ops import EPS, SENT, SENT16, f32, sentinel, untouched, within
@@ -55,22 +56,6 @@ def _buf(n, dev, bf16=False):
 def _guard(raw, n, what):
     sent = SENT16 if raw.dtype == torch.int16 else SENT
     assert bool((raw[n:] == sent).all()), "%s wrote past its %d elements" % (what, n)
-
-
-def vs_cpu32(got, want64, cpu32, what, floor_rel=2.0 ** -20, bf16=False):
-    """Every element finite and max |got - fp64| <= 4 x max |torch-CPU fp32 - fp64| + floor_rel x max |fp64|; a bf16
-    output may in addition be off by one bf16 rounding of its value (2^-8 |fp64|, elementwise)."""
-    got = got.detach().cpu().double()
-    bad = ~torch.isfinite(got)
-    assert not bool(bad.any()), "%s: %d/%d elements not finite" % (what, int(bad.sum()), bad.numel())
-    e_cpu = float((cpu32.double() - want64).abs().max())
-    err = (got - want64).abs()
-    if bf16:
-        err = err - 2.0 ** -8 * want64.abs()
-    e_gpu = float(err.max())
-    floor = floor_rel * float(want64.abs().max())
-    assert e_gpu <= 4 * e_cpu + floor, "%s: |err| vs fp64 %.3e > 4 x torch-CPU fp32's %.3e + floor %.3e" % (
-        what, e_gpu, e_cpu, floor)
 
 
 # ------------------------------------------------------------------------------------------------ temporal attention

@@ -7,6 +7,7 @@ section 0); tolerance 1e-4 relative with a small absolute floor, written per che
 import pytest
 import torch
 
+import step_stages as SS
 from helpers import check_close
 from oracle import layout_spec as O
 
@@ -205,27 +206,38 @@ def test_full_size_step_matches_fp64_oracle(dev, kw, precision, variable_n):
 def test_bf16_projection_mode(dev, precision, T):
     """BASELINE.json configs[2]: the same step with bf16 MFMA projections (fp32 accumulate), either with the
     projection-side activations stored as bf16 in HBM ("bf16") or with fp32 tensors and operands rounded on their
-    way to LDS ("bf16_mfma").  bf16 has 8 significand bits, so this is NOT a 1e-4 parity mode: the loss
-    must agree with the fp32 oracle to 2e-2 relative and every gradient tensor to 5e-2 in relative L2 (stated
-    tolerance), and training must still make progress."""
+    way to LDS ("bf16_mfma").  bf16 has 8 significand bits, so this is NOT a 1e-4 parity mode.  The bars come from the
+    reference, not from the kernels: step_stages.mode_distance measures, on the CPU, how far the fp32 specification is
+    from the float64 emulation of the mode (the stage functions chained with the mode's storage roundings, DESIGN.md,
+    "Layout step: storage contract of the reduced-precision modes"); the loss and every gradient tensor (relative L2)
+    must agree with the fp32 oracle to 4 x that distance, per quantity, and never looser than the 2e-2 / 5e-2 this
+    replaces.
+    Measured distances (loss; gradient tensors, smallest .. largest) and the resulting bars:
+      bf16, T=16       2.3e-5; 6.5e-4 (head_b) .. 4.1e-3 (l1.ln2_g)   ->  loss 9.2e-5, gradients 2.6e-3 .. 1.7e-2
+      bf16_mfma, T=16  1.2e-5; 9.7e-4 (head_b) .. 3.8e-3 (l1.ln2_g)   ->  loss 4.9e-5, gradients 3.9e-3 .. 1.5e-2
+      bf16, T=8        3.3e-5; 1.4e-2 (box_b) .. 1.9e-2 (box_w)       ->  loss 1.3e-4, gradients 5e-2 (4 x exceeds the old bar)
+    (at T=8 the 256 tokens are few enough that one IoU min / max branch taken the other way moves every gradient.)
+    Training must still make progress."""
     from vlg.engine import LayoutEngine
     from vlg.spec import LayoutConfig, param_shapes
-    cfg = LayoutConfig(B=2, T=T, N=16, d=256, n_layers=2)
+    kw = dict(B=2, T=T, N=16, d=256, n_layers=2)
+    cfg = LayoutConfig(**kw)
     eng = LayoutEngine(cfg, dev, precision=precision)
     p = O.init_params(param_shapes(cfg), seed=1024)
     batch = O.synthetic_batch(cfg.B, cfg.T, cfg.N, seed=7)
     parts, grads = O.loss_and_grads(p, batch, cfg.n_layers)
+    bar_loss, bar_grad, _ = SS.end_to_end_bars(kw, precision, seed=7)
+    assert bar_loss < 2e-2 and max(bar_grad.values()) <= 5e-2
     loss = eng.forward_backward(to_dev(batch, dev)).cpu()
-    assert abs(float(loss[0]) - parts[0]) <= 2e-2 * abs(parts[0]), (float(loss[0]), parts[0])
-    worst = 0.0
-    for name, g in eng.named_grads().items():
-        w = grads[name]
-        if float(w.norm()) < 1e-6 * max(float(x.norm()) for x in grads.values()):
-            continue                                     # key bias etc.: analytically zero gradient
-        err = float((g.cpu() - w).norm() / w.norm())
-        worst = max(worst, err)
-        assert err <= 5e-2, (name, err)
-    assert worst > 1e-5, "bf16 mode produced fp32-exact gradients: the flag is not reaching the kernels"
+    errs = {name: float((g.cpu() - grads[name]).norm() / grads[name].norm()) for name, g in eng.named_grads().items() if name in bar_grad}
+    print("\n%s T=%d: loss off by %.2e (bar %.2e); gradients (rel L2 / bar): %s" % (
+        precision, T, abs(float(loss[0]) - parts[0]) / abs(parts[0]), bar_loss,
+        ", ".join("%s %.1e/%.1e" % (n, e, bar_grad[n]) for n, e in errs.items())))
+    assert abs(float(loss[0]) - parts[0]) <= bar_loss * abs(parts[0]), (float(loss[0]), parts[0], bar_loss)
+    assert len(errs) >= len(grads) - 2 * cfg.n_layers            # only analytically zero gradients (key bias) are left out
+    for name, err in errs.items():
+        assert err <= bar_grad[name], (name, err, bar_grad[name])
+    assert max(errs.values()) > 1e-5, "bf16 mode produced fp32-exact gradients: the flag is not reaching the kernels"
     first = float(loss[0])
     b = to_dev(batch, dev)
     for _ in range(20):
@@ -237,10 +249,12 @@ def test_bf16_projection_mode(dev, precision, T):
 def test_bf16_mode_at_full_size(dev, shape):
     """BASELINE.json configs[2] AT SIZE - (32,16,32) and the metric shape (32,16,64), d = 256, 4 layers - in the bf16 mode
     (bf16 MFMA projections, bf16 activation storage, bf16 weight shadow).  The CPU oracle is too slow here, so the
-    reference is the native fp32 HIP step on the same batch (itself held to the oracle at 1e-4 on smaller shapes):
-    loss within 2e-2, every gradient tensor within 5e-2 relative L2 (the mode's stated tolerance), plus the
-    size-independent properties: bitwise reproducible, clip-permutation equivariant, weight shadow == rounded master
-    weights after every update, loss decreasing."""
+    reference is the native fp32 HIP step on the same batch (itself held to the oracle at 1e-4 on smaller shapes), at
+    the bars of the small shape of test_bf16_projection_mode (bf16, T=16: 4 x the CPU-measured distance between the fp32
+    specification and the float64 emulation of the mode - loss 9.2e-5, gradient tensors 2.6e-3 (head_b) .. 1.7e-2 (ln2_g),
+    per tensor kind the largest over that shape's layers; before: 2e-2 / 5e-2), plus the size-independent properties:
+    bitwise reproducible, clip-permutation equivariant, weight shadow == rounded master weights after every update, loss
+    decreasing."""
     from vlg.data import synthetic_clips, to_device
     from vlg.engine import LayoutEngine
     from vlg.spec import LayoutConfig
@@ -254,17 +268,21 @@ def test_bf16_mode_at_full_size(dev, shape):
     l0 = eng.forward_backward(batch).clone()
     g0 = eng.grads.clone()
     out0 = eng.out.clone()
-    assert abs(float(l0[0]) - float(l_ref[0])) <= 2e-2 * abs(float(l_ref[0])), (float(l0[0]), float(l_ref[0]))
+    bar_loss, _, bar_base = SS.end_to_end_bars(dict(B=2, T=16, N=16, d=256, n_layers=2), "bf16", seed=7)
     gmax = max(float(v.norm()) for v in g_ref.values())
-    worst = 0.0
+    errs = {}
     for name, g in eng.named_grads().items():
         w = g_ref[name]
         if float(w.norm()) < 1e-6 * gmax:
             continue                                     # analytically zero gradients (key bias)
-        err = float((g - w).norm() / w.norm())
-        worst = max(worst, err)
-        assert err <= 5e-2, (name, err)
-    assert worst > 1e-5, "bf16 mode produced fp32-exact gradients: the flag is not reaching the kernels"
+        errs[name] = float((g - w).norm() / w.norm())
+    print("\nbf16 %s: loss off by %.2e (bar %.2e); gradients (rel L2 / bar): %s" % (
+        shape, abs(float(l0[0]) - float(l_ref[0])) / abs(float(l_ref[0])), bar_loss,
+        ", ".join("%s %.1e/%.1e" % (n, e, bar_base[n.split(".")[-1]]) for n, e in errs.items())))
+    assert abs(float(l0[0]) - float(l_ref[0])) <= bar_loss * abs(float(l_ref[0])), (float(l0[0]), float(l_ref[0]), bar_loss)
+    for name, err in errs.items():
+        assert err <= bar_base[name.split(".")[-1]], (name, err, bar_base[name.split(".")[-1]])
+    assert max(errs.values()) > 1e-5, "bf16 mode produced fp32-exact gradients: the flag is not reaching the kernels"
     l1 = eng.forward_backward(batch).clone()
     assert torch.equal(l0, l1) and torch.equal(g0, eng.grads), "bf16 step is not bitwise reproducible"
     perm = torch.randperm(cfg.B)

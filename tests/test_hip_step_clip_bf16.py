@@ -1,11 +1,14 @@
 """GPU: the layout step with the per-clip attention option in the bf16 mode (precision = "bf16", attention = "clip"), through
-the engine and the Trainer.  Bars: the bf16 mode's stated tolerance (test_hip_step.py::test_bf16_projection_mode) - loss within
-2e-2 relative, every gradient tensor within 5e-2 relative L2 - plus the exact properties (reproducible, masked, equivariant)."""
+the engine and the Trainer.  Bars: the rule of test_hip_step.py::test_bf16_projection_mode - 4 x the CPU-measured distance
+between the fp32 specification and the float64 emulation of the mode (step_stages.mode_distance; DESIGN.md, "Layout
+step: storage contract of the reduced-precision modes"), per quantity, never above the 2e-2 (loss) / 5e-2 (gradient tensor, relative L2) it replaces -
+plus the exact properties (reproducible, masked, equivariant)."""
 import random
 
 import pytest
 import torch
 
+import step_stages as SS
 from helpers import check_close, reference_args
 from oracle import layout_spec as O
 
@@ -16,21 +19,31 @@ def to_dev(batch, dev):
     return {k: v.to(dev) for k, v in batch.items()}
 
 
-def check_grads(got, want):
+SMALL = dict(B=2, T=16, N=16, d=256, n_layers=2)
+
+
+def check_grads(got, want, bars):
+    """bars: {tensor name or, for a deeper model, its base name: relative-L2 bar}"""
     gmax = max(float(v.norm()) for v in want.values())
-    worst = 0.0
+    errs = {}
     for name, g in got.items():
         w = want[name].to(g.device)
         if float(w.norm()) < 1e-6 * gmax:
             continue                                     # analytically zero gradients (key bias)
-        err = float((g - w).norm() / w.norm())
-        worst = max(worst, err)
-        assert err <= 5e-2, (name, err)
-    assert worst > 1e-5, "bf16 + clip produced fp32-exact gradients: the mode is not reaching the kernels"
+        errs[name] = float((g - w).norm() / w.norm())
+    bar = lambda n: bars[n] if n in bars else bars[n.split(".")[-1]]
+    print("\ngradients (rel L2 / bar): %s" % ", ".join("%s %.1e/%.1e" % (n, e, bar(n)) for n, e in errs.items()))
+    for name, err in errs.items():
+        assert err <= bar(name) <= 5e-2, (name, err, bar(name))
+    assert max(errs.values()) > 1e-5, "bf16 + clip produced fp32-exact gradients: the mode is not reaching the kernels"
 
 
 @pytest.mark.parametrize("variable_n", [False, True])
 def test_bf16_clip_step_matches_oracle(dev, variable_n):
+    """Measured on the CPU (fp32 specification against the float64 emulation of bf16 + clip at this shape): loss 3.1e-5 (fixed
+    N) / 3.9e-5 (variable N) -> bars 1.2e-4 / 1.6e-4 (before: 2e-2); gradient tensors 7.3e-3 (box_w) .. 1.4e-2 (l1.ln2_g) / 9.3e-3
+    .. 1.5e-2 (head_w) -> 4 x is 2.9e-2 .. 5.8e-2, capped at the 5e-2 it replaces (box_w 2.9e-2, the qkv and proj weights
+    3.4e-2 .. 4.2e-2; the tensors above 1.25e-2 keep 5e-2)."""
     from vlg.engine import LayoutEngine
     from vlg.spec import LayoutConfig, param_shapes
     cfg = LayoutConfig(B=2, T=16, N=16, d=256, n_layers=2, attention="clip")
@@ -39,8 +52,10 @@ def test_bf16_clip_step_matches_oracle(dev, variable_n):
     batch = O.synthetic_batch(cfg.B, cfg.T, cfg.N, seed=11, variable_n=variable_n, min_valid=3)
     parts, grads = O.loss_and_grads(p, batch, cfg.n_layers, attention="clip")
     loss = eng.forward_backward(to_dev(batch, dev)).cpu()
-    assert abs(float(loss[0]) - parts[0]) <= 2e-2 * abs(parts[0]), (float(loss[0]), parts[0])
-    check_grads(eng.named_grads(), grads)
+    bar_loss, bar_grad, _ = SS.end_to_end_bars(SMALL, "bf16", "clip", variable_n, seed=11)
+    print("\nbf16 + clip: loss off by %.2e (bar %.2e)" % (abs(float(loss[0]) - parts[0]) / abs(parts[0]), bar_loss))
+    assert bar_loss < 2e-2 and abs(float(loss[0]) - parts[0]) <= bar_loss * abs(parts[0]), (float(loss[0]), parts[0], bar_loss)
+    check_grads(eng.named_grads(), grads, bar_grad)
     first = float(loss[0])
     b = to_dev(batch, dev)
     for _ in range(20):
@@ -49,7 +64,9 @@ def test_bf16_clip_step_matches_oracle(dev, variable_n):
 
 
 def test_bf16_clip_step_at_metric_shape(dev):
-    """(32,16,64), d = 256, 4 layers against the native fp32 per-clip HIP step on the same batch."""
+    """(32,16,64), d = 256, 4 layers against the native fp32 per-clip HIP step on the same batch, at the bars of the small
+    shape of test_bf16_clip_step_matches_oracle (fixed N): loss 1.2e-4 (before: 2e-2), gradient tensors per kind the largest
+    bar over that shape's layers, 2.9e-2 (box_w) .. 5e-2."""
     from vlg.data import synthetic_clips, to_device
     from vlg.engine import LayoutEngine
     from vlg.spec import LayoutConfig
@@ -63,8 +80,10 @@ def test_bf16_clip_step_at_metric_shape(dev):
     l0 = eng.forward_backward(batch).clone()
     g0 = eng.grads.clone()
     out0 = eng.out.clone()
-    assert abs(float(l0[0]) - float(l_ref[0])) <= 2e-2 * abs(float(l_ref[0])), (float(l0[0]), float(l_ref[0]))
-    check_grads(eng.named_grads(), g_ref)
+    bar_loss, _, bar_base = SS.end_to_end_bars(SMALL, "bf16", "clip", False, seed=11)
+    print("\nbf16 + clip at the metric shape: loss off by %.2e (bar %.2e)" % (abs(float(l0[0]) - float(l_ref[0])) / abs(float(l_ref[0])), bar_loss))
+    assert abs(float(l0[0]) - float(l_ref[0])) <= bar_loss * abs(float(l_ref[0])), (float(l0[0]), float(l_ref[0]), bar_loss)
+    check_grads(eng.named_grads(), g_ref, bar_base)
     l1 = eng.forward_backward(batch).clone()
     assert torch.equal(l0, l1) and torch.equal(g0, eng.grads), "bf16 + clip step is not bitwise reproducible"
     perm = torch.randperm(cfg.B)
