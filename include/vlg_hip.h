@@ -232,6 +232,39 @@ int vlg_attention_clip_bwd_bf16(const vlg_bf16* qkv, const float* valid, const v
                                 const float* lse, float* delta, vlg_bf16* dqkv,
                                 int64_t B, int T, int N, int d, void* stream);
 
+/* ------------------------------------------------------------------ generation (csrc/decode.hip)
+ * The forward-only tail of an autoregressive rollout (reference src/trainer.py:453-476 rolls its pixel model out the same
+ * way: predict, argmax, append, slide).  SELF-ORACLE (tests/decode_ref.py); rule and rooflines: DESIGN.md, "Generation".
+ *
+ * Final layer-norm + head on the LAST frame's rows only (generation needs no other row).
+ * x: residual stream [B*N*T, d] fp32 in the internal row order m = (b*N + n)*T + t; only rows m = r*T + (T-1),
+ * r = b*N + n, are read.  out_last[r, :] = head_w[n_out, d] . LN(x[m, :]; gamma, beta, eps) + head_b,  [B*N, n_out] fp32.
+ * F.layer_norm arithmetic as vlg_layernorm_fwd (biased variance, eps inside the sqrt); fp32 throughout, fp32 MASTER weights
+ * in every precision mode.  d % 64 == 0, d <= 1024, 1 <= n_out <= 32, else VLG_ERR_SHAPE; 16-byte-aligned pointers, else
+ * VLG_ERR_ALIGN. */
+int vlg_head_last_frame(const float* x, const float* gamma, const float* beta, const float* head_w, const float* head_b,
+                        float* out_last, int B, int T, int N, int d, int n_out, float eps, void* stream);
+/* One decoding step: choose the next frame from out_last ([B*N, n_classes + 4]: logits | raw box), write it to
+ * gen_cls[b, step, n] / gen_box[b, step, n, :] ((B, steps, N) int64 / (B, steps, N, 4) fp32; other step indices are not
+ * touched) and write the NEXT window: cls_out[:, t] = cls_in[:, t + 1] for t < T - 1, cls_out[:, T - 1] = the new frame
+ * (boxes likewise); valid_out (may be NULL) = 1.0f where cls_out < n_classes else 0.0f.  (B, T, N) public order.
+ * cls_in / box_in are only read; in and out must not alias (VLG_ERR_SHAPE).
+ *   box    sigmoid(raw)
+ *   class  temperature == 0: the first maximum of the logits (torch.argmax).  temperature > 0: kept set = every class
+ *          (top_k == 0) or the top_k largest RAW logits (equal values: lower index first); z = logit / temperature,
+ *          p = expf(z - max kept z) on the kept set, 0 elsewhere; cum = running sum of p in class order, S its last value
+ *          (fp32); the class is the first kept c with cum_c >= u * S (the last kept one if rounding leaves none)
+ *   u      (x0 >> 8) * 2^-24 + 2^-25, x0 = first word of Philox4x32-10 on counter (b*N + n, step, 0, 0) under key
+ *          (seed & 0xffffffff, seed >> 32): a draw depends on token, step and seed alone, never on the launch geometry
+ *   keep_padded != 0: a slot whose class in frame T-1 of cls_in is >= n_classes keeps that class id and its box
+ * VLG_ERR_SHAPE before anything is enqueued: temperature < 0 or not finite, top_k < 0 or > n_classes, n_classes < 1 or
+ * n_classes + 4 > 32, step outside [0, steps), B, T or N < 1.  Box pointers and out_last 16-byte, class pointers 8-byte
+ * aligned, else VLG_ERR_ALIGN. */
+int vlg_layout_decode(const float* out_last, const int64_t* cls_in, const float* box_in,
+                      int64_t* cls_out, float* box_out, float* valid_out, int64_t* gen_cls, float* gen_box,
+                      int B, int T, int N, int n_classes, int steps, int step,
+                      float temperature, int top_k, uint64_t seed, int keep_padded, void* stream);
+
 /* ------------------------------------------------------------------ reductions */
 int vlg_reduce_slabs(const float* slabs, int64_t slab_stride, int n_slabs,
                      float* dst, int64_t len, void* stream);

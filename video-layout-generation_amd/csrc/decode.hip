@@ -1,0 +1,239 @@
+// Generation tail of the layout-token model: the head on the last frame's rows, and one sampled decoding step.
+//
+// vlg_head_last_frame  final layer-norm + head of the B*N rows m = r*T + (T-1) only (a rollout uses no other row): one
+//     64-lane wavefront per row, the row in registers (d/64 floats per lane, float4 loads when d % 256 == 0), mean and
+//     variance by wavefront shuffles exactly as csrc/layernorm.hip, then n_out dot products against the fp32 head weights
+//     (each lane reads the columns it holds; a 24 x d weight matrix stays in the vector L1), lane o keeps output o and
+//     lanes < n_out store the row of outputs coalesced.  Algorithmic bytes: 4*d per row in, 4*n_out out, 4*n_out*d weights.
+// vlg_layout_decode    one block of 64 threads per 64 tokens: the block stages its tokens' rows of out_last in LDS
+//     (coalesced; row stride 33 floats = conflict-free per-thread rows), thread i then decodes token i (argmax or the
+//     temperature / top-k draw, Philox4x32-10 counter = token and step), writes the generated frame and the last frame of
+//     the next window; the T-1 earlier frames of the window are copied by all threads of the grid.  Every store is a plain
+//     vector store; no atomics, no state.
+#include "common.h"
+
+#define HL_BLOCK 256
+#define HL_WAVES (HL_BLOCK / 64)
+#define HL_MAX_OUT 32
+#define DEC_BLOCK 64
+#define DEC_LD (HL_MAX_OUT + 1)
+
+// E = floats per lane; V4: float4 at columns 4*lane + 256*i, else scalars at lane + 64*i (the layouts of layernorm.hip)
+template <int E, bool V4>
+__device__ __forceinline__ void hl_load(const float* __restrict__ row, int lane, float (&v)[E]) {
+    if constexpr (V4) {
+#pragma unroll
+        for (int i = 0; i < E / 4; ++i) {
+            const float4 t = ld4(row + 4 * lane + 256 * i);
+            v[4 * i] = t.x; v[4 * i + 1] = t.y; v[4 * i + 2] = t.z; v[4 * i + 3] = t.w;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < E; ++i) v[i] = row[lane + 64 * i];
+    }
+}
+
+// rows a wave holds per trip (short rows: more bytes in flight, and one pass over the weights serves them all)
+#define HL_ROWS(E) ((E) <= 4 ? 2 : 1)
+
+template <int E, bool V4>
+__global__ __launch_bounds__(HL_BLOCK) void head_last_kernel(
+    const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
+    const float* __restrict__ head_w, const float* __restrict__ head_b, float* __restrict__ out,
+    int64_t rows, int T, int n_out, float eps) {
+    constexpr int d = E * 64, R = HL_ROWS(E);
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * HL_WAVES + (threadIdx.x >> 6);
+    const int64_t nwaves = (int64_t)gridDim.x * HL_WAVES;
+    float g[E], b[E];
+    hl_load<E, V4>(gamma, lane, g);
+    hl_load<E, V4>(beta, lane, b);
+    const float bias = lane < n_out ? head_b[lane] : 0.f;
+    for (int64_t r0 = wave * R; r0 < rows; r0 += nwaves * R) {
+        float v[R][E], res[R];
+#pragma unroll
+        for (int i = 0; i < R; ++i) {                          // a short last group re-reads the last row, stores are guarded
+            const int64_t r = r0 + i < rows ? r0 + i : rows - 1;
+            hl_load<E, V4>(x + (r * T + (T - 1)) * d, lane, v[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            float s = 0.f;
+#pragma unroll
+            for (int j = 0; j < E; ++j) s += v[i][j];
+            const float mu = wave_sum(s) * (1.0f / d);
+            float q = 0.f;
+#pragma unroll
+            for (int j = 0; j < E; ++j) { const float t = v[i][j] - mu; q += t * t; }
+            const float rs = 1.0f / sqrtf(wave_sum(q) * (1.0f / d) + eps);
+#pragma unroll
+            for (int j = 0; j < E; ++j) v[i][j] = (v[i][j] - mu) * rs * g[j] + b[j];
+            res[i] = 0.f;
+        }
+        for (int o = 0; o < n_out; ++o) {
+            float w[E];
+            hl_load<E, V4>(head_w + (int64_t)o * d, lane, w);
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                float a = 0.f;
+#pragma unroll
+                for (int j = 0; j < E; ++j) a = fmaf(v[i][j], w[j], a);
+                a = wave_sum(a);
+                if (lane == o) res[i] = a;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+            if (r0 + i < rows && lane < n_out) out[(r0 + i) * n_out + lane] = res[i] + bias;
+    }
+}
+
+#define HL_CASE(E) case E: hipLaunchKernelGGL((head_last_kernel<E, (E) % 4 == 0>), grid, block, 0, s, x, gamma, beta, head_w, head_b, \
+                                              out_last, rows, T, n_out, eps); break;
+
+extern "C" int vlg_head_last_frame(const float* x, const float* gamma, const float* beta, const float* head_w,
+                                   const float* head_b, float* out_last, int B, int T, int N, int d, int n_out,
+                                   float eps, void* stream) {
+    if (B < 1 || T < 1 || N < 1 || d < 64 || d % 64 != 0 || d > 1024 || n_out < 1 || n_out > HL_MAX_OUT) return VLG_ERR_SHAPE;
+    if (!vlg_aligned16(x) || !vlg_aligned16(gamma) || !vlg_aligned16(beta) || !vlg_aligned16(head_w) ||
+        !vlg_aligned16(head_b) || !vlg_aligned16(out_last)) return VLG_ERR_ALIGN;
+    const int64_t rows = (int64_t)B * N;
+    const int E = d / 64, per_block = HL_WAVES * (E <= 4 ? 2 : 1);
+    const int64_t nb = (rows + per_block - 1) / per_block;
+    const dim3 grid((unsigned)(nb > 4096 ? 4096 : nb)), block(HL_BLOCK);
+    hipStream_t s = (hipStream_t)stream;
+    switch (E) {
+        HL_CASE(1) HL_CASE(2) HL_CASE(3) HL_CASE(4) HL_CASE(5) HL_CASE(6) HL_CASE(7) HL_CASE(8)
+        HL_CASE(9) HL_CASE(10) HL_CASE(11) HL_CASE(12) HL_CASE(13) HL_CASE(14) HL_CASE(15) HL_CASE(16)
+        default: return VLG_ERR_SHAPE;
+    }
+    return vlg_last_error();
+}
+
+// ---------------------------------------------------------------------------------------------------------- decoding
+// Philox4x32-10 (Salmon et al., Random123): first output word of counter (c0, c1, 0, 0) under key (k0, k1)
+__device__ __forceinline__ uint32_t philox_first(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1) {
+    uint32_t c2 = 0u, c3 = 0u;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return c0;
+}
+
+__global__ __launch_bounds__(DEC_BLOCK) void layout_decode_kernel(
+    const float* __restrict__ out_last, const int64_t* __restrict__ cls_in, const float* __restrict__ box_in,
+    int64_t* __restrict__ cls_out, float* __restrict__ box_out, float* __restrict__ valid_out,
+    int64_t* __restrict__ gen_cls, float* __restrict__ gen_box, int B, int T, int N, int C, int steps, int step,
+    float temperature, int top_k, uint32_t k0, uint32_t k1, int keep_padded) {
+    __shared__ float rows[DEC_BLOCK][DEC_LD];
+    const int n_out = C + 4, tid = threadIdx.x;
+    const int64_t BN = (int64_t)B * N, r_first = (int64_t)blockIdx.x * DEC_BLOCK;
+    const int here = (int)(BN - r_first < DEC_BLOCK ? BN - r_first : DEC_BLOCK);      // tokens of this block
+    for (int e = tid; e < here * n_out; e += DEC_BLOCK) rows[e / n_out][e % n_out] = out_last[r_first * n_out + e];
+    __syncthreads();
+    if (tid < here) {
+        float* l = rows[tid];                                  // this token's [logits | raw box]; the logits become cum below
+        const int64_t r = r_first + tid;
+        const int b = (int)(r / N), n = (int)(r % N);
+        const int64_t last = ((int64_t)b * T + (T - 1)) * N + n;
+        int64_t cls;
+        float4 box;
+        const int64_t prev = cls_in[last];
+        if (keep_padded && prev >= C) {                        // a padded slot stays padded, box and all
+            cls = prev;
+            box = ld4(box_in + 4 * last);
+        } else {
+            box = make_float4(1.0f / (1.0f + expf(-l[C])), 1.0f / (1.0f + expf(-l[C + 1])),
+                              1.0f / (1.0f + expf(-l[C + 2])), 1.0f / (1.0f + expf(-l[C + 3])));
+            int pick = 0;
+            if (temperature == 0.f) {
+                float best = l[0];
+                for (int c = 1; c < C; ++c)
+                    if (l[c] > best) { best = l[c]; pick = c; }    // first maximum
+            } else {
+                uint32_t kept = C >= 32 ? 0xffffffffu : (1u << C) - 1u;
+                if (top_k > 0 && top_k < C) {                  // the top_k largest RAW logits, equal values: lower index first
+                    kept = 0u;
+                    for (int c = 0; c < C; ++c) {
+                        const float lc = l[c];
+                        int rank = 0;
+                        for (int j = 0; j < C; ++j) rank += (l[j] > lc || (l[j] == lc && j < c)) ? 1 : 0;
+                        if (rank < top_k) kept |= 1u << c;
+                    }
+                }
+                float m = -INFINITY;
+                for (int c = 0; c < C; ++c)
+                    if ((kept >> c) & 1u) m = fmaxf(m, l[c] / temperature);
+                float cum = 0.f;
+                for (int c = 0; c < C; ++c) {
+                    if ((kept >> c) & 1u) cum += expf(l[c] / temperature - m);
+                    l[c] = cum;
+                }
+                const uint32_t x0 = philox_first((uint32_t)r, (uint32_t)step, k0, k1);
+                const float u = (float)(x0 >> 8) * 5.9604644775390625e-08f + 2.98023223876953125e-08f;    // 2^-24, 2^-25
+                const float thr = u * cum;                     // cum = S
+                pick = -1;
+                int last_kept = 0;
+                for (int c = 0; c < C; ++c)
+                    if ((kept >> c) & 1u) {
+                        last_kept = c;
+                        if (pick < 0 && l[c] >= thr) pick = c;
+                    }
+                if (pick < 0) pick = last_kept;
+            }
+            cls = pick;
+        }
+        const int64_t g = ((int64_t)b * steps + step) * N + n;
+        gen_cls[g] = cls;
+        st4(gen_box + 4 * g, box);
+        cls_out[last] = cls;
+        st4(box_out + 4 * last, box);
+        if (valid_out != nullptr) valid_out[last] = cls < C ? 1.0f : 0.0f;
+    }
+    // frames 0 .. T-2 of the next window = frames 1 .. T-1 of this one
+    const int64_t TN = (int64_t)T * N, keep = TN - N, total = (int64_t)B * TN;
+    for (int64_t i = (int64_t)blockIdx.x * DEC_BLOCK + tid; i < total; i += (int64_t)gridDim.x * DEC_BLOCK) {
+        if (i % TN >= keep) continue;
+        const int64_t c = cls_in[i + N];
+        cls_out[i] = c;
+        st4(box_out + 4 * i, ld4(box_in + 4 * (i + N)));
+        if (valid_out != nullptr) valid_out[i] = c < C ? 1.0f : 0.0f;
+    }
+}
+
+static inline bool dec_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return a != nullptr && b != nullptr && pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
+}
+
+extern "C" int vlg_layout_decode(const float* out_last, const int64_t* cls_in, const float* box_in, int64_t* cls_out,
+                                 float* box_out, float* valid_out, int64_t* gen_cls, float* gen_box, int B, int T, int N,
+                                 int n_classes, int steps, int step, float temperature, int top_k, uint64_t seed,
+                                 int keep_padded, void* stream) {
+    if (B < 1 || T < 1 || N < 1 || n_classes < 1 || n_classes + 4 > HL_MAX_OUT) return VLG_ERR_SHAPE;
+    if (!(temperature >= 0.f) || !(temperature <= 3.0e38f)) return VLG_ERR_SHAPE;      // negative, inf or NaN
+    if (top_k < 0 || top_k > n_classes || steps < 1 || step < 0 || step >= steps) return VLG_ERR_SHAPE;
+    const int64_t BN = (int64_t)B * N, M = BN * T;
+    if (BN > 0x7fffffffLL) return VLG_ERR_SHAPE;                                        // the Philox counter word is the token index
+    if (!out_last || !cls_in || !box_in || !cls_out || !box_out || !gen_cls || !gen_box) return VLG_ERR_SHAPE;
+    // inputs are only read and outputs only written: any overlap between the two groups is refused
+    const void* in_p[3] = {out_last, cls_in, box_in};
+    const int64_t in_n[3] = {BN * (n_classes + 4) * 4, M * 8, M * 16};
+    const void* out_p[5] = {cls_out, box_out, valid_out, gen_cls, gen_box};
+    const int64_t out_n[5] = {M * 8, M * 16, M * 4, BN * steps * 8, BN * steps * 16};
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 5; ++j)
+            if (dec_overlap(in_p[i], in_n[i], out_p[j], out_n[j])) return VLG_ERR_SHAPE;
+    if (!vlg_aligned16(out_last) || !vlg_aligned16(box_in) || !vlg_aligned16(box_out) || !vlg_aligned16(gen_box) ||
+        !vlg_aligned8(cls_in) || !vlg_aligned8(cls_out) || !vlg_aligned8(gen_cls) ||
+        (reinterpret_cast<uintptr_t>(valid_out) & 3u)) return VLG_ERR_ALIGN;
+    const dim3 grid((unsigned)((BN + DEC_BLOCK - 1) / DEC_BLOCK)), block(DEC_BLOCK);
+    hipLaunchKernelGGL(layout_decode_kernel, grid, block, 0, (hipStream_t)stream, out_last, cls_in, box_in, cls_out, box_out,
+                       valid_out, gen_cls, gen_box, B, T, N, n_classes, steps, step, temperature, top_k,
+                       (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), keep_padded);
+    return vlg_last_error();
+}

@@ -29,6 +29,12 @@ VLG_LR_DECAY = 1 honours --lr_decay_step / --lr_decay_gamma (epochs; the referen
 they stay ignored unless asked for).  Any of them switches the engine to its guarded step; the train log line then also
 shows the gradient norm and the number of skipped steps.
 
+Generation knobs of generate_sequence in layout mode (a keyword argument wins over them; csrc/decode.hip, DESIGN.md
+"Generation"): args.gen_temperature / VLG_GEN_TEMPERATURE (0 = argmax; > 0 samples from softmax(logits / temperature)),
+args.gen_top_k / VLG_GEN_TOP_K (0 = every class, else only the k largest logits), args.gen_seed / VLG_GEN_SEED (default
+args.seed; the same seed, prompt and weights give the same sequence), args.gen_keep_padded / VLG_GEN_KEEP_PADDED = 1 keeps a
+slot that is padded (reserved class id) in the window's last frame padded in every generated frame.
+
 Repairs of reference defects, all stated: gradients are overwritten each
 step (A-5 zero_grad), the train log line uses the `loss` key (A-6), one checkpoint schema
 {'epoch','arch','gridnet','optimizer'} for save/--ckpt/--resume (A-1,A-8,A-9), `.model` exists
@@ -111,6 +117,15 @@ def optim_knobs(args) -> Dict[str, object]:
     return {"clip_grad": max(_knob_float(args, "clip_grad", "VLG_CLIP_GRAD", 0.0), 0.0),
             "skip_nonfinite": bool(_knob(args, "skip_nonfinite", "VLG_SKIP_NONFINITE", 0)),
             "lr_decay": os.environ.get("VLG_LR_DECAY", "0") == "1"}
+
+
+def generation_knobs(args) -> Dict[str, object]:
+    """{temperature, top_k, seed, keep_padded} of generate_sequence in layout mode, from args / environment (module
+    docstring): argmax, every class, the run's seed, padded slots decoded like any other - unless asked otherwise."""
+    return {"temperature": _knob_float(args, "gen_temperature", "VLG_GEN_TEMPERATURE", 0.0),
+            "top_k": _knob(args, "gen_top_k", "VLG_GEN_TOP_K", 0),
+            "seed": _knob(args, "gen_seed", "VLG_GEN_SEED", int(getattr(args, "seed", SEED))),
+            "keep_padded": bool(_knob(args, "gen_keep_padded", "VLG_GEN_KEEP_PADDED", 0))}
 
 
 def epoch_lr(args, epoch: int) -> float:
@@ -509,7 +524,8 @@ class Trainer:
         self.args.logger.info("Checkpoint loaded")
 
     # ----------------------------------------------------------------------- rollout
-    def generate_sequence(self, *inputs, steps: int = 8):
+    def generate_sequence(self, *inputs, steps: int = 8, temperature: Optional[float] = None, top_k: Optional[int] = None,
+                          seed: Optional[int] = None, keep_padded: Optional[bool] = None):
         """Autoregressive rollout, `steps` predictions (8 in reference src/trainer.py:460).
 
         VLG_MODEL=gridnet - the reference's own method: generate_sequence(img1, img2, seg1, seg2) with two
@@ -519,7 +535,13 @@ class Trainer:
         arrays (b, 3*(steps+2), H, W), (b, steps+2, H, W).
 
         Layout mode: generate_sequence(slot_class (B,T,N), slot_box (B,T,N,4)): predict the frame after the clip,
-        append it, slide the T-frame window; returns classes (B,steps,N) and boxes (B,steps,N,4) on the CPU."""
+        append it, slide the T-frame window; returns classes (B,steps,N) and boxes (B,steps,N,4) on the CPU.
+        temperature / top_k / seed / keep_padded: None takes the generation knob from args or the environment
+        (generation_knobs; module docstring).  temperature 0 is the argmax; > 0 samples from softmax(logits / temperature)
+        over the top_k largest logits (0 = all), reproducibly per (seed, token, step); keep_padded keeps a slot that is
+        padded (reserved class id) in the window's last frame padded, with its box.  An engine with rollout()
+        (vlg.engine.LayoutEngine) generates on the device, without a host wait per frame, and the result is copied to the
+        CPU once; any other engine runs the host loop, which can only take the argmax."""
         if self.image_mode:
             if len(inputs) != 4:
                 raise TypeError("generate_sequence(img1, img2, seg1, seg2) in VLG_MODEL=gridnet mode")
@@ -534,6 +556,18 @@ class Trainer:
         if len(inputs) != 2:
             raise TypeError("generate_sequence(slot_class, slot_box) in layout mode")
         slot_class, slot_box = inputs
+        knobs = generation_knobs(self.args)
+        for name, given in (("temperature", temperature), ("top_k", top_k), ("seed", seed), ("keep_padded", keep_padded)):
+            if given is not None:
+                knobs[name] = type(knobs[name])(given)
+        if hasattr(self.engine, "rollout"):
+            gen_c, gen_b = self.engine.rollout(slot_class.to(self.device).contiguous(), slot_box.to(self.device).contiguous(),
+                                               steps=steps, **knobs)
+            return gen_c.cpu(), gen_b.cpu()
+        if knobs["temperature"] != 0.0 or knobs["keep_padded"]:
+            raise ValueError("temperature > 0 and keep_padded need an engine with rollout() (vlg.engine.LayoutEngine: the "
+                             "vlg_layout_decode kernel); %s has none, its host loop takes the argmax of every slot"
+                             % type(self.engine).__name__)
         cls = slot_class.clone().to(self.device)
         box = slot_box.clone().to(self.device)
         B, T, N = cls.shape

@@ -352,10 +352,26 @@ class LayoutEngine(AdamSurface):
         """Forward + fused loss (the loss kernel also leaves d(total)/d(out) in self.dout).
         Returns the device tensor {total, smooth_l1, iou, ce}.  padded_slots overrides the engine's setting for this
         forward and the backward that follows it: a rollout window can hold padded slots where training batches never do."""
-        cfg, d, ff = self.cfg, self.cfg.d, self.cfg.d_ff
+        cfg, d = self.cfg, self.cfg.d
         B, T, N, M = self._check_batch(batch)
         self._masked = self.padded_slots if padded_slots is None else bool(padded_slots)
         self._shape = (B, T, N, M)
+        s = self._stream()
+        self._encode(batch, B, T, N, M)
+        L = cfg.n_layers
+        self._ln_fwd(self.x[L], "lnf_g", self.xf, self.stats[2 * L], M)
+        self._linear(self.xf, self.pw("head_w"), self.p("head_b"), self.out, M, cfg.n_out, d, EPI_BIAS)
+        self._timed("loss", 0.0, "vlg_layout_loss", ptr(self.out), cfg.n_out, ptr(batch["tgt_class"]), ptr(batch["tgt_box"]),
+                    ptr(batch["valid"]), ptr(self.dout), ptr(self.loss_out), ptr(self.loss_scratch), B, T, N,
+                    cfg.n_classes, SMOOTH_L1_BETA, IOU_EPS, LOSS_W_REG, LOSS_W_STRUCT, LOSS_W_CE, s,
+                    nbytes=(2.0 * 4 * cfg.n_out + 8 + 16 + 4) * M)
+        return self.loss_out
+
+    def _encode(self, batch: Dict[str, torch.Tensor], B: int, T: int, N: int, M: int) -> None:
+        """The launches from the embedding through the last layer's second FFN projection: leaves the residual stream in
+        self.x[n_layers].  Shared by forward() and rollout(); reads slot_class, slot_box and - per-clip attention with
+        self._masked - valid of `batch`."""
+        cfg, d, ff = self.cfg, self.cfg.d, self.cfg.d_ff
         s = self._stream()
         self._timed("embed_fwd", 0.0, "vlg_embed_fwd", ptr(batch["slot_class"]), ptr(batch["slot_box"]), ptr(self.p("cls_emb")),
                     ptr(self.p("box_w")), ptr(self.p("box_b")), ptr(self.p("time_emb")), ptr(self.x[0]),
@@ -373,14 +389,6 @@ class LayoutEngine(AdamSurface):
                          self._epi_ff1, aux_out=self.u[l])
             self._linear(self.gl[l], self.pw(pre + "ff2_w"), self.p(pre + "ff2_b"), self.x[l + 1], M, d, ff,
                          EPI_BIAS | EPI_RESID, aux_in=self.xmid[l])
-        L = cfg.n_layers
-        self._ln_fwd(self.x[L], "lnf_g", self.xf, self.stats[2 * L], M)
-        self._linear(self.xf, self.pw("head_w"), self.p("head_b"), self.out, M, cfg.n_out, d, EPI_BIAS)
-        self._timed("loss", 0.0, "vlg_layout_loss", ptr(self.out), cfg.n_out, ptr(batch["tgt_class"]), ptr(batch["tgt_box"]),
-                    ptr(batch["valid"]), ptr(self.dout), ptr(self.loss_out), ptr(self.loss_scratch), B, T, N,
-                    cfg.n_classes, SMOOTH_L1_BETA, IOU_EPS, LOSS_W_REG, LOSS_W_STRUCT, LOSS_W_CE, s,
-                    nbytes=(2.0 * 4 * cfg.n_out + 8 + 16 + 4) * M)
-        return self.loss_out
 
     # -------------------------------------------------------------------- backward
     def backward(self, batch: Dict[str, torch.Tensor], reducer=None) -> None:
@@ -572,6 +580,66 @@ class LayoutEngine(AdamSurface):
             return self.loss_out
         run.graph, run.static_batch = graph, static
         return run
+
+    # ------------------------------------------------------------------ generation
+    def _windows(self) -> tuple:
+        """The two (class, box, valid) window buffers a rollout ping-pongs between, sized for the workspace capacity"""
+        if getattr(self, "_win", None) is None:
+            M = self.capacity
+            self._win = tuple((torch.empty(M, dtype=torch.int64, device=self.device),
+                               torch.empty(M, BOX_DIM, dtype=torch.float32, device=self.device),
+                               torch.empty(M, dtype=torch.float32, device=self.device)) for _ in range(2))
+        return self._win
+
+    def rollout(self, slot_class: torch.Tensor, slot_box: torch.Tensor, steps: int = 8, temperature: float = 0.0,
+                top_k: int = 0, seed: int = 0, keep_padded: bool = False, return_logits: bool = False) -> tuple:
+        """Autoregressive generation on the device: `steps` times predict the frame after the T-frame window, append it and
+        slide the window.  slot_class (B,T,N) int64 and slot_box (B,T,N,4) fp32 are device tensors and are not modified.
+        Per step: the encoder launches of forward(), vlg_head_last_frame on the B*N rows of the last frame (fp32 master
+        weights in every precision mode) and vlg_layout_decode, which draws the frame (temperature 0 = argmax; else
+        temperature / top-k sampling, Philox counter = token and step under `seed`; keep_padded carries a reserved class id
+        and its box forward), records it and writes the next window into the other of two engine-owned buffers.  No loss, no
+        targets, no host wait inside the loop.  Returns DEVICE tensors gen_cls (B,steps,N) int64, gen_box (B,steps,N,4) fp32
+        and, with return_logits, the (steps, B*N, n_out) buffer of each step's [logits | raw box]."""
+        cfg, d = self.cfg, self.cfg.d
+        if slot_class.dim() != 3 or tuple(slot_box.shape) != tuple(slot_class.shape) + (BOX_DIM,):
+            raise ValueError("rollout takes slot_class (B,T,N) and slot_box (B,T,N,4)")
+        B, T, N = slot_class.shape
+        M, BN = B * T * N, B * N
+        if T != cfg.T:
+            raise ValueError("window has T=%d, engine was built for T=%d" % (T, cfg.T))
+        if M > self.capacity:
+            raise ValueError("window of %d tokens exceeds workspace capacity %d" % (M, self.capacity))
+        for t, dt, what in ((slot_class, torch.int64, "slot_class"), (slot_box, torch.float32, "slot_box")):
+            if t.dtype != dt or not t.is_cuda:
+                raise ValueError("%s must be a %s HIP tensor" % (what, dt))
+        steps, top_k = int(steps), int(top_k)
+        if steps < 1:
+            raise ValueError("steps must be >= 1")
+        if not (math.isfinite(temperature) and temperature >= 0.0) or not 0 <= top_k <= cfg.n_classes:
+            raise ValueError("temperature must be finite and >= 0, top_k in [0, %d]" % cfg.n_classes)
+        win = [(c[:M].view(B, T, N), b[:M].view(B, T, N, BOX_DIM), v[:M].view(B, T, N)) for c, b, v in self._windows()]
+        win[0][0].copy_(slot_class)
+        win[0][1].copy_(slot_box)
+        torch.lt(slot_class, cfg.n_classes, out=win[0][2])          # the first window's validity comes from the prompt
+        # per-clip attention: masks are decided ONCE, here (the only host wait of the call).  Later windows are masked by the
+        # decode kernel's valid_out; they never gain a padded slot the prompt did not have
+        self._masked = cfg.attention == "clip" and (self.padded_slots or bool((win[0][2] == 0).any()))
+        gen_cls = torch.empty(B, steps, N, dtype=torch.int64, device=self.device)
+        gen_box = torch.empty(B, steps, N, BOX_DIM, dtype=torch.float32, device=self.device)
+        logits = torch.empty(steps, BN, cfg.n_out, dtype=torch.float32, device=self.device)
+        L, s = cfg.n_layers, self._stream()
+        for i in range(steps):
+            (cls, box, valid), (ncls, nbox, nvalid) = win[i & 1], win[(i + 1) & 1]
+            self._encode({"slot_class": cls, "slot_box": box, "valid": valid}, B, T, N, M)
+            self._timed("head_last", 2.0 * BN * cfg.n_out * d, "vlg_head_last_frame", ptr(self.x[L]), ptr(self.p("lnf_g")),
+                        ptr(self.p("lnf_b")), ptr(self.p("head_w")), ptr(self.p("head_b")), ptr(logits[i]), B, T, N, d,
+                        cfg.n_out, LN_EPS, s, nbytes=4.0 * BN * (d + cfg.n_out) + 4.0 * cfg.n_out * d)
+            self._timed("decode", 0.0, "vlg_layout_decode", ptr(logits[i]), ptr(cls), ptr(box), ptr(ncls), ptr(nbox),
+                        ptr(nvalid), ptr(gen_cls), ptr(gen_box), B, T, N, cfg.n_classes, steps, i, float(temperature),
+                        top_k, int(seed) & 0xFFFFFFFFFFFFFFFF, int(bool(keep_padded)), s,
+                        nbytes=4.0 * BN * cfg.n_out + 2.0 * 28 * M)
+        return (gen_cls, gen_box, logits) if return_logits else (gen_cls, gen_box)
 
     # ---------------------------------------------------------------- public views
     def outputs_btn(self) -> tuple:

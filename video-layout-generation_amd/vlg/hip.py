@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
+from ctypes import c_char_p, c_float, c_int, c_int64, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VLG_HIP_LIB: development override (A/B runs of two builds in one gpurun call, tools/kernel_bench.py); still no fallback
@@ -51,6 +51,8 @@ SIGNATURES = {
     "vlg_attention_clip_bwd_bf16": (I, [P, P, P, P, P, P, P, L, I, I, I, P]),
     "vlg_layout_loss_scratch": (I, []),
     "vlg_layout_loss": (I, [P, I, P, P, P, P, P, P, I, I, I, I, F, F, F, F, F, P]),
+    "vlg_head_last_frame": (I, [P, P, P, P, P, P, I, I, I, I, I, F, P]),
+    "vlg_layout_decode": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, c_uint64, I, P]),
     "vlg_reduce_slabs": (I, [P, L, I, P, L, P]),
     "vlg_reduce_slabs_table": (I, [P, I, I, P]),
     "vlg_sum_partials_table": (I, [P, I, P]),
