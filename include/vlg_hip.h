@@ -218,14 +218,17 @@ int vlg_layout_loss(const float* out, int ld, const int64_t* tgt_class, const fl
  * BASELINE.json's temporal encoder next to the per-slot default (vlg_attention_fwd / _bwd).  fp32, head dim 64, T*N a multiple
  * of 32.  qkv [B*N*T, 3d] / out, dout [B*N*T, d] in the internal row order; valid (B,T,N) floats in the public order;
  * lse and delta: B * (d/64) * T*N floats each (log-sum-exp in the log2 domain, written by fwd; <dO, O>, scratch of bwd).
- * bwd = two launches (query owner: dQ; key owner: dK, dV): every gradient element has one owner, no atomics. */
+ * bwd = two launches (query owner: dQ; key owner: dK, dV): every gradient element has one owner, no atomics.
+ * Refusals, before anything is enqueued: VLG_ERR_SHAPE for a shape outside the above; VLG_ERR_ALIGN if qkv, out (fwd) or qkv,
+ * out, dout, dqkv (bwd) is NULL or not 16-byte aligned, or if lse (fwd, bwd) or delta (bwd) is NULL.  Only valid may be NULL. */
 int vlg_attention_clip_fwd(const float* qkv, const float* valid, float* out, float* lse,
                            int64_t B, int T, int N, int d, void* stream);
 int vlg_attention_clip_bwd(const float* qkv, const float* valid, const float* out, const float* dout, const float* lse,
                            float* delta, float* dqkv, int64_t B, int T, int N, int d, void* stream);
 /* bf16 storage (precision "bf16"): qkv, out, dout and dqkv bf16; valid, lse and delta fp32 in the layouts above.  Products
  * on bf16 MFMA with fp32 accumulation; scores, softmax statistics, lse and delta fp32; P and dS rounded to bf16 only as
- * MFMA operands; O, dQ, dK, dV rounded once on store.  Same shape contract and return codes as the fp32 entries. */
+ * MFMA operands; O, dQ, dK, dV rounded once on store.  Same shape contract, refusals (a NULL or misaligned tensor included)
+ * and return codes as the fp32 entries: one host front end serves both. */
 int vlg_attention_clip_fwd_bf16(const vlg_bf16* qkv, const float* valid, vlg_bf16* out, float* lse,
                                 int64_t B, int T, int N, int d, void* stream);
 int vlg_attention_clip_bwd_bf16(const vlg_bf16* qkv, const float* valid, const vlg_bf16* out, const vlg_bf16* dout,

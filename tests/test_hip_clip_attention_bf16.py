@@ -166,3 +166,19 @@ def test_clip_attention_bf16_refuses_what_fp32_refuses(H):
         assert f == g != 0, (f, g, (B, T, N, d))
     assert lib.vlg_attention_clip_fwd_bf16(q16.data_ptr(), 0, o16.data_ptr(), lse.data_ptr(), 1, 3, 5, 64, s) == 1001
     assert lib.vlg_attention_clip_fwd_bf16(q16.data_ptr() + 2, 0, o16.data_ptr(), lse.data_ptr(), 1, 4, 8, 64, s) == 1002
+    # every tensor but valid is required: a null one is refused by all four entries before anything is enqueued
+    B, T, N, d = 1, 4, 8, 64
+    for sfx, dt in (("", torch.float32), ("_bf16", torch.bfloat16)):
+        fwd, bwd = getattr(lib, "vlg_attention_clip_fwd" + sfx), getattr(lib, "vlg_attention_clip_bwd" + sfx)
+        qkv, dout = torch.randn(32, 192, device=dev).to(dt), torch.randn(32, 64, device=dev).to(dt)
+        out, dqkv = torch.full((32, 64), 3.0, device=dev, dtype=dt), torch.full((32, 192), 5.0, device=dev, dtype=dt)
+        lse, delta = torch.full((32,), 7.0, device=dev), torch.full((32,), 9.0, device=dev)
+        written = (out, dqkv, lse, delta)
+        before = [t.clone() for t in written]
+        for entry, tensors in ((fwd, (qkv, out, lse)), (bwd, (qkv, out, dout, lse, delta, dqkv))):
+            for i in range(len(tensors)):
+                p = [0 if j == i else t.data_ptr() for j, t in enumerate(tensors)]
+                assert entry(p[0], 0, *p[1:], B, T, N, d, s) == 1002, (sfx, len(tensors), i)
+        torch.cuda.synchronize()
+        for t, keep in zip(written, before):
+            assert torch.equal(t, keep), sfx
