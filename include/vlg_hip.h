@@ -268,6 +268,56 @@ int vlg_layout_decode(const float* out_last, const int64_t* cls_in, const float*
                       int B, int T, int N, int n_classes, int steps, int step,
                       float temperature, int top_k, uint64_t seed, int keep_padded, void* stream);
 
+/* ------------------------------------------------------------------ validation metrics (csrc/metrics.hip)
+ * Scores head outputs against targets and ADDS the result to a running record in device memory: `counts` (int64 slots,
+ * vlg_layout_metrics_counts(n_classes) of them) and `sums` (double slots, vlg_layout_metrics_sums(n_classes)).  One launch,
+ * no host wait, nothing written per token; the caller zeroes a record to start one and reads it whenever it likes.
+ * SELF-ORACLE (tests/metrics_ref.py); DESIGN.md, "Validation metrics".
+ *   out       [rows, ld] fp32: logits | raw box, INTERNAL row order m = (b*N + n)*T + t.  T = 1 makes it the [B*N, n_out]
+ *             buffer vlg_head_last_frame writes, so one kernel serves training-shaped outputs and rollout steps
+ *   targets   tgt_class (B,tgt_T,N) int64, tgt_box (B,tgt_T,N,4) fp32, valid (B,tgt_T,N) fp32 or NULL, public order;
+ *             frame t of `out` is scored against frame t0 + t: src = (b*tgt_T + t0 + t)*N + n (no slice is ever copied)
+ * Per token:
+ *   scored      (valid == NULL or valid[src] != 0) and 0 <= tgt_class[src] < n_classes.  Anything else: UNSCORED += 1 and
+ *               the token's outputs are not examined (a padded slot may hold NaN there)
+ *   non-finite  a scored token with inf or NaN among its n_classes + 4 outputs: NONFINITE += 1 and nothing else
+ *   otherwise   SCORED += 1, and with l = logits, tgt = tgt_class[src]:
+ *               pred = the first maximum of l (vlg_layout_decode at temperature 0);  TOP1 += (pred == tgt);
+ *               CONF[tgt*n_classes + pred] += 1;
+ *               rank = #{c: l[c] > l[tgt]} + #{c < tgt: l[c] == l[tgt]} (decode's tie order);  TOPK += (rank < top_k);
+ *               p = sigmoid(raw);  iou = IoU of the (cx,cy,w,h) boxes p and tgt_box in fp32, formula and iou_eps of
+ *               vlg_layout_loss;  IOU_HIT += (iou >= iou_thr);  BOTH_HIT += (pred == tgt and iou >= iou_thr);
+ *               sums, each value computed in fp32 and accumulated in double:
+ *               NLL += logf(sum_c expf(l[c] - max)) + max - l[tgt];  IOU += iou;  BOX_L1 += mean_k |p[k] - tgt_box[k]|;
+ *               IOU_BY_CLASS[tgt] += iou
+ * Per launch SCORED + NONFINITE + UNSCORED grows by exactly B*T*N.  Counts are integer atomics: exact in any schedule.
+ * Sums use no floating-point atomics: per-block partials in `scratch`, added in block order by the last block (an integer
+ * ticket in scratch, which that block resets), so the same call on the same record gives the same bits.
+ * scratch: >= vlg_layout_metrics_scratch() 8-byte slots, 16-byte aligned, ZERO-INITIALISED ONCE by the caller; launches
+ * that share it must be ordered on one stream.
+ * Refusals, all before anything is enqueued.  VLG_ERR_SHAPE: n_classes < 1 or n_classes + 4 > 32; top_k outside
+ * [1, n_classes]; iou_thr not finite; B, T or N < 1; t0 < 0 or t0 + T > tgt_T; ld < n_classes + 4 or ld % 4 != 0;
+ * B*T*N > 2^38.  VLG_ERR_ALIGN: out, tgt_box, scratch (16 bytes), sums, tgt_class, counts (8 bytes) NULL or misaligned;
+ * valid non-NULL and not 4-byte aligned. */
+#define VLG_MET_SCORED     0   /* counts: tokens that reached the statistics                          */
+#define VLG_MET_TOP1       1
+#define VLG_MET_TOPK       2
+#define VLG_MET_IOU_HIT    3
+#define VLG_MET_BOTH_HIT   4
+#define VLG_MET_NONFINITE  5
+#define VLG_MET_UNSCORED   6
+#define VLG_MET_CONF       8   /* counts[VLG_MET_CONF + tgt*n_classes + pred]                          */
+#define VLG_MET_NLL        0   /* sums                                                                 */
+#define VLG_MET_IOU        1
+#define VLG_MET_BOX_L1     2
+#define VLG_MET_IOU_BY_CLASS 4 /* sums[VLG_MET_IOU_BY_CLASS + tgt]                                     */
+int vlg_layout_metrics_counts(int n_classes);   /* int64 slots of a record: VLG_MET_CONF + n_classes^2 */
+int vlg_layout_metrics_sums(int n_classes);     /* double slots: VLG_MET_IOU_BY_CLASS + n_classes */
+int vlg_layout_metrics_scratch(void);           /* 8-byte slots of scratch */
+int vlg_layout_metrics(const float* out, int ld, const int64_t* tgt_class, const float* tgt_box, const float* valid,
+                       int tgt_T, int t0, int64_t* counts, double* sums, void* scratch,
+                       int B, int T, int N, int n_classes, int top_k, float iou_thr, float iou_eps, void* stream);
+
 /* ------------------------------------------------------------------ reductions */
 int vlg_reduce_slabs(const float* slabs, int64_t slab_stride, int n_slabs,
                      float* dst, int64_t len, void* stream);

@@ -35,6 +35,13 @@ args.gen_top_k / VLG_GEN_TOP_K (0 = every class, else only the k largest logits)
 args.seed; the same seed, prompt and weights give the same sequence), args.gen_keep_padded / VLG_GEN_KEEP_PADDED = 1 keeps a
 slot that is padded (reserved class id) in the window's last frame padded in every generated frame.
 
+Validation metrics in layout mode (csrc/metrics.hip, vlg/metrics.py, DESIGN.md "Validation metrics"): args.val_metrics /
+VLG_VAL_METRICS = 1 makes validate() also score every batch on the device - class accuracy, top-k accuracy, NLL, mean IoU,
+the share of boxes with IoU above a threshold, per-class figures and the confusion matrix - one extra launch per batch and
+one host read per pass; the returned dict gains those keys.  args.val_topk / VLG_VAL_TOPK (5) is the k of the top-k
+accuracy, args.val_iou_thr / VLG_VAL_IOU_THR (0.5) the IoU threshold; evaluate_rollout uses the same two.  Off (the default)
+validate() returns {"loss": ...} as before.
+
 Repairs of reference defects, all stated: gradients are overwritten each
 step (A-5 zero_grad), the train log line uses the `loss` key (A-6), one checkpoint schema
 {'epoch','arch','gridnet','optimizer'} for save/--ckpt/--resume (A-1,A-8,A-9), `.model` exists
@@ -107,6 +114,10 @@ def _knob(args, name: str, env: str, default: int) -> int:
     return int(v) if v is not None else int(os.environ.get(env, default))
 
 
+def _fmt(v) -> str:
+    return "n/a" if v is None else "%.4f" % v
+
+
 def _knob_float(args, name: str, env: str, default: float) -> float:
     v = getattr(args, name, None)
     return float(v) if v is not None else float(os.environ.get(env, default))
@@ -126,6 +137,14 @@ def generation_knobs(args) -> Dict[str, object]:
             "top_k": _knob(args, "gen_top_k", "VLG_GEN_TOP_K", 0),
             "seed": _knob(args, "gen_seed", "VLG_GEN_SEED", int(getattr(args, "seed", SEED))),
             "keep_padded": bool(_knob(args, "gen_keep_padded", "VLG_GEN_KEEP_PADDED", 0))}
+
+
+def metrics_knobs(args) -> Dict[str, object]:
+    """{on, top_k, iou_thr} of the validation metrics in layout mode, from args / environment (module docstring): off,
+    top-5 accuracy and IoU >= 0.5 unless asked otherwise."""
+    return {"on": bool(_knob(args, "val_metrics", "VLG_VAL_METRICS", 0)),
+            "top_k": _knob(args, "val_topk", "VLG_VAL_TOPK", 5),
+            "iou_thr": _knob_float(args, "val_iou_thr", "VLG_VAL_IOU_THR", 0.5)}
 
 
 def epoch_lr(args, epoch: int) -> float:
@@ -460,6 +479,13 @@ class Trainer:
         self.args.logger.info("Validation started")
         self.gridnet.eval()
         val_loss = AverageMeter()
+        mk = metrics_knobs(self.args)
+        record = None
+        if mk["on"] and not self.image_mode:
+            if not hasattr(self.engine, "accumulate_metrics"):
+                raise ValueError("VLG_VAL_METRICS=1 needs an engine with accumulate_metrics() (vlg.engine.LayoutEngine: the "
+                                 "vlg_layout_metrics kernel); %s has none" % type(self.engine).__name__)
+            record = self.engine.metrics_record()
         end = time()
         n_batches = len(self.val_loader)
         for i, batch in enumerate(self.val_loader):
@@ -471,6 +497,8 @@ class Trainer:
                 loss = self.engine.eval_loss(batch).clone()
             else:
                 loss = self.engine.forward(batch)[0:1].clone()      # forward only, reference src/trainer.py:320-333
+                if record is not None:                              # one launch, adds to the device record; no host wait
+                    self.engine.accumulate_metrics(batch, record, top_k=mk["top_k"], iou_thr=mk["iou_thr"])
             size = torch.tensor([float(batch[keys[0]].shape[0])], device=loss.device)
             loss.mul_(size)
             self.sync([loss, size], mean=False)                     # size-weighted SUM, trainer.py:336-338
@@ -488,7 +516,20 @@ class Trainer:
             self.args.logger.info("Epoch [{epoch:d}/{tot_epoch:d}] loss [{loss:.4f}] ".format(
                 epoch=self.epoch, tot_epoch=int(self.args.epochs), loss=val_loss.avg))
             self.writer.add_scalar("val/loss", val_loss.avg, self.epoch)                # trainer.py:377
-        return {"loss": val_loss.avg}                                                   # trainer.py:379
+        if record is None:
+            return {"loss": val_loss.avg}                                               # trainer.py:379
+        record.all_reduce(lambda tensors: self.sync(tensors, mean=False))               # counts and sums are additive
+        summary = record.summary()[0]                                                   # the pass's one read of the record
+        if int(self.args.rank) == 0:
+            self.args.logger.info(
+                "Epoch [%d/%d] scored [%d] accuracy [%s] top%d [%s] nll [%s] mean_iou [%s] iou>=%g [%s] nonfinite [%d]"
+                % (self.epoch, int(self.args.epochs), summary["scored"], _fmt(summary["accuracy"]), mk["top_k"],
+                   _fmt(summary["topk_accuracy"]), _fmt(summary["nll"]), _fmt(summary["mean_iou"]), mk["iou_thr"],
+                   _fmt(summary["iou_hit"]), summary["nonfinite"]))
+            for key in ("accuracy", "mean_iou", "nll", "iou_hit"):
+                if summary[key] is not None:
+                    self.writer.add_scalar("val/" + key, summary[key], self.epoch)
+        return dict(summary, loss=val_loss.avg)
 
     def sync(self, tensors, mean=True):
         """Synchronize all tensors given using mean or sum (reference src/trainer.py:381-386)."""
@@ -590,6 +631,31 @@ class Trainer:
             cls = torch.cat([cls[:, 1:], nc[:, None]], dim=1)
             box = torch.cat([box[:, 1:], nb[:, None]], dim=1)
         return torch.stack(out_c, dim=1), torch.stack(out_b, dim=1)
+
+    def evaluate_rollout(self, clip_class, clip_box, temperature: Optional[float] = None, top_k: Optional[int] = None,
+                         seed: Optional[int] = None, keep_padded: Optional[bool] = None, val_topk: Optional[int] = None,
+                         val_iou_thr: Optional[float] = None):
+        """Layout mode: how prediction quality decays with the horizon.  clip_class (B,T+S,N) / clip_box (B,T+S,N,4), CPU or
+        device tensors: the first T frames prompt a rollout of S steps, and step i is scored against frame T+i of the
+        clip on the device (vlg.engine.LayoutEngine.evaluate_rollout; one host read at the end).  temperature / top_k /
+        seed / keep_padded are the generation knobs of generate_sequence (None = from args or the environment);
+        val_topk / val_iou_thr the metric's (None = metrics_knobs).  A step is scored on the model's distribution at that
+        step (arg-max, rank and NLL of the logits, box = sigmoid(raw)), also when the history was sampled.
+        Returns a list of S summary dicts (vlg/metrics.py), one per horizon step."""
+        if self.image_mode or not hasattr(self.engine, "evaluate_rollout"):
+            raise ValueError("evaluate_rollout needs the layout engine with evaluate_rollout() (vlg.engine.LayoutEngine: the "
+                             "vlg_layout_metrics kernel); %s has none" % type(self.engine).__name__)
+        knobs = generation_knobs(self.args)
+        for name, given in (("temperature", temperature), ("top_k", top_k), ("seed", seed), ("keep_padded", keep_padded)):
+            if given is not None:
+                knobs[name] = type(knobs[name])(given)
+        mk = metrics_knobs(self.args)
+        record = self.engine.evaluate_rollout(
+            clip_class.to(self.device).contiguous(), clip_box.to(self.device).contiguous(),
+            top_k=mk["top_k"] if val_topk is None else int(val_topk),
+            iou_thr=mk["iou_thr"] if val_iou_thr is None else float(val_iou_thr),
+            temperature=knobs["temperature"], sample_top_k=knobs["top_k"], seed=knobs["seed"], keep_padded=knobs["keep_padded"])
+        return record.summary()
 
     def eval_generate_sequence(self, img1, img2, seg1, seg2):
         """main.py:64-67 entry (reference src/trainer.py:429-451): read two frames and two segmentation-id maps from

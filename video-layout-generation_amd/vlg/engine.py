@@ -22,6 +22,7 @@ from typing import Dict, Optional
 import torch
 
 from . import hip
+from .metrics import MetricsRecord
 from .optim import AdamSurface, FlatAdam
 from .slabs import SlabBuckets
 from .hip import (EPI_A_BF16, EPI_B_BF16, EPI_BIAS, EPI_DGELU, EPI_GELU, EPI_NONE, EPI_OUT_BF16, EPI_RESID,
@@ -192,6 +193,8 @@ class LayoutEngine(AdamSurface):
         self.du = torch.empty(M, ff, **act)
         self.dqkv = torch.empty(M, 3 * d, **act)
         self.loss_scratch = torch.zeros(lib.vlg_layout_loss_scratch(), **f32)
+        # validation metrics (vlg_layout_metrics): per-block partial sums and the ticket, zero between launches
+        self.metrics_scratch = torch.zeros(lib.vlg_layout_metrics_scratch(), dtype=torch.float64, device=self.device)
         if cfg.attention == "clip":       # per query and head: log-sum-exp of every layer (saved for backward), <dO, O> scratch
             self.lse = torch.empty(L, cfg.n_heads * M, **f32)
             self.delta = torch.empty(cfg.n_heads * M, **f32)
@@ -640,6 +643,68 @@ class LayoutEngine(AdamSurface):
                         top_k, int(seed) & 0xFFFFFFFFFFFFFFFF, int(bool(keep_padded)), s,
                         nbytes=4.0 * BN * cfg.n_out + 2.0 * 28 * M)
         return (gen_cls, gen_box, logits) if return_logits else (gen_cls, gen_box)
+
+    # --------------------------------------------------------------------- metrics
+    def metrics_record(self, rows: int = 1) -> MetricsRecord:
+        """A zeroed MetricsRecord (vlg/metrics.py) on the engine's device, `rows` independent rows."""
+        return MetricsRecord(self.cfg.n_classes, rows, self.device)
+
+    def _metrics(self, out, ld, tgt_class, tgt_box, valid, tgt_T, t0, record, row, B, T, N, top_k, iou_thr) -> None:
+        C = self.cfg.n_classes
+        if not isinstance(record, MetricsRecord) or record.n_classes != C or not record.counts.is_cuda:
+            raise ValueError("record must be a MetricsRecord of %d classes on %s (engine.metrics_record())" % (C, self.device))
+        if not 0 <= int(row) < record.rows:
+            raise ValueError("row %d outside the record's %d rows" % (row, record.rows))
+        if not 1 <= int(top_k) <= C or not math.isfinite(iou_thr):
+            raise ValueError("top_k must be in [1, %d] and iou_thr finite" % C)
+        M = B * T * N
+        self._timed("metrics", 0.0, "vlg_layout_metrics", ptr(out), ld, ptr(tgt_class), ptr(tgt_box), ptr(valid), tgt_T, t0,
+                    ptr(record.counts[row]), ptr(record.sums[row]), ptr(self.metrics_scratch), B, T, N, C, int(top_k),
+                    float(iou_thr), IOU_EPS, self._stream(), nbytes=(4.0 * ld + 8 + 16 + (4 if valid is not None else 0)) * M)
+
+    def accumulate_metrics(self, batch: Dict[str, torch.Tensor], record: MetricsRecord, row: int = 0, top_k: int = 5,
+                           iou_thr: float = 0.5) -> None:
+        """Score self.out of the last forward() against that batch's tgt_class / tgt_box / valid and ADD the result to
+        row `row` of `record`: one launch of vlg_layout_metrics (definition: include/vlg_hip.h), no host wait.  `batch`
+        must be the batch that forward() was given."""
+        B, T, N, M = self._check_batch(batch)
+        if getattr(self, "_shape", None) != (B, T, N, M):
+            raise ValueError("accumulate_metrics scores the last forward(): call it with that forward's batch")
+        self._metrics(self.out, self.cfg.n_out, batch["tgt_class"], batch["tgt_box"], batch["valid"], T, 0, record, row,
+                      B, T, N, top_k, iou_thr)
+
+    def evaluate_rollout(self, clip_class: torch.Tensor, clip_box: torch.Tensor, record: Optional[MetricsRecord] = None,
+                         top_k: int = 5, iou_thr: float = 0.5, return_logits: bool = False, temperature: float = 0.0,
+                         sample_top_k: int = 0, seed: int = 0, keep_padded: bool = False):
+        """Score a rollout against the frames that really followed.  clip_class (B,T+S,N) int64 and clip_box (B,T+S,N,4)
+        fp32 are device tensors: the first T frames are the prompt, rollout(..., steps=S) generates S frames under the
+        sampling knobs (temperature, sample_top_k = rollout's top_k, seed, keep_padded), and step i's [logits | raw box]
+        are scored against frame T+i of the clip into row i of `record` (a fresh S-row record if None; a given one is
+        added to): S launches of vlg_layout_metrics reading the clip in place, no host wait.  top_k and iou_thr are the
+        METRIC's (top-k accuracy, IoU hit).  A truth slot with the reserved class id is unscored.
+        A step is scored on the model's DISTRIBUTION at that step - arg-max, rank and NLL of its logits, box =
+        sigmoid(raw) - not on the class that was drawn: with temperature > 0 the history the model conditions on is
+        sampled, the score is still that of the logits.
+        Returns the record, or (record, gen_cls, gen_box, logits) with return_logits."""
+        cfg = self.cfg
+        if clip_class.dim() != 3 or tuple(clip_box.shape) != tuple(clip_class.shape) + (BOX_DIM,):
+            raise ValueError("evaluate_rollout takes clip_class (B,T+S,N) and clip_box (B,T+S,N,4)")
+        B, TS, N = clip_class.shape
+        T, S = cfg.T, TS - cfg.T
+        if S < 1:
+            raise ValueError("the clip has %d frames: the engine's %d-frame prompt and at least one frame to score" % (TS, T))
+        for t, dt, what in ((clip_class, torch.int64, "clip_class"), (clip_box, torch.float32, "clip_box")):
+            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous %s HIP tensor" % (what, dt))
+        if record is None:
+            record = self.metrics_record(S)
+        elif record.rows < S:
+            raise ValueError("the record has %d rows, the rollout %d steps" % (record.rows, S))
+        gen_cls, gen_box, logits = self.rollout(clip_class[:, :T], clip_box[:, :T], steps=S, temperature=temperature,
+                                                top_k=sample_top_k, seed=seed, keep_padded=keep_padded, return_logits=True)
+        for i in range(S):
+            self._metrics(logits[i], cfg.n_out, clip_class, clip_box, None, TS, T + i, record, i, B, 1, N, top_k, iou_thr)
+        return (record, gen_cls, gen_box, logits) if return_logits else record
 
     # ---------------------------------------------------------------- public views
     def outputs_btn(self) -> tuple:

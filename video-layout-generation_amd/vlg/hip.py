@@ -53,6 +53,10 @@ SIGNATURES = {
     "vlg_layout_loss": (I, [P, I, P, P, P, P, P, P, I, I, I, I, F, F, F, F, F, P]),
     "vlg_head_last_frame": (I, [P, P, P, P, P, P, I, I, I, I, I, F, P]),
     "vlg_layout_decode": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, c_uint64, I, P]),
+    "vlg_layout_metrics_counts": (I, [I]),
+    "vlg_layout_metrics_sums": (I, [I]),
+    "vlg_layout_metrics_scratch": (I, []),
+    "vlg_layout_metrics": (I, [P, I, P, P, P, I, I, P, P, P, I, I, I, I, I, F, F, P]),
     "vlg_reduce_slabs": (I, [P, L, I, P, L, P]),
     "vlg_reduce_slabs_table": (I, [P, I, I, P]),
     "vlg_sum_partials_table": (I, [P, I, P]),
