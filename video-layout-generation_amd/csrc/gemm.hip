@@ -293,6 +293,25 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs& g, float* const sm
     constexpr int DEPTH = VLG_GEMM_DEPTH;
     v4f xas[DEPTH][TA::NV], xbs[DEPTH][TB::NV];      // staging registers and fragment sets live across the tiles of a run
     float ffa[2][TM][4], ffb[2][TN][4];
+    // The epilogue's auxiliary operand (residual, multiplier, dGELU argument): a lane's 16 values per 32x32 sub-tile.  The
+    // first AUX_EARLY sub-tiles of a tile are requested INSIDE its main loop, by its last two iterations (half each, behind
+    // that iteration's staging load), so they travel under the tile's last MFMAs and the epilogue finds them in registers
+    // (issued at the epilogue's start they cost one exposed memory round trip per tile, cold from HBM for the FFN's u').
+    // Loads retire in order: no staging load that an iteration's LDS write waits for sits behind a request, and a tile's
+    // requests are issued inside its own loop only, i.e. behind the previous tile's epilogue.  (Kernels with an auxiliary
+    // operand contract over at least one K tile - forward and data gradient are never split - so the requesting pair runs.)
+#ifndef VLG_AUX_EARLY
+#define VLG_AUX_EARLY 4      /* sub-tiles requested in the main loop (of TM * TN); 0 = all at the epilogue's start */
+#endif
+    constexpr int AUX_EARLY = (FAST && BK == 32 && (EPI & (VLG_EPI_RESID | VLG_EPI_DGELU | VLG_EPI_MUL)) != 0)
+                                  ? (VLG_AUX_EARLY < TM * TN ? VLG_AUX_EARLY : TM * TN) : 0;
+    float aux_early[AUX_EARLY > 0 ? AUX_EARLY : 1][16];     // (a tile's values live from its second-last iteration to its epilogue)
+    // (per-thread byte offset of its first element in a tile of the operand, which shares C's layout; bytes per row)
+    int vc_aux = 0, rowb_aux = 0;
+    if constexpr (AUX_EARLY > 0) {
+        vc_aux = ((wm * TM * 32 + 4 * h) * g.ldc + wn * TN * 32 + l31) * 4;
+        rowb_aux = g.ldc * 4;
+    }
     auto mainloop_fast = [&](int n0v, bool first, bool has_next) __attribute__((always_inline)) {
         const float* pa = A_KC ? gA + m0 * g.lda + kbeg : gA + kbeg * g.lda + m0;
         const float* pb = B_KC ? gB + (int64_t)n0v * g.ldb + kbeg : gB + kbeg * g.ldb + n0v;
@@ -391,7 +410,59 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs& g, float* const sm
             ldf(ffa[0], ffb[0], 0, 0);
         }
         __builtin_amdgcn_s_setprio(0);
-        for (int kt = 0; kt < nk; kt += 2) { iter(kt, 0); iter(kt + 1, 1); }
+        if constexpr (AUX_EARLY > 0) {
+            // The copies of the iteration that also request the tile's auxiliary operand, sub-tiles [T0, T1): in the chunk behind
+            // the staging one, the requests spread behind its MFMAs.  Only the last pair of a tile's iterations are these copies
+            // (cur and the sub-tiles are compile-time tags), so the steady-state iteration above is untouched.  Defined HERE, in
+            // the discarded branch of every other instantiation: a lambda merely defined beside `iter` changes this closure's
+            // layout and, through the register allocation, the code of kernels that never call it.
+            auto iter_req = [&](int kt, auto cur_tag, auto t0_tag, auto t1_tag) __attribute__((always_inline)) {
+                constexpr int cur = decltype(cur_tag)::value, T0 = decltype(t0_tag)::value, T1 = decltype(t1_tag)::value;
+#pragma unroll
+                for (int s = 0; s < NCH; ++s) {
+                    if (s + 1 < NCH) ldf(ffa[(s + 1) & 1], ffb[(s + 1) & 1], cur, s + 1);
+                    if (s == NCH - 1) {
+                        __syncthreads();
+                        ldf(ffa[0], ffb[0], cur ^ 1, 0);
+                    }
+                    VLG_SCHED_FENCE();
+                    if (s == SS) {
+                        store(cur ^ 1, 0);
+                        load(kt + 1 + DEPTH, 0);
+                    }
+                    if (s == SS + 1 && T1 > T0) {
+                        const __amdgpu_buffer_rsrc_t dxin = vlg_rsrc(gAuxIn ? gAuxIn + (m0 * g.ldc + n0v) : gA);
+#pragma unroll
+                        for (int t = T0; t < T1; ++t)
+#pragma unroll
+                            for (int r = 0; r < 16; ++r)       // (the loads of emit_fast's fetch: sub-tile (t / TN, t % TN), row of register r)
+                                aux_early[t][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+                                    dxin, vc_aux + (t % TN) * 128, ((t / TN) * 32 + (r & 3) + 8 * (r >> 2)) * rowb_aux, 0));
+                    }
+                    mma(ffa[s & 1], ffb[s & 1]);
+                    if (s == SS) pin_staging<4 * TM * TN, TA::NV + TB::NV, TA::NV + TB::NV>();
+                    if (s == SS + 1 && T1 > T0) pin_staging<4 * TM * TN, 0, 16 * (T1 - T0)>();
+                }
+            };
+            // The last pair of iterations is peeled (a block-uniform branch BETWEEN pairs) and carries the requests, half of the
+            // sub-tiles each: a wave then never has more than 8 + 32 + 8 + 32 loads outstanding when the first half has not
+            // returned yet, and 48 when it has - the in-order counter holds 63, and a wave that would exceed it stalls at the
+            // ISSUE of the load, MFMAs behind it included, until the oldest one returns (all 64 requests behind one staging load
+            // stall at the 56th until that staging load is back).  nk = 1, 2 run this pair alone, the requests then sit behind
+            // the prologue's loads.
+            static_assert(DEPTH == 1 && SS + 1 < NCH, "the requesting copies: one staging set, a chunk behind the staging chunk");
+            constexpr int E0 = (AUX_EARLY + 1) / 2;
+            using I0 = std::integral_constant<int, 0>;
+            using I1 = std::integral_constant<int, 1>;
+            int kt = 0;
+            for (; kt + 2 < nk; kt += 2) { iter(kt, 0); iter(kt + 1, 1); }
+            if (kt < nk) {
+                iter_req(kt, I0{}, I0{}, std::integral_constant<int, E0>{});
+                iter_req(kt + 1, I1{}, std::integral_constant<int, E0>{}, std::integral_constant<int, AUX_EARLY>{});
+            }
+        } else {
+            for (int kt = 0; kt < nk; kt += 2) { iter(kt, 0); iter(kt + 1, 1); }
+        }
         __builtin_amdgcn_s_setprio(2);
     };
     // interior blocks (every tile fully inside both operands) take the unguarded instantiation
@@ -477,9 +548,10 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs& g, float* const sm
         const int vc = ((wm * TM * 32 + 4 * h) * g.ldc + wn * TN * 32 + l31) * 4;
         const int rowb = g.ldc * 4;
         constexpr bool AUX = (EPI & (VLG_EPI_RESID | VLG_EPI_DGELU | VLG_EPI_MUL)) != 0;
-        // the auxiliary operand: ALL of it is requested before the first store where the registers allow (BK = 32: two blocks
-        // per CU, 256 registers) - loads and stores retire through one in-order counter, so a load issued behind a tile's
-        // stores is not usable before those stores have landed; with three blocks per CU (BK = 16) one tile ahead
+        // the auxiliary operand: what the main loop has not requested already (AUX_EARLY sub-tiles, see aux_early) is requested
+        // before the first store where the registers allow (BK = 32: two blocks per CU, 256 registers) - loads and stores
+        // retire through one in-order counter, so a load issued behind a tile's stores is not usable before those stores
+        // have landed; with three blocks per CU (BK = 16) one tile ahead
         constexpr bool AUX_ALL = BK == 32;
         constexpr int NAUX = AUX_ALL ? TM * TN : 2;
         float auxb[NAUX][16];
@@ -490,10 +562,16 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs& g, float* const sm
                 vlg_epi_pace(r + 1);
             }
         };
+        if constexpr (AUX_EARLY > 0) {
+#pragma unroll
+            for (int t = 0; t < AUX_EARLY; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) auxb[t][r] = aux_early[t][r];
+        }
         if constexpr (AUX) {
             if constexpr (AUX_ALL) {
 #pragma unroll
-                for (int t = 0; t < TM * TN; ++t) fetch(auxb[t], t / TN, t % TN);
+                for (int t = AUX_EARLY; t < TM * TN; ++t) fetch(auxb[t], t / TN, t % TN);
             } else {
                 fetch(auxb[0], 0, 0);
             }
