@@ -218,6 +218,9 @@ int vlg_layout_loss(const float* out, int ld, const int64_t* tgt_class, const fl
  * BASELINE.json's temporal encoder next to the per-slot default (vlg_attention_fwd / _bwd).  fp32, head dim 64, T*N a multiple
  * of 32.  qkv [B*N*T, 3d] / out, dout [B*N*T, d] in the internal row order; valid (B,T,N) floats in the public order;
  * lse and delta: B * (d/64) * T*N floats each (log-sum-exp in the log2 domain, written by fwd; <dO, O>, scratch of bwd).
+ * valid values: a slot is visible as a key iff its value is > 0 (any positive float, not only 1; -0.0, 0 and every negative
+ * value pad it), as the specification has it.  NaN is outside the contract: the kernels test `<= 0` and would see such a
+ * slot, the specification tests `> 0` and would not.  A clip may be padded anywhere - whole leading frames, every slot.
  * bwd = two launches (query owner: dQ; key owner: dK, dV): every gradient element has one owner, no atomics.
  * Refusals, before anything is enqueued: VLG_ERR_SHAPE for a shape outside the above; VLG_ERR_ALIGN if qkv, out (fwd) or qkv,
  * out, dout, dqkv (bwd) is NULL or not 16-byte aligned, or if lse (fwd, bwd) or delta (bwd) is NULL.  Only valid may be NULL. */

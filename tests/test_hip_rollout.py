@@ -178,6 +178,25 @@ def test_layout_rollout_clip_masks_padded_slots_at_fixed_n(tmp_path, monkeypatch
     _check_layout_rollout(tr, cls0, box0, "clip")
 
 
+def test_layout_rollout_clip_with_empty_leading_frames(tmp_path, monkeypatch, dev):
+    """A prompt whose frames 0-3 hold no object (every slot the reserved class id): the window's first 32 tokens are padded,
+    so the per-clip forward meets a fully masked key tile before any query of its last block has seen a key
+    (tests/test_clip_walk_cpu.py, lead-empty).  The predictions hold real classes, so the empty frames slide out of the
+    window over the 8 steps and both regimes are checked."""
+    (tmp_path / "src").mkdir()
+    monkeypatch.chdir(tmp_path / "src")
+    monkeypatch.delenv("VLG_MODEL", raising=False)
+    monkeypatch.delenv("VLG_VARIABLE_N", raising=False)
+    monkeypatch.setenv("VLG_ATTENTION", "clip")
+    from trainer import Trainer
+    tr = Trainer(reference_args(tmp_path / "exp", **LAYOUT_CFG))
+    assert tr.cfg.attention == "clip" and (tr.cfg.T, tr.cfg.N) == (8, 8)
+    batch = next(iter(tr.val_loader))
+    cls0, box0 = batch["slot_class"].cpu().clone(), batch["slot_box"].cpu()
+    cls0[:, :4] = tr.cfg.n_classes
+    _check_layout_rollout(tr, cls0, box0, "clip", steps=8)
+
+
 LAYOUT_CFG = dict(batch_size=3, epochs=1, print_freq=1, n_frames=8, n_slots=8, d_model=64, n_layers=2, train_clips=6,
                   val_clips=3)
 

@@ -39,6 +39,30 @@ for _prec in SS.PRECISIONS:
 for _prec in ("fp32", "bf16"):        # padded slots (variable N, at least 3 valid): masks in the loss and, per clip, on the keys
     CASES += [pytest.param(_prec, _att, S1, True, None, id="%s-%s-variable-n" % (_prec, _att)) for _att in ("slot", "clip")]
 CASES.append(pytest.param("bf16", "slot", S1, False, "0", id="bf16-slot-VLG_GELU_GRAD_SAVED-0"))
+# per-clip attention on whole masked key tiles (tests/test_clip_walk_cpu.py has what each reaches): the production padding
+# pattern - N = 64 with a prefix of <= 32 valid slots, the second half-frame tile all padded - and a clip whose first 32
+# tokens (four leading frames) are padded, so that its queries meet a fully masked tile before they have seen a key
+S4 = dict(B=2, T=4, N=64, d=64, n_layers=1)       # the smallest T a LayoutConfig takes
+S5 = dict(B=2, T=8, N=8, d=64, n_layers=1)
+for _prec in ("fp32", "bf16"):
+    CASES += [pytest.param(_prec, "clip", S4, "prefix", None, id="%s-clip-2x4x64-prefix-valid" % _prec),
+              pytest.param(_prec, "clip", S5, "lead-empty", None, id="%s-clip-2x8x8-lead-empty" % _prec)]
+
+
+def _batch(cfg, variable_n):
+    """variable_n False / True: oracle.synthetic_batch; "prefix": n_valid = 20 and 64 slots valid per clip; "lead-empty":
+    frames 0-3 of clip 0 without objects.  Padded slots as synthetic_clips writes them: valid = 0, the reserved class id."""
+    if not isinstance(variable_n, str):
+        return O.synthetic_batch(cfg.B, cfg.T, cfg.N, seed=7, variable_n=variable_n, min_valid=3)
+    batch = O.synthetic_batch(cfg.B, cfg.T, cfg.N, seed=7)
+    valid = torch.ones(cfg.B, cfg.T, cfg.N)
+    if variable_n == "prefix":
+        valid[0, :, 20:] = 0.0
+    else:
+        valid[0, :4] = 0.0
+    batch["valid"] = valid
+    batch["slot_class"][valid == 0] = cfg.n_classes
+    return batch
 
 
 def _summary(log):
@@ -58,10 +82,10 @@ def test_every_launch_matches_fp64_on_its_inputs(dev, monkeypatch, precision, at
         monkeypatch.setenv("VLG_GELU_GRAD_SAVED", gelu_saved)
     cfg = LayoutConfig(attention=attention, **kw)
     # fixed-N batches run the per-clip kernels without key masks (valid = NULL), variable-N ones with them
-    eng = LayoutEngine(cfg, dev, precision=precision, padded_slots=variable_n)
-    c = SS.Contract(precision, attention, masked=variable_n, gelu_grad_saved=None if gelu_saved is None else gelu_saved != "0")
+    eng = LayoutEngine(cfg, dev, precision=precision, padded_slots=bool(variable_n))
+    c = SS.Contract(precision, attention, masked=bool(variable_n), gelu_grad_saved=None if gelu_saved is None else gelu_saved != "0")
     assert eng.gelu_grad_saved == c.gelu_grad_saved and eng.pair_backward == c.paired and eng.bf16_store == c.store_bf16
-    batch = O.synthetic_batch(cfg.B, cfg.T, cfg.N, seed=7, variable_n=variable_n, min_valid=3)
+    batch = _batch(cfg, variable_n)
     if variable_n:
         assert bool((batch["valid"] == 0).any())
     b = {k: v.to(dev) for k, v in batch.items()}

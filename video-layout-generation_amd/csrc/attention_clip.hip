@@ -29,8 +29,12 @@
 //                                                                           (clip_kslice_pos), one 16-byte read per k-step
 //   operand fragment       32 floats; 32 MFMAs per product                  4 x bf16x8: k-step s of lane (l31, h) carries the dims
 //                                                                           32 h + 8 s .. + 7 (one 16-byte LDS read); 4 MFMAs per product
-//   log2(e) / sqrt(64)     folded into the Q (K) fragment as it is loaded   applied to S in fp32 (Q is never pre-scaled and rounded
-//                                                                           back)
+//   log2(e) / sqrt(64)     folded into Q in all three kernels (the query    applied to S in fp32 (Q is never pre-scaled and rounded
+//                          owners' Q fragment as it is loaded, the key      back)
+//                          owner's Q rows as they are staged): a score
+//                          recomputed in the backward is bitwise the
+//                          forward's, so P = exp2(s - lse) of a token that
+//                          sees only itself is exactly 1
 //   rounding points        none                                             P only as the operand of P.V and P^T.dO, dS only as the
 //                                                                           operand of dS.K and dS^T.Q (nearest even, in contract32);
 //                                                                           O, dQ, dK, dV accumulated in fp32, rounded once on store
@@ -148,6 +152,14 @@ struct ClipF32 {
         st4(Xs + tok * LDR + 4 * c, v.a);
         st4(Xs + tok * LDR + 4 * (c + 8), v.b);
     }
+    // ... carrying the score scale, rounded as frag_load_scored rounds it: the key owner's S = (Q scale) . K^T is then the
+    // forward's S^T = K . (Q scale)^T product for product, so P = exp2(S - lse) is recomputed from the bits lse was made of
+    __device__ static __forceinline__ void stage_rows_scored(float* Xs, int tok, int c, const Stage& v) {
+        st4(Xs + tok * LDR + 4 * c, make_float4(v.a.x * CLIP_SCALE_LOG2, v.a.y * CLIP_SCALE_LOG2, v.a.z * CLIP_SCALE_LOG2,
+                                                v.a.w * CLIP_SCALE_LOG2));
+        st4(Xs + tok * LDR + 4 * (c + 8), make_float4(v.b.x * CLIP_SCALE_LOG2, v.b.y * CLIP_SCALE_LOG2, v.b.z * CLIP_SCALE_LOG2,
+                                                      v.b.w * CLIP_SCALE_LOG2));
+    }
     __device__ static __forceinline__ void stage_transposed(float* Xt, int tok, int c, const Stage& v) {
         float* p = Xt + (4 * c) * LDT + tok;
         p[0] = v.a.x; p[LDT] = v.a.y; p[2 * LDT] = v.a.z; p[3 * LDT] = v.a.w;
@@ -242,6 +254,7 @@ struct ClipBf16 {
     __device__ static __forceinline__ void stage_rows(bf16_t* Xs, int tok, int c, Stage v) {
         *reinterpret_cast<uint4*>(Xs + tok * LDR + 8 * c) = v;
     }
+    __device__ static __forceinline__ void stage_rows_scored(bf16_t* Xs, int tok, int c, Stage v) { stage_rows(Xs, tok, c, v); }
     // tile token 16 s + 8 a + 4 h + c (C-layout row of register 8 s + 4 a + c, lane half h) -> position 16 s + 8 h + 4 a + c
     __device__ static __forceinline__ int clip_kslice_pos(int tok) { return (tok & ~12) | ((tok & 4) << 1) | ((tok & 8) >> 1); }
     __device__ static __forceinline__ void stage_transposed(bf16_t* Xt, int tok, int c, Stage v) {
@@ -510,7 +523,7 @@ __global__ __launch_bounds__(256, 2) void attn_clip_dkv_kernel(const typename P:
     typename P::Frag kf, vf;
     if (wact) {
         kfr_own = clip_frame_code(valid, b, sk, T, N);
-        P::frag_load_scored(kf, qkv + krow * ld + d + hh * CHD + 32 * h);
+        P::frag_load(kf, qkv + krow * ld + d + hh * CHD + 32 * h);   // the scale rides on the Q rows (stage_rows_scored)
         P::frag_load(vf, qkv + krow * ld + 2 * d + hh * CHD + 32 * h);
     }
     const int jfirst = clip_first_query_tile(kb0, N);
@@ -536,7 +549,7 @@ __global__ __launch_bounds__(256, 2) void attn_clip_dkv_kernel(const typename P:
     for (int r = 0; r < 16; ++r) { dk[0][r] = 0.f; dk[1][r] = 0.f; dv[0][r] = 0.f; dv[1][r] = 0.f; }
     for (int j = jfirst; j < ntiles; ++j) {
         __syncthreads();
-        P::stage_rows(Qs, tok, c, qn);
+        P::stage_rows_scored(Qs, tok, c, qn);
         P::stage_transposed(Qt, tok, c, qn);
         P::stage_rows(Gs, tok, c, gn);
         P::stage_transposed(Gt, tok, c, gn);
