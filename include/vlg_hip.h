@@ -390,6 +390,46 @@ int vlg_optim_control(float* ctl, const float* partials, int n_partials, float g
 int vlg_adam_step_ctl(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, vlg_bf16* shadow,
                       int64_t n, const float* ctl, float beta1, float beta2, float eps, void* stream);
 
+/* The training recipe on the guarded step: decoupled weight decay (torch.optim.AdamW) on marked float4s, a linear
+ * learning-rate warm-up counted in APPLIED steps, and an exponential moving average (EMA) of the weights - decided and
+ * applied on the device, so a captured graph replays them:
+ *     vlg_grad_sumsq -> vlg_optim_control_ext -> vlg_adamw_ema_step_ctl
+ * They share `ctl` (above, same contract) and `ext`, a second 16-float, 16-byte-aligned device record: */
+#define VLG_EXT_WEIGHT_DECAY 0   /* float  INPUT  the decay wd (0 = none)                                              */
+#define VLG_EXT_WARMUP_STEPS 1   /* int    INPUT  warm-up length W in applied steps; 0 = off                           */
+#define VLG_EXT_EMA_DECAY    2   /* float  INPUT  the EMA decay d                                                      */
+#define VLG_EXT_EMA_WARMUP   3   /* int    INPUT  0 or 1: d_t = min(d, (1 + step) / (10 + step))                       */
+#define VLG_EXT_LR_EFF       4   /* float  OUTPUT effective learning rate of this step                                 */
+#define VLG_EXT_DECAY_MULT   5   /* float  OUTPUT 1 - LR_EFF * wd: what a marked parameter is multiplied by            */
+#define VLG_EXT_EMA_OMD      6   /* float  OUTPUT 1 - d_t: the weight of the new parameters in the average             */
+#define VLG_EXT_FLOATS       16  /* inputs are written by the host and only read by the kernels; slots 7-15 are reserved
+                                    and stay as the host left them */
+/* vlg_optim_control, from the same code (same ctl slots, same bits whenever WARMUP_STEPS == 0), plus the outputs of ext.
+ * `step` = the 1-based count of the step being applied (STEP after its increment; skipped steps do not advance it).  In
+ * double, each output rounded to float once:
+ *     lr_eff = LR                                   WARMUP_STEPS == 0 (bit for bit)
+ *            = LR * min(1, step / WARMUP_STEPS)     otherwise
+ *     STEP_SIZE = lr_eff / (1 - beta1^step)         DECAY_MULT = 1 - lr_eff * wd
+ *     d_t = EMA_DECAY, or min(EMA_DECAY, (1 + step) / (10 + step)) with EMA_WARMUP;   EMA_OMD = 1 - d_t
+ * On a skipped step (non-finite norm) no output slot of ext changes.  ext non-NULL and 16-byte aligned. */
+int vlg_optim_control_ext(float* ctl, float* ext, const float* partials, int n_partials, float grad_scale, float max_norm,
+                          float beta1, float beta2, void* stream);
+/* vlg_adam_step_ctl plus two optional parts per float4 (group of 4 consecutive parameters; tensors start at multiples of 4
+ * floats, so a float4 never straddles two):
+ *   decay_mask  uint8[n/4] or NULL, one byte per float4.  Non-zero: p = p * DECAY_MULT (one rounded multiplication) BEFORE
+ *               Adam's update - torch.optim.AdamW's order.  Zero, or NULL: no multiplication is issued, the float4 is
+ *               bitwise vlg_adam_step_ctl's.
+ *   ema         fp32[n] or NULL.  After the update e = e + EMA_OMD * (p_new - e).  ema_shadow: bf16[n] or NULL, only with
+ *               ema (else VLG_ERR_SHAPE): bf16(e), round to nearest even, stored as `shadow` is.
+ * With decay_mask, ema NULL, wd = 0 and WARMUP_STEPS = 0 the pair is bitwise vlg_optim_control + vlg_adam_step_ctl.  With
+ * APPLY == 0 no element of any buffer is read or written, the average included.
+ * Algorithmic bytes on top of vlg_adam_step_ctl's 16 B read + 12 B written (+ 2 B shadow) per parameter: 4 + 4 (+ 2) B with
+ * ema, 0.25 B with the mask.  n >= 4, n % 4 == 0, ctl and ext non-NULL (VLG_ERR_SHAPE); param, grad, the moments, ema, ctl,
+ * ext 16-byte aligned, the shadows 8, decay_mask 4 (VLG_ERR_ALIGN).  A refused call enqueues nothing. */
+int vlg_adamw_ema_step_ctl(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, vlg_bf16* shadow,
+                           float* ema, vlg_bf16* ema_shadow, const uint8_t* decay_mask, int64_t n, const float* ctl,
+                           const float* ext, float beta1, float beta2, float eps, void* stream);
+
 /* ---------------------------------------------------- reference-real image ops
  * Pixel-space ops of the reference step that exist verbatim in the reference.
  *   vlg_ce_nchw        nn.CrossEntropyLoss('mean') on (b,C,H,W) logits / (b,H,W) int64

@@ -9,7 +9,6 @@
 //                    parameter (reference src/trainer.py:83,258 - Adam(lr, betas=(beta1,0.999)),
 //                    no weight decay, no amsgrad).  One launch per step instead of one per tensor.
 //                    Algorithmic bytes: 16 B read + 12 B written per parameter.
-//                    Algorithmic bytes: 16 B read + 12 B written per parameter.
 // The guarded step (global-norm clipping, skip of a non-finite gradient, learning rate in device memory) is three
 // launches around one 16-float device record `ctl` (layout: include/vlg_hip.h), so it needs no host synchronisation and
 // survives hipGraph replay:
@@ -20,6 +19,14 @@
 //                    step counter and bias-correction factors (as adam_state_kernel computes them).
 // vlg_adam_step_ctl: adam_kernel's arithmetic with {step_size, sqrt_bc2, gradient multiplier} read from ctl; when the
 //                    apply flag is 0 every block returns before it touches memory.
+// The training recipe on top of it (decoupled weight decay on marked float4s, linear warm-up counted in applied steps, an
+// exponential moving average of the weights) is the same three launches with a second 16-float record `ext` (VLG_EXT_*):
+// vlg_optim_control_ext : vlg_optim_control's decision from the same code, plus this step's effective learning rate,
+//                    decay multiplier and EMA weight, written to ext.
+// vlg_adamw_ema_step_ctl: vlg_adam_step_ctl plus, per float4, p *= DECAY_MULT where a byte mask marks it (before Adam's
+//                    update: torch.optim.AdamW's order) and e += EMA_OMD * (p_new - e) on an fp32 average (+ its bf16
+//                    copy).  Algorithmic bytes on top of the parent's: 4 B read + 4 B written (+ 2 B) per parameter with
+//                    the average, 0.25 B read with the mask.
 #include "common.h"
 #include "reduce_body.h"
 #include <math.h>
@@ -71,13 +78,11 @@ __global__ __launch_bounds__(256) void reduce_slabs_tall_kernel(const float* __r
 }
 
 // The update of four consecutive parameters: the one statement of Adam's arithmetic, shared by every Adam kernel here
-// (so the guarded step is bitwise the plain one whenever its gradient multiplier equals grad_scale).
-__device__ __forceinline__ void adam_update4(float* __restrict__ param, const float* __restrict__ grad, float* __restrict__ m,
-                                             float* __restrict__ v, bf16_t* __restrict__ shadow, int64_t e, float omb1,
-                                             float beta2, float omb2, float eps, float step_size, float sqrt_bc2,
-                                             float grad_scale) {
-    float4 p = ld4(param + e * 4), g = ld4(grad + e * 4), mm = ld4(m + e * 4), vv = ld4(v + e * 4);
-    float* pp = &p.x; float* gp = &g.x; float* mp = &mm.x; float* vp = &vv.x;
+// (so the guarded step is bitwise the plain one whenever its gradient multiplier equals grad_scale).  On registers:
+// adam_update4 wraps it in the loads and stores, the recipe kernel adds its own around it.
+__device__ __forceinline__ void adam_math4(float4& p, const float4& g, float4& mm, float4& vv, float omb1, float beta2,
+                                           float omb2, float eps, float step_size, float sqrt_bc2, float grad_scale) {
+    float* pp = &p.x; const float* gp = &g.x; float* mp = &mm.x; float* vp = &vv.x;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const float gk = gp[k] * grad_scale;
@@ -86,6 +91,14 @@ __device__ __forceinline__ void adam_update4(float* __restrict__ param, const fl
         const float denom = sqrtf(vp[k]) / sqrt_bc2 + eps;
         pp[k] -= step_size * (mp[k] / denom);
     }
+}
+
+__device__ __forceinline__ void adam_update4(float* __restrict__ param, const float* __restrict__ grad, float* __restrict__ m,
+                                             float* __restrict__ v, bf16_t* __restrict__ shadow, int64_t e, float omb1,
+                                             float beta2, float omb2, float eps, float step_size, float sqrt_bc2,
+                                             float grad_scale) {
+    float4 p = ld4(param + e * 4), g = ld4(grad + e * 4), mm = ld4(m + e * 4), vv = ld4(v + e * 4);
+    adam_math4(p, g, mm, vv, omb1, beta2, omb2, eps, step_size, sqrt_bc2, grad_scale);
     st4(param + e * 4, p); st4(m + e * 4, mm); st4(v + e * 4, vv);
     if (shadow != nullptr) st4(shadow + e * 4, p);         // bf16 copy of the updated weights for the bf16-MFMA projections
 }
@@ -267,11 +280,12 @@ extern "C" int vlg_grad_sumsq(const float* grad, int64_t n, float* partials, voi
     return vlg_last_error();
 }
 
-// ctl: the record include/vlg_hip.h documents (VLG_CTL_*).  One block; thread 0 decides.
-__global__ __launch_bounds__(256) void optim_control_kernel(float* __restrict__ ctl, const float* __restrict__ partials,
-                                                            int n_partials, float grad_scale, float max_norm,
-                                                            float beta1, float beta2) {
-    __shared__ double red[4];
+// ctl: the record include/vlg_hip.h documents (VLG_CTL_*).  One block; thread 0 decides.  `ext` (VLG_EXT_*, or NULL: the
+// plain guarded step) adds the recipe: the learning rate of THIS step under warm-up, and from it the decay multiplier, and
+// the EMA weight.  With ext == NULL, or warm-up off, every ctl slot gets the bits it always got ((double)LR * 1 is LR).
+__device__ __forceinline__ void optim_control_decide(float* __restrict__ ctl, float* __restrict__ ext,
+                                                     const float* __restrict__ partials, int n_partials, float grad_scale,
+                                                     float max_norm, float beta1, float beta2, double* red) {
     double acc = 0.0;
     for (int i = threadIdx.x; i < n_partials; i += 256) acc += (double)partials[i];
     const double sum = block_sum_f64(acc, red);
@@ -290,12 +304,38 @@ __global__ __launch_bounds__(256) void optim_control_kernel(float* __restrict__ 
     const double bc2 = 1.0 - pow((double)beta2, (double)step);
     double coef = 1.0;
     if (max_norm > 0.f) coef = fmin(1.0, (double)max_norm / (norm + 1e-6));     // torch.nn.utils.clip_grad_norm_
-    ctl[VLG_CTL_STEP_SIZE] = (float)((double)ctl[VLG_CTL_LR] / bc1);
+    double lr_eff = (double)ctl[VLG_CTL_LR];
+    if (ext != nullptr) {
+        const int* iext = reinterpret_cast<const int*>(ext);
+        const int warmup = iext[VLG_EXT_WARMUP_STEPS];
+        if (warmup > 0) lr_eff = __dmul_rn(lr_eff, fmin(1.0, (double)step / (double)warmup));
+        double d_t = (double)ext[VLG_EXT_EMA_DECAY];
+        if (iext[VLG_EXT_EMA_WARMUP] != 0) d_t = fmin(d_t, (1.0 + (double)step) / (10.0 + (double)step));
+        ext[VLG_EXT_LR_EFF] = (float)lr_eff;
+        // (products rounded on their own: a fused multiply-add would differ from 1 - lr * wd in the last bit of the double)
+        ext[VLG_EXT_DECAY_MULT] = (float)(1.0 - __dmul_rn(lr_eff, (double)ext[VLG_EXT_WEIGHT_DECAY]));
+        ext[VLG_EXT_EMA_OMD] = (float)(1.0 - d_t);
+    }
+    ctl[VLG_CTL_STEP_SIZE] = (float)(lr_eff / bc1);
     ctl[VLG_CTL_SQRT_BC2] = (float)sqrt(bc2);
     ictl[VLG_CTL_STEP] = step;
     ictl[VLG_CTL_APPLY] = 1;
     ctl[VLG_CTL_GRAD_MULT] = max_norm > 0.f ? (float)((double)grad_scale * coef) : grad_scale;
     ctl[VLG_CTL_CLIP_COEF] = (float)coef;
+}
+
+__global__ __launch_bounds__(256) void optim_control_kernel(float* __restrict__ ctl, const float* __restrict__ partials,
+                                                            int n_partials, float grad_scale, float max_norm,
+                                                            float beta1, float beta2) {
+    __shared__ double red[4];
+    optim_control_decide(ctl, nullptr, partials, n_partials, grad_scale, max_norm, beta1, beta2, red);
+}
+
+__global__ __launch_bounds__(256) void optim_control_ext_kernel(float* __restrict__ ctl, float* __restrict__ ext,
+                                                                const float* __restrict__ partials, int n_partials,
+                                                                float grad_scale, float max_norm, float beta1, float beta2) {
+    __shared__ double red[4];
+    optim_control_decide(ctl, ext, partials, n_partials, grad_scale, max_norm, beta1, beta2, red);
 }
 
 extern "C" int vlg_optim_control(float* ctl, const float* partials, int n_partials, float grad_scale, float max_norm,
@@ -304,6 +344,15 @@ extern "C" int vlg_optim_control(float* ctl, const float* partials, int n_partia
     if (!vlg_aligned16(ctl)) return VLG_ERR_ALIGN;
     hipLaunchKernelGGL(optim_control_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ctl, partials, n_partials,
                        grad_scale, max_norm, beta1, beta2);
+    return vlg_last_error();
+}
+
+extern "C" int vlg_optim_control_ext(float* ctl, float* ext, const float* partials, int n_partials, float grad_scale,
+                                     float max_norm, float beta1, float beta2, void* stream) {
+    if (!ctl || !ext || !partials || n_partials < 1 || n_partials > VLG_SUMSQ_MAX_BLOCKS) return VLG_ERR_SHAPE;
+    if (!vlg_aligned16(ctl) || !vlg_aligned16(ext)) return VLG_ERR_ALIGN;
+    hipLaunchKernelGGL(optim_control_ext_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ctl, ext, partials,
+                       n_partials, grad_scale, max_norm, beta1, beta2);
     return vlg_last_error();
 }
 
@@ -326,5 +375,66 @@ extern "C" int vlg_adam_step_ctl(float* param, const float* grad, float* exp_avg
         !vlg_aligned16(ctl) || (shadow && !vlg_aligned8(shadow))) return VLG_ERR_ALIGN;
     hipLaunchKernelGGL(adam_ctl_kernel, dim3(stream_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, param, grad,
                        exp_avg, exp_avg_sq, n / 4, beta1, beta2, eps, reinterpret_cast<bf16_t*>(shadow), ctl);
+    return vlg_last_error();
+}
+
+// ---- the recipe step: decoupled weight decay under a float4 mask, and the weights' moving average
+// One float4 per lane and trip, like adam_ctl_kernel: the mask is a byte per lane (one 64-byte line per wave, 0.25 B per
+// parameter), the average one more float4 stream in and out.  MASK / EMA are compile-time so that the plain shape of the
+// loop (neither) is adam_ctl_kernel's, instruction for instruction.
+template <bool MASK, bool EMA>
+__global__ __launch_bounds__(256) void adamw_ema_ctl_kernel(float* __restrict__ param, const float* __restrict__ grad,
+                                                            float* __restrict__ m, float* __restrict__ v, int64_t n4,
+                                                            float beta1, float beta2, float eps, bf16_t* __restrict__ shadow,
+                                                            float* __restrict__ ema, bf16_t* __restrict__ ema_shadow,
+                                                            const unsigned char* __restrict__ mask,
+                                                            const float* __restrict__ ctl, const float* __restrict__ ext) {
+    // a branch, not a multiplication by zero: 0 * inf would write NaN into the moments
+    if (reinterpret_cast<const int*>(ctl)[VLG_CTL_APPLY] == 0) return;
+    const float step_size = ctl[VLG_CTL_STEP_SIZE], sqrt_bc2 = ctl[VLG_CTL_SQRT_BC2], grad_mult = ctl[VLG_CTL_GRAD_MULT];
+    const float decay_mult = ext[VLG_EXT_DECAY_MULT], omd = ext[VLG_EXT_EMA_OMD];
+    const float omb1 = 1.f - beta1, omb2 = 1.f - beta2;
+    (void)decay_mult; (void)omd;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4; e += (int64_t)gridDim.x * blockDim.x) {
+        float4 p = ld4(param + e * 4), g = ld4(grad + e * 4), mm = ld4(m + e * 4), vv = ld4(v + e * 4);
+        float4 ev = f4_zero();
+        if (EMA) ev = ld4(ema + e * 4);
+        if (MASK) {
+            if (mask[e] != 0) {       // p.mul_(1 - lr * wd) BEFORE the update, rounded on its own (not fused into it)
+                p.x = __fmul_rn(p.x, decay_mult); p.y = __fmul_rn(p.y, decay_mult);
+                p.z = __fmul_rn(p.z, decay_mult); p.w = __fmul_rn(p.w, decay_mult);
+            }
+        }
+        adam_math4(p, g, mm, vv, omb1, beta2, omb2, eps, step_size, sqrt_bc2, grad_mult);
+        st4(param + e * 4, p); st4(m + e * 4, mm); st4(v + e * 4, vv);
+        if (shadow != nullptr) st4(shadow + e * 4, p);
+        if (EMA) {
+            ev.x = ev.x + omd * (p.x - ev.x); ev.y = ev.y + omd * (p.y - ev.y);
+            ev.z = ev.z + omd * (p.z - ev.z); ev.w = ev.w + omd * (p.w - ev.w);
+            st4(ema + e * 4, ev);
+            if (ema_shadow != nullptr) st4(ema_shadow + e * 4, ev);
+        }
+    }
+}
+
+extern "C" int vlg_adamw_ema_step_ctl(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, vlg_bf16* shadow,
+                                      float* ema, vlg_bf16* ema_shadow, const uint8_t* decay_mask, int64_t n,
+                                      const float* ctl, const float* ext, float beta1, float beta2, float eps, void* stream) {
+    if (n < 4 || (n & 3) || !ctl || !ext || (ema_shadow && !ema)) return VLG_ERR_SHAPE;
+    if (!vlg_aligned16(param) || !vlg_aligned16(grad) || !vlg_aligned16(exp_avg) || !vlg_aligned16(exp_avg_sq) ||
+        !vlg_aligned16(ctl) || !vlg_aligned16(ext) || (shadow && !vlg_aligned8(shadow)) || (ema && !vlg_aligned16(ema)) ||
+        (ema_shadow && !vlg_aligned8(ema_shadow)) || (reinterpret_cast<uintptr_t>(decay_mask) & 3u)) return VLG_ERR_ALIGN;
+    const dim3 grid(stream_blocks(n / 4)), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    bf16_t* sh = reinterpret_cast<bf16_t*>(shadow);
+    bf16_t* esh = reinterpret_cast<bf16_t*>(ema_shadow);
+#define VLG_RECIPE_LAUNCH(MASK, EMA)                                                                                       \
+    hipLaunchKernelGGL((adamw_ema_ctl_kernel<MASK, EMA>), grid, block, 0, s, param, grad, exp_avg, exp_avg_sq, n / 4, beta1, \
+                       beta2, eps, sh, ema, esh, decay_mask, ctl, ext)
+    if (decay_mask && ema) VLG_RECIPE_LAUNCH(true, true);
+    else if (decay_mask) VLG_RECIPE_LAUNCH(true, false);
+    else if (ema) VLG_RECIPE_LAUNCH(false, true);
+    else VLG_RECIPE_LAUNCH(false, false);
+#undef VLG_RECIPE_LAUNCH
     return vlg_last_error();
 }

@@ -29,6 +29,16 @@ VLG_LR_DECAY = 1 honours --lr_decay_step / --lr_decay_gamma (epochs; the referen
 they stay ignored unless asked for).  Any of them switches the engine to its guarded step; the train log line then also
 shows the gradient norm and the number of skipped steps.
 
+The training recipe on that step (all off by default; vlg/optim.py, DESIGN.md "Training recipe"): args.weight_decay /
+VLG_WEIGHT_DECAY = decoupled weight decay (AdamW) on the weight matrices (layout mode) or convolution weights (pixel mode);
+args.warmup_steps / VLG_WARMUP_STEPS = linear learning-rate warm-up over that many applied steps - it composes with
+VLG_LR_DECAY: the epoch's rate is written into the device record as before and the warm-up scales it on the device;
+args.ema_decay / VLG_EMA_DECAY = an exponential moving average of the weights with that decay, args.ema_warmup /
+VLG_EMA_WARMUP = 1 ramps the decay as min(d, (1 + step) / (10 + step)); args.ema_eval / VLG_EMA_EVAL (default 1, read only
+when the average is on): layout mode's validate(), generate_sequence() and evaluate_rollout() run on the averaged weights
+(LayoutEngine.ema_weights()).  save_checkpoint adds 'gridnet_ema', the averaged model in 'gridnet''s format; --resume
+restores the average through 'optimizer'.
+
 Generation knobs of generate_sequence in layout mode (a keyword argument wins over them; csrc/decode.hip, DESIGN.md
 "Generation"): args.gen_temperature / VLG_GEN_TEMPERATURE (0 = argmax; > 0 samples from softmax(logits / temperature)),
 args.gen_top_k / VLG_GEN_TOP_K (0 = every class, else only the k largest logits), args.gen_seed / VLG_GEN_SEED (default
@@ -51,6 +61,7 @@ which returns world x the mean), visualisation is not run every step (A-15).
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import random
 import shutil
@@ -124,10 +135,31 @@ def _knob_float(args, name: str, env: str, default: float) -> float:
 
 
 def optim_knobs(args) -> Dict[str, object]:
-    """{clip_grad, skip_nonfinite, lr_decay} from args / environment (module docstring); all off by default."""
-    return {"clip_grad": max(_knob_float(args, "clip_grad", "VLG_CLIP_GRAD", 0.0), 0.0),
-            "skip_nonfinite": bool(_knob(args, "skip_nonfinite", "VLG_SKIP_NONFINITE", 0)),
-            "lr_decay": os.environ.get("VLG_LR_DECAY", "0") == "1"}
+    """{clip_grad, skip_nonfinite, lr_decay} from args / environment (module docstring); all off by default.  The recipe's
+    knobs join the dict only where they are ON, so with all of them off it is the dict it always was: weight_decay,
+    warmup_steps, ema_decay, and with ema_decay also ema_warmup and ema_eval (default on; not read without the average).
+    Read them with .get(name, 0)."""
+    knobs = {"clip_grad": max(_knob_float(args, "clip_grad", "VLG_CLIP_GRAD", 0.0), 0.0),
+             "skip_nonfinite": bool(_knob(args, "skip_nonfinite", "VLG_SKIP_NONFINITE", 0)),
+             "lr_decay": os.environ.get("VLG_LR_DECAY", "0") == "1"}
+    weight_decay = _knob_float(args, "weight_decay", "VLG_WEIGHT_DECAY", 0.0)
+    warmup_steps = _knob(args, "warmup_steps", "VLG_WARMUP_STEPS", 0)
+    ema_decay = _knob_float(args, "ema_decay", "VLG_EMA_DECAY", 0.0)
+    if weight_decay < 0.0 or warmup_steps < 0 or not 0.0 <= ema_decay < 1.0:
+        raise ValueError("VLG_WEIGHT_DECAY and VLG_WARMUP_STEPS must be >= 0, VLG_EMA_DECAY in [0, 1)")
+    if weight_decay > 0.0:
+        knobs["weight_decay"] = weight_decay
+    if warmup_steps > 0:
+        knobs["warmup_steps"] = warmup_steps
+    if ema_decay > 0.0:
+        knobs.update(ema_decay=ema_decay, ema_warmup=bool(_knob(args, "ema_warmup", "VLG_EMA_WARMUP", 0)),
+                     ema_eval=bool(_knob(args, "ema_eval", "VLG_EMA_EVAL", 1)))
+    return knobs
+
+
+def recipe_kwargs(knobs: Dict[str, object]) -> Dict[str, object]:
+    """the recipe's engine keyword arguments - only those that are on, so an engine factory without them is never handed one"""
+    return {k: knobs[k] for k in ("weight_decay", "warmup_steps", "ema_decay", "ema_warmup") if knobs.get(k)}
 
 
 def generation_knobs(args) -> Dict[str, object]:
@@ -175,7 +207,7 @@ def get_layout_engine(args, cfg: Optional[LayoutConfig] = None, engine_factory: 
                               lr=float(getattr(args, "lr", ADAM_LR)), beta1=float(getattr(args, "beta1", ADAM_BETA1)),
                               precision=precision,
                               padded_slots=bool(_knob(args, "variable_n", "VLG_VARIABLE_N", 0)),   # fixed-N feeds hold no padded slots
-                              clip_grad=knobs["clip_grad"], skip_nonfinite=knobs["skip_nonfinite"])
+                              clip_grad=knobs["clip_grad"], skip_nonfinite=knobs["skip_nonfinite"], **recipe_kwargs(knobs))
     else:
         engine = engine_factory(cfg, args)
     if knobs["lr_decay"]:                            # guarded from the start, so a checkpoint's lr and skip count are resumed
@@ -248,7 +280,8 @@ class _ImageModel:
             precision = "fp32"
         self.engine = ImageEngine(batch, size, size, self.device, arch=arch, lr=float(getattr(args, "lr", ADAM_LR)),
                                   beta1=float(getattr(args, "beta1", ADAM_BETA1)), with_hed=with_hed, with_vgg=with_vgg,
-                                  precision=precision, clip_grad=knobs["clip_grad"], skip_nonfinite=knobs["skip_nonfinite"])
+                                  precision=precision, clip_grad=knobs["clip_grad"], skip_nonfinite=knobs["skip_nonfinite"],
+                                  **recipe_kwargs(knobs))
         if knobs["lr_decay"]:
             self.engine.set_lr(float(getattr(args, "lr", ADAM_LR)))
         for net, env in ((self.engine.hed, "VLG_HED_CKPT"), (self.engine.vgg, "VLG_VGG_CKPT")):
@@ -281,6 +314,9 @@ class _ImageModel:
 
     def named_params(self):
         return self.engine.state_dict()
+
+    def ema_named_params(self):
+        return self.engine.ema_state_dict()
 
     def load_params(self, sd):
         self.engine.load_state_dict(sd)
@@ -375,7 +411,8 @@ class Trainer:
         self.device = self.engine.device
         self.gridnet = self.model = _ModelHandle(self.engine)   # reference attr `gridnet`; main.py:65 wants `.model`
         self.optim = optim_knobs(args)
-        self.guarded = self.optim["clip_grad"] > 0.0 or self.optim["skip_nonfinite"] or self.optim["lr_decay"]
+        self.guarded = bool(self.optim["clip_grad"] > 0.0 or self.optim["skip_nonfinite"] or self.optim["lr_decay"]
+                            or recipe_kwargs(self.optim))
         self.global_step = 0
         self.epoch = 0
         if getattr(args, "resume", None) is not None:           # reference src/trainer.py:138-139
@@ -474,8 +511,19 @@ class Trainer:
                     self.writer.add_scalar("train/lr", stats["lr"], self.global_step)
             end = time()
 
+    def _eval_weights(self):
+        """The weights evaluation and generation run on: the moving average (LayoutEngine.ema_weights()) when it is on and
+        VLG_EMA_EVAL is, else the live weights.  Layout mode only: the pixel model is not evaluated under its average."""
+        if self.optim.get("ema_eval") and not self.image_mode and hasattr(self.engine, "ema_weights"):
+            return self.engine.ema_weights()
+        return contextlib.nullcontext()
+
     # ---------------------------------------------------------------------- validate
     def validate(self):
+        with self._eval_weights():
+            return self._validate()
+
+    def _validate(self):
         self.args.logger.info("Validation started")
         self.gridnet.eval()
         val_loss = AverageMeter()
@@ -547,9 +595,12 @@ class Trainer:
         self.args.logger.info("Saving checkpoint..")
         prefix = "../checkpoint"
         os.makedirs(prefix, exist_ok=True)
-        torch.save({"epoch": self.epoch, "arch": self.args.arch, "gridnet": self.gridnet.state_dict(),
-                    "optimizer": self.engine.optimizer_state(), "metrics": dict(metrics or {})},
-                   "%s/%03d.pth" % (prefix, self.epoch))
+        ckpt = {"epoch": self.epoch, "arch": self.args.arch, "gridnet": self.gridnet.state_dict(),
+                "optimizer": self.engine.optimizer_state(), "metrics": dict(metrics or {})}
+        if self.optim.get("ema_decay") and hasattr(self.engine, "ema_named_params"):
+            # the averaged model, in 'gridnet''s format: {'gridnet': ckpt['gridnet_ema']} is a checkpoint --ckpt loads as a model
+            ckpt["gridnet_ema"] = {k: v.detach().cpu().clone() for k, v in self.engine.ema_named_params().items()}
+        torch.save(ckpt, "%s/%03d.pth" % (prefix, self.epoch))
         shutil.copy("%s/%03d.pth" % (prefix, self.epoch), "%s/latest.pth" % prefix)
 
     def load_checkpoint(self, resume):
@@ -602,8 +653,9 @@ class Trainer:
             if given is not None:
                 knobs[name] = type(knobs[name])(given)
         if hasattr(self.engine, "rollout"):
-            gen_c, gen_b = self.engine.rollout(slot_class.to(self.device).contiguous(), slot_box.to(self.device).contiguous(),
-                                               steps=steps, **knobs)
+            with self._eval_weights():
+                gen_c, gen_b = self.engine.rollout(slot_class.to(self.device).contiguous(), slot_box.to(self.device).contiguous(),
+                                                   steps=steps, **knobs)
             return gen_c.cpu(), gen_b.cpu()
         if knobs["temperature"] != 0.0 or knobs["keep_padded"]:
             raise ValueError("temperature > 0 and keep_padded need an engine with rollout() (vlg.engine.LayoutEngine: the "
@@ -650,11 +702,12 @@ class Trainer:
             if given is not None:
                 knobs[name] = type(knobs[name])(given)
         mk = metrics_knobs(self.args)
-        record = self.engine.evaluate_rollout(
-            clip_class.to(self.device).contiguous(), clip_box.to(self.device).contiguous(),
-            top_k=mk["top_k"] if val_topk is None else int(val_topk),
-            iou_thr=mk["iou_thr"] if val_iou_thr is None else float(val_iou_thr),
-            temperature=knobs["temperature"], sample_top_k=knobs["top_k"], seed=knobs["seed"], keep_padded=knobs["keep_padded"])
+        with self._eval_weights():
+            record = self.engine.evaluate_rollout(
+                clip_class.to(self.device).contiguous(), clip_box.to(self.device).contiguous(),
+                top_k=mk["top_k"] if val_topk is None else int(val_topk),
+                iou_thr=mk["iou_thr"] if val_iou_thr is None else float(val_iou_thr),
+                temperature=knobs["temperature"], sample_top_k=knobs["top_k"], seed=knobs["seed"], keep_padded=knobs["keep_padded"])
         return record.summary()
 
     def eval_generate_sequence(self, img1, img2, seg1, seg2):

@@ -15,6 +15,7 @@ Row order of every (M, .) activation is the internal  m = (b*N + n)*T + t.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from typing import Dict, Optional
@@ -23,7 +24,7 @@ import torch
 
 from . import hip
 from .metrics import MetricsRecord
-from .optim import AdamSurface, FlatAdam
+from .optim import AdamSurface, FlatAdam, build_decay_mask, decays_matrix
 from .slabs import SlabBuckets
 from .hip import (EPI_A_BF16, EPI_B_BF16, EPI_BIAS, EPI_DGELU, EPI_GELU, EPI_NONE, EPI_OUT_BF16, EPI_RESID,
                   call, ptr)
@@ -64,11 +65,18 @@ class LayoutEngine(AdamSurface):
 
     def __init__(self, cfg: LayoutConfig, device: torch.device, seed: int = 1024,
                  lr: float = ADAM_LR, beta1: float = ADAM_BETA1, precision: str = "fp32", padded_slots: bool = True,
-                 clip_grad: float = 0.0, skip_nonfinite: bool = False):
+                 clip_grad: float = 0.0, skip_nonfinite: bool = False, weight_decay: float = 0.0, warmup_steps: int = 0,
+                 ema_decay: float = 0.0, ema_warmup: bool = False):
         """clip_grad > 0 clips the gradient to that global L2 norm (torch.nn.utils.clip_grad_norm_'s rule); skip_nonfinite
         leaves parameters, moments and step count untouched when the gradient holds inf or NaN.  Either one - or a call
         of set_lr - turns on the GUARDED optimiser step (vlg/optim.py), eager and captured alike; with both off and
         set_lr never called, the step's launches are exactly those of an engine without these options.
+        The recipe (vlg/optim.py; each off at 0, any of them turns the guarded step on): weight_decay = decoupled decay
+        (torch.optim.AdamW) on the weight matrices - every tensor whose name ends in _w; not biases, layer-norm gains and
+        biases, cls_emb or time_emb; warmup_steps = linear learning-rate warm-up over that many APPLIED steps, scaling
+        whatever set_lr wrote; ema_decay = an exponential moving average of the weights (ema_warmup: decay
+        min(d, (1 + step) / (10 + step))), kept by the Adam launch, in the bf16 mode with its own bf16 copy:
+        `with engine.ema_weights():` evaluates and generates on it.
         precision:
         "fp32"      exact-fp32 MFMA projections, every tensor fp32 (parity 1e-4);
         "bf16"      BASELINE.json configs[2]: bf16 MFMA projections (fp32 accumulate) AND the activations that only
@@ -110,7 +118,11 @@ class LayoutEngine(AdamSurface):
         self.grads = self.grads_ext[:self.n_params]
         # bf16 mode: a bf16 copy of the weights feeds the projections (the Adam kernel refreshes it with every update)
         self.params_bf16 = torch.zeros(self.n_params, dtype=torch.bfloat16, device=device) if self.bf16_store else None
-        self.optim = FlatAdam(self.n_params, device, lr, beta1, clip_grad, skip_nonfinite, shadow=self.params_bf16)
+        self._w32, self._w16, self._on_ema = self.params, self.params_bf16, False    # what p() / pw() resolve to (ema_weights)
+        mask = build_decay_mask(self.layout, self.n_params, decays_matrix) if weight_decay > 0.0 else None
+        self.optim = FlatAdam(self.n_params, device, lr, beta1, clip_grad, skip_nonfinite, shadow=self.params_bf16,
+                              weight_decay=weight_decay, warmup_steps=warmup_steps, ema_decay=ema_decay, ema_warmup=ema_warmup,
+                              decay_mask=mask, ema_shadow=self.bf16_store)
         self.load_params(init_params(cfg, seed))
         self._wgrad_plans: Dict[tuple, tuple] = {}
         self._alloc_workspace(cfg.tokens)
@@ -123,11 +135,38 @@ class LayoutEngine(AdamSurface):
         return flat[off:off + math.prod(shape)].view(shape)
 
     def p(self, name: str) -> torch.Tensor:
-        return self.view(self.params, name)
+        """a parameter as the kernels read it: the live fp32 master - inside ema_weights(), its moving average"""
+        return self.view(self._w32, name)
 
     def pw(self, name: str) -> torch.Tensor:
-        """weight operand of a projection: the fp32 master, or its bf16 shadow in the bf16 mode"""
-        return self.view(self.params_bf16 if self.bf16_store else self.params, name)
+        """weight operand of a projection: the fp32 master, or its bf16 shadow in the bf16 mode (inside ema_weights(): the
+        average, or the average's bf16 shadow)"""
+        return self.view(self._w16 if self.bf16_store else self._w32, name)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block p() / pw() resolve to the weights' moving average (and its bf16 shadow): forward, rollout,
+        accumulate_metrics and evaluate_rollout run on the averaged model.  Nothing is copied.  Whatever would train or
+        overwrite weights raises inside it; leaving the block restores the live weights."""
+        if self.optim.ema is None:
+            raise RuntimeError("ema_weights() needs an engine built with ema_decay > 0")
+        self._not_on_ema("ema_weights")
+        self._w32, self._w16, self._on_ema = self.optim.ema, self.optim.ema_shadow, True
+        try:
+            yield self
+        finally:
+            self._w32, self._w16, self._on_ema = self.params, self.params_bf16, False
+
+    def _not_on_ema(self, what: str) -> None:
+        if self._on_ema:
+            raise RuntimeError("%s inside ema_weights(): the block evaluates on the averaged weights, it cannot train on or "
+                               "replace them" % what)
+
+    def ema_named_params(self) -> Dict[str, torch.Tensor]:
+        """name -> view of the moving average, the form named_params() / load_params() use"""
+        if self.optim.ema is None:
+            raise RuntimeError("ema_named_params() needs an engine built with ema_decay > 0")
+        return {n: self.view(self.optim.ema, n) for n in self.layout}
 
     def _refresh_shadow(self) -> None:
         if self.params_bf16 is not None:
@@ -137,26 +176,35 @@ class LayoutEngine(AdamSurface):
         return self.view(self.grads, name)
 
     def load_params(self, tensors: Dict[str, torch.Tensor]) -> None:
+        """(the moving average, where there is one, restarts from the loaded parameters)"""
+        self._not_on_ema("load_params")
         for name in self.layout:
-            self.p(name).copy_(tensors[name].to(torch.float32))
+            self.view(self.params, name).copy_(tensors[name].to(torch.float32))
         self._refresh_shadow()
+        self.optim.seed_ema(self.params)
 
     def named_params(self) -> Dict[str, torch.Tensor]:
-        return {n: self.p(n) for n in self.layout}
+        return {n: self.view(self.params, n) for n in self.layout}
 
     def named_grads(self) -> Dict[str, torch.Tensor]:
         return {n: self.g(n) for n in self.layout}
 
     def state_dict(self) -> Dict[str, object]:
-        return {"params": self.params.detach().cpu().clone(), "exp_avg": self.exp_avg.cpu().clone(),
-                "exp_avg_sq": self.exp_avg_sq.cpu().clone(), "step": self.optim.applied_steps(),
-                "layout": {k: (o, tuple(s)) for k, (o, s) in self.layout.items()}}
+        sd = {"params": self.params.detach().cpu().clone(), "exp_avg": self.exp_avg.cpu().clone(),
+              "exp_avg_sq": self.exp_avg_sq.cpu().clone(), "step": self.optim.applied_steps(),
+              "layout": {k: (o, tuple(s)) for k, (o, s) in self.layout.items()}}
+        if self.optim.ema is not None:
+            sd["ema"] = self.optim.ema.cpu().clone()
+        return sd
 
     def load_state_dict(self, sd: Dict[str, object]) -> None:
         if tuple(sd["params"].shape) != (self.n_params,):
             raise ValueError("checkpoint has %d parameters, model has %d" % (sd["params"].numel(), self.n_params))
+        self._not_on_ema("load_state_dict")
         self.params.copy_(sd["params"])
         self._refresh_shadow()
+        # the moving average: the checkpoint's where it brings one, else it restarts from the loaded parameters
+        self.optim.seed_ema(sd["ema"].to(self.device) if sd.get("ema") is not None else self.params)
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.optim.set_step(int(sd["step"]))
@@ -406,6 +454,7 @@ class LayoutEngine(AdamSurface):
         (+ its slab reduction) is launched on `self.side` as soon as its dY exists and runs CONCURRENTLY with the chain, filling the
         gaps its launches leave in the matrix pipes.  Ordering is by events: a side kernel waits for the producer of its dY, and the
         chain waits before it overwrites a buffer a side kernel still reads (du, dqkv, dx) and before a bucket goes to the reducer."""
+        self._not_on_ema("backward")
         cfg, d, ff = self.cfg, self.cfg.d, self.cfg.d_ff
         B, T, N, M = self._shape
         main = torch.cuda.current_stream(self.device)
@@ -512,6 +561,7 @@ class LayoutEngine(AdamSurface):
         Guarded step: the norm needs every gradient, so with a reducer it waits for ALL buckets and then runs one
         squared-norm pass and one Adam over the whole buffer - the split Adam below, which updates everything but the
         embeddings while their bucket is still in flight, is given up in that mode (and only there)."""
+        self._not_on_ema("train_step")
         loss = self.forward_backward(batch, reducer)
         if self.optim.guard is not None:
             if reducer is not None:
@@ -533,13 +583,20 @@ class LayoutEngine(AdamSurface):
     def adam_step(self, grad_scale: float = 1.0, lo: int = 0, hi: Optional[int] = None, advance: bool = True) -> None:
         """torch.optim.Adam(lr, betas=(beta1, 0.999)) on the flat buffer (reference src/trainer.py:83,258), or on its
         [lo, hi) slice (both multiples of 4); `advance` = False keeps the step count (second slice of one step)."""
+        self._not_on_ema("adam_step")
+        if self.optim.guard is not None:             # (whole buffer or an error: FlatAdam.step)
+            self.optim.step(self.params, self.grads, grad_scale, lo, hi, advance, self._stream())
+            return
         launch = call if self.timer is None else (
             lambda name, *a: self._timed("adam", 0.0, name, *a, nbytes=28.0 * ((self.n_params if hi is None else hi) - lo)))
         self.optim.step(self.params, self.grads, grad_scale, lo, hi, advance, self._stream(), launch)
 
     def optimizer_update(self, grad_scale: float = 1.0) -> None:
         """The guarded stage after backward and every gradient bucket; the 4 loss floats behind the parameters are not in the norm."""
-        self.optim.update_guarded(self.params, self.grads, grad_scale, self._stream())
+        self._not_on_ema("optimizer_update")
+        launch = None if self.timer is None else (        # bytes of the guarded Adam launch: FlatAdam.adam_bytes
+            lambda name, *a: self._timed("adam", 0.0, name, *a, nbytes=self.optim.adam_bytes()))
+        self.optim.update_guarded(self.params, self.grads, grad_scale, self._stream(), launch)
 
     # ------------------------------------------------------------------- hipGraph
     def capture_train_step(self, example_batch: Dict[str, torch.Tensor]):
@@ -549,16 +606,23 @@ class LayoutEngine(AdamSurface):
         touches is preallocated and no launch argument changes between steps (the Adam step counter moves to the
         device), so replay is bitwise identical to the eager step.  A guarded engine captures its guarded step: clipping,
         the skip and set_lr keep working across replays."""
+        self._not_on_ema("capture_train_step")
         self._check_batch(example_batch)
         counter = self.optim.begin_capture()     # the optimiser's device-side scalars
         static = {k: example_batch[k].clone() for k in ("slot_class", "slot_box", "tgt_class", "tgt_box", "valid")}
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         keep = (self.params.clone(), self.exp_avg.clone(), self.exp_avg_sq.clone(), counter.clone(), self.step_count)
+        # the recipe's state moves with the two capture passes too: the average, its bf16 copy, the outputs of ext
+        more = [t for t in (self.optim.ema, self.optim.ema_shadow, self.optim.guard.ext if self.optim.guard is not None else None)
+                if t is not None]
+        kept_more = [t.clone() for t in more]
         def restore():
             self.params.copy_(keep[0]); self.exp_avg.copy_(keep[1]); self.exp_avg_sq.copy_(keep[2])
             counter.copy_(keep[3]); self.step_count = keep[4]
             self._refresh_shadow()
+            for t, k in zip(more, kept_more):
+                t.copy_(k)
 
         with torch.cuda.stream(side):            # warm-up on a side stream, as stream capture requires
             self.train_step(static)

@@ -329,6 +329,11 @@ class GridNetHIP:
     def state_dict(self) -> Dict[str, torch.Tensor]:
         return self._export(self.params)
 
+    def weight_ranges(self) -> List[Tuple[int, int]]:
+        """[lo, hi) of every convolution weight in the flat layout (padded lanes included: they are zero and stay zero) -
+        what decoupled weight decay applies to; biases and PReLU slopes are outside."""
+        return [(op.w_off, op.b_off) for op in self.tape if isinstance(op, _Conv)]
+
     def named_grads(self) -> Dict[str, torch.Tensor]:
         return self._export(self.grads)
 

@@ -67,6 +67,8 @@ SIGNATURES = {
     "vlg_grad_sumsq": (I, [P, L, P, P]),
     "vlg_optim_control": (I, [P, P, I, F, F, F, F, P]),
     "vlg_adam_step_ctl": (I, [P, P, P, P, P, L, P, F, F, F, P]),
+    "vlg_optim_control_ext": (I, [P, P, P, I, F, F, F, F, P]),
+    "vlg_adamw_ema_step_ctl": (I, [P, P, P, P, P, P, P, P, L, P, P, F, F, F, P]),
     "vlg_image_loss_scratch": (I, []),
     "vlg_ce_nchw": (I, [P, P, P, P, P, I, I, L, F, P]),
     "vlg_l1_mean": (I, [P, P, P, P, P, L, F, P]),

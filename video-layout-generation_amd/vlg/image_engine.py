@@ -28,7 +28,7 @@ import torch
 from . import hip
 from .gridnet import GridNetHIP, reference_param_order
 from .hip import call, ptr
-from .optim import AdamSurface, FlatAdam
+from .optim import AdamSurface, FlatAdam, decay_mask_ranges
 from .spec import ADAM_BETA1, ADAM_BETA2, ADAM_EPS, ADAM_LR, IMG_MEAN, IMG_STD, OUT_MEAN, OUT_STD
 
 IMAGE_KEYS = ("frame1", "seg1", "frame2", "seg2", "frame3", "seg3", "e1", "e2")
@@ -38,10 +38,14 @@ W_L1, W_STYLE, W_CE = 40.0, 20.0, 10.0          # reference src/trainer.py:248-2
 class ImageEngine(AdamSurface):
     def __init__(self, batch: int, H: int, W: int, device, arch: str = "CoordGridNet", lr: float = ADAM_LR,
                  beta1: float = ADAM_BETA1, filters=(32, 64, 96), with_hed: bool = False, with_vgg: bool = False,
-                 precision: str = "fp32", clip_grad: float = 0.0, skip_nonfinite: bool = False):
+                 precision: str = "fp32", clip_grad: float = 0.0, skip_nonfinite: bool = False, weight_decay: float = 0.0,
+                 warmup_steps: int = 0, ema_decay: float = 0.0, ema_warmup: bool = False):
         """clip_grad / skip_nonfinite: the guarded optimiser step, as LayoutEngine's (vlg/optim.py, one FlatAdam each): global-norm
         clipping and a step that a non-finite gradient skips; set_lr turns it on too.  Off, the step is unchanged.  As there, the
         guard cannot be turned on after a capture with the plain optimiser - this engine has no capture, so nothing sets that latch.
+        weight_decay / warmup_steps / ema_decay / ema_warmup: the recipe of vlg/optim.py through the same FlatAdam - decoupled
+        decay on the convolution weights (not biases or PReLU slopes), warm-up in applied steps, a moving average of the
+        weights (`ema_state_dict()`; evaluating the pixel model under it is not built).
         precision: "fp32" (the reference's) or "bf16" - the 3x3 convolutions of GridNet, HED and VGG on bf16-rounded
         GEMM operands with fp32 accumulation (csrc/conv_bf16.hip); tensors, losses, gradients and Adam stay fp32."""
         if arch not in ("GridNet", "CoordGridNet"):
@@ -58,7 +62,11 @@ class ImageEngine(AdamSurface):
         if with_hed:
             from .hned import HNEDHIP
             self.hed = HNEDHIP(batch, H, W, device, precision=precision)
-        self.optim = FlatAdam(self.net.params.numel(), device, lr, beta1, clip_grad, skip_nonfinite)   # exp_avg, step_count, guard ...
+        n = self.net.params.numel()
+        mask = decay_mask_ranges(n, self.net.weight_ranges()) if weight_decay > 0.0 else None
+        self.optim = FlatAdam(n, device, lr, beta1, clip_grad, skip_nonfinite, weight_decay=weight_decay,      # exp_avg, step_count, guard ...
+                              warmup_steps=warmup_steps, ema_decay=ema_decay, ema_warmup=ema_warmup, decay_mask=mask)
+        self.optim.seed_ema(self.net.params)
         f32 = dict(dtype=torch.float32, device=device)
         self.x10 = torch.empty(batch, 10, H, W, **f32)
         self.f3 = torch.empty(batch, 3, H, W, **f32)
@@ -80,7 +88,15 @@ class ImageEngine(AdamSurface):
         return torch.cuda.current_stream().cuda_stream
 
     def load_state_dict(self, sd) -> None:
+        """(the moving average, where there is one, restarts from the loaded parameters)"""
         self.net.load_state_dict(sd)
+        self.optim.seed_ema(self.net.params)
+
+    def ema_state_dict(self):
+        """The moving average of the weights in state_dict()'s format: loadable as a model."""
+        if self.optim.ema is None:
+            raise RuntimeError("ema_state_dict() needs an engine built with ema_decay > 0")
+        return self.net._export(self.optim.ema)
 
     def state_dict(self):
         return self.net.state_dict()
@@ -100,7 +116,11 @@ class ImageEngine(AdamSurface):
         group = {"lr": self.lr, "betas": (self.beta1, ADAM_BETA2), "eps": ADAM_EPS, "weight_decay": 0, "amsgrad": False,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
                  "params": list(range(len(order)))}
-        return {"state": state, "param_groups": [group], "skipped": skipped}
+        out = {"state": state, "param_groups": [group], "skipped": skipped}
+        if self.optim.recipe:        # the recipe's scalars and the moving average (flat kernel layout), beside torch's keys
+            out.update({k: v for k, v in self.optim.flat_state().items()
+                        if k in ("weight_decay", "warmup_steps", "ema_decay", "ema_warmup", "ema")})
+        return out
 
     def load_optimizer(self, st: Dict[str, object]) -> None:
         """Accepts a torch.optim.Adam state_dict over the reference model's parameters (reference trainer.py:92) - mapped
@@ -120,7 +140,8 @@ class ImageEngine(AdamSurface):
             if len(steps) != 1:
                 raise ValueError("per-parameter step counts differ (%s): one flat Adam step cannot represent that" % sorted(steps)[:4])
             st = {"exp_avg": torch.zeros(n), "exp_avg_sq": torch.zeros(n), "step": steps.pop(), "skipped": st.get("skipped", 0),
-                  "lr": st["param_groups"][0].get("lr")}
+                  "lr": st["param_groups"][0].get("lr"),
+                  **{k: st[k] for k in ("weight_decay", "warmup_steps", "ema_decay", "ema_warmup", "ema") if k in st}}
             if state:
                 self.net.pack({name: state[i]["exp_avg"] for i, name in zip(ids, order)}, st["exp_avg"])
                 self.net.pack({name: state[i]["exp_avg_sq"] for i, name in zip(ids, order)}, st["exp_avg_sq"])
