@@ -93,6 +93,60 @@ int vlg_layernorm_bwd_bf16(const vlg_bf16* dy, const float* x, const float* mean
                            float* slabs, int64_t slab_stride, int64_t slab_capacity,
                            int64_t rows, int d, void* stream);
 
+/* --------------------------------------------------------------------- dropout
+ * SELF-ORACLE (tests/dropout_ref.py restates it): inverted dropout on a (rows, d) activation, fused into the layer-norm
+ * launch that follows it (forward) or precedes it (backward).  Sites of the layout-token model, 2L + 1 of them:
+ *   site 0        x0      = drop(embed(...))
+ *   site 1 + 2l   xmid_l  = x_l    + drop(proj(att_l) + proj_b)
+ *   site 2 + 2l   x_{l+1} = xmid_l + drop(ff2(gelu(...)) + ff2_b)          (the bias is inside the dropout)
+ * Mask: thr = min(floor(p * 2^32 + 0.5), 2^32 - 1), scale = fp32(1 / (1 - thr / 2^32)) computed in double
+ * (vlg_dropout_plan is the one place this rule lives).  Element (row m, column c) of site s at step k under the 64-bit
+ * seed is KEPT iff x_w >= thr, x_w = word w = c % 4 of Philox4x32-10 with counter (m, c / 4, s, k) and key
+ * (seed & 0xffffffff, seed >> 32); m is the internal row index.  One Philox call serves one float4; a mask bit is a
+ * function of (m, c, s, k, seed) alone, never of the launch geometry; thr = 0 keeps everything with scale 1.
+ * Values are chosen by SELECT, not by a product: select(v) = kept ? v * scale : 0, exactly 0 whatever a dropped v holds
+ * (inf, NaN).  k is an int32 in DEVICE memory that the kernels read when they run, so a captured graph advances it by
+ * replaying vlg_dropout_step_advance.  Nothing is stored for backward: it recomputes the mask.
+ *
+ * vlg_dropout_plan (host only; thr_host / scale_host are HOST pointers): VLG_ERR_SHAPE unless 0 <= p < 1.
+ *
+ * vlg_dropout_add_layernorm_fwd:  x_out = (resid ? resid : 0) + select(y);  h = LN(x_out), mean / rstd saved, with
+ * vlg_layernorm_fwd's arithmetic, d set, row grouping and wave-per-row layout.  resid may be NULL (site 0).  x_out may
+ * BE y (in place); every other overlap among y, resid, x_out, h is refused.  _bf16: h stored as bf16, as
+ * vlg_layernorm_fwd_bf16 does.  Algorithmic bytes per row: (8 + 4 [resid] + 4 | 2 [h]) * d.
+ *
+ * vlg_layernorm_bwd_dropout:  exactly vlg_layernorm_bwd - dx_out and every slab bit for bit: it is the same kernel with
+ * its second output switched on - plus dy_drop = select(dx_out) under the mask of the site that FEEDS this layer-norm (the gradient of that site's y).  dres
+ * may BE dx_out, as in vlg_layernorm_bwd; dy_drop overlaps none of dy, x, dres, dx_out; dx_out overlaps neither dy nor x.
+ * _bf16: dy read as bf16.  One more 4 * d bytes per row than vlg_layernorm_bwd, no extra launch.
+ *
+ * Refusals, all before anything is enqueued.  VLG_ERR_SHAPE: rows < 1 or rows >= 2^32 (the row is a 32-bit counter
+ * word), d outside vlg_layernorm_fwd's set, site < 0, scale outside [1, 2^32], step NULL, a short slab buffer, a
+ * forbidden overlap.  VLG_ERR_ALIGN: a NULL pointer (resid and dres excepted) or y, resid, x_out, gamma, beta, fp32 h,
+ * dy, x, dres, dx_out, dy_drop not 16-byte aligned (bf16 h / dy: 8), mean, rstd, slabs, step not 4.
+ *
+ * vlg_dropout_step_advance: a one-thread launch, *step += 1. */
+int vlg_dropout_plan(double p, uint32_t* thr_host, float* scale_host);
+int vlg_dropout_add_layernorm_fwd(const float* y, const float* resid, const float* gamma, const float* beta,
+                                  float* x_out, float* h, float* mean, float* rstd,
+                                  int64_t rows, int d, float eps,
+                                  uint32_t thr, float scale, uint64_t seed, int site, const int* step, void* stream);
+int vlg_dropout_add_layernorm_fwd_bf16(const float* y, const float* resid, const float* gamma, const float* beta,
+                                       float* x_out, vlg_bf16* h, float* mean, float* rstd,
+                                       int64_t rows, int d, float eps,
+                                       uint32_t thr, float scale, uint64_t seed, int site, const int* step, void* stream);
+int vlg_layernorm_bwd_dropout(const float* dy, const float* x, const float* mean, const float* rstd,
+                              const float* gamma, const float* dres, float* dx_out, float* dy_drop,
+                              float* slabs, int64_t slab_stride, int64_t slab_capacity,
+                              int64_t rows, int d,
+                              uint32_t thr, float scale, uint64_t seed, int site, const int* step, void* stream);
+int vlg_layernorm_bwd_dropout_bf16(const vlg_bf16* dy, const float* x, const float* mean, const float* rstd,
+                                   const float* gamma, const float* dres, float* dx_out, float* dy_drop,
+                                   float* slabs, int64_t slab_stride, int64_t slab_capacity,
+                                   int64_t rows, int d,
+                                   uint32_t thr, float scale, uint64_t seed, int site, const int* step, void* stream);
+int vlg_dropout_step_advance(int* step, void* stream);
+
 /* ------------------------------------------------------------------------ GEMM
  * fp32 MFMA (v_mfma_f32_32x32x2_f32) GEMMs for the dense QKV/FFN/head projections.
  * SELF-ORACLE (F.linear arithmetic); the reference's dense contraction is conv only.

@@ -7,49 +7,11 @@
 // sums stay in registers across the grid-stride loop, are combined across the block's 4
 // waves through LDS and leave as one [dgamma | dbeta] slab per block (reduced by
 // vlg_reduce_slabs: reproducible, no atomics).
-#include "common.h"
-
-#define LN_BLOCK 256
-#define LN_WAVES (LN_BLOCK / 64)
-#define LN_BWD_MAX_BLOCKS 512
-
-// E = floats per lane; V4 => lane holds E/4 float4 at columns 4*lane + 256*i, else scalars at lane + 64*i
-template <int E, bool V4>
-struct RowIO {
-    template <typename EL>
-    __device__ static __forceinline__ void load(const EL* __restrict__ row, int lane, float (&v)[E]) {
-        if constexpr (V4) {
-#pragma unroll
-            for (int i = 0; i < E / 4; ++i) {
-                const float4 t = ld4(row + 4 * lane + 256 * i);
-                v[4 * i] = t.x; v[4 * i + 1] = t.y; v[4 * i + 2] = t.z; v[4 * i + 3] = t.w;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < E; ++i) v[i] = ld1(row + lane + 64 * i);
-        }
-    }
-    template <typename EL>
-    __device__ static __forceinline__ void store(EL* __restrict__ row, int lane, const float (&v)[E]) {
-        if constexpr (V4) {
-#pragma unroll
-            for (int i = 0; i < E / 4; ++i)
-                st4(row + 4 * lane + 256 * i, make_float4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]));
-        } else {
-#pragma unroll
-            for (int i = 0; i < E; ++i) st1(row + lane + 64 * i, v[i]);
-        }
-    }
-    // column index of register j
-    __device__ static __forceinline__ int col(int lane, int j) {
-        if constexpr (V4) return 4 * lane + 256 * (j >> 2) + (j & 3);
-        else return lane + 64 * j;
-    }
-};
-
-// rows a wave holds in flight per loop trip: one 1-KB row per wave leaves too few bytes in flight to cover the HBM latency
-// (8 192 resident waves x 1 KB = 8 MB against ~16 MB for 8 TB/s x 2 us), so short rows are processed LN_ROWS(E) at a time
-#define LN_ROWS(E) ((E) <= 4 ? 4 : (E) <= 8 ? 2 : 1)
+// The backward kernel also serves the fused dropout backward of dropout.hip: with dp.out set it writes a second output,
+// select(dx_out), behind a wave-uniform branch.  ONE kernel for both, so that vlg_layernorm_bwd_dropout's dx_out and
+// slabs are vlg_layernorm_bwd's bit for bit by construction: two kernels compiled from the same statements are not (the
+// compiler contracts a - s1 with the 1/d product or not depending on the code around it).
+#include "layernorm_rows.h"      // RowIO, LN_ROWS, the block counts and LN_DISPATCH (shared with dropout.hip)
 
 template <int E, bool V4, typename EY = float>
 __global__ __launch_bounds__(LN_BLOCK) void ln_fwd_kernel(
@@ -93,7 +55,7 @@ template <int E, bool V4, typename EY = float>
 __global__ __launch_bounds__(LN_BLOCK) void ln_bwd_kernel(
     const EY* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean,
     const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ dres,
-    float* __restrict__ dx_out, float* __restrict__ slabs, int64_t slab_stride, int64_t rows) {
+    float* __restrict__ dx_out, float* __restrict__ slabs, int64_t slab_stride, int64_t rows, const LnDrop dp) {
     constexpr int d = E * 64, R = LN_ROWS(E);
     __shared__ float red[LN_WAVES][2 * d];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -138,7 +100,16 @@ __global__ __launch_bounds__(LN_BLOCK) void ln_bwd_kernel(
             s2 = wave_sum(s2) * (1.0f / d);
 #pragma unroll
             for (int j = 0; j < E; ++j) o[i][j] += rs[i] * (gy[i][j] - s1 - xv[i][j] * s2);
-            if (r0 + i < rows) RowIO<E, V4>::store(dx_out + (r0 + i) * d, lane, o[i]);
+            if (r0 + i < rows) {
+                RowIO<E, V4>::store(dx_out + (r0 + i) * d, lane, o[i]);
+                if (dp.out != nullptr) {       // fused dropout (dropout.hip): kept ? dx_out * scale : 0 under the feeding site's mask
+                    bool keep[E];
+                    drop_keep<E, V4>(dp, (uint32_t)*dp.step, r0 + i, lane, keep);
+#pragma unroll
+                    for (int j = 0; j < E; ++j) o[i][j] = keep[j] ? o[i][j] * dp.scale : 0.f;
+                    RowIO<E, V4>::store(dp.out + (r0 + i) * d, lane, o[i]);
+                }
+            }
         }
     }
 #pragma unroll
@@ -157,27 +128,6 @@ __global__ __launch_bounds__(LN_BLOCK) void ln_bwd_kernel(
     }
 }
 
-static int ln_fwd_blocks(int64_t rows) {
-    int64_t b = (rows + LN_WAVES - 1) / LN_WAVES;
-    return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
-}
-static int ln_bwd_blocks(int64_t rows) {
-    int64_t b = (rows + LN_WAVES - 1) / LN_WAVES;
-    return (int)(b > LN_BWD_MAX_BLOCKS ? LN_BWD_MAX_BLOCKS : (b < 1 ? 1 : b));
-}
-
-#define LN_DISPATCH(d, CALL)                                 \
-    switch (d) {                                             \
-        case 64:   { CALL(1, false) } break;                 \
-        case 128:  { CALL(2, false) } break;                 \
-        case 192:  { CALL(3, false) } break;                 \
-        case 256:  { CALL(4, true) } break;                  \
-        case 512:  { CALL(8, true) } break;                  \
-        case 768:  { CALL(12, true) } break;                 \
-        case 1024: { CALL(16, true) } break;                 \
-        default: return VLG_ERR_SHAPE;                       \
-    }
-
 extern "C" int vlg_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y,
                                  float* mean, float* rstd, int64_t rows, int d, float eps, void* stream) {
     if (rows < 1) return VLG_ERR_SHAPE;
@@ -192,6 +142,25 @@ extern "C" int vlg_layernorm_fwd(const float* x, const float* gamma, const float
 
 extern "C" int vlg_layernorm_bwd_slabs(int64_t rows) { return ln_bwd_blocks(rows); }
 
+// launch of the one backward kernel, arguments already checked (declared in layernorm_rows.h; dropout.hip calls it with dp.out set)
+int ln_bwd_launch(const void* dy, bool dy_bf16, const float* x, const float* mean, const float* rstd, const float* gamma,
+                  const float* dres, float* dx_out, float* slabs, int64_t slab_stride, int64_t rows, int d, const LnDrop& dp,
+                  hipStream_t s) {
+    const dim3 grid(ln_bwd_blocks(rows)), block(LN_BLOCK);
+    if (dy_bf16) {
+        const bf16_t* dyb = static_cast<const bf16_t*>(dy);
+#define CALL(E, V4) hipLaunchKernelGGL((ln_bwd_kernel<E, V4, bf16_t>), grid, block, 0, s, dyb, x, mean, rstd, gamma, dres, dx_out, slabs, slab_stride, rows, dp);
+        LN_DISPATCH(d, CALL)
+#undef CALL
+    } else {
+        const float* dyf = static_cast<const float*>(dy);
+#define CALL(E, V4) hipLaunchKernelGGL((ln_bwd_kernel<E, V4>), grid, block, 0, s, dyf, x, mean, rstd, gamma, dres, dx_out, slabs, slab_stride, rows, dp);
+        LN_DISPATCH(d, CALL)
+#undef CALL
+    }
+    return vlg_last_error();
+}
+
 extern "C" int vlg_layernorm_bwd(const float* dy, const float* x, const float* mean, const float* rstd,
                                  const float* gamma, const float* dres, float* dx_out, float* slabs,
                                  int64_t slab_stride, int64_t slab_capacity, int64_t rows, int d, void* stream) {
@@ -199,12 +168,7 @@ extern "C" int vlg_layernorm_bwd(const float* dy, const float* x, const float* m
     if (slab_capacity < (int64_t)ln_bwd_blocks(rows) * slab_stride) return VLG_ERR_SHAPE;   // every block writes one slab
     if (!vlg_aligned16(dy) || !vlg_aligned16(x) || !vlg_aligned16(gamma) || !vlg_aligned16(dx_out) ||
         (dres && !vlg_aligned16(dres))) return VLG_ERR_ALIGN;
-    const dim3 grid(ln_bwd_blocks(rows)), block(LN_BLOCK);
-    hipStream_t s = (hipStream_t)stream;
-#define CALL(E, V4) hipLaunchKernelGGL((ln_bwd_kernel<E, V4>), grid, block, 0, s, dy, x, mean, rstd, gamma, dres, dx_out, slabs, slab_stride, rows);
-    LN_DISPATCH(d, CALL)
-#undef CALL
-    return vlg_last_error();
+    return ln_bwd_launch(dy, false, x, mean, rstd, gamma, dres, dx_out, slabs, slab_stride, rows, d, LnDrop{}, (hipStream_t)stream);
 }
 
 extern "C" int vlg_layernorm_fwd_bf16(const float* x, const float* gamma, const float* beta, vlg_bf16* y,
@@ -227,11 +191,5 @@ extern "C" int vlg_layernorm_bwd_bf16(const vlg_bf16* dy, const float* x, const 
     if (slab_capacity < (int64_t)ln_bwd_blocks(rows) * slab_stride) return VLG_ERR_SHAPE;   // every block writes one slab
     if (!vlg_aligned8(dy) || !vlg_aligned16(x) || !vlg_aligned16(gamma) || !vlg_aligned16(dx_out) ||
         (dres && !vlg_aligned16(dres))) return VLG_ERR_ALIGN;
-    const dim3 grid(ln_bwd_blocks(rows)), block(LN_BLOCK);
-    hipStream_t s = (hipStream_t)stream;
-    const bf16_t* dyb = reinterpret_cast<const bf16_t*>(dy);
-#define CALL(E, V4) hipLaunchKernelGGL((ln_bwd_kernel<E, V4, bf16_t>), grid, block, 0, s, dyb, x, mean, rstd, gamma, dres, dx_out, slabs, slab_stride, rows);
-    LN_DISPATCH(d, CALL)
-#undef CALL
-    return vlg_last_error();
+    return ln_bwd_launch(dy, true, x, mean, rstd, gamma, dres, dx_out, slabs, slab_stride, rows, d, LnDrop{}, (hipStream_t)stream);
 }

@@ -39,6 +39,11 @@ when the average is on): layout mode's validate(), generate_sequence() and evalu
 (LayoutEngine.ema_weights()).  save_checkpoint adds 'gridnet_ema', the averaged model in 'gridnet''s format; --resume
 restores the average through 'optimizer'.
 
+Dropout in layout mode (off by default; csrc/dropout.hip, DESIGN.md "Dropout"): args.dropout / VLG_DROPOUT = p in [0, 1) drops
+the embedding and the two residual branches of every layer in training steps only - validate(), generation and the
+averaged weights stay evaluation; VLG_DROPOUT_SEED (default args.seed) seeds the stateless mask, and data-parallel rank r
+uses seed + r so that ranks draw different masks.
+
 Generation knobs of generate_sequence in layout mode (a keyword argument wins over them; csrc/decode.hip, DESIGN.md
 "Generation"): args.gen_temperature / VLG_GEN_TEMPERATURE (0 = argmax; > 0 samples from softmax(logits / temperature)),
 args.gen_top_k / VLG_GEN_TOP_K (0 = every class, else only the k largest logits), args.gen_seed / VLG_GEN_SEED (default
@@ -157,6 +162,20 @@ def optim_knobs(args) -> Dict[str, object]:
     return knobs
 
 
+def dropout_knobs(args) -> Dict[str, object]:
+    """the engine's dropout keyword arguments from args / environment (module docstring): {} with the knob off, so an
+    engine without the option is never handed one; else {dropout, dropout_seed}, the seed offset by the data-parallel rank."""
+    p = _knob_float(args, "dropout", "VLG_DROPOUT", 0.0)
+    if not 0.0 <= p < 1.0:                              # (also refuses NaN)
+        raise ValueError("VLG_DROPOUT must be in [0, 1), got %r" % p)
+    seed = _knob(args, "dropout_seed", "VLG_DROPOUT_SEED", int(getattr(args, "seed", SEED)))
+    if not 0 <= seed < 2 ** 63:
+        raise ValueError("VLG_DROPOUT_SEED must be in [0, 2^63), got %r" % seed)
+    if p == 0.0:
+        return {}
+    return {"dropout": p, "dropout_seed": seed + int(getattr(args, "rank", 0) or 0)}
+
+
 def recipe_kwargs(knobs: Dict[str, object]) -> Dict[str, object]:
     """the recipe's engine keyword arguments - only those that are on, so an engine factory without them is never handed one"""
     return {k: knobs[k] for k in ("weight_decay", "warmup_steps", "ema_decay", "ema_warmup") if knobs.get(k)}
@@ -207,7 +226,8 @@ def get_layout_engine(args, cfg: Optional[LayoutConfig] = None, engine_factory: 
                               lr=float(getattr(args, "lr", ADAM_LR)), beta1=float(getattr(args, "beta1", ADAM_BETA1)),
                               precision=precision,
                               padded_slots=bool(_knob(args, "variable_n", "VLG_VARIABLE_N", 0)),   # fixed-N feeds hold no padded slots
-                              clip_grad=knobs["clip_grad"], skip_nonfinite=knobs["skip_nonfinite"], **recipe_kwargs(knobs))
+                              clip_grad=knobs["clip_grad"], skip_nonfinite=knobs["skip_nonfinite"], **recipe_kwargs(knobs),
+                              **dropout_knobs(args))
     else:
         engine = engine_factory(cfg, args)
     if knobs["lr_decay"]:                            # guarded from the start, so a checkpoint's lr and skip count are resumed
@@ -396,8 +416,11 @@ class Trainer:
         if torch.cuda.is_available() and engine_factory is None:
             torch.cuda.set_device(int(args.rank))               # reference src/trainer.py:110
         self.cfg = layout_config(args)
+        self.dropout = dropout_knobs(args)                      # (out-of-range values raise here, before any engine exists)
         self.image_mode = engine_factory is None and os.environ.get("VLG_MODEL", "layout").lower() == "gridnet"
         self.reducer = None
+        if self.image_mode and self.dropout:
+            raise ValueError("VLG_DROPOUT is a knob of the layout-token step; VLG_MODEL=gridnet has no dropout")
         if self.image_mode:
             self.engine = _ImageModel(args, self.cfg.B)
             if self.distributed:                                # replaces DDP(gridnet), trainer.py:113: bucket per grid column

@@ -16,6 +16,7 @@ Row order of every (M, .) activation is the internal  m = (b*N + n)*T + t.
 from __future__ import annotations
 
 import contextlib
+import ctypes
 import math
 import os
 from typing import Dict, Optional
@@ -66,7 +67,7 @@ class LayoutEngine(AdamSurface):
     def __init__(self, cfg: LayoutConfig, device: torch.device, seed: int = 1024,
                  lr: float = ADAM_LR, beta1: float = ADAM_BETA1, precision: str = "fp32", padded_slots: bool = True,
                  clip_grad: float = 0.0, skip_nonfinite: bool = False, weight_decay: float = 0.0, warmup_steps: int = 0,
-                 ema_decay: float = 0.0, ema_warmup: bool = False):
+                 ema_decay: float = 0.0, ema_warmup: bool = False, dropout: float = 0.0, dropout_seed: int = 0):
         """clip_grad > 0 clips the gradient to that global L2 norm (torch.nn.utils.clip_grad_norm_'s rule); skip_nonfinite
         leaves parameters, moments and step count untouched when the gradient holds inf or NaN.  Either one - or a call
         of set_lr - turns on the GUARDED optimiser step (vlg/optim.py), eager and captured alike; with both off and
@@ -87,8 +88,21 @@ class LayoutEngine(AdamSurface):
                     three bf16 terms, six bf16 MFMAs per product block (csrc/gemm_split.hip).
         The residual stream and its gradient, layer-norm statistics, softmax, losses, weight gradients, Adam and the
         master weights are fp32 in all three.  attention = "clip" follows the storage: its bf16 entry points under "bf16"
-        (bf16 MFMA, fp32 scores and softmax statistics), the fp32 kernels otherwise (bf16_mfma included)."""
+        (bf16 MFMA, fp32 scores and softmax statistics), the fp32 kernels otherwise (bf16_mfma included).
+        dropout = p in [0, 1) (0 = off: nothing allocated, no launch changed): inverted dropout on the embedding and on
+        the two residual branches of every layer (2L + 1 sites; rule and sites: include/vlg_hip.h, "dropout"), fused into
+        the step's layer-norm launches.  Only forward_backward / train_step / capture_train_step apply it; a bare
+        forward(), rollout(), evaluate_rollout(), accumulate_metrics() and everything under ema_weights() stay
+        evaluation.  The mask is a stateless Philox function of (row, column, site, step) under dropout_seed; the step is a
+        device counter (dropout_step / set_dropout_step) advanced once per training forward+backward, whether or not the
+        guarded optimiser then skips.  Not combined with VLG_OVERLAP_WGRAD=1."""
         cfg.validate()
+        self.dropout = float(dropout)
+        if not 0.0 <= self.dropout < 1.0:
+            raise ValueError("dropout must be in [0, 1), got %r" % (dropout,))
+        if self.dropout > 0.0 and os.environ.get("VLG_OVERLAP_WGRAD", "0") == "1":
+            raise ValueError("VLG_OVERLAP_WGRAD=1 together with dropout=%g is not supported: the side stream's hazard "
+                             "tracking does not cover the dropout gradient buffer" % self.dropout)
         if precision not in ("fp32", "bf16", "bf16_mfma", "fp32x3"):
             raise ValueError("precision must be fp32, fp32x3, bf16 or bf16_mfma")
         # attention = "clip": padded slots (batch['valid'] == 0) must not be attended to; padded_slots = False tells the engine
@@ -109,6 +123,13 @@ class LayoutEngine(AdamSurface):
         if device.type != "cuda":
             raise hip.HipError("LayoutEngine needs a HIP device (got %s); there is no CPU path" % device)
         self.cfg, self.device = cfg, device
+        # dropout: (thr, scale, seed) for the kernels + the device step counter, or None with the knob off
+        self._drop, self.drop_step, self._dropped = None, None, False
+        if self.dropout > 0.0:
+            thr, scale = ctypes.c_uint32(), ctypes.c_float()
+            hip.check(hip.load().vlg_dropout_plan(self.dropout, ctypes.byref(thr), ctypes.byref(scale)), "vlg_dropout_plan")
+            self._drop = (thr.value, scale.value, int(dropout_seed) & 0xFFFFFFFFFFFFFFFF)
+            self.drop_step = torch.zeros(1, dtype=torch.int32, device=device)
         self.layout, self.n_params = param_layout(cfg)
         f32 = dict(dtype=torch.float32, device=device)
         self.params = torch.zeros(self.n_params, **f32)
@@ -195,6 +216,8 @@ class LayoutEngine(AdamSurface):
               "layout": {k: (o, tuple(s)) for k, (o, s) in self.layout.items()}}
         if self.optim.ema is not None:
             sd["ema"] = self.optim.ema.cpu().clone()
+        if self._drop is not None:               # (knob off: the checkpoint is what it was without the option)
+            sd["dropout_step"] = self.dropout_step
         return sd
 
     def load_state_dict(self, sd: Dict[str, object]) -> None:
@@ -208,6 +231,22 @@ class LayoutEngine(AdamSurface):
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.optim.set_step(int(sd["step"]))
+        if self._drop is not None and sd.get("dropout_step") is not None:
+            self.set_dropout_step(int(sd["dropout_step"]))
+
+    @property
+    def dropout_step(self) -> int:
+        """the dropout step counter k the next training step will read (a host read: it waits for the device)"""
+        if self._drop is None:
+            raise RuntimeError("dropout_step needs an engine built with dropout > 0")
+        return int(self.drop_step.item())
+
+    def set_dropout_step(self, k: int) -> None:
+        if self._drop is None:
+            raise RuntimeError("set_dropout_step needs an engine built with dropout > 0")
+        if not 0 <= int(k) < 2 ** 31:
+            raise ValueError("dropout step must be in [0, 2^31), got %r" % (k,))
+        self.drop_step.fill_(int(k))
 
     def optimizer_state(self) -> Dict[str, object]:
         """Adam state for the checkpoint's 'optimizer' entry (flat tensors, CPU)."""
@@ -240,6 +279,11 @@ class LayoutEngine(AdamSurface):
         self.dh = torch.empty(M, d, **act)
         self.du = torch.empty(M, ff, **act)
         self.dqkv = torch.empty(M, 3 * d, **act)
+        if self._drop is not None:
+            if M >= 2 ** 32:
+                raise ValueError("dropout: %d rows do not fit the mask's 32-bit row counter" % M)
+            self.ybranch = torch.empty(M, d, **f32)       # proj / ff2 output (+ bias) on its way into a dropout site
+            self.ddrop = torch.empty(M, d, **f32)         # gradient of that output: select(dx) of the site's layer-norm backward
         self.loss_scratch = torch.zeros(lib.vlg_layout_loss_scratch(), **f32)
         # validation metrics (vlg_layout_metrics): per-block partial sums and the ticket, zero between launches
         self.metrics_scratch = torch.zeros(lib.vlg_layout_metrics_scratch(), dtype=torch.float64, device=self.device)
@@ -373,11 +417,30 @@ class LayoutEngine(AdamSurface):
                     ptr(self.p(gname[:-1] + "b")), ptr(y), ptr(stat[0]), ptr(stat[1]), M, d, LN_EPS, self._stream(),
                     nbytes=(4.0 + y.element_size()) * M * d)
 
-    def _ln_bwd(self, dy, x, stat, gname, dres, dx_out, M):
+    def _drop_ln_fwd(self, y, resid, x_out, gname, h, stat, site, M):
+        """x_out = resid + drop_site(y), h = LN(x_out): the fused launch that stands where a training forward had _ln_fwd"""
+        d = self.cfg.d
+        thr, scale, seed = self._drop
+        self._timed("ln_fwd", 0.0, "vlg_dropout_add_layernorm_fwd" + ("_bf16" if h.dtype == torch.bfloat16 else ""), ptr(y), ptr(resid),
+                    ptr(self.p(gname)), ptr(self.p(gname[:-1] + "b")), ptr(x_out), ptr(h), ptr(stat[0]), ptr(stat[1]), M, d,
+                    LN_EPS, thr, scale, seed, site, ptr(self.drop_step), self._stream(),
+                    nbytes=(8.0 + (4.0 if resid is not None else 0.0) + h.element_size()) * M * d)
+
+    def _ln_bwd(self, dy, x, stat, gname, dres, dx_out, M, site=None):
+        """site: the dropout site that produced x.  After a training forward with dropout the fused variant also leaves
+        select(dx_out) under that site's mask in self.ddrop"""
         d = self.cfg.d
         n_slabs = hip.load().vlg_layernorm_bwd_slabs(M)
         arena = self.buckets.reserve(n_slabs * 2 * d)
         s = self._stream()
+        if self._dropped:
+            thr, scale, seed = self._drop
+            self._timed("ln_bwd", 0.0, "vlg_layernorm_bwd_dropout" + ("_bf16" if dy.dtype == torch.bfloat16 else ""), ptr(dy), ptr(x),
+                        ptr(stat[0]), ptr(stat[1]), ptr(self.p(gname)), ptr(dres), ptr(dx_out), ptr(self.ddrop), ptr(arena), 2 * d,
+                        arena.numel(), M, d, thr, scale, seed, site, ptr(self.drop_step), s,
+                        nbytes=(dy.element_size() + 4.0 + 4.0 + 4.0 + (4.0 if dres is not None else 0.0)) * M * d)
+            self.buckets.add(arena, 2 * d, n_slabs, self.grads.data_ptr() + 4 * self.layout[gname][0], 2 * d, s)
+            return
         self._timed("ln_bwd", 0.0, "vlg_layernorm_bwd_bf16" if dy.dtype == torch.bfloat16 else "vlg_layernorm_bwd", ptr(dy), ptr(x), ptr(stat[0]),
                     ptr(stat[1]), ptr(self.p(gname)), ptr(dres), ptr(dx_out), ptr(arena), 2 * d, arena.numel(), M, d, s,
                     nbytes=(dy.element_size() + 4.0 + 4.0 + (4.0 if dres is not None else 0.0)) * M * d)
@@ -402,15 +465,23 @@ class LayoutEngine(AdamSurface):
     def forward(self, batch: Dict[str, torch.Tensor], padded_slots: Optional[bool] = None) -> torch.Tensor:
         """Forward + fused loss (the loss kernel also leaves d(total)/d(out) in self.dout).
         Returns the device tensor {total, smooth_l1, iou, ce}.  padded_slots overrides the engine's setting for this
-        forward and the backward that follows it: a rollout window can hold padded slots where training batches never do."""
+        forward and the backward that follows it: a rollout window can hold padded slots where training batches never do.
+        Evaluation on a dropout engine too: only forward_backward / train_step drop."""
+        return self._forward(batch, padded_slots, False)
+
+    def _forward(self, batch: Dict[str, torch.Tensor], padded_slots: Optional[bool], train: bool) -> torch.Tensor:
         cfg, d = self.cfg, self.cfg.d
         B, T, N, M = self._check_batch(batch)
         self._masked = self.padded_slots if padded_slots is None else bool(padded_slots)
         self._shape = (B, T, N, M)
+        self._dropped = bool(train) and self._drop is not None and not self._on_ema    # this forward's choice; its backward follows it
         s = self._stream()
-        self._encode(batch, B, T, N, M)
         L = cfg.n_layers
-        self._ln_fwd(self.x[L], "lnf_g", self.xf, self.stats[2 * L], M)
+        if self._dropped:
+            self._encode_dropout(batch, B, T, N, M)                 # (ends with the fused final norm)
+        else:
+            self._encode(batch, B, T, N, M)
+            self._ln_fwd(self.x[L], "lnf_g", self.xf, self.stats[2 * L], M)
         self._linear(self.xf, self.pw("head_w"), self.p("head_b"), self.out, M, cfg.n_out, d, EPI_BIAS)
         self._timed("loss", 0.0, "vlg_layout_loss", ptr(self.out), cfg.n_out, ptr(batch["tgt_class"]), ptr(batch["tgt_box"]),
                     ptr(batch["valid"]), ptr(self.dout), ptr(self.loss_out), ptr(self.loss_scratch), B, T, N,
@@ -441,6 +512,31 @@ class LayoutEngine(AdamSurface):
             self._linear(self.gl[l], self.pw(pre + "ff2_w"), self.p(pre + "ff2_b"), self.x[l + 1], M, d, ff,
                          EPI_BIAS | EPI_RESID, aux_in=self.xmid[l])
 
+    def _encode_dropout(self, batch: Dict[str, torch.Tensor], B: int, T: int, N: int, M: int) -> None:
+        """_encode for a training forward with dropout, through the final norm.  As many launches as _encode + that norm:
+        proj and ff2 write branch + bias into self.ybranch (no residual epilogue), and every layer-norm launch is the fused
+        one, which forms the residual sum under its site's mask on the way.  Site 0 runs in place on x[0]."""
+        cfg, d, ff = self.cfg, self.cfg.d, self.cfg.d_ff
+        s, L, y = self._stream(), cfg.n_layers, self.ybranch
+        self._timed("embed_fwd", 0.0, "vlg_embed_fwd", ptr(batch["slot_class"]), ptr(batch["slot_box"]), ptr(self.p("cls_emb")),
+                    ptr(self.p("box_w")), ptr(self.p("box_b")), ptr(self.p("time_emb")), ptr(self.x[0]),
+                    B, T, N, d, cfg.vocab, s, nbytes=4.0 * M * d + 24.0 * M)
+        self._drop_ln_fwd(self.x[0], None, self.x[0], "l0.ln1_g", self.h1[0], self.stats[0], 0, M)
+        for l in range(L):
+            pre = "l%d." % l
+            self._linear(self.h1[l], self.pw(pre + "qkv_w"), self.p(pre + "qkv_b"), self.qkv[l], M, 3 * d, d, EPI_BIAS)
+            self._attn_fwd(l, batch, B, T, N, M)
+            self._linear(self.att[l], self.pw(pre + "proj_w"), self.p(pre + "proj_b"), y, M, d, d, EPI_BIAS)
+            self._drop_ln_fwd(y, self.x[l], self.xmid[l], pre + "ln2_g", self.h2[l], self.stats[2 * l + 1], 1 + 2 * l, M)
+            self._linear(self.h2[l], self.pw(pre + "ff1_w"), self.p(pre + "ff1_b"), self.gl[l], M, ff, d,
+                         self._epi_ff1, aux_out=self.u[l])
+            self._linear(self.gl[l], self.pw(pre + "ff2_w"), self.p(pre + "ff2_b"), y, M, d, ff, EPI_BIAS)
+            if l + 1 < L:
+                self._drop_ln_fwd(y, self.xmid[l], self.x[l + 1], "l%d.ln1_g" % (l + 1), self.h1[l + 1], self.stats[2 * l + 2],
+                                  2 + 2 * l, M)
+            else:
+                self._drop_ln_fwd(y, self.xmid[l], self.x[L], "lnf_g", self.xf, self.stats[2 * L], 2 + 2 * l, M)
+
     # -------------------------------------------------------------------- backward
     def backward(self, batch: Dict[str, torch.Tensor], reducer=None) -> None:
         """Fills self.grads (every element overwritten) from the state forward() left.  `reducer`
@@ -450,6 +546,9 @@ class LayoutEngine(AdamSurface):
         Default: ONE stream.  Each projection's data and weight gradient go through one paired call (`pair_backward`), one
         table-driven launch reduces the partial sums of a bucket - the head, a layer, the embeddings (`group_reduce`) - and a
         finished bucket's reduction rides in the next paired launch instead (`ride_reduces`, vlg/slabs.py).
+        After a training forward with dropout every layer-norm backward is the fused variant: it also writes select(dx) under the
+        mask of the site that fed it into self.ddrop, which - not self.dx - is the dY of the next proj / ff2 backward and what the
+        embedding backward reads; self.dx keeps carrying the residual gradient.  One counter advance ends the backward.
         Option, VLG_OVERLAP_WGRAD=1: two HIP streams.  The data-gradient chain stays on the caller's stream; every weight gradient
         (+ its slab reduction) is launched on `self.side` as soon as its dY exists and runs CONCURRENTLY with the chain, filling the
         gaps its launches leave in the matrix pipes.  Ordering is by events: a side kernel waits for the producer of its dY, and the
@@ -461,6 +560,7 @@ class LayoutEngine(AdamSurface):
         side = self.side if self.overlap_wgrad else main
         s = main.cuda_stream
         L = cfg.n_layers
+        dxy = self.ddrop if self._dropped else self.dx      # gradient of a residual BRANCH's output (= the stream's without dropout)
         last_read: Dict[str, torch.cuda.Event] = {}
 
         def on_side(reads, fn):
@@ -495,7 +595,7 @@ class LayoutEngine(AdamSurface):
         self.buckets.reset()         # a backward that raised half way leaves nothing behind for this one
         on_side(("dout",), lambda: self._wgrad(self.dout, self.xf, "head_w", M, cfg.n_out, d))
         self._dgrad(self.dout, self.pw("head_w"), self.dh, M, cfg.n_out, d)
-        self._ln_bwd(self.dh, self.x[L], self.stats[2 * L], "lnf_g", None, self.dx, M)
+        self._ln_bwd(self.dh, self.x[L], self.stats[2 * L], "lnf_g", None, self.dx, M, site=2 * L)
         ready = (lambda tag: (lambda: reducer.ready(tag))) if reducer is not None else (lambda tag: None)
         if reducer is not None or self.group_reduce:
             join()
@@ -503,33 +603,33 @@ class LayoutEngine(AdamSurface):
         for l in reversed(range(L)):
             pre = "l%d." % l
             if self.pair_backward:
-                self._dgrad_wgrad(self.dx, self.pw(pre + "ff2_w"), self.du, self.gl[l], pre + "ff2_w", M, d, ff, self._epi_dff2, aux_in=self.u[l])
+                self._dgrad_wgrad(dxy, self.pw(pre + "ff2_w"), self.du, self.gl[l], pre + "ff2_w", M, d, ff, self._epi_dff2, aux_in=self.u[l])
                 self._dgrad_wgrad(self.du, self.pw(pre + "ff1_w"), self.dh, self.h2[l], pre + "ff1_w", M, ff, d)
-                self._ln_bwd(self.dh, self.xmid[l], self.stats[2 * l + 1], pre + "ln2_g", self.dx, self.dx, M)
-                self._dgrad_wgrad(self.dx, self.pw(pre + "proj_w"), self.dh, self.att[l], pre + "proj_w", M, d, d)
+                self._ln_bwd(self.dh, self.xmid[l], self.stats[2 * l + 1], pre + "ln2_g", self.dx, self.dx, M, site=1 + 2 * l)
+                self._dgrad_wgrad(dxy, self.pw(pre + "proj_w"), self.dh, self.att[l], pre + "proj_w", M, d, d)
                 self._attn_bwd(l, batch, B, T, N, M)
                 self._dgrad_wgrad(self.dqkv, self.pw(pre + "qkv_w"), self.dh, self.h1[l], pre + "qkv_w", M, 3 * d, d)
-                self._ln_bwd(self.dh, self.x[l], self.stats[2 * l], pre + "ln1_g", self.dx, self.dx, M)
+                self._ln_bwd(self.dh, self.x[l], self.stats[2 * l], pre + "ln1_g", self.dx, self.dx, M, site=2 * l)
                 # the layer's bucket rides in the next layer's first paired launch (layer 0: in the embedding bucket's table)
                 self.buckets.close(s, defer=True, then=ready("l%d" % l))
                 continue
             # FFN:  x_out = xmid + W2 gelu(W1 h2 + b1) + b2
-            on_side(("dx",), lambda: self._wgrad(self.dx, self.gl[l], pre + "ff2_w", M, d, ff))
+            on_side(("dx",), lambda: self._wgrad(dxy, self.gl[l], pre + "ff2_w", M, d, ff))
             before_write("du")
-            self._dgrad(self.dx, self.pw(pre + "ff2_w"), self.du, M, d, ff, self._epi_dff2, aux_in=self.u[l])
+            self._dgrad(dxy, self.pw(pre + "ff2_w"), self.du, M, d, ff, self._epi_dff2, aux_in=self.u[l])
             on_side(("du",), lambda: self._wgrad(self.du, self.h2[l], pre + "ff1_w", M, ff, d))
             self._dgrad(self.du, self.pw(pre + "ff1_w"), self.dh, M, ff, d)
             before_write("dx")
-            self._ln_bwd(self.dh, self.xmid[l], self.stats[2 * l + 1], pre + "ln2_g", self.dx, self.dx, M)
+            self._ln_bwd(self.dh, self.xmid[l], self.stats[2 * l + 1], pre + "ln2_g", self.dx, self.dx, M, site=1 + 2 * l)
             # attention:  xmid = x + Wo attn(Wqkv h1 + b) + bo
-            on_side(("dx",), lambda: self._wgrad(self.dx, self.att[l], pre + "proj_w", M, d, d))
-            self._dgrad(self.dx, self.pw(pre + "proj_w"), self.dh, M, d, d)
+            on_side(("dx",), lambda: self._wgrad(dxy, self.att[l], pre + "proj_w", M, d, d))
+            self._dgrad(dxy, self.pw(pre + "proj_w"), self.dh, M, d, d)
             before_write("dqkv")
             self._attn_bwd(l, batch, B, T, N, M)
             on_side(("dqkv",), lambda: self._wgrad(self.dqkv, self.h1[l], pre + "qkv_w", M, 3 * d, d))
             self._dgrad(self.dqkv, self.pw(pre + "qkv_w"), self.dh, M, 3 * d, d)
             before_write("dx")
-            self._ln_bwd(self.dh, self.x[l], self.stats[2 * l], pre + "ln1_g", self.dx, self.dx, M)
+            self._ln_bwd(self.dh, self.x[l], self.stats[2 * l], pre + "ln1_g", self.dx, self.dx, M, site=2 * l)
             if reducer is not None or self.group_reduce:
                 join()
                 self.buckets.close(s)
@@ -537,6 +637,8 @@ class LayoutEngine(AdamSurface):
                 reducer.ready("l%d" % l)
         join()
         self._backward_tail(batch, B, T, N, M, reducer)
+        if self._dropped:            # the next training step draws new masks (a captured graph advances by replaying this launch)
+            self._timed("dropout_step", 0.0, "vlg_dropout_step_advance", ptr(self.drop_step), s, nbytes=8.0)
 
     def _backward_tail(self, batch, B, T, N, M, reducer) -> None:
         cfg, d = self.cfg, self.cfg.d
@@ -544,14 +646,14 @@ class LayoutEngine(AdamSurface):
         emb_len = self.layout["l0.ln1_g"][0]
         n_slabs = hip.load().vlg_embed_bwd_slabs_for(B, T, N, d, cfg.vocab)          # by shape: few clips write (and reduce) few slabs
         arena = self.buckets.reserve(n_slabs * emb_len)
-        self._timed("embed_bwd", 0.0, "vlg_embed_bwd", ptr(self.dx), ptr(batch["slot_class"]), ptr(batch["slot_box"]), ptr(arena),
+        self._timed("embed_bwd", 0.0, "vlg_embed_bwd", ptr(self.ddrop if self._dropped else self.dx), ptr(batch["slot_class"]), ptr(batch["slot_box"]), ptr(arena),
                     emb_len, arena.numel(), B, T, N, d, cfg.vocab, s, nbytes=4.0 * M * d + 24.0 * M)
         self.buckets.add(arena, emb_len, n_slabs, self.grads.data_ptr(), emb_len, s)
         # (flushes a bucket still waiting for a ride in the same table: the gradient buffer is complete for whoever runs next)
         self.buckets.close(s, then=(lambda: reducer.ready("embed")) if reducer is not None else None)
 
     def forward_backward(self, batch: Dict[str, torch.Tensor], reducer=None) -> torch.Tensor:
-        loss = self.forward(batch)
+        loss = self._forward(batch, None, True)       # (a training forward: the one place dropout is applied)
         self.backward(batch, reducer)
         return loss
 
@@ -614,8 +716,8 @@ class LayoutEngine(AdamSurface):
         side.wait_stream(torch.cuda.current_stream(self.device))
         keep = (self.params.clone(), self.exp_avg.clone(), self.exp_avg_sq.clone(), counter.clone(), self.step_count)
         # the recipe's state moves with the two capture passes too: the average, its bf16 copy, the outputs of ext
-        more = [t for t in (self.optim.ema, self.optim.ema_shadow, self.optim.guard.ext if self.optim.guard is not None else None)
-                if t is not None]
+        more = [t for t in (self.optim.ema, self.optim.ema_shadow, self.optim.guard.ext if self.optim.guard is not None else None,
+                            self.drop_step) if t is not None]
         kept_more = [t.clone() for t in more]
         def restore():
             self.params.copy_(keep[0]); self.exp_avg.copy_(keep[1]); self.exp_avg_sq.copy_(keep[2])

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_uint64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VLG_HIP_LIB: development override (A/B runs of two builds in one gpurun call, tools/kernel_bench.py); still no fallback
@@ -34,6 +34,12 @@ SIGNATURES = {
     "vlg_layernorm_bwd_slabs": (I, [L]),
     "vlg_layernorm_bwd": (I, [P, P, P, P, P, P, P, P, L, L, L, I, P]),
     "vlg_layernorm_bwd_bf16": (I, [P, P, P, P, P, P, P, P, L, L, L, I, P]),
+    "vlg_dropout_plan": (I, [c_double, P, P]),                   # host only: (p, uint32* thr, float* scale)
+    "vlg_dropout_add_layernorm_fwd": (I, [P, P, P, P, P, P, P, P, L, I, F, c_uint32, F, c_uint64, I, P, P]),
+    "vlg_dropout_add_layernorm_fwd_bf16": (I, [P, P, P, P, P, P, P, P, L, I, F, c_uint32, F, c_uint64, I, P, P]),
+    "vlg_layernorm_bwd_dropout": (I, [P, P, P, P, P, P, P, P, P, L, L, L, I, c_uint32, F, c_uint64, I, P, P]),
+    "vlg_layernorm_bwd_dropout_bf16": (I, [P, P, P, P, P, P, P, P, P, L, L, L, I, c_uint32, F, c_uint64, I, P, P]),
+    "vlg_dropout_step_advance": (I, [P, P]),
     "vlg_linear_fwd": (I, [P, I, P, I, P, P, I, P, P, L, I, I, I, P]),
     "vlg_linear_dgrad": (I, [P, I, P, I, P, I, P, L, I, I, I, P]),
     "vlg_linear_wgrad_slabs": (I, [L, I, I]),
