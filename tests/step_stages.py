@@ -18,12 +18,21 @@ contract of the reduced-precision modes") enters as arguments and is read from v
 
 Stage outputs are returned UNROUNDED: the comparison allows a bf16 output its one rounding (vs_cpu32 bf16=True) and
 `emulate` rounds when it stores.  Rows of every (M, .) tensor are in the engine's order m = (b*N + n)*T + t.
+
+Dropout (Contract(dropout=(p, seed, k)); LayoutEngine._encode_dropout and the `_dropped` backward): proj and ff2 write
+branch + bias into `ybranch` without a residual epilogue; every layer-norm launch is the fused dropout + add + layer-norm
+of its site (0, then 1 + 2l and 2 + 2l; site 0 in place on x[0]); every layer-norm backward is the fused one of the site
+that FED it (2L, then 1 + 2l and 2l) and also leaves select(dx) in `ddrop`, which the proj / ff2 backward and the
+embedding backward read in place of dx; one counter advance ends the step.  ybranch and ddrop are fp32 in every mode.
+The masks are dropout_ref.keep_mask's, in the row order above; tests/dropout_ref.py states the rule.
 """
+import functools
 import math
 
 import torch
 import torch.nn.functional as F
 
+import dropout_ref
 from oracle import layout_spec as O
 
 BF = torch.bfloat16
@@ -34,14 +43,18 @@ EPI_GELU_GRAD, EPI_MUL = 1024, 2048
 PRECISIONS = ("fp32", "fp32x3", "bf16", "bf16_mfma")
 BF16_BUFFERS = ("h1", "qkv", "att", "h2", "u", "gl", "xf", "dh", "du", "dqkv")      # bf16 in memory under "bf16"
 BACKWARD_BUFFERS = ("dx", "dh", "du", "dqkv", "dout", "delta")                        # reused by the backward: snapshot per launch
+DROPOUT_BUFFERS = ("ybranch", "x[0]", "ddrop")              # rewritten within a dropout step: snapshot per launch there
 LOG2E = 1.0 / math.log(2.0)
 
 
 class Contract:
-    """What a precision mode stores and rounds (see the module docstring)."""
+    """What a precision mode stores and rounds (see the module docstring).  dropout = (p, seed, k): the step of an engine
+    built with dropout=p, dropout_seed=seed whose counter reads k."""
 
-    def __init__(self, precision, attention="slot", masked=True, gelu_grad_saved=None, paired=None):
+    def __init__(self, precision, attention="slot", masked=True, gelu_grad_saved=None, paired=None, dropout=None):
         assert precision in PRECISIONS
+        self.dropout = dropout
+        self.snapshots = BACKWARD_BUFFERS + (DROPOUT_BUFFERS if dropout is not None else ())
         self.precision, self.attention = precision, attention
         self.store_bf16 = precision == "bf16"
         self.round_operands = precision in ("bf16", "bf16_mfma")
@@ -106,6 +119,34 @@ def ln_fwd(x, g, b):
     xc = x - mean
     rstd = 1.0 / torch.sqrt((xc * xc).mean(-1, keepdim=True) + O.LN_EPS)
     return xc * rstd * g + b, mean.squeeze(-1), rstd.squeeze(-1)
+
+
+@functools.lru_cache(maxsize=64)
+def _keep(M, d, site, k, seed, thr):
+    return torch.from_numpy(dropout_ref.keep_mask(M, d, site, k, seed, thr))
+
+
+def site_mask(c, M, d, site, k=None):
+    """-> (keep (M, d) bool, rows in the engine's order; scale) of a dropout site under contract c.  k: a counter value
+    other than the contract's (the checker's own test)"""
+    p, seed, k0 = c.dropout
+    thr, scale = dropout_ref.plan(p)
+    return _keep(M, d, site, k0 if k is None else k, int(seed) & (2 ** 64 - 1), thr), scale
+
+
+def dropout_scalars(c, site):
+    """the scalar arguments a fused launch of `site` must carry: dropout_ref.plan's thr and fp32 scale, the 64-bit seed"""
+    p, seed, _ = c.dropout
+    thr, scale = dropout_ref.plan(p)
+    return dict(thr=thr, scale=scale, seed=int(seed) & (2 ** 64 - 1), site=site)
+
+
+def drop_ln_fwd(y, resid, g, b, keep, scale):
+    """x_out = (resid or 0) + select(y), h = LN(x_out) -> (x_out, h, mean, rstd): csrc/dropout.hip's forward"""
+    x = dropout_ref.select(y, keep, scale)
+    if resid is not None:
+        x = resid + x
+    return (x,) + ln_fwd(x, g, b)
 
 
 def linear_fwd(a, w, b, rnd=ident, resid=None, gelu=None):
@@ -205,6 +246,12 @@ def ln_bwd(dy, x, mean, rstd, g, dres=None):
     return (dx + dres if dres is not None else dx), (dy * xh).sum(0), dy.sum(0)
 
 
+def ln_bwd_drop(dy, x, mean, rstd, g, dres, keep, scale):
+    """ln_bwd and ddrop = select(dx (+ dres)) under the mask of the site that produced x -> (dx, ddrop, dgamma, dbeta)"""
+    dx, dg, db = ln_bwd(dy, x, mean, rstd, g, dres)
+    return dx, dropout_ref.select(dx, keep, scale), dg, db
+
+
 def slot_attention_bwd(qkv, do, T):
     q = qkv.detach().clone().requires_grad_(True)
     slot_attention_fwd(q, T).backward(do)
@@ -259,14 +306,25 @@ def embed_bwd(dx, slot_class, slot_box, vocab, B, T, N):
 def schedule(cfg, c):
     """The launches of one forward_backward in order, as vlg/engine.py makes them under contract `c`.  Each entry: stage
     (a name for messages), family, entry (C-ABI name), ops (names of the pointer arguments in order; None = NULL, "arena"
-    = a slab arena, "*" = not pinned), flags (projection calls), kind + the operand names the stage function takes."""
+    = a slab arena, "*" = not pinned), flags (projection calls), kind + the operand names the stage function takes.
+    Under c.dropout the launches are _encode_dropout's and the `_dropped` backward's (module docstring): a fused entry also
+    carries its site."""
     L, d, ff = cfg.n_layers, cfg.d, cfg.d_ff
     clip = c.attention == "clip"
     valid = "batch:valid" if c.masked else None
+    drop = c.dropout is not None
     P = lambda n: "p:" + n
     out = []
 
-    def ln_f(stage, x, gname, y, i):
+    def ln_f(stage, x, gname, y, i, branch=None):
+        """the layer-norm of statistics slot i; dropout: the fused launch of site i, which first forms x = resid + drop(branch)
+        (resid = the `x` of the launch this one replaces: site 0 has none and runs in place on x[0])"""
+        if drop:
+            src, resid = (x, None) if branch is None else ("ybranch", branch)
+            out.append(dict(stage=stage, kind="drop_ln_fwd", family="ln_fwd", entry="vlg_dropout_add_layernorm_fwd" + c.sfx, y=src,
+                            resid=resid, g=gname, x_out=x, h=y, stat=i, site=i,
+                            ops=(src, resid, P(gname), P(gname[:-1] + "b"), x, y, "stats[%d].mean" % i, "stats[%d].rstd" % i, "drop_step")))
+            return
         out.append(dict(stage=stage, kind="ln_fwd", family="ln_fwd", entry="vlg_layernorm_fwd" + c.sfx, x=x, g=gname, y=y, stat=i,
                         ops=(x, P(gname), P(gname[:-1] + "b"), y, "stats[%d].mean" % i, "stats[%d].rstd" % i)))
 
@@ -282,7 +340,7 @@ def schedule(cfg, c):
     for l in range(L):
         pre = "l%d." % l
         x, h1, qkv, att, xmid, h2, u, gl = ("%s[%d]" % (n, l) for n in ("x", "h1", "qkv", "att", "xmid", "h2", "u", "gl"))
-        ln_f(pre + "ln1", x, pre + "ln1_g", h1, 2 * l)
+        ln_f(pre + "ln1", x, pre + "ln1_g", h1, 2 * l, branch="xmid[%d]" % (l - 1) if l else None)
         lin(pre + "qkv", h1, pre + "qkv_w", qkv, EPI_BIAS)
         if clip:
             out.append(dict(stage=pre + "attention", kind="clip_fwd", family="attn_clip_fwd", entry="vlg_attention_clip_fwd" + c.sfx,
@@ -290,11 +348,17 @@ def schedule(cfg, c):
         else:
             out.append(dict(stage=pre + "attention", kind="slot_fwd", family="attn_fwd", entry="vlg_attention_fwd" + c.sfx, l=l,
                             ops=(qkv, att)))
-        lin(pre + "proj", att, pre + "proj_w", xmid, EPI_BIAS | EPI_RESID, aux_in=x)
-        ln_f(pre + "ln2", xmid, pre + "ln2_g", h2, 2 * l + 1)
+        if drop:
+            lin(pre + "proj", att, pre + "proj_w", "ybranch", EPI_BIAS)
+        else:
+            lin(pre + "proj", att, pre + "proj_w", xmid, EPI_BIAS | EPI_RESID, aux_in=x)
+        ln_f(pre + "ln2", xmid, pre + "ln2_g", h2, 2 * l + 1, branch=x)
         lin(pre + "ff1", h2, pre + "ff1_w", gl, epi_ff1, aux_out=u)
-        lin(pre + "ff2", gl, pre + "ff2_w", "x[%d]" % (l + 1), EPI_BIAS | EPI_RESID, aux_in=xmid)
-    ln_f("lnf", "x[%d]" % L, "lnf_g", "xf", 2 * L)
+        if drop:
+            lin(pre + "ff2", gl, pre + "ff2_w", "ybranch", EPI_BIAS)
+        else:
+            lin(pre + "ff2", gl, pre + "ff2_w", "x[%d]" % (l + 1), EPI_BIAS | EPI_RESID, aux_in=xmid)
+    ln_f("lnf", "x[%d]" % L, "lnf_g", "xf", 2 * L, branch="xmid[%d]" % (L - 1))
     lin("head", "xf", "head_w", "out", EPI_BIAS)
     out.append(dict(stage="loss", kind="loss", family="loss", entry="vlg_layout_loss",
                     ops=("out", "batch:tgt_class", "batch:tgt_box", "batch:valid", "dout", "loss_out", "loss_scratch")))
@@ -318,24 +382,31 @@ def schedule(cfg, c):
                         ops=(dy, c.weight(wname), dx, aux_in, x, "arena", "*")))
 
     def ln_b(stage, dy, x, i, gname, dres):
+        """dropout: the fused backward under the mask of site i, the site that produced x (its statistics slot)"""
+        if drop:
+            out.append(dict(stage=stage + " bwd", kind="ln_bwd_drop", family="ln_bwd", entry="vlg_layernorm_bwd_dropout" + c.sfx, dy=dy,
+                            x=x, stat=i, g=gname, dres=dres, site=i,
+                            ops=(dy, x, "stats[%d].mean" % i, "stats[%d].rstd" % i, P(gname), dres, "dx", "ddrop", "arena", "drop_step")))
+            return
         out.append(dict(stage=stage + " bwd", kind="ln_bwd", family="ln_bwd", entry="vlg_layernorm_bwd" + c.sfx, dy=dy, x=x, stat=i,
                         g=gname, dres=dres, ops=(dy, x, "stats[%d].mean" % i, "stats[%d].rstd" % i, P(gname), dres, "dx", "arena")))
 
     epi_dff2 = EPI_MUL if c.gelu_grad_saved else EPI_DGELU
+    dxy = "ddrop" if drop else "dx"             # gradient of a residual BRANCH's output (engine.backward's dxy)
     wg("head", "dout", "xf", "head_w")
     dg("head", "dout", "head_w", "dh")
     ln_b("lnf", "dh", "x[%d]" % L, 2 * L, "lnf_g", None)
     for l in reversed(range(L)):
         pre = "l%d." % l
         x, h1, qkv, att, xmid, h2, u, gl = ("%s[%d]" % (n, l) for n in ("x", "h1", "qkv", "att", "xmid", "h2", "u", "gl"))
-        pair(pre + "ff2", "dx", pre + "ff2_w", "du", gl, epi_dff2, aux_in=u)
+        pair(pre + "ff2", dxy, pre + "ff2_w", "du", gl, epi_dff2, aux_in=u)
         pair(pre + "ff1", "du", pre + "ff1_w", "dh", h2)
         ln_b(pre + "ln2", "dh", xmid, 2 * l + 1, pre + "ln2_g", "dx")
         if c.paired:
-            pair(pre + "proj", "dx", pre + "proj_w", "dh", att)
+            pair(pre + "proj", dxy, pre + "proj_w", "dh", att)
         else:
-            wg(pre + "proj", "dx", att, pre + "proj_w")
-            dg(pre + "proj", "dx", pre + "proj_w", "dh")
+            wg(pre + "proj", dxy, att, pre + "proj_w")
+            dg(pre + "proj", dxy, pre + "proj_w", "dh")
         if clip:
             out.append(dict(stage=pre + "attention bwd", kind="clip_bwd", family="attn_clip_bwd", entry="vlg_attention_clip_bwd" + c.sfx,
                             l=l, ops=(qkv, valid, att, "dh", "lse[%d]" % l, "delta", "dqkv")))
@@ -345,7 +416,9 @@ def schedule(cfg, c):
         pair(pre + "qkv", "dqkv", pre + "qkv_w", "dh", h1)
         ln_b(pre + "ln1", "dh", x, 2 * l, pre + "ln1_g", "dx")
     out.append(dict(stage="embedding bwd", kind="embed_bwd", family="embed_bwd", entry="vlg_embed_bwd",
-                    ops=("dx", "batch:slot_class", "batch:slot_box", "arena")))
+                    ops=(dxy, "batch:slot_class", "batch:slot_box", "arena")))
+    if drop:
+        out.append(dict(stage="dropout step", kind="advance", family="dropout_step", entry="vlg_dropout_step_advance", ops=("drop_step",)))
     return out
 
 
@@ -378,6 +451,10 @@ def run_stage(e, cfg, c, batch, val, detail=None):
     elif k == "ln_fwd":
         o[e["y"]], o["stats[%d].mean" % e["stat"]], o["stats[%d].rstd" % e["stat"]] = ln_fwd(
             val(e["x"]), val("p:" + e["g"]), val("p:" + e["g"][:-1] + "b"))
+    elif k == "drop_ln_fwd":
+        i = e["stat"]
+        o[e["x_out"]], o[e["h"]], o["stats[%d].mean" % i], o["stats[%d].rstd" % i] = drop_ln_fwd(
+            val(e["y"]), val(e["resid"]), val("p:" + e["g"]), val("p:" + e["g"][:-1] + "b"), *site_mask(c, B * T * N, cfg.d, e["site"]))
     elif k == "linear_fwd":
         o[e["c"]], aux = linear_fwd(val(e["a"]), val(c.weight(e["w"])), val("p:" + e["w"][:-1] + "b"), rnd,
                                     val(e["aux_in"]) if e["epi"] & EPI_RESID else None, epi_modes(e["epi"])[0])
@@ -401,6 +478,11 @@ def run_stage(e, cfg, c, batch, val, detail=None):
         i = e["stat"]
         o["dx"], g[e["g"]], g[e["g"][:-1] + "b"] = ln_bwd(val(e["dy"]), val(e["x"]), val("stats[%d].mean" % i), val("stats[%d].rstd" % i),
                                                           val("p:" + e["g"]), val(e["dres"]))
+    elif k == "ln_bwd_drop":
+        i = e["stat"]
+        o["dx"], o["ddrop"], g[e["g"]], g[e["g"][:-1] + "b"] = ln_bwd_drop(
+            val(e["dy"]), val(e["x"]), val("stats[%d].mean" % i), val("stats[%d].rstd" % i), val("p:" + e["g"]), val(e["dres"]),
+            *site_mask(c, B * T * N, cfg.d, e["site"]))
     elif k == "slot_bwd":
         o["dqkv"] = slot_attention_bwd(val("qkv[%d]" % e["l"]), val("dh"), T)
     elif k == "clip_bwd":
@@ -408,7 +490,9 @@ def run_stage(e, cfg, c, batch, val, detail=None):
         o["dqkv"], o["delta"] = clip_attention_bwd(val("qkv[%d]" % l), val("dh"), val("att[%d]" % l), val("lse[%d]" % l), valid,
                                                    B, T, N, arnd, detail)
     elif k == "embed_bwd":
-        g.update(embed_bwd(val("dx"), batch["slot_class"], batch["slot_box"], cfg.vocab, B, T, N))
+        g.update(embed_bwd(val(e["ops"][0]), batch["slot_class"], batch["slot_box"], cfg.vocab, B, T, N))
+    elif k == "advance":
+        pass                                                 # the counter: step_trace.check reads it after every launch
     else:
         raise KeyError(k)
     return o, g
@@ -420,7 +504,8 @@ def emulate(cfg, c, params, batch, dtype, mutate=None):
     step_trace.trace: a record = dict(family, name, flags, ops, after = {backward buffer: clone}); state = every
     forward buffer, "grads" {name: tensor} and "loss".  In float64 this is the emulated oracle of the mode.
     `mutate(entry, val, outputs, grads, record)` may change what a launch leaves behind before it is stored (the checker's
-    own test); an output wrapped in Raw is stored as it is."""
+    own test); an output wrapped in Raw is stored as it is.  Under c.dropout a record also has the scalars of a fused
+    launch and the counter value after the launch (dropout_scalars, "drop_step"), as step_trace.trace records them."""
     st = {"p:" + k: v.to(dtype) for k, v in params.items()}
     st.update({"pb:" + k: v.to(BF) for k, v in params.items()})
     grads = {}
@@ -429,20 +514,23 @@ def emulate(cfg, c, params, batch, dtype, mutate=None):
     for e in schedule(cfg, c):
         o, g = run_stage(e, cfg, c, batch, val)
         rec = dict(family=e["family"], name=e["entry"], flags=e.get("flags"), ops=e["ops"])
+        if c.dropout is not None:
+            rec["scalars"] = dropout_scalars(c, e["site"]) if "site" in e else None
+            rec["drop_step"] = c.dropout[2] + (e["kind"] == "advance")
         if mutate is not None:
             mutate(e, val, o, g, rec)
         for n, t in o.items():
             st[n] = t.t if isinstance(t, Raw) else t.to(BF if c.dtype(n) == BF else dtype)
         grads.update(g)
-        rec["after"] = {n: st[n].clone() for n in BACKWARD_BUFFERS if n in st}
+        rec["after"] = {n: st[n].clone() for n in c.snapshots if n in st}
         records.append(rec)
     st["grads"], st["loss"] = grads, st["loss_out"]
     return records, st
 
 
-def emulated_oracle(cfg, precision, params, batch, attention="slot", masked=True):
+def emulated_oracle(cfg, precision, params, batch, attention="slot", masked=True, dropout=None):
     """Loss scalars and gradients of the mode, chained end to end in float64 with its storage roundings."""
-    _, st = emulate(cfg, Contract(precision, attention, masked), params, batch, torch.float64)
+    _, st = emulate(cfg, Contract(precision, attention, masked, dropout=dropout), params, batch, torch.float64)
     return st["loss"], st["grads"]
 
 

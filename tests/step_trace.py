@@ -20,6 +20,13 @@ check(records, state, cfg, contract, batch)  walks step_stages.schedule next to 
       parameter gradients  test_hip_gemm_paths.check_wgrad's bar (1e-4 / 1e-5 after 1 / sqrt(M)), native fp32 dW also 4 x
                          torch-CPU fp32's error
     A failure is an AssertionError whose message starts with "[<stage>]".
+Dropout (an engine built with dropout > 0, a Contract with dropout=(p, seed, k)): trace also clones per launch the three
+    buffers a dropout step rewrites before it ends (ybranch, x[0] - overwritten in place by site 0 -, ddrop) and records the
+    scalar arguments of the fused entry points and, after each synchronisation, the device counter.  check holds a fused launch
+    to the above - names (a stale dx where ddrop belongs fails by name), the bars of the plain layer-norm stages on x_out, h,
+    mean, rstd / dx, ddrop - and to: thr, scale, seed equal to dropout_ref.plan / the contract's seed, site the schedule's;
+    the counter at k after every launch, k + 1 after the advance; the dropped set EXACTLY dropout_ref.keep_mask's
+    (_dropped_set_fwd, _dropped_set_bwd: the rules of test_hip_dropout's kernel tests).
 Storage contract: DESIGN.md, "Layout step: storage contract of the reduced-precision modes"."""
 import math
 
@@ -57,12 +64,14 @@ def _buffers(engine, batch, M):
     for k, t in batch.items():
         b["batch:" + k] = t
     b["loss_out"], b["loss_scratch"] = engine.loss_out, engine.loss_scratch
+    if engine.drop_step is not None:                         # an engine built with dropout > 0
+        b["ybranch"], b["ddrop"], b["drop_step"] = engine.ybranch[:M], engine.ddrop[:M], engine.drop_step
     return b
 
 
 def trace(engine, batch):
     """Run engine.forward_backward(batch) under the recording wrapper -> (records, state)."""
-    from ctypes import c_void_p
+    from ctypes import c_uint32, c_void_p
     from vlg import hip
     B, T, N = batch["slot_class"].shape
     M = B * T * N
@@ -71,14 +80,21 @@ def trace(engine, batch):
     assert len(by_ptr) == len(bufs), "two buffers share a pointer"
     records = []
     launch = engine._timed                                   # the bound method
+    dropout = "drop_step" in bufs
+    snapshots = SS.BACKWARD_BUFFERS + (SS.DROPOUT_BUFFERS if dropout else ())
 
     def recording(family, flops, name, *args, nbytes=0.0):
         launch(family, flops, name, *args, nbytes=nbytes)
         torch.cuda.synchronize()
         types = hip.SIGNATURES[name][1]
         ops = tuple(None if a == 0 else by_ptr.get(a, "arena") for a, ty in list(zip(args, types))[:-1] if ty is c_void_p)
-        records.append(dict(family=family, name=name, flags=args[_FLAGS_AT[name]] if name in _FLAGS_AT else None, ops=ops,
-                            after={n: bufs[n].detach().cpu().clone() for n in SS.BACKWARD_BUFFERS if n in bufs}))
+        rec = dict(family=family, name=name, flags=args[_FLAGS_AT[name]] if name in _FLAGS_AT else None, ops=ops,
+                   after={n: bufs[n].detach().cpu().clone() for n in snapshots if n in bufs})
+        if dropout:                                          # the fused entry points: (uint32 thr, float scale, uint64 seed, int site)
+            i = types.index(c_uint32) if c_uint32 in types else None
+            rec["scalars"] = None if i is None else dict(zip(("thr", "scale", "seed", "site"), args[i:i + 4]))
+            rec["drop_step"] = int(engine.drop_step.item())
+        records.append(rec)
 
     engine._timed = recording                                # instance attribute: this engine only
     try:
@@ -86,7 +102,8 @@ def trace(engine, batch):
         torch.cuda.synchronize()
     finally:
         del engine._timed
-    state = {n: t.detach().cpu().clone() for n, t in bufs.items() if n not in SS.BACKWARD_BUFFERS and not n.startswith("batch:")}
+    state = {n: t.detach().cpu().clone() for n, t in bufs.items()
+             if n not in SS.BACKWARD_BUFFERS + ("ybranch", "ddrop") and not n.startswith("batch:")}
     state["loss"] = state.pop("loss_out")
     state["grads"] = {n: g.detach().cpu().clone() for n, g in engine.named_grads().items()}
     return records, state
@@ -108,6 +125,33 @@ def _less(t, want64, slack):
     return want64 + torch.sign(err) * (err.abs() - slack).clamp(min=0)
 
 
+def _bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def _dropped_set_fwd(x_out, y, resid, keep, scale):
+    """test_hip_dropout.test_forward_kernel's rule on a fused forward launch: the elements of x_out that are bitwise resid
+    (+0.0 without one) are EXACTLY the complement of the reference mask.  That test keeps |y| >= 0.1 so that a kept element
+    always moves its residual; here y is what the step computed, and a kept element with |y * scale| <= 2^-23 |resid| (half
+    an ulp of resid is at most 2^-24 |resid|; the factor 2 covers the product's rounding), or y = 0 at site 0, cannot show
+    that it was kept.  Those - of the order of one element in 10^7 - are left out; every other element decides."""
+    base = torch.zeros_like(x_out) if resid is None else resid
+    dropped = _bits(x_out) == _bits(base)
+    silent = keep & (y.double().abs() * scale <= 2.0 ** -23 * base.double().abs())
+    wrong = (dropped != ~keep) & ~silent
+    assert not bool(wrong.any()), "the dropped set of x_out differs from the reference mask in %d elements" % int(wrong.sum())
+
+
+def _dropped_set_bwd(ddrop, dx, keep, scale):
+    """test_hip_dropout.test_backward_kernel's rule: ddrop is bitwise 0 on the reference's dropped set and within 1 ulp of
+    fp32(dx * scale), of the dx this launch stored, elsewhere"""
+    assert bool((_bits(ddrop)[~keep] == 0).all()), "ddrop is not exactly 0 on the dropped set"
+    want = dx * torch.tensor(scale, dtype=torch.float32)
+    lo, hi = (torch.nextafter(want, torch.full_like(want, s * float("inf"))) for s in (-1, 1))
+    ok = (ddrop >= lo) & (ddrop <= hi)
+    assert bool(ok[keep].all()), "ddrop off by more than 1 ulp from dx * scale in %d kept elements" % int((~ok[keep]).sum())
+
+
 def check(records, state, cfg, c, batch, log=None):
     """See the module docstring.  `log`, a list, receives (stage, output, max |err| vs fp64, torch-CPU fp32's) per output."""
     B, T, N = batch["slot_class"].shape
@@ -126,8 +170,14 @@ def check(records, state, cfg, c, batch, log=None):
                 "operands %s, contract %s" % (r["ops"], e["ops"])
 
             def get(n):
-                return prev[n] if n in SS.BACKWARD_BUFFERS else state["loss"] if n == "loss_out" else state[n]
+                return prev[n] if n in c.snapshots else state["loss"] if n == "loss_out" else state[n]
 
+            if c.dropout is not None:
+                k = c.dropout[2] + (e["kind"] == "advance")
+                assert r["drop_step"] == k, "the step counter reads %s after this launch, contract %d" % (r["drop_step"], k)
+                if "site" in e:
+                    assert r["scalars"] == SS.dropout_scalars(c, e["site"]), "mask arguments %s, contract %s" % (
+                        r["scalars"], SS.dropout_scalars(c, e["site"]))
             want, detail = {}, {torch.float64: {}, torch.float32: {}}
             for dt in (torch.float64, torch.float32):
                 want[dt] = SS.run_stage(e, cfg, c, batch, lambda n: None if n is None else get(n).to(dt), detail[dt])
@@ -135,9 +185,15 @@ def check(records, state, cfg, c, batch, log=None):
             slack = {}
             if c.store_bf16 and e["kind"] in ("clip_fwd", "clip_bwd"):      # P and dS are rounded on chip: step_stages.flip_step
                 slack = SS.operand_flip_slack(e["kind"], detail[torch.float64], detail[torch.float32], B, T, N)
-            got = {n: (r["after"][n] if n in SS.BACKWARD_BUFFERS else state["loss"] if n == "loss_out" else state[n]) for n in o64}
+            got = {n: (r["after"][n] if n in c.snapshots else state["loss"] if n == "loss_out" else state[n]) for n in o64}
             for n, t in got.items():
                 assert t.dtype == c.dtype(n), "%s is stored as %s, contract %s" % (n, t.dtype, c.dtype(n))
+            if "site" in e:
+                keep, scale = SS.site_mask(c, M, cfg.d, e["site"])
+                if e["kind"] == "drop_ln_fwd":
+                    _dropped_set_fwd(got[e["x_out"]], get(e["y"]), None if e["resid"] is None else get(e["resid"]), keep, scale)
+                else:
+                    _dropped_set_bwd(got["ddrop"], got["dx"], keep, scale)
             if e["kind"] == "loss":
                 from test_hip_layout_ops import _loss_check
                 assert bool((got["dout"][pad] == 0).all()), "dout rows of padded slots are not exactly 0"

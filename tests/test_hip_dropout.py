@@ -1,7 +1,7 @@
 """Dropout on the GPU (csrc/dropout.hip, vlg/engine.py): the two fused kernels against the CPU restatement of the mask
-(tests/dropout_ref.py) and fp64 arithmetic, their refusals, and the engine with the knob on - against dropout_ref's
-fp64 model with the masks of the counter value the step read - the step counter, capture, checkpoints, evaluation
-entry points and the knob-off engine."""
+(tests/dropout_ref.py) and fp64 arithmetic - also past one trip of their row loops ("prod") -, their refusals, and the
+engine with the knob on - against dropout_ref's fp64 model with the masks of the counter value the step read - the step
+counter, capture, checkpoints, evaluation entry points and the knob-off engine."""
 import ctypes
 import functools
 
@@ -13,7 +13,7 @@ import dropout_ref as R
 import step_stages as SS
 from helpers import check_close
 from oracle import layout_spec as O
-from test_hip_layout_ops import GUARD, H, S, _buf, _guard, _ln_bars, _ln_inputs  # noqa: F401  (H is a fixture)
+from test_hip_layout_ops import GUARD, H, S, _buf, _guard, _ln_bars, _ln_inputs, _ln_R  # noqa: F401  (H is a fixture)
 from test_hip_pixel_ops import ERR_ALIGN, ERR_SHAPE, SENT, f32, sentinel, untouched, within
 
 pytestmark = pytest.mark.gpu
@@ -75,11 +75,17 @@ def test_forward_kernel(H, dev, d, p):
     (x_out == resid bitwise) is EXACTLY the reference's; kept values within rtol 1e-6 of resid + y * scale (fp64);
     h, mean, rstd of the x_out the kernel formed within test_hip_layout_ops' layer-norm bounds; in place == out of place;
     the bf16 entry's h == the fp32 entry's rounded to nearest even; rows 0..4 of the 259-row launch == the 5-row launch."""
+    _forward_rows(H, dev, d, p, ROWS)
+
+
+def _forward_rows(H, dev, d, p, row_counts):
+    """test_forward_kernel's checks at every row count of `row_counts` (ascending, 5 among them; the last one is the launch
+    whose rows 0..4 are compared with the 5-row launch)"""
     thr, scale = R.plan(p)
     site, k = 3, 6
-    y, resid, gam, bet = _fwd_inputs(259, d, seed=d + int(p * 100))
+    y, resid, gam, bet = _fwd_inputs(row_counts[-1], d, seed=d + int(p * 100))
     small = {}
-    for rows in ROWS:
+    for rows in row_counts:
         keep = torch.from_numpy(R.keep_mask(rows, d, site, k, SEED, thr))
         assert bool(keep.all()) == (p == 0.0)
         for with_resid in (True, False):
@@ -106,9 +112,21 @@ def test_forward_kernel(H, dev, d, p):
             assert torch.equal(hb.view(torch.int16), got[1].to(BF).view(torch.int16)), tag + "bf16 h != fp32 h rounded to nearest even"
             if rows == 5:
                 small[with_resid] = got
-            if rows == 259:
+            if rows == row_counts[-1]:
                 for a, b, what in zip(small[with_resid], got, ("x_out", "h", "mean", "rstd")):
                     assert torch.equal(_bits(a), _bits(b[:5])), tag + "rows 0..4 depend on the launch geometry: " + what
+
+
+PROD_DS = (64, 256, 512, 1024)            # both mask layouts (scalar below 256), LN_ROWS = 4 / 4 / 2 / 1
+
+
+@pytest.mark.parametrize("d", PROD_DS)
+def test_forward_kernel_prod(H, dev, d):
+    """Past one trip of the row loop, as test_hip_layout_ops' "prod" cases of the plain layer-norm: 2048 blocks x 4 waves x
+    LN_ROWS rows + 1003 (a second trip that ends on a short row group), p = 0.25.  Every check of test_forward_kernel;
+    the point is the first: the dropped set over ALL rows is the reference's, so the Philox row counter is the global row
+    in every trip (a launch-local index would pass every single-trip case)."""
+    _forward_rows(H, dev, d, 0.25, (5, 2048 * 4 * _ln_R(d) + 1003))
 
 
 @pytest.mark.parametrize("d", DS)
@@ -137,11 +155,19 @@ def test_backward_kernel(H, dev, d, p):
     """vlg_layernorm_bwd_dropout (in place on dres, as the engine runs it) and its bf16-dy entry (dres = NULL): dx_out and
     every slab BITWISE equal to vlg_layernorm_bwd / _bf16 on the same inputs; dy_drop exactly 0 on the reference's
     dropped set and within 1 ulp of fp32(dx_out * scale) elsewhere."""
+    _backward_rows(H, dev, d, p, [_ln_inputs(rows, d, seed=rows + d) for rows in ROWS])
+
+
+def _backward_rows(H, dev, d, p, cases):
+    """test_backward_kernel's checks on every (x, gamma, beta, dy, res) of `cases` -> per case {bf16 entry?: (dx_out, dy_drop)
+    of the fused launch, on the CPU}"""
     lib = H.load()
     thr, scale = R.plan(p)
     site, k = 4, 9
-    for rows in ROWS:
-        x, gam, bet, dy, res = _ln_inputs(rows, d, seed=rows + d)
+    results = []
+    for x, gam, bet, dy, res in cases:
+        rows = x.shape[0]
+        results.append({})
         keep = torch.from_numpy(R.keep_mask(rows, d, site, k, SEED, thr))
         n = rows * d
         xd, gd, bd = x.to(dev), gam.to(dev), bet.to(dev)
@@ -185,6 +211,23 @@ def test_backward_kernel(H, dev, d, p):
             lo, hi = _ulp_neighbours(dxc * torch.tensor(scale, dtype=torch.float32))
             ok = (got >= lo) & (got <= hi)
             assert bool(ok[keep].all()), tag + "dy_drop off by more than 1 ulp from dx_out * scale in %d elements" % int((~ok[keep]).sum())
+            results[-1][bf16] = (dxc, got)
+    return results
+
+
+@pytest.mark.parametrize("d", PROD_DS)
+def test_backward_kernel_prod(H, dev, d):
+    """Past one trip of the backward's row loop: 512 blocks (LN_BWD_MAX_BLOCKS) x 4 waves x LN_ROWS rows + 1003, p = 0.25.
+    Every check of test_backward_kernel - dy_drop exactly 0 on the reference's dropped set over ALL rows, so the mask's row
+    counter is the global row in every trip - and rows 0..4 of dx_out and dy_drop bitwise those of the 5-row launch on the
+    same rows."""
+    rows = 512 * 4 * _ln_R(d) + 1003
+    assert H.load().vlg_layernorm_bwd_slabs(rows) == 512
+    x, gam, bet, dy, res = _ln_inputs(rows, d, seed=rows + d)
+    small, big = _backward_rows(H, dev, d, 0.25, [(x[:5], gam, bet, dy[:5], res[:5]), (x, gam, bet, dy, res)])
+    for bf16 in (False, True):
+        for a, b, what in zip(small[bf16], big[bf16], ("dx_out", "dy_drop")):
+            assert torch.equal(_bits(a), _bits(b[:5])), "d=%d%s: rows 0..4 depend on the launch geometry: %s" % (d, " bf16" if bf16 else "", what)
 
 
 def test_kernel_refusals(H, dev):

@@ -16,8 +16,9 @@ missing rounding, a dropped bias / residual / mask and a short bias gradient at 
 Shapes are the smallest that take each path: (2,16,12) x d=256 x 2 layers - M = 384 is no multiple of 128, and a layer's
 slab bucket rides in the next layer's paired launch; (1,32,8) x d=128 - the T = 32 attention kernels; (3,8,5) x d=64 -
 the generic-T kernel, ragged everything (T*N = 40 is no multiple of 32, so the per-clip attention refuses this one:
-asserted below).  VLG_OVERLAP_WGRAD=1 is not traced: the synchronising wrapper would serialise it, and
-test_stream_options_do_not_change_results holds it bitwise to the default."""
+asserted below).  The dropout step has cases of its own at the same shapes (DROP_CASES).  VLG_OVERLAP_WGRAD=1 is not
+traced: the synchronising wrapper would serialise it, and test_stream_options_do_not_change_results holds it bitwise to
+the default."""
 import pytest
 import torch
 
@@ -107,6 +108,68 @@ def test_every_launch_matches_fp64_on_its_inputs(dev, monkeypatch, precision, at
         step_trace.check(records, state, cfg, c, batch, log=log)
     finally:
         print("\n%s %s %s: worst |err| vs fp64 per launch kind: %s" % (precision, attention, kw, _summary(log)))
+
+
+# The dropout step (LayoutEngine._encode_dropout and the `_dropped` backward; schedule: step_stages' module docstring) at
+# p = 0.25 and counter k = 3 - a step at which test_hip_dropout documents the bf16 modes of its shape OUTSIDE the
+# end-to-end bars; the per-launch bars hold regardless, nothing amplifies between launches.  Beyond the precisions: masks
+# and dropout together (variable N), the plain backward (VLG_PAIR_BACKWARD=0 and fp32x3), the T = 32 attention with
+# d = 128 and the generic-T attention with d = 64, where the mask takes the scalar row layout (one Philox call per element).
+DROP_SEED = (0x9E3779B9 << 32) | 1024          # both key words in use
+DROP_K = 3
+DROP_CASES = [
+    pytest.param("fp32", "slot", S1, False, 0.25, None, id="fp32-slot"),
+    pytest.param("fp32", "clip", S1, True, 0.25, None, id="fp32-clip-variable-n"),
+    pytest.param("fp32", "slot", S1, False, 0.5, "0", id="fp32-slot-p0.5-VLG_PAIR_BACKWARD-0"),
+    pytest.param("fp32x3", "slot", S3, False, 0.25, None, id="fp32x3-slot-3x8x5-d64"),
+    pytest.param("bf16", "slot", S1, False, 0.25, None, id="bf16-slot"),
+    pytest.param("bf16", "slot", S2, False, 0.25, None, id="bf16-slot-1x32x8-d128"),
+    pytest.param("bf16", "clip", S1, True, 0.25, None, id="bf16-clip-variable-n"),
+    pytest.param("bf16_mfma", "slot", S1, False, 0.25, None, id="bf16_mfma-slot"),
+]
+
+
+@pytest.mark.parametrize("precision,attention,kw,variable_n,p,pair_env", DROP_CASES)
+def test_every_launch_of_the_dropout_step_matches_fp64_on_its_inputs(dev, monkeypatch, precision, attention, kw, variable_n, p, pair_env):
+    """As test_every_launch_matches_fp64_on_its_inputs, with dropout in the engine and in the contract: step_trace.check
+    also holds every fused launch to the mask arguments and the counter value by name, to the reference's dropped set
+    exactly, and x_out, h, mean, rstd / dx, ddrop to the bars of the plain layer-norm stages."""
+    from vlg.engine import LayoutEngine
+    from vlg.spec import LayoutConfig
+    if pair_env is not None:
+        monkeypatch.setenv("VLG_PAIR_BACKWARD", pair_env)
+    cfg = LayoutConfig(attention=attention, **kw)
+    eng = LayoutEngine(cfg, dev, precision=precision, padded_slots=bool(variable_n), dropout=p, dropout_seed=DROP_SEED)
+    c = SS.Contract(precision, attention, masked=bool(variable_n), paired=None if pair_env is None else pair_env != "0",
+                    dropout=(p, DROP_SEED, DROP_K))
+    assert eng.gelu_grad_saved == c.gelu_grad_saved and eng.pair_backward == c.paired and eng.bf16_store == c.store_bf16
+    batch = _batch(cfg, variable_n)
+    if variable_n:
+        assert bool((batch["valid"] == 0).any())
+    b = {k: v.to(dev) for k, v in batch.items()}
+    eng.set_dropout_step(DROP_K)
+    loss0 = eng.forward_backward(b).clone()
+    grads0 = eng.grads.clone()
+    assert eng.dropout_step == DROP_K + 1
+    eng.set_dropout_step(DROP_K)
+    records, state = step_trace.trace(eng, b)
+    assert torch.equal(eng.loss_out, loss0) and torch.equal(eng.grads, grads0), "the traced run is not bitwise the untraced one"
+    names, fams = [r["name"] for r in records], [r["family"] for r in records]
+    L = cfg.n_layers
+    assert names.count("vlg_dropout_add_layernorm_fwd" + c.sfx) == 2 * L + 1 and not any(n.startswith("vlg_layernorm_fwd") for n in names)
+    assert names.count("vlg_layernorm_bwd_dropout" + c.sfx) == 2 * L + 1
+    assert "vlg_layernorm_bwd" not in names and "vlg_layernorm_bwd_bf16" not in names
+    assert names.count("vlg_dropout_step_advance") == 1 and names[-1] == "vlg_dropout_step_advance"
+    assert len(records) == len(SS.schedule(cfg, SS.Contract(precision, attention, masked=bool(variable_n), paired=c.paired))) + 1
+    if c.paired:
+        assert fams.count("gemm_pair") == 4 * L and fams.count("gemm_wgrad") == 0 and fams.count("gemm_dgrad") == 1, fams
+    else:
+        assert fams.count("gemm_pair") == 0 and fams.count("gemm_wgrad") == 4 * L and fams.count("gemm_dgrad") == 4 * L + 1, fams
+    log = []
+    try:
+        step_trace.check(records, state, cfg, c, batch, log=log)
+    finally:
+        print("\n%s %s %s dropout p=%g k=%d: worst |err| vs fp64 per launch kind: %s" % (precision, attention, kw, p, DROP_K, _summary(log)))
 
 
 def test_per_clip_attention_refuses_the_ragged_shape():
