@@ -249,6 +249,15 @@ int vlg_attention_bwd(const float* qkv, const float* dout, float* dqkv,
 int vlg_attention_fwd_bf16(const vlg_bf16* qkv, vlg_bf16* o, int64_t n_seq, int T, int d, void* stream);
 int vlg_attention_bwd_bf16(const vlg_bf16* qkv, const vlg_bf16* dout, vlg_bf16* dqkv,
                            int64_t n_seq, int T, int d, void* stream);
+/* The same attention for ONE query position p against a K/V cache (generation while the history is shorter than the
+ * window; DESIGN.md, "Generation").  qkv is the [n_seq*T, 3d] buffer above; for sequence r and head h the query is row
+ * r*T + p, keys and values are rows r*T + j, j <= p.  Rows j > p are never read (they may hold anything, NaN included).
+ * o is [n_seq, d] with leading dimension ldo >= d elements: o[r, :] is written and nothing else.  Scale 1/8 and the
+ * max-subtracted expf softmax of vlg_attention_fwd: p = T-1 agrees with row T-1 of that entry to rounding.
+ * VLG_ERR_SHAPE, nothing enqueued: T outside {4, 8, 16, 32}, p outside [0, T), d % 64 != 0, ldo < d, n_seq < 1.
+ * VLG_ERR_ALIGN: qkv or o NULL or misaligned (16 bytes fp32, 8 bytes bf16). */
+int vlg_attention_step(const float* qkv, float* o, int64_t n_seq, int T, int d, int p, int64_t ldo, void* stream);
+int vlg_attention_step_bf16(const vlg_bf16* qkv, vlg_bf16* o, int64_t n_seq, int T, int d, int p, int64_t ldo, void* stream);
 
 /* ---------------------------------------------------------------------- losses
  * Fused softmax-cross-entropy + smooth-L1 + IoU, forward and backward in one pass.
@@ -304,6 +313,11 @@ int vlg_attention_clip_bwd_bf16(const vlg_bf16* qkv, const float* valid, const v
  * VLG_ERR_ALIGN. */
 int vlg_head_last_frame(const float* x, const float* gamma, const float* beta, const float* head_w, const float* head_b,
                         float* out_last, int B, int T, int N, int d, int n_out, float eps, void* stream);
+/* The same on frame t_read, 0 <= t_read < T (else VLG_ERR_SHAPE): rows m = r*T + t_read are read and no other.  One kernel,
+ * one arithmetic: vlg_head_last_frame IS the t_read = T-1 call and gives bit-identical results.  A rollout whose history is
+ * still shorter than the window reads the newest real frame with it; T = 1 serves a compact [B*N, d] residual stream. */
+int vlg_head_frame(const float* x, const float* gamma, const float* beta, const float* head_w, const float* head_b,
+                   float* out_last, int B, int T, int N, int d, int n_out, int t_read, float eps, void* stream);
 /* One decoding step: choose the next frame from out_last ([B*N, n_classes + 4]: logits | raw box), write it to
  * gen_cls[b, step, n] / gen_box[b, step, n, :] ((B, steps, N) int64 / (B, steps, N, 4) fp32; other step indices are not
  * touched) and write the NEXT window: cls_out[:, t] = cls_in[:, t + 1] for t < T - 1, cls_out[:, T - 1] = the new frame
@@ -324,6 +338,18 @@ int vlg_layout_decode(const float* out_last, const int64_t* cls_in, const float*
                       int64_t* cls_out, float* box_out, float* valid_out, int64_t* gen_cls, float* gen_box,
                       int B, int T, int N, int n_classes, int steps, int step,
                       float temperature, int top_k, uint64_t seed, int keep_padded, void* stream);
+/* The same step while the history holds pos < T frames: nothing slides, the window (cls, box, valid; (B, T, N) public
+ * order) is updated IN PLACE.  The newest frame pos-1 is read (keep_padded looks at it), the frame drawn from out_last by
+ * the rule above (one device function serves both entries; Philox counter (b*N + n, step, 0, 0)) is written to frame pos
+ * of cls / box, with valid[:, pos] (valid may be NULL) = 1.0f where the class is < n_classes else 0.0f, to
+ * gen_cls[:, step] / gen_box[:, step], and to the compact copy frame_cls (B, N) int64 / frame_box (B, N, 4) fp32 that the
+ * next step's embedding reads (vlg_embed_fwd with T = 1).  No other element of any buffer is touched; plain vector stores.
+ * Refusals as vlg_layout_decode, plus VLG_ERR_SHAPE for pos outside [1, T), a NULL frame_cls / frame_box, or any two of
+ * the eight buffers overlapping. */
+int vlg_layout_decode_append(const float* out_last, int64_t* cls, float* box, float* valid,
+                             int64_t* gen_cls, float* gen_box, int64_t* frame_cls, float* frame_box,
+                             int B, int T, int N, int n_classes, int pos, int steps, int step,
+                             float temperature, int top_k, uint64_t seed, int keep_padded, void* stream);
 
 /* ------------------------------------------------------------------ validation metrics (csrc/metrics.hip)
  * Scores head outputs against targets and ADDS the result to a running record in device memory: `counts` (int64 slots,

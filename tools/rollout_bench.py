@@ -3,7 +3,11 @@
 launches + vlg_head_last_frame + vlg_layout_decode, no host wait inside the loop) against the host loop it replaced
 (restated here from forward() + outputs_btn(): training forward with the loss on dummy targets, argmax / sigmoid / cat in
 torch, two copies to the CPU per frame), alternately in one process on the same prompt, fp32 and bf16.
-    python tools/rollout_bench.py [B] [T] [N] [d] [--layers L] [--steps S] [--attention slot|clip]
+    python tools/rollout_bench.py [B] [T] [N] [d] [--layers L] [--steps S] [--attention slot|clip] [--prompt P] [--no-cache]
+--prompt P (1 <= P < T) measures the short-prompt rollout instead: the prompt pass on its own (steps = 1), and --steps
+frames (default T - P: the history grows to the window) with the cached grow step and with the re-encoding one
+(cache=False), alternately; ms per grown frame = (the call - the prompt pass) / (frames - 1).  --no-cache leaves the
+cached variant out (per-clip attention has none).
 Times are host wall-clock around a call that ends with the results on the CPU (what generate_sequence returns), so the
 host waits of the loop are in the figure; launches per frame are counted through the engine's single launch point."""
 import os, sys, time
@@ -59,7 +63,49 @@ def launches(eng, fn, *args):
     return seen
 
 
-skip = {i + 1 for i, x in enumerate(sys.argv) if x in ("--layers", "--steps", "--attention")}
+def prompt_bench(cfg, dev, cls, box, P, frames, with_cache):
+    """the short-prompt rollout: every variant once per round, 9 rounds, in one process on the same prompt"""
+    cls, box = cls[:, :P].contiguous(), box[:, :P].contiguous()
+
+    def variant(steps, cache):
+        def run(eng):
+            c, b = eng.rollout(cls, box, steps=steps, cache=cache)
+            return c.cpu(), b.cpu()
+        return run
+
+    paths = {"prompt pass": variant(1, False), "re-encode": variant(frames, False)}
+    if with_cache:
+        paths["cached"] = variant(frames, None)
+    for precision in ("fp32", "bf16"):
+        eng = LayoutEngine(cfg, dev, precision=precision, padded_slots=False)
+        res = {k: fn(eng) for k, fn in paths.items()}                        # warm-up
+        count = {k: sum(launches(eng, fn).values()) for k, fn in paths.items()}
+        ts = {k: [] for k in paths}
+        for _ in range(9):
+            for k, fn in paths.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(4):
+                    fn(eng)
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) * 1e3 / 4)
+        head = "%-4s (B,T,N,d)=(%d,%d,%d,%d) %d layers %s prompt %d" % (precision, cfg.B, cfg.T, cfg.N, cfg.d, cfg.n_layers,
+                                                                        cfg.attention, P)
+        t = sorted(ts["prompt pass"])
+        print("%s prompt pass: %.3f ms (median of 9; min %.3f max %.3f)  %d launches" % (head, t[4], t[0], t[-1], count["prompt pass"]))
+        for k in paths:
+            if k == "prompt pass" or frames < 2:
+                continue
+            per = sorted((a - b) / (frames - 1) for a, b in zip(ts[k], ts["prompt pass"]))      # round by round
+            print("%s %-9s: %.3f ms per grown frame over %d frames (median of 9; min %.3f max %.3f)  %.1f launches/frame" % (
+                head, k, per[4], frames - 1, per[0], per[-1], (count[k] - count["prompt pass"]) / (frames - 1)))
+        if with_cache:
+            same = float((res["cached"][0] == res["re-encode"][0]).float().mean())
+            print("%s: cached vs re-encode, first-frame boxes differ by at most %.2e, %.2f %% of class ids equal" % (
+                head, float((res["cached"][1][:, 0] - res["re-encode"][1][:, 0]).abs().max()), 100 * same))
+
+
+skip = {i + 1 for i, x in enumerate(sys.argv) if x in ("--layers", "--steps", "--attention", "--prompt")}
 a = [x for i, x in enumerate(sys.argv[1:], 1) if not x.startswith("--") and i not in skip]
 B, T, N, d = (int(a[i]) if len(a) > i else v for i, v in enumerate((32, 16, 64, 256)))
 steps = int(opt("--steps", 8))
@@ -67,6 +113,12 @@ cfg = LayoutConfig(B=B, T=T, N=N, d=d, n_layers=int(opt("--layers", 4)), attenti
 dev = torch.device("cuda:0")
 batch = to_device(synthetic_clips(B, T, N, seed=3), dev)
 cls, box = batch["slot_class"], batch["slot_box"]
+if "--prompt" in sys.argv:
+    P = int(opt("--prompt", 2))
+    if not 1 <= P < T:
+        sys.exit("--prompt takes 1 <= P < T")
+    prompt_bench(cfg, dev, cls, box, P, int(opt("--steps", T - P)), "--no-cache" not in sys.argv and cfg.attention != "clip")
+    sys.exit(0)
 paths = {"host loop": host_loop, "rollout()": device_path}
 for precision in ("fp32", "bf16"):
     eng = LayoutEngine(cfg, dev, precision=precision, padded_slots=False)

@@ -619,6 +619,78 @@ __global__ __launch_bounds__(256) void attn32_bwd_bf16_kernel(const bf16_t* __re
     attn32_bwd_body(qkv, dout, dqkv, d, n_heads, n_items);
 }
 
+// ------------------------------------------------------------------------------------------------
+// One query position against the cache (generation while the history grows): query row r*T + p, keys and values of rows
+// r*T + j, j <= p; rows j > p are never read.  One wavefront per (sequence, head), lane = channel: a key or value row of
+// a head is one coalesced 64-element load, a score is one wavefront reduction, and the softmax is the max-subtracted expf
+// one of the kernels above.  Every load of the wave is issued before the first reduction.  Bytes per (sequence, head):
+// 2*(p+1)*64 elements in, 64 out; at B*N sequences the launch is latency-bound, not bandwidth-bound.
+// The score reduction runs in fp64 (a product of two fp32 values is exact there, so the score is rounded once): a
+// shuffle tree cannot accumulate by FMA the way the tile kernels' dot products do, and with |score| ~ 60-90 the rounding
+// of 64 fp32 products showed against the fp64 reference.  6 x 2 more shuffles per key in a kernel that waits on launches.
+__device__ __forceinline__ double wave_sum64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+template <int T, typename EL>
+__global__ __launch_bounds__(256) void attn_step_kernel(const EL* __restrict__ qkv, EL* __restrict__ o, int d, int n_heads,
+                                                        int64_t n_items, int p, int64_t ldo) {
+    const int lane = threadIdx.x & 63;
+    const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= n_items) return;                             // wave-uniform
+    const int64_t seq = item / n_heads;
+    const int hh = (int)(item - seq * n_heads);
+    const int64_t ld = 3 * (int64_t)d;
+    const EL* base = qkv + seq * T * ld + hh * HD + lane;
+    const double q = (double)ld1(base + p * ld);
+    float k[T], v[T], s[T];
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        k[j] = v[j] = 0.f;
+        if (j <= p) {                                         // wave-uniform
+            k[j] = ld1(base + j * ld + d);
+            v[j] = ld1(base + j * ld + 2 * d);
+        }
+    }
+    float mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        s[j] = -INFINITY;
+        if (j <= p) {
+            s[j] = (float)wave_sum64(q * (double)k[j]) * 0.125f;      // 1/sqrt(64)
+            mx = fmaxf(mx, s[j]);
+        }
+    }
+    float sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        s[j] = j <= p ? expf(s[j] - mx) : 0.f;
+        sum += s[j];
+    }
+    const float inv = 1.0f / sum;
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < T; ++j)
+        if (j <= p) acc += (s[j] * inv) * v[j];
+    st1(o + seq * ldo + hh * HD + lane, acc);
+}
+
+template <typename EL>
+static int attn_step_launch(const EL* qkv, EL* o, int64_t n_seq, int T, int d, int p, int64_t ldo, void* stream) {
+    const int H = d / HD;
+    const int64_t items = n_seq * H;
+    const dim3 grid((unsigned)((items + 3) / 4)), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    switch (T) {
+        case 4:  hipLaunchKernelGGL((attn_step_kernel<4, EL>),  grid, block, 0, s, qkv, o, d, H, items, p, ldo); break;
+        case 8:  hipLaunchKernelGGL((attn_step_kernel<8, EL>),  grid, block, 0, s, qkv, o, d, H, items, p, ldo); break;
+        case 16: hipLaunchKernelGGL((attn_step_kernel<16, EL>), grid, block, 0, s, qkv, o, d, H, items, p, ldo); break;
+        default: hipLaunchKernelGGL((attn_step_kernel<32, EL>), grid, block, 0, s, qkv, o, d, H, items, p, ldo); break;
+    }
+    return vlg_last_error();
+}
+
 static int attn_check(const void* a, const void* b, int64_t n_seq, int T, int d) {
     if (n_seq < 1 || d < HD || (d % HD) != 0) return VLG_ERR_SHAPE;
     if (T != 4 && T != 8 && T != 16 && T != 32) return VLG_ERR_SHAPE;
@@ -699,4 +771,23 @@ extern "C" int vlg_attention_bwd(const float* qkv, const float* dout, float* dqk
                                     dqkv, d, H, n_seq * H); break;
     }
     return vlg_last_error();
+}
+
+static int attn_step_check(const void* qkv, const void* o, int64_t n_seq, int T, int d, int p, int64_t ldo) {
+    if (int e = attn_check(qkv, o, n_seq, T, d)) return e;
+    if (p < 0 || p >= T || ldo < d) return VLG_ERR_SHAPE;
+    if (!qkv || !o) return VLG_ERR_ALIGN;
+    return 0;
+}
+
+extern "C" int vlg_attention_step(const float* qkv, float* o, int64_t n_seq, int T, int d, int p, int64_t ldo, void* stream) {
+    if (int e = attn_step_check(qkv, o, n_seq, T, d, p, ldo)) return e;
+    if (!vlg_aligned16(qkv) || !vlg_aligned16(o)) return VLG_ERR_ALIGN;
+    return attn_step_launch(qkv, o, n_seq, T, d, p, ldo, stream);
+}
+
+extern "C" int vlg_attention_step_bf16(const vlg_bf16* qkv, vlg_bf16* o, int64_t n_seq, int T, int d, int p, int64_t ldo,
+                                       void* stream) {
+    if (int e = attn_step_check(qkv, o, n_seq, T, d, p, ldo)) return e;
+    return attn_step_launch(reinterpret_cast<const bf16_t*>(qkv), reinterpret_cast<bf16_t*>(o), n_seq, T, d, p, ldo, stream);
 }

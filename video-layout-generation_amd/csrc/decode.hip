@@ -1,6 +1,7 @@
-// Generation tail of the layout-token model: the head on the last frame's rows, and one sampled decoding step.
+// Generation tail of the layout-token model: the head on one frame's rows, and one sampled decoding step.
 //
-// vlg_head_last_frame  final layer-norm + head of the B*N rows m = r*T + (T-1) only (a rollout uses no other row): one
+// vlg_head_frame       final layer-norm + head of the B*N rows m = r*T + t_read only (a rollout uses no other row;
+//     vlg_head_last_frame is the t_read = T-1 call: the window is full and slides): one
 //     64-lane wavefront per row, the row in registers (d/64 floats per lane, float4 loads when d % 256 == 0), mean and
 //     variance by wavefront shuffles exactly as csrc/layernorm.hip, then n_out dot products against the fp32 head weights
 //     (each lane reads the columns it holds; a 24 x d weight matrix stays in the vector L1), lane o keeps output o and
@@ -10,6 +11,8 @@
 //     temperature / top-k draw, Philox4x32-10 counter = token and step), writes the generated frame and the last frame of
 //     the next window; the T-1 earlier frames of the window are copied by all threads of the grid.  Every store is a plain
 //     vector store; no atomics, no state.
+// vlg_layout_decode_append  the same step while the history is shorter than the window: the decoding rule is one device
+//     function (decode_token) for both; the new frame is written at its position of the window in place, nothing slides.
 #include "common.h"
 
 #define HL_BLOCK 256
@@ -40,7 +43,7 @@ template <int E, bool V4>
 __global__ __launch_bounds__(HL_BLOCK) void head_last_kernel(
     const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
     const float* __restrict__ head_w, const float* __restrict__ head_b, float* __restrict__ out,
-    int64_t rows, int T, int n_out, float eps) {
+    int64_t rows, int T, int t_read, int n_out, float eps) {
     constexpr int d = E * 64, R = HL_ROWS(E);
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * HL_WAVES + (threadIdx.x >> 6);
@@ -54,7 +57,7 @@ __global__ __launch_bounds__(HL_BLOCK) void head_last_kernel(
 #pragma unroll
         for (int i = 0; i < R; ++i) {                          // a short last group re-reads the last row, stores are guarded
             const int64_t r = r0 + i < rows ? r0 + i : rows - 1;
-            hl_load<E, V4>(x + (r * T + (T - 1)) * d, lane, v[i]);
+            hl_load<E, V4>(x + (r * T + t_read) * d, lane, v[i]);
         }
 #pragma unroll
         for (int i = 0; i < R; ++i) {
@@ -89,12 +92,13 @@ __global__ __launch_bounds__(HL_BLOCK) void head_last_kernel(
 }
 
 #define HL_CASE(E) case E: hipLaunchKernelGGL((head_last_kernel<E, (E) % 4 == 0>), grid, block, 0, s, x, gamma, beta, head_w, head_b, \
-                                              out_last, rows, T, n_out, eps); break;
+                                              out_last, rows, T, t_read, n_out, eps); break;
 
-extern "C" int vlg_head_last_frame(const float* x, const float* gamma, const float* beta, const float* head_w,
-                                   const float* head_b, float* out_last, int B, int T, int N, int d, int n_out,
-                                   float eps, void* stream) {
+extern "C" int vlg_head_frame(const float* x, const float* gamma, const float* beta, const float* head_w,
+                              const float* head_b, float* out_last, int B, int T, int N, int d, int n_out, int t_read,
+                              float eps, void* stream) {
     if (B < 1 || T < 1 || N < 1 || d < 64 || d % 64 != 0 || d > 1024 || n_out < 1 || n_out > HL_MAX_OUT) return VLG_ERR_SHAPE;
+    if (t_read < 0 || t_read >= T) return VLG_ERR_SHAPE;
     if (!vlg_aligned16(x) || !vlg_aligned16(gamma) || !vlg_aligned16(beta) || !vlg_aligned16(head_w) ||
         !vlg_aligned16(head_b) || !vlg_aligned16(out_last)) return VLG_ERR_ALIGN;
     const int64_t rows = (int64_t)B * N;
@@ -108,6 +112,13 @@ extern "C" int vlg_head_last_frame(const float* x, const float* gamma, const flo
         default: return VLG_ERR_SHAPE;
     }
     return vlg_last_error();
+}
+
+// the frame a sliding rollout reads: the same launch at t_read = T - 1
+extern "C" int vlg_head_last_frame(const float* x, const float* gamma, const float* beta, const float* head_w,
+                                   const float* head_b, float* out_last, int B, int T, int N, int d, int n_out,
+                                   float eps, void* stream) {
+    return vlg_head_frame(x, gamma, beta, head_w, head_b, out_last, B, T, N, d, n_out, T - 1, eps, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------- decoding
@@ -124,69 +135,83 @@ __device__ __forceinline__ uint32_t philox_first(uint32_t c0, uint32_t c1, uint3
     return c0;
 }
 
+// The decoding rule, written once for the sliding step and the appending one.  l: token r's [logits | raw box] (the logits
+// become the running sums); prev / prev_box: the token's class and box in the newest frame of the history.
+__device__ __forceinline__ void decode_token(float* l, int C, int64_t prev, const float* __restrict__ prev_box, int64_t r, int step,
+                                             float temperature, int top_k, uint32_t k0, uint32_t k1, int keep_padded,
+                                             int64_t& cls, float4& box) {
+    if (keep_padded && prev >= C) {                        // a padded slot stays padded, box and all
+        cls = prev;
+        box = ld4(prev_box);
+    } else {
+        box = make_float4(1.0f / (1.0f + expf(-l[C])), 1.0f / (1.0f + expf(-l[C + 1])),
+                          1.0f / (1.0f + expf(-l[C + 2])), 1.0f / (1.0f + expf(-l[C + 3])));
+        int pick = 0;
+        if (temperature == 0.f) {
+            float best = l[0];
+            for (int c = 1; c < C; ++c)
+                if (l[c] > best) { best = l[c]; pick = c; }    // first maximum
+        } else {
+            uint32_t kept = C >= 32 ? 0xffffffffu : (1u << C) - 1u;
+            if (top_k > 0 && top_k < C) {                  // the top_k largest RAW logits, equal values: lower index first
+                kept = 0u;
+                for (int c = 0; c < C; ++c) {
+                    const float lc = l[c];
+                    int rank = 0;
+                    for (int j = 0; j < C; ++j) rank += (l[j] > lc || (l[j] == lc && j < c)) ? 1 : 0;
+                    if (rank < top_k) kept |= 1u << c;
+                }
+            }
+            float m = -INFINITY;
+            for (int c = 0; c < C; ++c)
+                if ((kept >> c) & 1u) m = fmaxf(m, l[c] / temperature);
+            float cum = 0.f;
+            for (int c = 0; c < C; ++c) {
+                if ((kept >> c) & 1u) cum += expf(l[c] / temperature - m);
+                l[c] = cum;
+            }
+            const uint32_t x0 = philox_first((uint32_t)r, (uint32_t)step, k0, k1);
+            const float u = (float)(x0 >> 8) * 5.9604644775390625e-08f + 2.98023223876953125e-08f;    // 2^-24, 2^-25
+            const float thr = u * cum;                     // cum = S
+            pick = -1;
+            int last_kept = 0;
+            for (int c = 0; c < C; ++c)
+                if ((kept >> c) & 1u) {
+                    last_kept = c;
+                    if (pick < 0 && l[c] >= thr) pick = c;
+                }
+            if (pick < 0) pick = last_kept;
+        }
+        cls = pick;
+    }
+}
+
+// stage the block's rows of out_last in LDS; returns the number of tokens of this block
+__device__ __forceinline__ int decode_stage(float (*rows)[DEC_LD], const float* __restrict__ out_last, int64_t BN, int n_out) {
+    const int tid = threadIdx.x;
+    const int64_t r_first = (int64_t)blockIdx.x * DEC_BLOCK;
+    const int here = (int)(BN - r_first < DEC_BLOCK ? BN - r_first : DEC_BLOCK);
+    for (int e = tid; e < here * n_out; e += DEC_BLOCK) rows[e / n_out][e % n_out] = out_last[r_first * n_out + e];
+    __syncthreads();
+    return here;
+}
+
 __global__ __launch_bounds__(DEC_BLOCK) void layout_decode_kernel(
     const float* __restrict__ out_last, const int64_t* __restrict__ cls_in, const float* __restrict__ box_in,
     int64_t* __restrict__ cls_out, float* __restrict__ box_out, float* __restrict__ valid_out,
     int64_t* __restrict__ gen_cls, float* __restrict__ gen_box, int B, int T, int N, int C, int steps, int step,
     float temperature, int top_k, uint32_t k0, uint32_t k1, int keep_padded) {
     __shared__ float rows[DEC_BLOCK][DEC_LD];
-    const int n_out = C + 4, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     const int64_t BN = (int64_t)B * N, r_first = (int64_t)blockIdx.x * DEC_BLOCK;
-    const int here = (int)(BN - r_first < DEC_BLOCK ? BN - r_first : DEC_BLOCK);      // tokens of this block
-    for (int e = tid; e < here * n_out; e += DEC_BLOCK) rows[e / n_out][e % n_out] = out_last[r_first * n_out + e];
-    __syncthreads();
+    const int here = decode_stage(rows, out_last, BN, C + 4);
     if (tid < here) {
-        float* l = rows[tid];                                  // this token's [logits | raw box]; the logits become cum below
         const int64_t r = r_first + tid;
         const int b = (int)(r / N), n = (int)(r % N);
         const int64_t last = ((int64_t)b * T + (T - 1)) * N + n;
         int64_t cls;
         float4 box;
-        const int64_t prev = cls_in[last];
-        if (keep_padded && prev >= C) {                        // a padded slot stays padded, box and all
-            cls = prev;
-            box = ld4(box_in + 4 * last);
-        } else {
-            box = make_float4(1.0f / (1.0f + expf(-l[C])), 1.0f / (1.0f + expf(-l[C + 1])),
-                              1.0f / (1.0f + expf(-l[C + 2])), 1.0f / (1.0f + expf(-l[C + 3])));
-            int pick = 0;
-            if (temperature == 0.f) {
-                float best = l[0];
-                for (int c = 1; c < C; ++c)
-                    if (l[c] > best) { best = l[c]; pick = c; }    // first maximum
-            } else {
-                uint32_t kept = C >= 32 ? 0xffffffffu : (1u << C) - 1u;
-                if (top_k > 0 && top_k < C) {                  // the top_k largest RAW logits, equal values: lower index first
-                    kept = 0u;
-                    for (int c = 0; c < C; ++c) {
-                        const float lc = l[c];
-                        int rank = 0;
-                        for (int j = 0; j < C; ++j) rank += (l[j] > lc || (l[j] == lc && j < c)) ? 1 : 0;
-                        if (rank < top_k) kept |= 1u << c;
-                    }
-                }
-                float m = -INFINITY;
-                for (int c = 0; c < C; ++c)
-                    if ((kept >> c) & 1u) m = fmaxf(m, l[c] / temperature);
-                float cum = 0.f;
-                for (int c = 0; c < C; ++c) {
-                    if ((kept >> c) & 1u) cum += expf(l[c] / temperature - m);
-                    l[c] = cum;
-                }
-                const uint32_t x0 = philox_first((uint32_t)r, (uint32_t)step, k0, k1);
-                const float u = (float)(x0 >> 8) * 5.9604644775390625e-08f + 2.98023223876953125e-08f;    // 2^-24, 2^-25
-                const float thr = u * cum;                     // cum = S
-                pick = -1;
-                int last_kept = 0;
-                for (int c = 0; c < C; ++c)
-                    if ((kept >> c) & 1u) {
-                        last_kept = c;
-                        if (pick < 0 && l[c] >= thr) pick = c;
-                    }
-                if (pick < 0) pick = last_kept;
-            }
-            cls = pick;
-        }
+        decode_token(rows[tid], C, cls_in[last], box_in + 4 * last, r, step, temperature, top_k, k0, k1, keep_padded, cls, box);
         const int64_t g = ((int64_t)b * steps + step) * N + n;
         gen_cls[g] = cls;
         st4(gen_box + 4 * g, box);
@@ -234,6 +259,63 @@ extern "C" int vlg_layout_decode(const float* out_last, const int64_t* cls_in, c
     const dim3 grid((unsigned)((BN + DEC_BLOCK - 1) / DEC_BLOCK)), block(DEC_BLOCK);
     hipLaunchKernelGGL(layout_decode_kernel, grid, block, 0, (hipStream_t)stream, out_last, cls_in, box_in, cls_out, box_out,
                        valid_out, gen_cls, gen_box, B, T, N, n_classes, steps, step, temperature, top_k,
+                       (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), keep_padded);
+    return vlg_last_error();
+}
+
+// ---------------------------------------------------------------------------------------- decoding, growing history
+// The same step while the history is shorter than the window: nothing slides.  Thread i decodes token i from the newest
+// frame pos - 1 and writes frame pos of the window in place, the generated frame and a compact copy of it (the next
+// step's embedding input).  64 B per token out; no other element of any buffer is touched.
+__global__ __launch_bounds__(DEC_BLOCK) void layout_decode_append_kernel(
+    const float* __restrict__ out_last, int64_t* __restrict__ cls, float* __restrict__ box, float* __restrict__ valid,
+    int64_t* __restrict__ gen_cls, float* __restrict__ gen_box, int64_t* __restrict__ frame_cls, float* __restrict__ frame_box,
+    int B, int T, int N, int C, int pos, int steps, int step, float temperature, int top_k, uint32_t k0, uint32_t k1,
+    int keep_padded) {
+    __shared__ float rows[DEC_BLOCK][DEC_LD];
+    const int tid = threadIdx.x;
+    const int64_t BN = (int64_t)B * N, r_first = (int64_t)blockIdx.x * DEC_BLOCK;
+    const int here = decode_stage(rows, out_last, BN, C + 4);
+    if (tid >= here) return;
+    const int64_t r = r_first + tid;
+    const int b = (int)(r / N), n = (int)(r % N);
+    const int64_t newest = ((int64_t)b * T + (pos - 1)) * N + n, at = newest + N;
+    int64_t c;
+    float4 bx;
+    decode_token(rows[tid], C, cls[newest], box + 4 * newest, r, step, temperature, top_k, k0, k1, keep_padded, c, bx);
+    const int64_t g = ((int64_t)b * steps + step) * N + n;
+    gen_cls[g] = c;
+    st4(gen_box + 4 * g, bx);
+    cls[at] = c;
+    st4(box + 4 * at, bx);
+    if (valid != nullptr) valid[at] = c < C ? 1.0f : 0.0f;
+    frame_cls[r] = c;
+    st4(frame_box + 4 * r, bx);
+}
+
+extern "C" int vlg_layout_decode_append(const float* out_last, int64_t* cls, float* box, float* valid, int64_t* gen_cls,
+                                        float* gen_box, int64_t* frame_cls, float* frame_box, int B, int T, int N,
+                                        int n_classes, int pos, int steps, int step, float temperature, int top_k,
+                                        uint64_t seed, int keep_padded, void* stream) {
+    if (B < 1 || T < 1 || N < 1 || n_classes < 1 || n_classes + 4 > HL_MAX_OUT) return VLG_ERR_SHAPE;
+    if (!(temperature >= 0.f) || !(temperature <= 3.0e38f)) return VLG_ERR_SHAPE;      // negative, inf or NaN
+    if (top_k < 0 || top_k > n_classes || steps < 1 || step < 0 || step >= steps) return VLG_ERR_SHAPE;
+    if (pos < 1 || pos >= T) return VLG_ERR_SHAPE;
+    const int64_t BN = (int64_t)B * N, M = BN * T;
+    if (BN > 0x7fffffffLL) return VLG_ERR_SHAPE;                                        // the Philox counter word is the token index
+    if (!out_last || !cls || !box || !gen_cls || !gen_box || !frame_cls || !frame_box) return VLG_ERR_SHAPE;
+    // the window is updated in place (frame pos - 1 read, frame pos written); every other pair of buffers must be disjoint
+    const void* p[8] = {out_last, cls, box, valid, gen_cls, gen_box, frame_cls, frame_box};
+    const int64_t n[8] = {BN * (n_classes + 4) * 4, M * 8, M * 16, M * 4, BN * steps * 8, BN * steps * 16, BN * 8, BN * 16};
+    for (int i = 0; i < 8; ++i)
+        for (int j = i + 1; j < 8; ++j)
+            if (dec_overlap(p[i], n[i], p[j], n[j])) return VLG_ERR_SHAPE;
+    if (!vlg_aligned16(out_last) || !vlg_aligned16(box) || !vlg_aligned16(gen_box) || !vlg_aligned16(frame_box) ||
+        !vlg_aligned8(cls) || !vlg_aligned8(gen_cls) || !vlg_aligned8(frame_cls) ||
+        (reinterpret_cast<uintptr_t>(valid) & 3u)) return VLG_ERR_ALIGN;
+    const dim3 grid((unsigned)((BN + DEC_BLOCK - 1) / DEC_BLOCK)), block(DEC_BLOCK);
+    hipLaunchKernelGGL(layout_decode_append_kernel, grid, block, 0, (hipStream_t)stream, out_last, cls, box, valid, gen_cls,
+                       gen_box, frame_cls, frame_box, B, T, N, n_classes, pos, steps, step, temperature, top_k,
                        (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), keep_padded);
     return vlg_last_error();
 }

@@ -649,14 +649,16 @@ class Trainer:
         FrameRollout), writes ../predict/val_<time>_{img,seg}.npy like trainer.py:474-476 and ALSO returns the two
         arrays (b, 3*(steps+2), H, W), (b, steps+2, H, W).
 
-        Layout mode: generate_sequence(slot_class (B,T,N), slot_box (B,T,N,4)): predict the frame after the clip,
-        append it, slide the T-frame window; returns classes (B,steps,N) and boxes (B,steps,N,4) on the CPU.
+        Layout mode: generate_sequence(slot_class (B,P,N), slot_box (B,P,N,4)) with a prompt of 1 <= P <= T frames: predict
+        the frame after the history, append it, and once the history fills the T-frame window slide it; returns classes
+        (B,steps,N) and boxes (B,steps,N,4) on the CPU.  A prompt shorter than T (the reference's generate_sequence starts
+        from two observed frames) grows to T with a K/V cache where the engine has one (LayoutEngine.rollout).
         temperature / top_k / seed / keep_padded: None takes the generation knob from args or the environment
         (generation_knobs; module docstring).  temperature 0 is the argmax; > 0 samples from softmax(logits / temperature)
         over the top_k largest logits (0 = all), reproducibly per (seed, token, step); keep_padded keeps a slot that is
         padded (reserved class id) in the window's last frame padded, with its box.  An engine with rollout()
         (vlg.engine.LayoutEngine) generates on the device, without a host wait per frame, and the result is copied to the
-        CPU once; any other engine runs the host loop, which can only take the argmax."""
+        CPU once; any other engine runs the host loop, which can only take the argmax of a full T-frame prompt."""
         if self.image_mode:
             if len(inputs) != 4:
                 raise TypeError("generate_sequence(img1, img2, seg1, seg2) in VLG_MODEL=gridnet mode")
@@ -684,6 +686,10 @@ class Trainer:
             raise ValueError("temperature > 0 and keep_padded need an engine with rollout() (vlg.engine.LayoutEngine: the "
                              "vlg_layout_decode kernel); %s has none, its host loop takes the argmax of every slot"
                              % type(self.engine).__name__)
+        if slot_class.shape[1] != self.cfg.T:
+            raise ValueError("a prompt of %d frames needs an engine with rollout() (vlg.engine.LayoutEngine grows a short "
+                             "history to the window); the host loop of %s takes exactly T=%d frames"
+                             % (slot_class.shape[1], type(self.engine).__name__, self.cfg.T))
         cls = slot_class.clone().to(self.device)
         box = slot_box.clone().to(self.device)
         B, T, N = cls.shape
@@ -709,10 +715,10 @@ class Trainer:
 
     def evaluate_rollout(self, clip_class, clip_box, temperature: Optional[float] = None, top_k: Optional[int] = None,
                          seed: Optional[int] = None, keep_padded: Optional[bool] = None, val_topk: Optional[int] = None,
-                         val_iou_thr: Optional[float] = None):
-        """Layout mode: how prediction quality decays with the horizon.  clip_class (B,T+S,N) / clip_box (B,T+S,N,4), CPU or
-        device tensors: the first T frames prompt a rollout of S steps, and step i is scored against frame T+i of the
-        clip on the device (vlg.engine.LayoutEngine.evaluate_rollout; one host read at the end).  temperature / top_k /
+                         val_iou_thr: Optional[float] = None, prompt_frames: Optional[int] = None):
+        """Layout mode: how prediction quality decays with the horizon.  clip_class (B,P+S,N) / clip_box (B,P+S,N,4), CPU or
+        device tensors: the first P = prompt_frames frames (None: T; 1 <= P <= T) prompt a rollout of S steps, and step i is
+        scored against frame P+i of the clip on the device (vlg.engine.LayoutEngine.evaluate_rollout; one host read at the end).  temperature / top_k /
         seed / keep_padded are the generation knobs of generate_sequence (None = from args or the environment);
         val_topk / val_iou_thr the metric's (None = metrics_knobs).  A step is scored on the model's distribution at that
         step (arg-max, rank and NLL of the logits, box = sigmoid(raw)), also when the history was sampled.
@@ -730,7 +736,8 @@ class Trainer:
                 clip_class.to(self.device).contiguous(), clip_box.to(self.device).contiguous(),
                 top_k=mk["top_k"] if val_topk is None else int(val_topk),
                 iou_thr=mk["iou_thr"] if val_iou_thr is None else float(val_iou_thr),
-                temperature=knobs["temperature"], sample_top_k=knobs["top_k"], seed=knobs["seed"], keep_padded=knobs["keep_padded"])
+                temperature=knobs["temperature"], sample_top_k=knobs["top_k"], seed=knobs["seed"], keep_padded=knobs["keep_padded"],
+                prompt_frames=prompt_frames)
         return record.summary()
 
     def eval_generate_sequence(self, img1, img2, seg1, seg2):

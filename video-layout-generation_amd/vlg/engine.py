@@ -61,6 +61,21 @@ def init_params(cfg: LayoutConfig, seed: int) -> Dict[str, torch.Tensor]:
     return out
 
 
+def grow_schedule(P: int, T: int, steps: int, cached: bool) -> list:
+    """What each of a rollout's `steps` generated frames does, from a prompt of P frames in a T-frame window: a list of
+    (encoder, t_read, pos).  encoder: "window" = the encoder on all T frames of the window buffer, "step" = the cached step
+    on the newest frame's rows alone; t_read: the window position whose output predicts the frame (the newest real frame);
+    pos: the position the new frame is appended at in place, or None once the window is full and slides instead.
+    The history grows while P + i < T; the step at P + i == T reads position T-1 and is the first to slide."""
+    if not 1 <= P <= T or steps < 1:
+        raise ValueError("grow_schedule takes 1 <= P <= T and steps >= 1")
+    out = []
+    for i in range(steps):
+        h = min(P + i, T)                                # frames of history the step predicts from
+        out.append(("step" if cached and 0 < i and P + i <= T else "window", h - 1, h if h < T else None))
+    return out
+
+
 class LayoutEngine(AdamSurface):
     """Owns parameters, optimiser state and workspace; runs forward/backward/Adam."""
 
@@ -341,12 +356,14 @@ class LayoutEngine(AdamSurface):
         return ((EPI_A_BF16 if a is not None and a.dtype == bf else 0) | (EPI_B_BF16 if b is not None and b.dtype == bf else 0) |
                 (EPI_OUT_BF16 if out is not None and out.dtype == bf else 0))
 
-    def _linear(self, a, w, b, c, M, N, K, epi, aux_in=None, aux_out=None):
+    def _linear(self, a, w, b, c, M, N, K, epi, aux_in=None, aux_out=None, ldc=None):
+        """ldc: leading dimension of c in elements (None = N, a dense output; the cached generation step writes one
+        position's q k v rows straight into the [rows, 3d] cache with ldc = T*3d)"""
         nb = (a.element_size() * M * K + w.element_size() * N * K +
               c.element_size() * M * N * (1 + (aux_in is not None) + (aux_out is not None)))
         flags = epi | self.gemm_flags | self._storage_bits(a, w, c)
         self._timed("gemm_fwd" if N > 32 else "gemm_head", 2.0 * M * N * K, "vlg_linear_fwd", ptr(a), K, ptr(w), K,
-                    ptr(b), ptr(c), N, ptr(aux_in), ptr(aux_out), M, N, K, flags, self._stream(), nbytes=nb)
+                    ptr(b), ptr(c), N if ldc is None else ldc, ptr(aux_in), ptr(aux_out), M, N, K, flags, self._stream(), nbytes=nb)
 
     def _dgrad(self, dy, w, dx, M, N, K, epi=EPI_NONE, aux_in=None):
         nb = dy.element_size() * M * N + w.element_size() * N * K + dx.element_size() * M * K * (1 + (aux_in is not None))
@@ -760,23 +777,75 @@ class LayoutEngine(AdamSurface):
                                torch.empty(M, dtype=torch.float32, device=self.device)) for _ in range(2))
         return self._win
 
+    def _grow_buffers(self) -> dict:
+        """Compact buffers of the cached grow step: one frame's B*N rows of every activation an encoder layer passes on,
+        capacity / T rows each, allocated on first use like _windows"""
+        if getattr(self, "_grow", None) is None:
+            cfg, R = self.cfg, -(-self.capacity // self.cfg.T)
+            f32 = dict(dtype=torch.float32, device=self.device)
+            act = dict(dtype=torch.bfloat16 if self.bf16_store else torch.float32, device=self.device)
+            self._grow = dict(cls=torch.empty(R, dtype=torch.int64, device=self.device), box=torch.empty(R, BOX_DIM, **f32),
+                              xa=torch.empty(R, cfg.d, **f32), xb=torch.empty(R, cfg.d, **f32), xmid=torch.empty(R, cfg.d, **f32),
+                              h=torch.empty(R, cfg.d, **act), att=torch.empty(R, cfg.d, **act), u=torch.empty(R, cfg.d_ff, **act),
+                              gl=torch.empty(R, cfg.d_ff, **act), stat=torch.empty(2, R, **f32))
+        return self._grow
+
+    def _encode_step(self, p: int, B: int, N: int) -> torch.Tensor:
+        """The encoder on the B*N rows of position p alone, against the K/V cache that self.qkv[l] holds for positions < p
+        (per-slot attention): embeds the compact frame vlg_layout_decode_append left, writes that position's q k v rows
+        into the cache and returns the compact residual stream [B*N, d] leaving the last layer.  As many launches as
+        _encode (1 + 7 per layer), on 1/T of its rows."""
+        cfg, d, ff, T = self.cfg, self.cfg.d, self.cfg.d_ff, self.cfg.T
+        g, BN, s = self._grow_buffers(), B * N, self._stream()
+        self._timed("embed_fwd", 0.0, "vlg_embed_fwd", ptr(g["cls"]), ptr(g["box"]), ptr(self.p("cls_emb")), ptr(self.p("box_w")),
+                    ptr(self.p("box_b")), ptr(self.p("time_emb")[p]), ptr(g["xa"]), B, 1, N, d, cfg.vocab, s,
+                    nbytes=4.0 * BN * d + 24.0 * BN)
+        x, y, h, stat = g["xa"], g["xb"], g["h"], g["stat"]
+        for l in range(cfg.n_layers):
+            pre = "l%d." % l
+            self._ln_fwd(x, pre + "ln1_g", h, stat, BN)
+            self._linear(h, self.pw(pre + "qkv_w"), self.p(pre + "qkv_b"), self.qkv[l].view(-1)[p * 3 * d:], BN, 3 * d, d, EPI_BIAS,
+                         ldc=T * 3 * d)
+            self._timed("attn_step", 0.0, "vlg_attention_step" + self._sfx, ptr(self.qkv[l]), ptr(g["att"]), BN, T, d, p, d, s,
+                        nbytes=self.qkv.element_size() * BN * d * (2.0 * (p + 1) + 2.0))
+            self._linear(g["att"], self.pw(pre + "proj_w"), self.p(pre + "proj_b"), g["xmid"], BN, d, d, EPI_BIAS | EPI_RESID, aux_in=x)
+            self._ln_fwd(g["xmid"], pre + "ln2_g", h, stat, BN)
+            self._linear(h, self.pw(pre + "ff1_w"), self.p(pre + "ff1_b"), g["gl"], BN, ff, d, self._epi_ff1, aux_out=g["u"])
+            self._linear(g["gl"], self.pw(pre + "ff2_w"), self.p(pre + "ff2_b"), y, BN, d, ff, EPI_BIAS | EPI_RESID, aux_in=g["xmid"])
+            x, y = y, x
+        return x
+
     def rollout(self, slot_class: torch.Tensor, slot_box: torch.Tensor, steps: int = 8, temperature: float = 0.0,
-                top_k: int = 0, seed: int = 0, keep_padded: bool = False, return_logits: bool = False) -> tuple:
-        """Autoregressive generation on the device: `steps` times predict the frame after the T-frame window, append it and
-        slide the window.  slot_class (B,T,N) int64 and slot_box (B,T,N,4) fp32 are device tensors and are not modified.
-        Per step: the encoder launches of forward(), vlg_head_last_frame on the B*N rows of the last frame (fp32 master
-        weights in every precision mode) and vlg_layout_decode, which draws the frame (temperature 0 = argmax; else
-        temperature / top-k sampling, Philox counter = token and step under `seed`; keep_padded carries a reserved class id
-        and its box forward), records it and writes the next window into the other of two engine-owned buffers.  No loss, no
-        targets, no host wait inside the loop.  Returns DEVICE tensors gen_cls (B,steps,N) int64, gen_box (B,steps,N,4) fp32
-        and, with return_logits, the (steps, B*N, n_out) buffer of each step's [logits | raw box]."""
+                top_k: int = 0, seed: int = 0, keep_padded: bool = False, return_logits: bool = False,
+                cache: Optional[bool] = None) -> tuple:
+        """Autoregressive generation on the device from a prompt of P frames, 1 <= P <= T: slot_class (B,P,N) int64 and
+        slot_box (B,P,N,4) fp32 are device tensors and are not modified.  Returns DEVICE tensors gen_cls (B,steps,N) int64,
+        gen_box (B,steps,N,4) fp32 and, with return_logits, the (steps, B*N, n_out) buffer of each step's [logits | raw box].
+        P == T: `steps` times predict the frame after the T-frame window, append it and slide the window.  Per step: the
+        encoder launches of forward(), vlg_head_last_frame on the B*N rows of the last frame (fp32 master weights in every
+        precision mode) and vlg_layout_decode, which draws the frame (temperature 0 = argmax; else temperature / top-k
+        sampling, Philox counter = token and step under `seed`; keep_padded carries a reserved class id and its box
+        forward), records it and writes the next window into the other of two engine-owned buffers.
+        P < T: the history GROWS until it fills the window, and the frame after an h-frame history is the model's output
+        at position h-1 of those h frames alone (all mixing along time is causal).  The window buffer holds T frames
+        throughout - the reserved class id, zero boxes and valid = 0 after the history; causality hides them.  The prompt
+        pass encodes that window once, reads frame P-1 (vlg_head_frame) and appends in place (vlg_layout_decode_append).
+        Each further frame until the window is full is a CACHED step with per-slot attention (cache None or True): the
+        encoder runs on the newest frame's B*N rows only, against the keys and values self.qkv[l] already holds for the
+        earlier positions (_encode_step, vlg_attention_step).  cache=False, and per-clip attention always, re-encodes the
+        window per grown frame instead; cache=True with per-clip attention raises.  Once the window is full the steps are
+        the sliding ones above, from the same buffers.
+        No loss, no targets, no host wait inside the loop (one before it with per-clip attention: the mask decision)."""
         cfg, d = self.cfg, self.cfg.d
         if slot_class.dim() != 3 or tuple(slot_box.shape) != tuple(slot_class.shape) + (BOX_DIM,):
-            raise ValueError("rollout takes slot_class (B,T,N) and slot_box (B,T,N,4)")
-        B, T, N = slot_class.shape
+            raise ValueError("rollout takes slot_class (B,P,N) and slot_box (B,P,N,4)")
+        B, P, N = slot_class.shape
+        T = cfg.T
         M, BN = B * T * N, B * N
-        if T != cfg.T:
-            raise ValueError("window has T=%d, engine was built for T=%d" % (T, cfg.T))
+        if not 1 <= P <= T:
+            raise ValueError("prompt has %d frames, the engine's window takes 1 to T=%d" % (P, T))
+        if cache and cfg.attention == "clip":
+            raise ValueError("cache=True: there is no cached step for per-clip attention (cache=None re-encodes the window)")
         if M > self.capacity:
             raise ValueError("window of %d tokens exceeds workspace capacity %d" % (M, self.capacity))
         for t, dt, what in ((slot_class, torch.int64, "slot_class"), (slot_box, torch.float32, "slot_box")):
@@ -787,27 +856,53 @@ class LayoutEngine(AdamSurface):
             raise ValueError("steps must be >= 1")
         if not (math.isfinite(temperature) and temperature >= 0.0) or not 0 <= top_k <= cfg.n_classes:
             raise ValueError("temperature must be finite and >= 0, top_k in [0, %d]" % cfg.n_classes)
+        cached = P < T and cfg.attention != "clip" and (cache is None or bool(cache))
         win = [(c[:M].view(B, T, N), b[:M].view(B, T, N, BOX_DIM), v[:M].view(B, T, N)) for c, b, v in self._windows()]
-        win[0][0].copy_(slot_class)
-        win[0][1].copy_(slot_box)
-        torch.lt(slot_class, cfg.n_classes, out=win[0][2])          # the first window's validity comes from the prompt
-        # per-clip attention: masks are decided ONCE, here (the only host wait of the call).  Later windows are masked by the
-        # decode kernel's valid_out; they never gain a padded slot the prompt did not have
-        self._masked = cfg.attention == "clip" and (self.padded_slots or bool((win[0][2] == 0).any()))
+        if P == T:
+            win[0][0].copy_(slot_class)
+            win[0][1].copy_(slot_box)
+            torch.lt(slot_class, cfg.n_classes, out=win[0][2])      # the first window's validity comes from the prompt
+        else:                                                       # frames after the history: reserved id, zero boxes, valid 0
+            win[0][0][:, :P].copy_(slot_class)
+            win[0][0][:, P:].fill_(cfg.n_classes)
+            win[0][1][:, :P].copy_(slot_box)
+            win[0][1][:, P:].zero_()
+            torch.lt(win[0][0], cfg.n_classes, out=win[0][2])
+        # per-clip attention: masks are decided ONCE, here (the only host wait of the call), on the prompt's real frames.  Later
+        # frames are masked by the decode kernels' valid; they never gain a padded slot the prompt did not have
+        self._masked = cfg.attention == "clip" and (self.padded_slots or bool((win[0][2][:, :P] == 0).any()))
         gen_cls = torch.empty(B, steps, N, dtype=torch.int64, device=self.device)
         gen_box = torch.empty(B, steps, N, BOX_DIM, dtype=torch.float32, device=self.device)
         logits = torch.empty(steps, BN, cfg.n_out, dtype=torch.float32, device=self.device)
         L, s = cfg.n_layers, self._stream()
-        for i in range(steps):
-            (cls, box, valid), (ncls, nbox, nvalid) = win[i & 1], win[(i + 1) & 1]
-            self._encode({"slot_class": cls, "slot_box": box, "valid": valid}, B, T, N, M)
-            self._timed("head_last", 2.0 * BN * cfg.n_out * d, "vlg_head_last_frame", ptr(self.x[L]), ptr(self.p("lnf_g")),
-                        ptr(self.p("lnf_b")), ptr(self.p("head_w")), ptr(self.p("head_b")), ptr(logits[i]), B, T, N, d,
-                        cfg.n_out, LN_EPS, s, nbytes=4.0 * BN * (d + cfg.n_out) + 4.0 * cfg.n_out * d)
+        grow = self._grow_buffers() if P < T else None
+        head = (ptr(self.p("lnf_g")), ptr(self.p("lnf_b")), ptr(self.p("head_w")), ptr(self.p("head_b")))
+        head_kw = dict(nbytes=4.0 * BN * (d + cfg.n_out) + 4.0 * cfg.n_out * d)
+        knobs = (float(temperature), top_k, int(seed) & 0xFFFFFFFFFFFFFFFF, int(bool(keep_padded)), s)
+        cur = 0                                                     # the window buffer that holds the history
+        for i, (encoder, t_read, pos) in enumerate(grow_schedule(P, T, steps, cached)):
+            (cls, box, valid), (ncls, nbox, nvalid) = win[cur], win[cur ^ 1]
+            if encoder == "step":                                   # the newest frame alone, against the cache
+                x = self._encode_step(t_read, B, N)
+                self._timed("head_last", 2.0 * BN * cfg.n_out * d, "vlg_head_last_frame", ptr(x), *head, ptr(logits[i]), B, 1, N, d,
+                            cfg.n_out, LN_EPS, s, **head_kw)
+            else:
+                self._encode({"slot_class": cls, "slot_box": box, "valid": valid}, B, T, N, M)
+                if t_read < T - 1:
+                    self._timed("head_last", 2.0 * BN * cfg.n_out * d, "vlg_head_frame", ptr(self.x[L]), *head, ptr(logits[i]), B, T, N,
+                                d, cfg.n_out, t_read, LN_EPS, s, **head_kw)
+                else:
+                    self._timed("head_last", 2.0 * BN * cfg.n_out * d, "vlg_head_last_frame", ptr(self.x[L]), *head, ptr(logits[i]),
+                                B, T, N, d, cfg.n_out, LN_EPS, s, **head_kw)
+            if pos is not None:                                     # append in place; the window does not move
+                self._timed("decode", 0.0, "vlg_layout_decode_append", ptr(logits[i]), ptr(cls), ptr(box), ptr(valid), ptr(gen_cls),
+                            ptr(gen_box), ptr(grow["cls"]), ptr(grow["box"]), B, T, N, cfg.n_classes, pos, steps, i, *knobs,
+                            nbytes=4.0 * BN * cfg.n_out + 3.0 * 28 * BN)
+                continue
             self._timed("decode", 0.0, "vlg_layout_decode", ptr(logits[i]), ptr(cls), ptr(box), ptr(ncls), ptr(nbox),
-                        ptr(nvalid), ptr(gen_cls), ptr(gen_box), B, T, N, cfg.n_classes, steps, i, float(temperature),
-                        top_k, int(seed) & 0xFFFFFFFFFFFFFFFF, int(bool(keep_padded)), s,
+                        ptr(nvalid), ptr(gen_cls), ptr(gen_box), B, T, N, cfg.n_classes, steps, i, *knobs,
                         nbytes=4.0 * BN * cfg.n_out + 2.0 * 28 * M)
+            cur ^= 1
         return (gen_cls, gen_box, logits) if return_logits else (gen_cls, gen_box)
 
     # --------------------------------------------------------------------- metrics
@@ -841,11 +936,13 @@ class LayoutEngine(AdamSurface):
 
     def evaluate_rollout(self, clip_class: torch.Tensor, clip_box: torch.Tensor, record: Optional[MetricsRecord] = None,
                          top_k: int = 5, iou_thr: float = 0.5, return_logits: bool = False, temperature: float = 0.0,
-                         sample_top_k: int = 0, seed: int = 0, keep_padded: bool = False):
-        """Score a rollout against the frames that really followed.  clip_class (B,T+S,N) int64 and clip_box (B,T+S,N,4)
-        fp32 are device tensors: the first T frames are the prompt, rollout(..., steps=S) generates S frames under the
-        sampling knobs (temperature, sample_top_k = rollout's top_k, seed, keep_padded), and step i's [logits | raw box]
-        are scored against frame T+i of the clip into row i of `record` (a fresh S-row record if None; a given one is
+                         sample_top_k: int = 0, seed: int = 0, keep_padded: bool = False, prompt_frames: Optional[int] = None,
+                         cache: Optional[bool] = None):
+        """Score a rollout against the frames that really followed.  clip_class (B,P+S,N) int64 and clip_box (B,P+S,N,4)
+        fp32 are device tensors: the first P = prompt_frames frames (None: T; 1 <= P <= T; `cache` as rollout takes it) are
+        the prompt, rollout(..., steps=S) generates S frames under the sampling knobs (temperature, sample_top_k =
+        rollout's top_k, seed, keep_padded), and step i's [logits | raw box]
+        are scored against frame P+i of the clip into row i of `record` (a fresh S-row record if None; a given one is
         added to): S launches of vlg_layout_metrics reading the clip in place, no host wait.  top_k and iou_thr are the
         METRIC's (top-k accuracy, IoU hit).  A truth slot with the reserved class id is unscored.
         A step is scored on the model's DISTRIBUTION at that step - arg-max, rank and NLL of its logits, box =
@@ -854,11 +951,14 @@ class LayoutEngine(AdamSurface):
         Returns the record, or (record, gen_cls, gen_box, logits) with return_logits."""
         cfg = self.cfg
         if clip_class.dim() != 3 or tuple(clip_box.shape) != tuple(clip_class.shape) + (BOX_DIM,):
-            raise ValueError("evaluate_rollout takes clip_class (B,T+S,N) and clip_box (B,T+S,N,4)")
+            raise ValueError("evaluate_rollout takes clip_class (B,P+S,N) and clip_box (B,P+S,N,4)")
         B, TS, N = clip_class.shape
-        T, S = cfg.T, TS - cfg.T
+        P = cfg.T if prompt_frames is None else int(prompt_frames)
+        if not 1 <= P <= cfg.T:
+            raise ValueError("prompt_frames must be in [1, T=%d], got %r" % (cfg.T, prompt_frames))
+        S = TS - P
         if S < 1:
-            raise ValueError("the clip has %d frames: the engine's %d-frame prompt and at least one frame to score" % (TS, T))
+            raise ValueError("the clip has %d frames: the %d-frame prompt and at least one frame to score" % (TS, P))
         for t, dt, what in ((clip_class, torch.int64, "clip_class"), (clip_box, torch.float32, "clip_box")):
             if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
                 raise ValueError("%s must be a contiguous %s HIP tensor" % (what, dt))
@@ -866,10 +966,11 @@ class LayoutEngine(AdamSurface):
             record = self.metrics_record(S)
         elif record.rows < S:
             raise ValueError("the record has %d rows, the rollout %d steps" % (record.rows, S))
-        gen_cls, gen_box, logits = self.rollout(clip_class[:, :T], clip_box[:, :T], steps=S, temperature=temperature,
-                                                top_k=sample_top_k, seed=seed, keep_padded=keep_padded, return_logits=True)
+        gen_cls, gen_box, logits = self.rollout(clip_class[:, :P], clip_box[:, :P], steps=S, temperature=temperature,
+                                                top_k=sample_top_k, seed=seed, keep_padded=keep_padded, return_logits=True,
+                                                cache=cache)
         for i in range(S):
-            self._metrics(logits[i], cfg.n_out, clip_class, clip_box, None, TS, T + i, record, i, B, 1, N, top_k, iou_thr)
+            self._metrics(logits[i], cfg.n_out, clip_class, clip_box, None, TS, P + i, record, i, B, 1, N, top_k, iou_thr)
         return (record, gen_cls, gen_box, logits) if return_logits else record
 
     # ---------------------------------------------------------------- public views

@@ -51,6 +51,8 @@ SIGNATURES = {
     "vlg_attention_bwd": (I, [P, P, P, L, I, I, P]),
     "vlg_attention_fwd_bf16": (I, [P, P, L, I, I, P]),
     "vlg_attention_bwd_bf16": (I, [P, P, P, L, I, I, P]),
+    "vlg_attention_step": (I, [P, P, L, I, I, I, L, P]),           # (qkv, o, n_seq, T, d, p, ldo, stream)
+    "vlg_attention_step_bf16": (I, [P, P, L, I, I, I, L, P]),
     "vlg_attention_clip_fwd": (I, [P, P, P, P, L, I, I, I, P]),
     "vlg_attention_clip_bwd": (I, [P, P, P, P, P, P, P, L, I, I, I, P]),
     "vlg_attention_clip_fwd_bf16": (I, [P, P, P, P, L, I, I, I, P]),
@@ -58,7 +60,9 @@ SIGNATURES = {
     "vlg_layout_loss_scratch": (I, []),
     "vlg_layout_loss": (I, [P, I, P, P, P, P, P, P, I, I, I, I, F, F, F, F, F, P]),
     "vlg_head_last_frame": (I, [P, P, P, P, P, P, I, I, I, I, I, F, P]),
+    "vlg_head_frame": (I, [P, P, P, P, P, P, I, I, I, I, I, I, F, P]),
     "vlg_layout_decode": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, c_uint64, I, P]),
+    "vlg_layout_decode_append": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, I, c_uint64, I, P]),
     "vlg_layout_metrics_counts": (I, [I]),
     "vlg_layout_metrics_sums": (I, [I]),
     "vlg_layout_metrics_scratch": (I, []),
