@@ -19,7 +19,7 @@ contract of the reduced-precision modes") enters as arguments and is read from v
 Stage outputs are returned UNROUNDED: the comparison allows a bf16 output its one rounding (vs_cpu32 bf16=True) and
 `emulate` rounds when it stores.  Rows of every (M, .) tensor are in the engine's order m = (b*N + n)*T + t.
 
-Dropout (Contract(dropout=(p, seed, k)); LayoutEngine._encode_dropout and the `_dropped` backward): proj and ff2 write
+Dropout (Contract(dropout=(p, seed, k)); LayoutEngine._encode with drop and the `_dropped` backward): proj and ff2 write
 branch + bias into `ybranch` without a residual epilogue; every layer-norm launch is the fused dropout + add + layer-norm
 of its site (0, then 1 + 2l and 2 + 2l; site 0 in place on x[0]); every layer-norm backward is the fused one of the site
 that FED it (2L, then 1 + 2l and 2l) and also leaves select(dx) in `ddrop`, which the proj / ff2 backward and the
@@ -307,7 +307,7 @@ def schedule(cfg, c):
     """The launches of one forward_backward in order, as vlg/engine.py makes them under contract `c`.  Each entry: stage
     (a name for messages), family, entry (C-ABI name), ops (names of the pointer arguments in order; None = NULL, "arena"
     = a slab arena, "*" = not pinned), flags (projection calls), kind + the operand names the stage function takes.
-    Under c.dropout the launches are _encode_dropout's and the `_dropped` backward's (module docstring): a fused entry also
+    Under c.dropout the launches are those of _encode with drop and the `_dropped` backward's (module docstring): a fused entry also
     carries its site."""
     L, d, ff = cfg.n_layers, cfg.d, cfg.d_ff
     clip = c.attention == "clip"

@@ -397,3 +397,44 @@ def test_stream_options_do_not_change_results(dev, precision, base, option, valu
         assert torch.equal(lp, lo), (lp, lo)
     torch.cuda.synchronize()
     assert torch.equal(plain.params, opt.params) and torch.equal(plain.exp_avg_sq, opt.exp_avg_sq)
+
+
+def test_overlap_option_launches_weight_gradients_on_the_side_stream(dev, monkeypatch):
+    """VLG_OVERLAP_WGRAD=1 really uses the second stream (the result test above would pass on one stream too): over one
+    forward_backward every weight gradient - the head's and four per layer - is a launch of its own on engine.side, enqueued
+    before the data gradient of the same projection; every other launch is on the caller's stream; nothing is paired."""
+    from vlg.engine import LayoutEngine
+    from vlg.spec import LayoutConfig
+    cfg = LayoutConfig(B=2, T=16, N=12, d=256, n_layers=2)
+    L, d, ff = cfg.n_layers, cfg.d, cfg.d_ff
+    monkeypatch.setenv("VLG_OVERLAP_WGRAD", "1")
+    eng = LayoutEngine(cfg, dev, precision="fp32")
+    monkeypatch.delenv("VLG_OVERLAP_WGRAD")
+    assert eng.overlap_wgrad and not eng.pair_backward
+    batch = to_dev(O.synthetic_batch(cfg.B, cfg.T, cfg.N, seed=70), dev)
+    seen = []                                            # (entry point, (N, K) of a projection's backward, stream handle)
+    launch = eng._timed
+
+    def recording(family, flops, name, *a, nbytes=0.0):
+        seen.append((name, tuple(a[-4:-2]), a[-1]))      # every launch of the step ends (..., flags or a size, stream)
+        launch(family, flops, name, *a, nbytes=nbytes)
+
+    eng._timed = recording
+    try:
+        eng.forward_backward(batch)
+    finally:
+        del eng._timed
+    torch.cuda.synchronize()
+    main, side = torch.cuda.current_stream().cuda_stream, eng.side.cuda_stream
+    assert side != main
+    names = [n for n, _, _ in seen]
+    assert names.count("vlg_linear_wgrad") == 1 + 4 * L
+    assert "vlg_linear_dgrad_wgrad" not in names
+    for i, (name, _, stream) in enumerate(seen):
+        assert stream == (side if name == "vlg_linear_wgrad" else main), (i, name, stream)
+    for shape, count in (((cfg.n_out, d), 1), ((d, ff), L), ((ff, d), L), ((d, d), L), ((3 * d, d), L)):
+        at = {n: [i for i, (name, nk, _) in enumerate(seen) if name == n and nk == shape]
+              for n in ("vlg_linear_wgrad", "vlg_linear_dgrad")}
+        assert len(at["vlg_linear_wgrad"]) == len(at["vlg_linear_dgrad"]) == count, (shape, at)
+        for w, g in zip(at["vlg_linear_wgrad"], at["vlg_linear_dgrad"]):       # backward visits the layers one after another
+            assert w < g, (shape, w, g)

@@ -110,7 +110,7 @@ def test_every_launch_matches_fp64_on_its_inputs(dev, monkeypatch, precision, at
         print("\n%s %s %s: worst |err| vs fp64 per launch kind: %s" % (precision, attention, kw, _summary(log)))
 
 
-# The dropout step (LayoutEngine._encode_dropout and the `_dropped` backward; schedule: step_stages' module docstring) at
+# The dropout step (LayoutEngine._encode with drop and the `_dropped` backward; schedule: step_stages' module docstring) at
 # p = 0.25 and counter k = 3 - a step at which test_hip_dropout documents the bf16 modes of its shape OUTSIDE the
 # end-to-end bars; the per-launch bars hold regardless, nothing amplifies between launches.  Beyond the precisions: masks
 # and dropout together (variable N), the plain backward (VLG_PAIR_BACKWARD=0 and fp32x3), the T = 32 attention with

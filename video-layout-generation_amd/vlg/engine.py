@@ -11,6 +11,11 @@ src/trainer.py:209-258): forward -> weighted loss (40/20/10) -> backward ->
 [gradient all-reduce by the caller] -> Adam.  Gradients are overwritten every
 step, i.e. the zero_grad() the reference forgot is implied.
 
+A transformer layer is written once per direction.  Forward: LayoutEngine._encode, the walk that forward(), the training
+forward with dropout and the cached generation step all take - they differ in the buffer set, the attention launch and
+whether the residual sums form in a GEMM epilogue or in the fused dropout norm.  Backward: the loop in backward(), whose
+projection step is one paired call or a weight gradient (on the side stream, with VLG_OVERLAP_WGRAD=1) and a data gradient.
+
 Row order of every (M, .) activation is the internal  m = (b*N + n)*T + t.
 """
 from __future__ import annotations
@@ -19,6 +24,7 @@ import contextlib
 import ctypes
 import math
 import os
+import types
 from typing import Dict, Optional
 
 import torch
@@ -450,17 +456,13 @@ class LayoutEngine(AdamSurface):
         n_slabs = hip.load().vlg_layernorm_bwd_slabs(M)
         arena = self.buckets.reserve(n_slabs * 2 * d)
         s = self._stream()
+        # the fused variant: + the ddrop output behind dx_out, + (thr, scale, seed, site, step) before the stream, + 4 bytes per element
+        name, out2, mask = "vlg_layernorm_bwd", (), ()
         if self._dropped:
-            thr, scale, seed = self._drop
-            self._timed("ln_bwd", 0.0, "vlg_layernorm_bwd_dropout" + ("_bf16" if dy.dtype == torch.bfloat16 else ""), ptr(dy), ptr(x),
-                        ptr(stat[0]), ptr(stat[1]), ptr(self.p(gname)), ptr(dres), ptr(dx_out), ptr(self.ddrop), ptr(arena), 2 * d,
-                        arena.numel(), M, d, thr, scale, seed, site, ptr(self.drop_step), s,
-                        nbytes=(dy.element_size() + 4.0 + 4.0 + 4.0 + (4.0 if dres is not None else 0.0)) * M * d)
-            self.buckets.add(arena, 2 * d, n_slabs, self.grads.data_ptr() + 4 * self.layout[gname][0], 2 * d, s)
-            return
-        self._timed("ln_bwd", 0.0, "vlg_layernorm_bwd_bf16" if dy.dtype == torch.bfloat16 else "vlg_layernorm_bwd", ptr(dy), ptr(x), ptr(stat[0]),
-                    ptr(stat[1]), ptr(self.p(gname)), ptr(dres), ptr(dx_out), ptr(arena), 2 * d, arena.numel(), M, d, s,
-                    nbytes=(dy.element_size() + 4.0 + 4.0 + (4.0 if dres is not None else 0.0)) * M * d)
+            name, out2, mask = name + "_dropout", (ptr(self.ddrop),), self._drop + (site, ptr(self.drop_step))
+        self._timed("ln_bwd", 0.0, name + ("_bf16" if dy.dtype == torch.bfloat16 else ""), ptr(dy), ptr(x), ptr(stat[0]), ptr(stat[1]),
+                    ptr(self.p(gname)), ptr(dres), ptr(dx_out), *out2, ptr(arena), 2 * d, arena.numel(), M, d, *mask, s,
+                    nbytes=(dy.element_size() + 4.0 + 4.0 + 4.0 * len(out2) + (4.0 if dres is not None else 0.0)) * M * d)
         self.buckets.add(arena, 2 * d, n_slabs, self.grads.data_ptr() + 4 * self.layout[gname][0], 2 * d, s)
 
     def _check_batch(self, batch) -> tuple:
@@ -493,12 +495,7 @@ class LayoutEngine(AdamSurface):
         self._shape = (B, T, N, M)
         self._dropped = bool(train) and self._drop is not None and not self._on_ema    # this forward's choice; its backward follows it
         s = self._stream()
-        L = cfg.n_layers
-        if self._dropped:
-            self._encode_dropout(batch, B, T, N, M)                 # (ends with the fused final norm)
-        else:
-            self._encode(batch, B, T, N, M)
-            self._ln_fwd(self.x[L], "lnf_g", self.xf, self.stats[2 * L], M)
+        self._encode_window(batch, B, T, N, drop=self._dropped, final=True)
         self._linear(self.xf, self.pw("head_w"), self.p("head_b"), self.out, M, cfg.n_out, d, EPI_BIAS)
         self._timed("loss", 0.0, "vlg_layout_loss", ptr(self.out), cfg.n_out, ptr(batch["tgt_class"]), ptr(batch["tgt_box"]),
                     ptr(batch["valid"]), ptr(self.dout), ptr(self.loss_out), ptr(self.loss_scratch), B, T, N,
@@ -506,53 +503,56 @@ class LayoutEngine(AdamSurface):
                     nbytes=(2.0 * 4 * cfg.n_out + 8 + 16 + 4) * M)
         return self.loss_out
 
-    def _encode(self, batch: Dict[str, torch.Tensor], B: int, T: int, N: int, M: int) -> None:
-        """The launches from the embedding through the last layer's second FFN projection: leaves the residual stream in
-        self.x[n_layers].  Shared by forward() and rollout(); reads slot_class, slot_box and - per-clip attention with
-        self._masked - valid of `batch`."""
-        cfg, d, ff = self.cfg, self.cfg.d, self.cfg.d_ff
-        s = self._stream()
-        self._timed("embed_fwd", 0.0, "vlg_embed_fwd", ptr(batch["slot_class"]), ptr(batch["slot_box"]), ptr(self.p("cls_emb")),
-                    ptr(self.p("box_w")), ptr(self.p("box_b")), ptr(self.p("time_emb")), ptr(self.x[0]),
-                    B, T, N, d, cfg.vocab, s, nbytes=4.0 * M * d + 24.0 * M)
-        for l in range(cfg.n_layers):
-            pre = "l%d." % l
-            x = self.x[l]
-            self._ln_fwd(x, pre + "ln1_g", self.h1[l], self.stats[2 * l], M)
-            self._linear(self.h1[l], self.pw(pre + "qkv_w"), self.p(pre + "qkv_b"), self.qkv[l], M, 3 * d, d, EPI_BIAS)
-            self._attn_fwd(l, batch, B, T, N, M)
-            self._linear(self.att[l], self.pw(pre + "proj_w"), self.p(pre + "proj_b"), self.xmid[l], M, d, d,
-                         EPI_BIAS | EPI_RESID, aux_in=x)
-            self._ln_fwd(self.xmid[l], pre + "ln2_g", self.h2[l], self.stats[2 * l + 1], M)
-            self._linear(self.h2[l], self.pw(pre + "ff1_w"), self.p(pre + "ff1_b"), self.gl[l], M, ff, d,
-                         self._epi_ff1, aux_out=self.u[l])
-            self._linear(self.gl[l], self.pw(pre + "ff2_w"), self.p(pre + "ff2_b"), self.x[l + 1], M, d, ff,
-                         EPI_BIAS | EPI_RESID, aux_in=self.xmid[l])
+    def _encode(self, cls, box, time_emb, w, attn, B: int, T: int, N: int, drop: bool = False, final: bool = False, ldc=None) -> None:
+        """THE forward walk: the launches from the embedding through the last layer's second FFN projection - with `final`,
+        through the final norm into self.xf.  A layer reads  norm -> qkv -> attention -> proj -> norm -> ff1 -> ff2  and every
+        norm is a RESIDUAL norm: x_out = resid + branch, h = LN(x_out).
+        drop False: the projection that ends a branch forms x_out in its EPI_BIAS | EPI_RESID epilogue; the norm is _ln_fwd.
+        drop True (a training forward with dropout): that projection writes branch + bias into self.ybranch and the norm is the
+        fused _drop_ln_fwd, which forms x_out under its site's mask on the way (site 0: the embedding, in place, no residual).
+        As many launches either way.
+        cls, box, time_emb: what the embedding reads, B*T*N rows of it.  w: the buffer set, indexed by layer - x (L + 1), h1,
+        qkv (what the qkv projection WRITES, leading dimension ldc), att, xmid, h2, u, gl (L each), stats (2L, + 1 with final):
+        the engine itself for the window, _encode_step's compact set.  attn(l): the attention launch of layer l."""
+        cfg, d, ff, L = self.cfg, self.cfg.d, self.cfg.d_ff, self.cfg.n_layers
+        M = B * T * N
 
-    def _encode_dropout(self, batch: Dict[str, torch.Tensor], B: int, T: int, N: int, M: int) -> None:
-        """_encode for a training forward with dropout, through the final norm.  As many launches as _encode + that norm:
-        proj and ff2 write branch + bias into self.ybranch (no residual epilogue), and every layer-norm launch is the fused
-        one, which forms the residual sum under its site's mask on the way.  Site 0 runs in place on x[0]."""
-        cfg, d, ff = self.cfg, self.cfg.d, self.cfg.d_ff
-        s, L, y = self._stream(), cfg.n_layers, self.ybranch
-        self._timed("embed_fwd", 0.0, "vlg_embed_fwd", ptr(batch["slot_class"]), ptr(batch["slot_box"]), ptr(self.p("cls_emb")),
-                    ptr(self.p("box_w")), ptr(self.p("box_b")), ptr(self.p("time_emb")), ptr(self.x[0]),
-                    B, T, N, d, cfg.vocab, s, nbytes=4.0 * M * d + 24.0 * M)
-        self._drop_ln_fwd(self.x[0], None, self.x[0], "l0.ln1_g", self.h1[0], self.stats[0], 0, M)
+        def linear(a, wname, c, n, k, epi, **kw):
+            self._linear(a, self.pw(wname), self.p(wname[:-1] + "b"), c, M, n, k, epi, **kw)
+
+        def branch_out(a, wname, k, resid, x_out):
+            if drop:
+                linear(a, wname, self.ybranch, d, k, EPI_BIAS)
+            else:
+                linear(a, wname, x_out, d, k, EPI_BIAS | EPI_RESID, aux_in=resid)
+
+        def resid_norm(resid, x_out, gname, h, site):
+            if drop:
+                self._drop_ln_fwd(self.ybranch if site else x_out, resid, x_out, gname, h, w.stats[site], site, M)
+            else:
+                self._ln_fwd(x_out, gname, h, w.stats[site], M)
+
+        self._timed("embed_fwd", 0.0, "vlg_embed_fwd", ptr(cls), ptr(box), ptr(self.p("cls_emb")), ptr(self.p("box_w")),
+                    ptr(self.p("box_b")), ptr(time_emb), ptr(w.x[0]), B, T, N, d, cfg.vocab, self._stream(),
+                    nbytes=4.0 * M * d + 24.0 * M)
         for l in range(L):
             pre = "l%d." % l
-            self._linear(self.h1[l], self.pw(pre + "qkv_w"), self.p(pre + "qkv_b"), self.qkv[l], M, 3 * d, d, EPI_BIAS)
-            self._attn_fwd(l, batch, B, T, N, M)
-            self._linear(self.att[l], self.pw(pre + "proj_w"), self.p(pre + "proj_b"), y, M, d, d, EPI_BIAS)
-            self._drop_ln_fwd(y, self.x[l], self.xmid[l], pre + "ln2_g", self.h2[l], self.stats[2 * l + 1], 1 + 2 * l, M)
-            self._linear(self.h2[l], self.pw(pre + "ff1_w"), self.p(pre + "ff1_b"), self.gl[l], M, ff, d,
-                         self._epi_ff1, aux_out=self.u[l])
-            self._linear(self.gl[l], self.pw(pre + "ff2_w"), self.p(pre + "ff2_b"), y, M, d, ff, EPI_BIAS)
-            if l + 1 < L:
-                self._drop_ln_fwd(y, self.xmid[l], self.x[l + 1], "l%d.ln1_g" % (l + 1), self.h1[l + 1], self.stats[2 * l + 2],
-                                  2 + 2 * l, M)
-            else:
-                self._drop_ln_fwd(y, self.xmid[l], self.x[L], "lnf_g", self.xf, self.stats[2 * L], 2 + 2 * l, M)
+            resid_norm(w.xmid[l - 1] if l else None, w.x[l], pre + "ln1_g", w.h1[l], 2 * l)
+            linear(w.h1[l], pre + "qkv_w", w.qkv[l], 3 * d, d, EPI_BIAS, ldc=ldc)
+            attn(l)
+            branch_out(w.att[l], pre + "proj_w", d, w.x[l], w.xmid[l])
+            resid_norm(w.x[l], w.xmid[l], pre + "ln2_g", w.h2[l], 2 * l + 1)
+            linear(w.h2[l], pre + "ff1_w", w.gl[l], ff, d, self._epi_ff1, aux_out=w.u[l])
+            branch_out(w.gl[l], pre + "ff2_w", ff, w.xmid[l], w.x[l + 1])
+        if final:
+            resid_norm(w.xmid[L - 1], w.x[L], "lnf_g", self.xf, 2 * L)
+
+    def _encode_window(self, batch: Dict[str, torch.Tensor], B: int, T: int, N: int, drop: bool = False, final: bool = False) -> None:
+        """_encode on all T frames, in the workspace's per-layer buffers: leaves the residual stream in self.x[n_layers] (final:
+        and its norm in self.xf).  forward() and rollout(); reads slot_class, slot_box and - per-clip attention with
+        self._masked - valid of `batch`."""
+        self._encode(batch["slot_class"], batch["slot_box"], self.p("time_emb"), self,
+                     lambda l: self._attn_fwd(l, batch, B, T, N, B * T * N), B, T, N, drop, final)
 
     # -------------------------------------------------------------------- backward
     def backward(self, batch: Dict[str, torch.Tensor], reducer=None) -> None:
@@ -560,12 +560,16 @@ class LayoutEngine(AdamSurface):
         (vlg.dp.GradReducer) is told as soon as each contiguous gradient bucket is complete so its
         all-reduce overlaps the rest of backward.
 
+        One walk: head, final norm, then per layer  ff2, ff1, norm, proj, attention, qkv, norm  and the close of the layer's
+        bucket, then the embedding.  Its modes differ in two steps only, proj_bwd (a projection's backward) and close.
         Default: ONE stream.  Each projection's data and weight gradient go through one paired call (`pair_backward`), one
         table-driven launch reduces the partial sums of a bucket - the head, a layer, the embeddings (`group_reduce`) - and a
         finished bucket's reduction rides in the next paired launch instead (`ride_reduces`, vlg/slabs.py).
         After a training forward with dropout every layer-norm backward is the fused variant: it also writes select(dx) under the
         mask of the site that fed it into self.ddrop, which - not self.dx - is the dY of the next proj / ff2 backward and what the
         embedding backward reads; self.dx keeps carrying the residual gradient.  One counter advance ends the backward.
+        Not paired (fp32x3, bf16_mfma, VLG_PAIR_BACKWARD=0, two streams): a projection's backward is a weight-gradient launch,
+        then a data-gradient launch; a bucket is reduced when it closes, or (two streams) each producer right behind itself.
         Option, VLG_OVERLAP_WGRAD=1: two HIP streams.  The data-gradient chain stays on the caller's stream; every weight gradient
         (+ its slab reduction) is launched on `self.side` as soon as its dY exists and runs CONCURRENTLY with the chain, filling the
         gaps its launches leave in the matrix pipes.  Ordering is by events: a side kernel waits for the producer of its dY, and the
@@ -609,49 +613,46 @@ class LayoutEngine(AdamSurface):
                 main.wait_event(e)
                 last_read.clear()
 
+        def proj_bwd(dy, wname, dx, x, N, K, reads, writes=(), epi=EPI_NONE, aux_in=None):
+            """backward of the projection y = x W^T + b given dy: grad[w | b], and dx = dy . W.  reads: what the weight gradient
+            reads of the buffers the chain reuses; writes: those of them the data gradient overwrites"""
+            if self.pair_backward:
+                self._dgrad_wgrad(dy, self.pw(wname), dx, x, wname, M, N, K, epi, aux_in)
+                return
+            on_side(reads, lambda: self._wgrad(dy, x, wname, M, N, K))       # (enqueued first: it waits for dy alone)
+            before_write(*writes)
+            self._dgrad(dy, self.pw(wname), dx, M, N, K, epi, aux_in)
+
+        ready = (lambda tag: (lambda: reducer.ready(tag))) if reducer is not None else (lambda tag: None)
+
+        def close(tag):
+            """the open bucket - the head's, a layer's - is complete.  Paired: it rides in the next paired launch (the head's in
+            the last layer's first, layer 0's in the embedding bucket's table) and ready(tag) follows that launch.  Two streams
+            without a reducer: nothing to do, and no join - the chain must not wait for the side stream once per layer."""
+            if reducer is not None or self.group_reduce:
+                join()
+                self.buckets.close(s, defer=self.pair_backward, then=ready(tag))
+
         self.buckets.reset()         # a backward that raised half way leaves nothing behind for this one
         on_side(("dout",), lambda: self._wgrad(self.dout, self.xf, "head_w", M, cfg.n_out, d))
         self._dgrad(self.dout, self.pw("head_w"), self.dh, M, cfg.n_out, d)
         self._ln_bwd(self.dh, self.x[L], self.stats[2 * L], "lnf_g", None, self.dx, M, site=2 * L)
-        ready = (lambda tag: (lambda: reducer.ready(tag))) if reducer is not None else (lambda tag: None)
-        if reducer is not None or self.group_reduce:
-            join()
-            self.buckets.close(s, defer=self.pair_backward, then=ready("head"))      # (paired: rides in the last layer's first launch)
+        close("head")
         for l in reversed(range(L)):
             pre = "l%d." % l
-            if self.pair_backward:
-                self._dgrad_wgrad(dxy, self.pw(pre + "ff2_w"), self.du, self.gl[l], pre + "ff2_w", M, d, ff, self._epi_dff2, aux_in=self.u[l])
-                self._dgrad_wgrad(self.du, self.pw(pre + "ff1_w"), self.dh, self.h2[l], pre + "ff1_w", M, ff, d)
-                self._ln_bwd(self.dh, self.xmid[l], self.stats[2 * l + 1], pre + "ln2_g", self.dx, self.dx, M, site=1 + 2 * l)
-                self._dgrad_wgrad(dxy, self.pw(pre + "proj_w"), self.dh, self.att[l], pre + "proj_w", M, d, d)
-                self._attn_bwd(l, batch, B, T, N, M)
-                self._dgrad_wgrad(self.dqkv, self.pw(pre + "qkv_w"), self.dh, self.h1[l], pre + "qkv_w", M, 3 * d, d)
-                self._ln_bwd(self.dh, self.x[l], self.stats[2 * l], pre + "ln1_g", self.dx, self.dx, M, site=2 * l)
-                # the layer's bucket rides in the next layer's first paired launch (layer 0: in the embedding bucket's table)
-                self.buckets.close(s, defer=True, then=ready("l%d" % l))
-                continue
             # FFN:  x_out = xmid + W2 gelu(W1 h2 + b1) + b2
-            on_side(("dx",), lambda: self._wgrad(dxy, self.gl[l], pre + "ff2_w", M, d, ff))
-            before_write("du")
-            self._dgrad(dxy, self.pw(pre + "ff2_w"), self.du, M, d, ff, self._epi_dff2, aux_in=self.u[l])
-            on_side(("du",), lambda: self._wgrad(self.du, self.h2[l], pre + "ff1_w", M, ff, d))
-            self._dgrad(self.du, self.pw(pre + "ff1_w"), self.dh, M, ff, d)
+            proj_bwd(dxy, pre + "ff2_w", self.du, self.gl[l], d, ff, ("dx",), ("du",), self._epi_dff2, self.u[l])
+            proj_bwd(self.du, pre + "ff1_w", self.dh, self.h2[l], ff, d, ("du",))
             before_write("dx")
             self._ln_bwd(self.dh, self.xmid[l], self.stats[2 * l + 1], pre + "ln2_g", self.dx, self.dx, M, site=1 + 2 * l)
             # attention:  xmid = x + Wo attn(Wqkv h1 + b) + bo
-            on_side(("dx",), lambda: self._wgrad(dxy, self.att[l], pre + "proj_w", M, d, d))
-            self._dgrad(dxy, self.pw(pre + "proj_w"), self.dh, M, d, d)
+            proj_bwd(dxy, pre + "proj_w", self.dh, self.att[l], d, d, ("dx",))
             before_write("dqkv")
             self._attn_bwd(l, batch, B, T, N, M)
-            on_side(("dqkv",), lambda: self._wgrad(self.dqkv, self.h1[l], pre + "qkv_w", M, 3 * d, d))
-            self._dgrad(self.dqkv, self.pw(pre + "qkv_w"), self.dh, M, 3 * d, d)
+            proj_bwd(self.dqkv, pre + "qkv_w", self.dh, self.h1[l], 3 * d, d, ("dqkv",))
             before_write("dx")
             self._ln_bwd(self.dh, self.x[l], self.stats[2 * l], pre + "ln1_g", self.dx, self.dx, M, site=2 * l)
-            if reducer is not None or self.group_reduce:
-                join()
-                self.buckets.close(s)
-            if reducer is not None:
-                reducer.ready("l%d" % l)
+            close("l%d" % l)
         join()
         self._backward_tail(batch, B, T, N, M, reducer)
         if self._dropped:            # the next training step draws new masks (a captured graph advances by replaying this launch)
@@ -793,27 +794,22 @@ class LayoutEngine(AdamSurface):
     def _encode_step(self, p: int, B: int, N: int) -> torch.Tensor:
         """The encoder on the B*N rows of position p alone, against the K/V cache that self.qkv[l] holds for positions < p
         (per-slot attention): embeds the compact frame vlg_layout_decode_append left, writes that position's q k v rows
-        into the cache and returns the compact residual stream [B*N, d] leaving the last layer.  As many launches as
-        _encode (1 + 7 per layer), on 1/T of its rows."""
-        cfg, d, ff, T = self.cfg, self.cfg.d, self.cfg.d_ff, self.cfg.T
+        into the cache and returns the compact residual stream [B*N, d] leaving the last layer.  _encode with T = 1 and
+        time_emb[p] on the compact set: the residual stream ping-pongs between xa and xb, one h and one stat serve every norm,
+        and the qkv projection writes its rows into the cache with ldc = T*3d.  As many launches as on the window (1 + 7 per
+        layer), on 1/T of its rows."""
+        d, T, L = self.cfg.d, self.cfg.T, self.cfg.n_layers
         g, BN, s = self._grow_buffers(), B * N, self._stream()
-        self._timed("embed_fwd", 0.0, "vlg_embed_fwd", ptr(g["cls"]), ptr(g["box"]), ptr(self.p("cls_emb")), ptr(self.p("box_w")),
-                    ptr(self.p("box_b")), ptr(self.p("time_emb")[p]), ptr(g["xa"]), B, 1, N, d, cfg.vocab, s,
-                    nbytes=4.0 * BN * d + 24.0 * BN)
-        x, y, h, stat = g["xa"], g["xb"], g["h"], g["stat"]
-        for l in range(cfg.n_layers):
-            pre = "l%d." % l
-            self._ln_fwd(x, pre + "ln1_g", h, stat, BN)
-            self._linear(h, self.pw(pre + "qkv_w"), self.p(pre + "qkv_b"), self.qkv[l].view(-1)[p * 3 * d:], BN, 3 * d, d, EPI_BIAS,
-                         ldc=T * 3 * d)
+        h, one = [g["h"]] * L, lambda name: [g[name]] * L
+        w = types.SimpleNamespace(x=[g["xa"], g["xb"]] * L, h1=h, h2=h, qkv=[self.qkv[l].view(-1)[p * 3 * d:] for l in range(L)],
+                                  att=one("att"), xmid=one("xmid"), u=one("u"), gl=one("gl"), stats=[g["stat"]] * (2 * L))
+
+        def attn(l):
             self._timed("attn_step", 0.0, "vlg_attention_step" + self._sfx, ptr(self.qkv[l]), ptr(g["att"]), BN, T, d, p, d, s,
                         nbytes=self.qkv.element_size() * BN * d * (2.0 * (p + 1) + 2.0))
-            self._linear(g["att"], self.pw(pre + "proj_w"), self.p(pre + "proj_b"), g["xmid"], BN, d, d, EPI_BIAS | EPI_RESID, aux_in=x)
-            self._ln_fwd(g["xmid"], pre + "ln2_g", h, stat, BN)
-            self._linear(h, self.pw(pre + "ff1_w"), self.p(pre + "ff1_b"), g["gl"], BN, ff, d, self._epi_ff1, aux_out=g["u"])
-            self._linear(g["gl"], self.pw(pre + "ff2_w"), self.p(pre + "ff2_b"), y, BN, d, ff, EPI_BIAS | EPI_RESID, aux_in=g["xmid"])
-            x, y = y, x
-        return x
+
+        self._encode(g["cls"], g["box"], self.p("time_emb")[p], w, attn, B, 1, N, ldc=T * 3 * d)
+        return w.x[L]
 
     def rollout(self, slot_class: torch.Tensor, slot_box: torch.Tensor, steps: int = 8, temperature: float = 0.0,
                 top_k: int = 0, seed: int = 0, keep_padded: bool = False, return_logits: bool = False,
@@ -882,18 +878,13 @@ class LayoutEngine(AdamSurface):
         cur = 0                                                     # the window buffer that holds the history
         for i, (encoder, t_read, pos) in enumerate(grow_schedule(P, T, steps, cached)):
             (cls, box, valid), (ncls, nbox, nvalid) = win[cur], win[cur ^ 1]
-            if encoder == "step":                                   # the newest frame alone, against the cache
-                x = self._encode_step(t_read, B, N)
-                self._timed("head_last", 2.0 * BN * cfg.n_out * d, "vlg_head_last_frame", ptr(x), *head, ptr(logits[i]), B, 1, N, d,
-                            cfg.n_out, LN_EPS, s, **head_kw)
-            else:
-                self._encode({"slot_class": cls, "slot_box": box, "valid": valid}, B, T, N, M)
-                if t_read < T - 1:
-                    self._timed("head_last", 2.0 * BN * cfg.n_out * d, "vlg_head_frame", ptr(self.x[L]), *head, ptr(logits[i]), B, T, N,
-                                d, cfg.n_out, t_read, LN_EPS, s, **head_kw)
-                else:
-                    self._timed("head_last", 2.0 * BN * cfg.n_out * d, "vlg_head_last_frame", ptr(self.x[L]), *head, ptr(logits[i]),
-                                B, T, N, d, cfg.n_out, LN_EPS, s, **head_kw)
+            if encoder == "step":                                   # the newest frame alone, against the cache: its rows are the last
+                x, Tx, frame = self._encode_step(t_read, B, N), 1, ()
+            else:                                                   # the window: the last frame, or - still growing - frame t_read
+                self._encode_window({"slot_class": cls, "slot_box": box, "valid": valid}, B, T, N)
+                x, Tx, frame = self.x[L], T, (t_read,) if t_read < T - 1 else ()
+            self._timed("head_last", 2.0 * BN * cfg.n_out * d, "vlg_head_frame" if frame else "vlg_head_last_frame", ptr(x), *head,
+                        ptr(logits[i]), B, Tx, N, d, cfg.n_out, *frame, LN_EPS, s, **head_kw)
             if pos is not None:                                     # append in place; the window does not move
                 self._timed("decode", 0.0, "vlg_layout_decode_append", ptr(logits[i]), ptr(cls), ptr(box), ptr(valid), ptr(gen_cls),
                             ptr(gen_box), ptr(grow["cls"]), ptr(grow["box"]), B, T, N, cfg.n_classes, pos, steps, i, *knobs,
