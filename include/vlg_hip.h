@@ -300,6 +300,26 @@ int vlg_attention_clip_fwd_bf16(const vlg_bf16* qkv, const float* valid, vlg_bf1
 int vlg_attention_clip_bwd_bf16(const vlg_bf16* qkv, const float* valid, const vlg_bf16* out, const vlg_bf16* dout,
                                 const float* lse, float* delta, vlg_bf16* dqkv,
                                 int64_t B, int T, int N, int d, void* stream);
+/* The same attention for the N queries of ONE frame p against a K/V cache (generation while the history is shorter than the
+ * window, LayoutEngine(clip_cache=True); DESIGN.md, "Generation").  qkv and valid are the buffers above.  Per clip b and head
+ * h the queries are the tokens (p, n): query n is row (b*N + n)*T + p of qkv, columns h*64 .. + 63.  Query (p, n) sees key
+ * (j, n') iff j <= p and (valid == NULL or valid[(b*T + j)*N + n'] > 0 or (j, n') == (p, n)) - vlg_attention_clip_fwd
+ * restricted to the query tokens s = p*N + n of its frame-major walk over the key tokens s < (p + 1)*N, with its scale,
+ * its max-subtracted softmax (masked keys are -inf before the row maximum) and, in bf16, its rounding points.
+ * o is [B*N, d] with leading dimension ldo >= d elements: o[b*N + n, h*64 .. + 63] is written and nothing else; no lse
+ * (generation has no backward).  NEVER READ: rows of qkv at positions j > p and valid[:, j > p] - they may hold anything,
+ * NaN included; what the last 32-key tile holds past (p + 1)*N reaches neither a load nor the P.V product.
+ * The fp32 entry accumulates its scores in fp64 (a step computes few rows, and at |score| ~ 100 one chain of fp32 sums shows
+ * against fp64, as in vlg_attention_step); softmax and P.V are the forward's.  The bf16 entry is the forward's arithmetic throughout.
+ * One block per (clip, head, 32 queries); its four waves split the key tiles and merge in a fixed order: no atomics, the
+ * same bits from run to run and for a clip alone or inside a larger batch.
+ * VLG_ERR_SHAPE, nothing enqueued: the shape contract of vlg_attention_clip_fwd, p outside [0, T), ldo < d.
+ * VLG_ERR_ALIGN: qkv or o NULL or misaligned (16 bytes fp32, 8 bytes bf16; bf16: ldo not a multiple of 4).  Only valid may
+ * be NULL. */
+int vlg_attention_clip_step(const float* qkv, const float* valid, float* o,
+                            int64_t B, int T, int N, int d, int p, int64_t ldo, void* stream);
+int vlg_attention_clip_step_bf16(const vlg_bf16* qkv, const float* valid, vlg_bf16* o,
+                                 int64_t B, int T, int N, int d, int p, int64_t ldo, void* stream);
 
 /* ------------------------------------------------------------------ generation (csrc/decode.hip)
  * The forward-only tail of an autoregressive rollout (reference src/trainer.py:453-476 rolls its pixel model out the same

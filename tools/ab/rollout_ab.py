@@ -4,7 +4,8 @@ commit exported (git archive) and built next to it - where both the library and 
 One child process per tree and round, alternating A B A B ..., never two at a time; a child imports the package from its
 tree, rolls out (32,16,64), d = 256, 4 layers from a full T-frame prompt in fp32 and bf16 and reports ms per generated
 frame (host wall-clock around calls that end with the frames on the CPU, as tools/rollout_bench.py measures).  Prints per
-tree and precision the median of the rounds with their spread.  A child that fails ends the run: nothing is started after it."""
+tree and precision the median of the rounds with their spread.  A child that fails ends the run: nothing is started after it.
+VLG_ATTENTION=clip in the environment rolls out with per-clip attention (default: per-slot)."""
 import json
 import os
 import subprocess
@@ -21,7 +22,7 @@ def child(tree, steps):
     from vlg.spec import LayoutConfig
     B, T, N, d = 32, 16, 64, 256
     dev = torch.device("cuda:0")
-    cfg = LayoutConfig(B=B, T=T, N=N, d=d, n_layers=4)
+    cfg = LayoutConfig(B=B, T=T, N=N, d=d, n_layers=4, attention=os.environ.get("VLG_ATTENTION", "slot"))
     batch = to_device(synthetic_clips(B, T, N, seed=3), dev)
     cls, box = batch["slot_class"], batch["slot_box"]
     out = {}

@@ -1,4 +1,5 @@
-"""Whole-step time of the in-tree engine with whatever libvlg VLG_HIP_LIB names (one process per variant, same box)."""
+"""Whole-step time of the in-tree engine with whatever libvlg VLG_HIP_LIB names (one process per variant, same box);
+VLG_ATTENTION=clip times the step with per-clip attention."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "video-layout-generation_amd")]
@@ -7,7 +8,7 @@ from vlg.data import synthetic_clips, to_device
 from vlg.engine import LayoutEngine
 from vlg.spec import LayoutConfig, SEED
 dev = torch.device("cuda:0")
-cfg = LayoutConfig(B=32, T=16, N=64, d=256, n_layers=4)
+cfg = LayoutConfig(B=32, T=16, N=64, d=256, n_layers=4, attention=os.environ.get("VLG_ATTENTION", "slot"))
 eng = LayoutEngine(cfg, dev, seed=SEED)
 batch = to_device(synthetic_clips(cfg.B, cfg.T, cfg.N, seed=SEED), dev)
 res = []

@@ -4,10 +4,11 @@ launches + vlg_head_last_frame + vlg_layout_decode, no host wait inside the loop
 (restated here from forward() + outputs_btn(): training forward with the loss on dummy targets, argmax / sigmoid / cat in
 torch, two copies to the CPU per frame), alternately in one process on the same prompt, fp32 and bf16.
     python tools/rollout_bench.py [B] [T] [N] [d] [--layers L] [--steps S] [--attention slot|clip] [--prompt P] [--no-cache]
+                                  [--clip-cache]
 --prompt P (1 <= P < T) measures the short-prompt rollout instead: the prompt pass on its own (steps = 1), and --steps
 frames (default T - P: the history grows to the window) with the cached grow step and with the re-encoding one
 (cache=False), alternately; ms per grown frame = (the call - the prompt pass) / (frames - 1).  --no-cache leaves the
-cached variant out (per-clip attention has none).
+cached variant out; per-clip attention has it with --clip-cache alone (the engine option clip_cache).
 Times are host wall-clock around a call that ends with the results on the CPU (what generate_sequence returns), so the
 host waits of the loop are in the figure; launches per frame are counted through the engine's single launch point."""
 import os, sys, time
@@ -63,7 +64,7 @@ def launches(eng, fn, *args):
     return seen
 
 
-def prompt_bench(cfg, dev, cls, box, P, frames, with_cache):
+def prompt_bench(cfg, dev, cls, box, P, frames, with_cache, clip_cache=False):
     """the short-prompt rollout: every variant once per round, 9 rounds, in one process on the same prompt"""
     cls, box = cls[:, :P].contiguous(), box[:, :P].contiguous()
 
@@ -77,7 +78,7 @@ def prompt_bench(cfg, dev, cls, box, P, frames, with_cache):
     if with_cache:
         paths["cached"] = variant(frames, None)
     for precision in ("fp32", "bf16"):
-        eng = LayoutEngine(cfg, dev, precision=precision, padded_slots=False)
+        eng = LayoutEngine(cfg, dev, precision=precision, padded_slots=False, clip_cache=clip_cache)
         res = {k: fn(eng) for k, fn in paths.items()}                        # warm-up
         count = {k: sum(launches(eng, fn).values()) for k, fn in paths.items()}
         ts = {k: [] for k in paths}
@@ -101,8 +102,8 @@ def prompt_bench(cfg, dev, cls, box, P, frames, with_cache):
                 head, k, per[4], frames - 1, per[0], per[-1], (count[k] - count["prompt pass"]) / (frames - 1)))
         if with_cache:
             same = float((res["cached"][0] == res["re-encode"][0]).float().mean())
-            print("%s: cached vs re-encode, first-frame boxes differ by at most %.2e, %.2f %% of class ids equal" % (
-                head, float((res["cached"][1][:, 0] - res["re-encode"][1][:, 0]).abs().max()), 100 * same))
+            print("%s: cached vs re-encode, first-frame boxes differ by at most %.2e, %.2f %% of class ids equal over %d frames" % (
+                head, float((res["cached"][1][:, 0] - res["re-encode"][1][:, 0]).abs().max()), 100 * same, frames))
 
 
 skip = {i + 1 for i, x in enumerate(sys.argv) if x in ("--layers", "--steps", "--attention", "--prompt")}
@@ -117,7 +118,9 @@ if "--prompt" in sys.argv:
     P = int(opt("--prompt", 2))
     if not 1 <= P < T:
         sys.exit("--prompt takes 1 <= P < T")
-    prompt_bench(cfg, dev, cls, box, P, int(opt("--steps", T - P)), "--no-cache" not in sys.argv and cfg.attention != "clip")
+    clip_cache = "--clip-cache" in sys.argv and cfg.attention == "clip"
+    prompt_bench(cfg, dev, cls, box, P, int(opt("--steps", T - P)),
+                 "--no-cache" not in sys.argv and (cfg.attention != "clip" or clip_cache), clip_cache)
     sys.exit(0)
 paths = {"host loop": host_loop, "rollout()": device_path}
 for precision in ("fp32", "bf16"):

@@ -20,6 +20,8 @@
 //                     dKV (key owner)     S, dP = dO . V^T, dV += P^T . dO, dK += dS^T . Q                      4 products / tile
 //                 P is recomputed from the saved log-sum-exp (one float per query and head, log2 domain); delta = <dO, O> per
 //                 query.  valid, lse and delta are fp32 in both storages, in the same layouts.
+//   step          generation against a K/V cache, a fourth template: the forward's tile body (CLIP_FWD_TILE) for the N queries
+//                 of one frame, the KEY tiles split among a block's four waves and merged in a fixed order (see the kernel)
 //
 // WHAT A STORAGE POLICY DECIDES (everything else - dealing order, wave activity, tile classification, the prefetch / two-barrier
 // staging loop, the online softmax, lse / delta - is the templates' and exists once):
@@ -236,6 +238,73 @@ struct ClipF32 {
             p[32] = acc[1][r];
         }
     }
+    // the generation step: a tile of 32 owner tokens on CONSECUTIVE rows from row0 of which the first n are real - the rest
+    // are not stored - and a staged token that is not loaded
+    __device__ static __forceinline__ void store_rows(float* __restrict__ dst, int64_t ld, int64_t row0, int n, const f32x16 (&acc)[2],
+                                                      int l31, int h) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = clip_crow(r, h);
+            if (row < n) {
+                float* p = dst + (row0 + row) * ld + l31;
+                p[0] = acc[0][r];
+                p[32] = acc[1][r];
+            }
+        }
+    }
+    __device__ static __forceinline__ Stage stage_zero() {
+        Stage v;
+        v.a = v.b = make_float4(0.f, 0.f, 0.f, 0.f);
+        return v;
+    }
+    // The generation step's scores.  dot64 is one chain of 64 fp32 FMAs per score: at |s| ~ 100 (peaked softmax rows) it is
+    // off by a few ulp of 7.6e-6, which shows against fp64 in the few rows a step computes (as it did in vlg_attention_step,
+    // which accumulates in fp64 for that reason).  So the step forms its scores on the vector unit in fp64 - the product of
+    // two fp32 values is exact there - from the UNSCALED query rows Qs (row-major like Ks, the block's 32 queries) and
+    // returns each as the fp32 value st nearest to it and the remainder lo: exp2(st - m) (1 + ln2 lo) is the probability of
+    // the unrounded score, whatever m the online softmax subtracts.  Lane (l31, h): query l31, keys clip_crow(r, h).
+    static constexpr bool STEP_EXACT = true;
+    __device__ static __forceinline__ void step_scores(f32x16& st, float (&lo)[16], const float* Ks, const float* Qs, int l31, int h,
+                                                       const Frag&) {
+        double acc[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.0;
+#pragma unroll 1
+        for (int c = 0; c < 8; ++c) {                                // 8 dims at a time
+            const float4 qa = ld4(Qs + l31 * LDR + 8 * c), qb = ld4(Qs + l31 * LDR + 8 * c + 4);
+            const double q[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float* kp = Ks + clip_crow(r, h) * LDR + 8 * c;
+                const float4 ka = ld4(kp), kb = ld4(kp + 4);
+                const double k[8] = {ka.x, ka.y, ka.z, ka.w, kb.x, kb.y, kb.z, kb.w};
+#pragma unroll
+                for (int i = 0; i < 8; ++i) acc[r] = fma(k[i], q[i], acc[r]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const double s = acc[r] * 0.18033688011112042;           // log2(e) / sqrt(64)
+            st[r] = (float)s;
+            lo[r] = (float)(s - (double)st[r]);
+        }
+    }
+    // ... and the remainder of a query's score with ITSELF as a key (always visible), by the same operations in the same order,
+    // so it is bitwise the lo that step_scores finds for that key.  The step subtracts it from every lo of the query - a factor
+    // common to all keys of a softmax row changes nothing - so that a token that sees only itself still has P exactly 1.
+    __device__ static __forceinline__ float step_self_lo(const float* __restrict__ qrow, const float* __restrict__ krow) {
+        double acc = 0.0;
+#pragma unroll 1
+        for (int c = 0; c < 8; ++c) {
+            const float4 qa = ld4(qrow + 8 * c), qb = ld4(qrow + 8 * c + 4), ka = ld4(krow + 8 * c), kb = ld4(krow + 8 * c + 4);
+            const double q[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
+            const double k[8] = {ka.x, ka.y, ka.z, ka.w, kb.x, kb.y, kb.z, kb.w};
+#pragma unroll
+            for (int i = 0; i < 8; ++i) acc = fma(k[i], q[i], acc);
+        }
+        const double s = acc * 0.18033688011112042;
+        return (float)(s - (double)(float)s);
+    }
 };
 
 struct ClipBf16 {
@@ -311,9 +380,57 @@ struct ClipBf16 {
                 st4(dst + row * ld + 32 * dt + 8 * g + 4 * h,
                     make_float4(acc[dt][4 * g], acc[dt][4 * g + 1], acc[dt][4 * g + 2], acc[dt][4 * g + 3]));
     }
+    __device__ static __forceinline__ void store_rows(bf16_t* __restrict__ dst, int64_t ld, int64_t row0, int n, const f32x16 (&acc)[2],
+                                                      int l31, int h) {
+        if (l31 < n) store(Rows(), dst, ld, row0 + l31, acc, 0, l31, h);
+    }
+    __device__ static __forceinline__ Stage stage_zero() { return make_uint4(0u, 0u, 0u, 0u); }
+    // the generation step's scores: the forward's (bf16 products are exact in fp32; the storage's error is far above fp32 sums)
+    static constexpr bool STEP_EXACT = false;
+    __device__ static __forceinline__ void step_scores(f32x16& st, float (&lo)[16], const bf16_t* Ks, const bf16_t*, int l31, int h,
+                                                       const Frag& qf) {
+        st = dot64(Ks, l31, h, qf);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { st[r] = log2_score(st[r]); lo[r] = 0.f; }
+    }
+    __device__ static __forceinline__ float step_self_lo(const bf16_t*, const bf16_t*) { return 0.f; }
 };
 
 // ---------------------------------------------------------------------------------------------------------- forward
+// One key tile of a query owner's walk, staged as Ks (row-major K), Vt (transposed V) and kfr (the keys' frame codes): the
+// scores, the mask, the online softmax and O += P . V.  The forward and the generation step share it.  It reads the walk's
+// names from the scope it stands in: qf (the wave's scored Q fragment), valid, k0 (the tile's first key token), N, the
+// lane's query token sq and its frame tq, the wave's first query frame tq_min, the running m_run / l_run / o, turn, w, l31, h.
+// (a macro for the reason CLIP_VISIBLE is one: the forward's code stays as tuned)
+// SCORES declares and fills st, the tile's log2-domain scores; PFIX is appended to every probability exp2(st - m): the forward
+// takes the MFMA scores and no fix, the fp32 generation step exact scores with their rounding remainder (ClipF32::step_scores).
+#define CLIP_SCORES_MFMA(P, Ks)                                                                                          \
+        f32x16 st = P::dot64(Ks, l31, h, qf);                        /* S^T[key (r, h)][query l31] */                    \
+        _Pragma("unroll") for (int r = 0; r < 16; ++r) st[r] = P::log2_score(st[r]);
+#define CLIP_FWD_TILE(P, Ks, Vt, kfr, SCORES, PFIX)                                                                      \
+    {                                                                                                                    \
+        SCORES                                                                                                           \
+        if (CLIP_TILE_ELEMENTWISE(valid, k0, N, tq_min)) {                                                               \
+            int fr[16];                                                                                                  \
+            rows16i(fr, kfr, h);                                                                                         \
+            _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                             \
+                st[r] = CLIP_VISIBLE(fr[r], tq, k0 + clip_crow(r, h), sq) ? st[r] : -INFINITY;                           \
+            }                                                                                                            \
+        }                                                                                                                \
+        float tmax = st[0];                                                                                              \
+        _Pragma("unroll") for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, st[r]);                                        \
+        tmax = fmaxf(tmax, __shfl_xor(tmax, 32));                                                                        \
+        const float m_new = fmaxf(m_run, tmax);                                                                          \
+        const float m_use = m_new == -INFINITY ? 0.f : m_new;                                                            \
+        const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);                                                       \
+        float p[16], rs = 0.f;                                                                                           \
+        _Pragma("unroll") for (int r = 0; r < 16; ++r) { p[r] = __builtin_amdgcn_exp2f(st[r] - m_use) PFIX; rs += p[r]; } \
+        rs += __shfl_xor(rs, 32);                                                                                        \
+        l_run = l_run * alpha + rs;                                                                                      \
+        m_run = m_new;                                                                                                   \
+        if (__any(alpha != 1.0f)) P::rescale(turn, o, alpha, w, l31, h);      /* O by its query's factor */              \
+        P::contract32(o, p, Vt, l31, h);                             /* O[query][dim] += P[query][key] V[key][dim] */    \
+    }
 template <typename P>
 __global__ __launch_bounds__(256, 3) void attn_clip_fwd_kernel(const typename P::elem* __restrict__ qkv, const float* __restrict__ valid,
                                                             typename P::elem* __restrict__ out, float* __restrict__ lse, int T, int N, int d) {
@@ -363,37 +480,136 @@ __global__ __launch_bounds__(256, 3) void attn_clip_fwd_kernel(const typename P:
         if (j + 1 < ntiles) tile_load(j + 1, kn, vn, frn);           // in flight under this tile's MFMAs
         const int k0 = j * CKT;
         if (!wact || CLIP_TILE_HIDDEN(k0, N, tq_max)) continue;
-        f32x16 st = P::dot64(Ks, l31, h, qf);                        // S^T[key (r, h)][query l31]
-#pragma unroll
-        for (int r = 0; r < 16; ++r) st[r] = P::log2_score(st[r]);
-        if (CLIP_TILE_ELEMENTWISE(valid, k0, N, tq_min)) {
-            int fr[16];
-            rows16i(fr, kfr, h);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                st[r] = CLIP_VISIBLE(fr[r], tq, k0 + clip_crow(r, h), sq) ? st[r] : -INFINITY;
-            }
-        }
-        float tmax = st[0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, st[r]);
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
-        const float m_new = fmaxf(m_run, tmax);
-        const float m_use = m_new == -INFINITY ? 0.f : m_new;
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);
-        float p[16], rs = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { p[r] = __builtin_amdgcn_exp2f(st[r] - m_use); rs += p[r]; }
-        rs += __shfl_xor(rs, 32);
-        l_run = l_run * alpha + rs;
-        m_run = m_new;
-        if (__any(alpha != 1.0f)) P::rescale(turn, o, alpha, w, l31, h);      // O by its query's factor
-        P::contract32(o, p, Vt, l31, h);                             // O[query][dim] += P[query][key] V[key][dim]
+        CLIP_FWD_TILE(P, Ks, Vt, kfr, CLIP_SCORES_MFMA(P, Ks), )
     }
     if (!wact) return;
     if (h == 0) lse[((b * heads + hh) * (int64_t)S) + sq] = m_run + __builtin_amdgcn_logf(l_run);       // log2 domain
     P::rescale(turn, o, 1.0f / l_run, w, l31, h);
     P::store(rows, out + hh * CHD, d, qrow, o, w, l31, h);
+}
+
+// ------------------------------------------------------------------------------------------- generation step (forward)
+// The forward restricted to the N queries of frame pos, against the keys of frames <= pos (the K/V cache): out is compact,
+// row b*N + n.  The forward's decomposition does not fit - N queries are a fraction of a 128-query block, and its one wave
+// per 32 queries would walk every key tile alone - so the KEYS are split: a block = one 32-query tile of (clip, head), all
+// four waves hold the same 32 queries (lanes past N repeat query N-1 and do not store) and each walks a contiguous quarter
+// of the visible key tiles through tile images of its own.  The partial (m, l, O) meet in LDS: every wave forms the merged
+// maximum and sum from the four (m, l) pairs in wave order, scales its O by exp2(m_w - m) / l, and wave 0 adds the four O
+// in wave order and stores.  No atomics; the order is fixed by the shape, so the bits are too.
+// Scores: P::step_scores - bf16 the forward's MFMA product; fp32 exact (fp64 on the vector unit, from an LDS image Qs of the
+// block's unscaled queries), handed to the shared softmax as the nearest fp32 value and a remainder that corrects P.
+// Tokens from (pos + 1) N on - the tail of the last key tile - belong to later frames: their rows and their valid are NOT
+// read (they may hold NaN); the images get zeros and a frame code no query sees, so P = 0 meets V = 0.
+template <typename P>
+struct ClipStepTiles {
+    typename P::elem Ks[CKT * P::LDR];
+    typename P::elem Vt[CHD * P::LDT];
+    int kfr[CKT];
+};
+template <typename P>
+__global__ __launch_bounds__(256, P::STEP_EXACT ? 1 : 2) void attn_clip_step_kernel(const typename P::elem* __restrict__ qkv, const float* __restrict__ valid,
+                                                             typename P::elem* __restrict__ out, int T, int N, int d, int pos,
+                                                             int64_t ldo) {
+    __shared__ __attribute__((aligned(16))) ClipStepTiles<P> tiles[4];
+    __shared__ __attribute__((aligned(16))) float part_m[4][32];
+    __shared__ __attribute__((aligned(16))) float part_l[4][32];
+    __shared__ __attribute__((aligned(16))) typename P::Turn turn;
+    __shared__ __attribute__((aligned(16))) typename P::elem Qs[P::STEP_EXACT ? CKT * P::LDR : 8];      // the block's unscaled queries
+    static_assert(sizeof(ClipStepTiles<P>) % 16 == 0 && sizeof(tiles) >= 3 * 64 * 32 * sizeof(float), "the merge reuses the tile images");
+    const int heads = d / CHD;
+    const ClipBlock blk = clip_block(heads);
+    const int hh = blk.hh;
+    const int64_t b = blk.b;
+    const int n0 = blockIdx.y * CKT;                                 // the block's first query slot
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l31 = lane & 31, h = lane >> 5;
+    const int nlive = N - n0 < CKT ? N - n0 : CKT;
+    const int64_t ld = 3 * (int64_t)d;
+    const int tq = pos, tq_min = pos;
+    const int sq = pos * N + n0 + (l31 < nlive ? l31 : nlive - 1);
+    typename P::Frag qf;
+    P::frag_load_scored(qf, qkv + clip_row(b, sq, T, N) * ld + hh * CHD + 32 * h);
+    const float lo_self = P::step_self_lo(qkv + clip_row(b, sq, T, N) * ld + hh * CHD, qkv + clip_row(b, sq, T, N) * ld + d + hh * CHD);
+    if (P::STEP_EXACT) {                                             // (the first barrier of the tile loop orders it; there is a tile)
+        const int qt = tid >> 3;                                     // 8 threads per query row
+        const int sr = pos * N + n0 + (qt < nlive ? qt : nlive - 1);
+        P::stage_rows(Qs, qt, tid & 7, P::stage_load(qkv + clip_row(b, sr, T, N) * ld + hh * CHD, tid & 7));
+    }
+    const int kend = (pos + 1) * N;                                  // the keys: tokens s < kend
+    const int ntiles = (kend + CKT - 1) / CKT;
+    const int jlo = (w * ntiles) / 4, jhi = ((w + 1) * ntiles) / 4;  // this wave's tiles; at most (ntiles + 3) / 4 of them
+    typename P::elem* Ks = tiles[w].Ks;
+    typename P::elem* Vt = tiles[w].Vt;
+    int* kfr = tiles[w].kfr;
+    const int tok = lane >> 3, c = lane & 7;                         // a lane stages the tokens tok + 8 i, column group c
+    typename P::Stage kn[4], vn[4];
+    int frn[4];
+    auto tile_load = [&](int j) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int sk = j * CKT + tok + 8 * i;
+            kn[i] = P::stage_zero();
+            vn[i] = P::stage_zero();
+            frn[i] = CINVALID + T;
+            if (sk < kend) {
+                const typename P::elem* p = qkv + clip_row(b, sk, T, N) * ld + hh * CHD;
+                kn[i] = P::stage_load(p + d, c);
+                vn[i] = P::stage_load(p + 2 * d, c);
+                frn[i] = clip_frame_code(valid, b, sk, T, N);
+            }
+        }
+    };
+    tile_load(jlo < jhi ? jlo : ntiles);                             // (no tile: zeros, never staged)
+    float m_run = -INFINITY, l_run = 0.f;
+    f32x16 o[2];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { o[0][r] = 0.f; o[1][r] = 0.f; }
+    const int nit = (ntiles + 3) / 4;
+    for (int it = 0; it < nit; ++it) {
+        const int j = jlo + it;
+        __syncthreads();                                             // the previous tile is consumed
+        if (j < jhi) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                P::stage_rows(Ks, tok + 8 * i, c, kn[i]);
+                P::stage_transposed(Vt, tok + 8 * i, c, vn[i]);
+                if (c == 0) kfr[tok + 8 * i] = frn[i];
+            }
+        }
+        __syncthreads();
+        if (j >= jhi) continue;                                      // wave-uniform
+        if (j + 1 < jhi) tile_load(j + 1);                           // in flight under this tile's MFMAs
+        const int k0 = j * CKT;
+        CLIP_FWD_TILE(P, Ks, Vt, kfr, f32x16 st; float lo[16]; P::step_scores(st, lo, Ks, Qs, l31, h, qf);,
+                      * (1.0f + 0.69314718f * (lo[r] - lo_self)))
+    }
+    if (h == 0) { part_m[w][l31] = m_run; part_l[w][l31] = l_run; }
+    __syncthreads();                                                 // every wave is past its last tile: the images are free
+    float m_all = part_m[0][l31];
+#pragma unroll
+    for (int v = 1; v < 4; ++v) m_all = fmaxf(m_all, part_m[v][l31]);
+    const float m_use = m_all == -INFINITY ? 0.f : m_all;
+    float l_all = 0.f;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) l_all += part_l[v][l31] * __builtin_amdgcn_exp2f(part_m[v][l31] - m_use);
+    P::rescale(turn, o, __builtin_amdgcn_exp2f(m_run - m_use) / l_all, w, l31, h);
+    float* part_o = reinterpret_cast<float*>(tiles);                 // [3 waves][32 registers][64 lanes]
+    if (w > 0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            part_o[((w - 1) * 32 + r) * 64 + lane] = o[0][r];
+            part_o[((w - 1) * 32 + 16 + r) * 64 + lane] = o[1][r];
+        }
+    }
+    __syncthreads();
+    if (w > 0) return;
+#pragma unroll
+    for (int v = 0; v < 3; ++v)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            o[0][r] += part_o[(v * 32 + r) * 64 + lane];
+            o[1][r] += part_o[(v * 32 + 16 + r) * 64 + lane];
+        }
+    P::store_rows(out + hh * CHD, ldo, b * N + n0, nlive, o, l31, h);
 }
 
 // ------------------------------------------------------------------------------------------- backward, query owner (dQ)
@@ -630,6 +846,30 @@ static int clip_bwd(const typename P::elem* qkv, const float* valid, const typen
     return vlg_last_error();
 }
 
+// one block per (clip, head) x 32 queries of frame p.  The pointers: 16 bytes fp32, 8 bytes bf16 (its stores are 8 bytes wide,
+// so its rows must keep that: ldo a multiple of 4 elements)
+template <typename P>
+static int clip_step(const typename P::elem* qkv, const float* valid, typename P::elem* o, int64_t B, int T, int N, int d, int p,
+                     int64_t ldo, void* stream) {
+    if (const int rc = clip_check(B, T, N, d)) return rc;
+    if (p < 0 || p >= T || ldo < d) return VLG_ERR_SHAPE;
+    const bool wide = sizeof(typename P::elem) == 4;
+    for (const void* t : {(const void*)qkv, (const void*)o})
+        if (t == nullptr || !(wide ? vlg_aligned16(t) : vlg_aligned8(t))) return VLG_ERR_ALIGN;
+    if (!wide && (ldo % 4) != 0) return VLG_ERR_ALIGN;
+    hipLaunchKernelGGL(attn_clip_step_kernel<P>, dim3((unsigned)(B * (d / CHD)), (unsigned)((N + CKT - 1) / CKT)), dim3(256), 0,
+                       (hipStream_t)stream, qkv, valid, o, T, N, d, p, ldo);
+    return vlg_last_error();
+}
+
+extern "C" int vlg_attention_clip_step(const float* qkv, const float* valid, float* o, int64_t B, int T, int N, int d, int p,
+                                       int64_t ldo, void* stream) {
+    return clip_step<ClipF32>(qkv, valid, o, B, T, N, d, p, ldo, stream);
+}
+extern "C" int vlg_attention_clip_step_bf16(const vlg_bf16* qkv, const float* valid, vlg_bf16* o, int64_t B, int T, int N, int d,
+                                            int p, int64_t ldo, void* stream) {
+    return clip_step<ClipBf16>(reinterpret_cast<const bf16_t*>(qkv), valid, reinterpret_cast<bf16_t*>(o), B, T, N, d, p, ldo, stream);
+}
 extern "C" int vlg_attention_clip_fwd(const float* qkv, const float* valid, float* out, float* lse, int64_t B, int T, int N,
                                       int d, void* stream) {
     return clip_fwd<ClipF32>(qkv, valid, out, lse, B, T, N, d, stream);

@@ -49,6 +49,9 @@ Generation knobs of generate_sequence in layout mode (a keyword argument wins ov
 args.gen_top_k / VLG_GEN_TOP_K (0 = every class, else only the k largest logits), args.gen_seed / VLG_GEN_SEED (default
 args.seed; the same seed, prompt and weights give the same sequence), args.gen_keep_padded / VLG_GEN_KEEP_PADDED = 1 keeps a
 slot that is padded (reserved class id) in the window's last frame padded in every generated frame.
+args.gen_clip_cache / VLG_GEN_CLIP_CACHE = 1 (off by default; an engine knob, LayoutEngine(clip_cache=True)): with
+VLG_ATTENTION=clip a prompt shorter than the window grows through the K/V-cached step (vlg_attention_clip_step) instead of
+re-encoding the window per grown frame.
 
 Validation metrics in layout mode (csrc/metrics.hip, vlg/metrics.py, DESIGN.md "Validation metrics"): args.val_metrics /
 VLG_VAL_METRICS = 1 makes validate() also score every batch on the device - class accuracy, top-k accuracy, NLL, mean IoU,
@@ -190,6 +193,11 @@ def generation_knobs(args) -> Dict[str, object]:
             "keep_padded": bool(_knob(args, "gen_keep_padded", "VLG_GEN_KEEP_PADDED", 0))}
 
 
+def clip_cache_knob(args) -> Dict[str, object]:
+    """the engine's clip_cache keyword argument from args / environment (module docstring): {} with the knob off"""
+    return {"clip_cache": True} if _knob(args, "gen_clip_cache", "VLG_GEN_CLIP_CACHE", 0) else {}
+
+
 def metrics_knobs(args) -> Dict[str, object]:
     """{on, top_k, iou_thr} of the validation metrics in layout mode, from args / environment (module docstring): off,
     top-5 accuracy and IoU >= 0.5 unless asked otherwise."""
@@ -227,7 +235,7 @@ def get_layout_engine(args, cfg: Optional[LayoutConfig] = None, engine_factory: 
                               precision=precision,
                               padded_slots=bool(_knob(args, "variable_n", "VLG_VARIABLE_N", 0)),   # fixed-N feeds hold no padded slots
                               clip_grad=knobs["clip_grad"], skip_nonfinite=knobs["skip_nonfinite"], **recipe_kwargs(knobs),
-                              **dropout_knobs(args))
+                              **dropout_knobs(args), **clip_cache_knob(args))
     else:
         engine = engine_factory(cfg, args)
     if knobs["lr_decay"]:                            # guarded from the start, so a checkpoint's lr and skip count are resumed

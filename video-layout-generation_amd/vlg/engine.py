@@ -88,7 +88,8 @@ class LayoutEngine(AdamSurface):
     def __init__(self, cfg: LayoutConfig, device: torch.device, seed: int = 1024,
                  lr: float = ADAM_LR, beta1: float = ADAM_BETA1, precision: str = "fp32", padded_slots: bool = True,
                  clip_grad: float = 0.0, skip_nonfinite: bool = False, weight_decay: float = 0.0, warmup_steps: int = 0,
-                 ema_decay: float = 0.0, ema_warmup: bool = False, dropout: float = 0.0, dropout_seed: int = 0):
+                 ema_decay: float = 0.0, ema_warmup: bool = False, dropout: float = 0.0, dropout_seed: int = 0,
+                 clip_cache: bool = False):
         """clip_grad > 0 clips the gradient to that global L2 norm (torch.nn.utils.clip_grad_norm_'s rule); skip_nonfinite
         leaves parameters, moments and step count untouched when the gradient holds inf or NaN.  Either one - or a call
         of set_lr - turns on the GUARDED optimiser step (vlg/optim.py), eager and captured alike; with both off and
@@ -116,8 +117,12 @@ class LayoutEngine(AdamSurface):
         forward(), rollout(), evaluate_rollout(), accumulate_metrics() and everything under ema_weights() stay
         evaluation.  The mask is a stateless Philox function of (row, column, site, step) under dropout_seed; the step is a
         device counter (dropout_step / set_dropout_step) advanced once per training forward+backward, whether or not the
-        guarded optimiser then skips.  Not combined with VLG_OVERLAP_WGRAD=1."""
+        guarded optimiser then skips.  Not combined with VLG_OVERLAP_WGRAD=1.
+        clip_cache = True (off by default; it matters with attention = "clip" alone): rollout() from a prompt shorter than
+        the window runs its grow steps through the K/V-cached step of per-clip attention (vlg_attention_clip_step) instead of
+        re-encoding the window per grown frame.  Off, rollout(cache=True) raises with per-clip attention, as before."""
         cfg.validate()
+        self.clip_cache = bool(clip_cache)
         self.dropout = float(dropout)
         if not 0.0 <= self.dropout < 1.0:
             raise ValueError("dropout must be in [0, 1), got %r" % (dropout,))
@@ -791,24 +796,33 @@ class LayoutEngine(AdamSurface):
                               gl=torch.empty(R, cfg.d_ff, **act), stat=torch.empty(2, R, **f32))
         return self._grow
 
-    def _encode_step(self, p: int, B: int, N: int) -> torch.Tensor:
-        """The encoder on the B*N rows of position p alone, against the K/V cache that self.qkv[l] holds for positions < p
-        (per-slot attention): embeds the compact frame vlg_layout_decode_append left, writes that position's q k v rows
+    def _encode_step(self, p: int, B: int, N: int, valid: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The encoder on the B*N rows of position p alone, against the K/V cache that self.qkv[l] holds for positions < p:
+        embeds the compact frame vlg_layout_decode_append left, writes that position's q k v rows
         into the cache and returns the compact residual stream [B*N, d] leaving the last layer.  _encode with T = 1 and
         time_emb[p] on the compact set: the residual stream ping-pongs between xa and xb, one h and one stat serve every norm,
         and the qkv projection writes its rows into the cache with ldc = T*3d.  As many launches as on the window (1 + 7 per
-        layer), on 1/T of its rows."""
+        layer), on 1/T of its rows.  Per-slot attention: vlg_attention_step.  Per-clip attention (clip_cache): the N queries of
+        frame p against every slot of the frames <= p, vlg_attention_clip_step, masked by the window's `valid` when
+        self._masked - its frame p is what the previous vlg_layout_decode_append wrote."""
         d, T, L = self.cfg.d, self.cfg.T, self.cfg.n_layers
         g, BN, s = self._grow_buffers(), B * N, self._stream()
         h, one = [g["h"]] * L, lambda name: [g[name]] * L
         w = types.SimpleNamespace(x=[g["xa"], g["xb"]] * L, h1=h, h2=h, qkv=[self.qkv[l].view(-1)[p * 3 * d:] for l in range(L)],
                                   att=one("att"), xmid=one("xmid"), u=one("u"), gl=one("gl"), stats=[g["stat"]] * (2 * L))
 
+        def attn_clip(l):
+            e = self.qkv.element_size()                             # q and o rows of the frame, k and v of p + 1 frames
+            self._timed("attn_clip_step", 4.0 * B * d * N * N * (p + 1), "vlg_attention_clip_step" + self._sfx, ptr(self.qkv[l]),
+                        ptr(valid) if self._masked else 0, ptr(g["att"]), B, T, N, d, p, d, s,
+                        nbytes=e * BN * d * (2.0 * (p + 1) + 2.0) + (4.0 * BN * (p + 1) if self._masked else 0.0))
+
         def attn(l):
             self._timed("attn_step", 0.0, "vlg_attention_step" + self._sfx, ptr(self.qkv[l]), ptr(g["att"]), BN, T, d, p, d, s,
                         nbytes=self.qkv.element_size() * BN * d * (2.0 * (p + 1) + 2.0))
 
-        self._encode(g["cls"], g["box"], self.p("time_emb")[p], w, attn, B, 1, N, ldc=T * 3 * d)
+        self._encode(g["cls"], g["box"], self.p("time_emb")[p], w, attn_clip if self.cfg.attention == "clip" else attn, B, 1, N,
+                     ldc=T * 3 * d)
         return w.x[L]
 
     def rollout(self, slot_class: torch.Tensor, slot_box: torch.Tensor, steps: int = 8, temperature: float = 0.0,
@@ -826,11 +840,12 @@ class LayoutEngine(AdamSurface):
         at position h-1 of those h frames alone (all mixing along time is causal).  The window buffer holds T frames
         throughout - the reserved class id, zero boxes and valid = 0 after the history; causality hides them.  The prompt
         pass encodes that window once, reads frame P-1 (vlg_head_frame) and appends in place (vlg_layout_decode_append).
-        Each further frame until the window is full is a CACHED step with per-slot attention (cache None or True): the
-        encoder runs on the newest frame's B*N rows only, against the keys and values self.qkv[l] already holds for the
-        earlier positions (_encode_step, vlg_attention_step).  cache=False, and per-clip attention always, re-encodes the
-        window per grown frame instead; cache=True with per-clip attention raises.  Once the window is full the steps are
-        the sliding ones above, from the same buffers.
+        Each further frame until the window is full is a CACHED step (cache None or True): the encoder runs on the newest
+        frame's B*N rows only, against the keys and values self.qkv[l] already holds for the earlier positions
+        (_encode_step; vlg_attention_step, or with per-clip attention vlg_attention_clip_step under the window's valid).
+        Per-clip attention has the cached step only in an engine built with clip_cache=True: without the option it
+        re-encodes the window per grown frame and cache=True raises.  cache=False always re-encodes.  Once the window is
+        full the steps are the sliding ones above, from the same buffers.
         No loss, no targets, no host wait inside the loop (one before it with per-clip attention: the mask decision)."""
         cfg, d = self.cfg, self.cfg.d
         if slot_class.dim() != 3 or tuple(slot_box.shape) != tuple(slot_class.shape) + (BOX_DIM,):
@@ -840,8 +855,9 @@ class LayoutEngine(AdamSurface):
         M, BN = B * T * N, B * N
         if not 1 <= P <= T:
             raise ValueError("prompt has %d frames, the engine's window takes 1 to T=%d" % (P, T))
-        if cache and cfg.attention == "clip":
-            raise ValueError("cache=True: there is no cached step for per-clip attention (cache=None re-encodes the window)")
+        if cache and cfg.attention == "clip" and not self.clip_cache:
+            raise ValueError("cache=True: the cached step of per-clip attention is an option, LayoutEngine(clip_cache=True) / "
+                             "VLG_GEN_CLIP_CACHE=1 (without it cache=None re-encodes the window)")
         if M > self.capacity:
             raise ValueError("window of %d tokens exceeds workspace capacity %d" % (M, self.capacity))
         for t, dt, what in ((slot_class, torch.int64, "slot_class"), (slot_box, torch.float32, "slot_box")):
@@ -852,7 +868,7 @@ class LayoutEngine(AdamSurface):
             raise ValueError("steps must be >= 1")
         if not (math.isfinite(temperature) and temperature >= 0.0) or not 0 <= top_k <= cfg.n_classes:
             raise ValueError("temperature must be finite and >= 0, top_k in [0, %d]" % cfg.n_classes)
-        cached = P < T and cfg.attention != "clip" and (cache is None or bool(cache))
+        cached = P < T and (cfg.attention != "clip" or self.clip_cache) and (cache is None or bool(cache))
         win = [(c[:M].view(B, T, N), b[:M].view(B, T, N, BOX_DIM), v[:M].view(B, T, N)) for c, b, v in self._windows()]
         if P == T:
             win[0][0].copy_(slot_class)
@@ -879,7 +895,7 @@ class LayoutEngine(AdamSurface):
         for i, (encoder, t_read, pos) in enumerate(grow_schedule(P, T, steps, cached)):
             (cls, box, valid), (ncls, nbox, nvalid) = win[cur], win[cur ^ 1]
             if encoder == "step":                                   # the newest frame alone, against the cache: its rows are the last
-                x, Tx, frame = self._encode_step(t_read, B, N), 1, ()
+                x, Tx, frame = self._encode_step(t_read, B, N, valid), 1, ()
             else:                                                   # the window: the last frame, or - still growing - frame t_read
                 self._encode_window({"slot_class": cls, "slot_box": box, "valid": valid}, B, T, N)
                 x, Tx, frame = self.x[L], T, (t_read,) if t_read < T - 1 else ()

@@ -57,6 +57,8 @@ SIGNATURES = {
     "vlg_attention_clip_bwd": (I, [P, P, P, P, P, P, P, L, I, I, I, P]),
     "vlg_attention_clip_fwd_bf16": (I, [P, P, P, P, L, I, I, I, P]),
     "vlg_attention_clip_bwd_bf16": (I, [P, P, P, P, P, P, P, L, I, I, I, P]),
+    "vlg_attention_clip_step": (I, [P, P, P, L, I, I, I, I, L, P]),      # (qkv, valid, o, B, T, N, d, p, ldo, stream)
+    "vlg_attention_clip_step_bf16": (I, [P, P, P, L, I, I, I, I, L, P]),
     "vlg_layout_loss_scratch": (I, []),
     "vlg_layout_loss": (I, [P, I, P, P, P, P, P, P, I, I, I, I, F, F, F, F, F, P]),
     "vlg_head_last_frame": (I, [P, P, P, P, P, P, I, I, I, I, I, F, P]),
