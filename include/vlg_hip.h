@@ -273,6 +273,29 @@ int vlg_layout_loss(const float* out, int ld, const int64_t* tgt_class, const fl
                     const float* valid, float* dout, float* loss_out, float* scratch,
                     int B, int T, int N, int n_classes, float beta, float iou_eps,
                     float w_reg, float w_iou, float w_ce, void* stream);
+/* The same launch with the options of the classification and overlap terms ("Loss options"; definition in
+ * fp64: tests/loss_ext_ref.py).  One kernel body serves both entries; the options are its compile-time parameters and
+ * vlg_layout_loss is the all-off instantiation, so class_weight = NULL, label_smoothing = 0, flags = 0 gives its bits.
+ *   class_weight     NULL, or n_classes floats >= 0 ON THE DEVICE: F.cross_entropy(weight=) - token i counts w[y_i]
+ *                    times, and the CE mean divides by W = sum_i valid_i w[y_i] instead of the valid count.  W == 0 (every
+ *                    valid target has weight 0): the CE term and its gradient are exactly 0 (torch: NaN).  Every block
+ *                    forms W by the same operations in the same order, so a launch is reproducible bit for bit; that
+ *                    loop reads tgt_class as well (8 B per token).  The box terms keep the valid count.
+ *   label_smoothing  eps in [0, 1): F.cross_entropy(label_smoothing=) - the target distribution of token i is
+ *                    q_i[c] = (eps/C) w[c] + (1-eps) w[y_i] [c == y_i]  (w = 1 without weights);
+ *                    CE = (1/W) sum_i valid_i sum_c q_i[c] (-log p_i[c]),  dCE/dz_i[k] = valid_i/W (Q_i p_i[k] - q_i[k]),
+ *                    Q_i = sum_c q_i[c]
+ *   flags            VLG_LOSS_GIOU: the overlap term is mean_valid(1 - giou) in [0, 2],
+ *                    giou = inter/(uni + iou_eps) - (ac - uni)/(ac + iou_eps), ac = the area of the smallest box
+ *                    enclosing both; min / max split 0.5 / 0.5 at a tie and clamp passes the gradient at 0, as torch's.
+ *                    loss_out[2] is then that term.  Unlike 1 - IoU it has a gradient for boxes that do not touch.
+ * Layout, scratch contract (ticket reset), ld rule and alignment checks are vlg_layout_loss's.  VLG_ERR_SHAPE, nothing
+ * enqueued: label_smoothing outside [0, 1) or NaN, a flag bit other than VLG_LOSS_GIOU, and every refusal of the plain entry. */
+#define VLG_LOSS_GIOU 1
+int vlg_layout_loss_ext(const float* out, int ld, const int64_t* tgt_class, const float* tgt_box,
+                        const float* valid, const float* class_weight, float* dout, float* loss_out, float* scratch,
+                        int B, int T, int N, int n_classes, float beta, float iou_eps,
+                        float w_reg, float w_iou, float w_ce, float label_smoothing, int flags, void* stream);
 
 /* ------------------------------------------------------------------ per-clip attention (option attention = "clip")
  * Block-causal softmax attention over ALL T*N tokens of a clip, per (clip, head): token (t, n) attends to every slot of

@@ -44,6 +44,13 @@ the embedding and the two residual branches of every layer in training steps onl
 averaged weights stay evaluation; VLG_DROPOUT_SEED (default args.seed) seeds the stateless mask, and data-parallel rank r
 uses seed + r so that ranks draw different masks.
 
+Loss options in layout mode (all off by default; csrc/loss.hip, DESIGN.md "Loss options"): args.class_weights /
+VLG_CLASS_WEIGHTS = 20 comma-separated floats, finite and >= 0 with at least one > 0, the weight= of F.cross_entropy
+(vlg.metrics.balanced_class_weights turns the confusion matrix of VLG_VAL_METRICS=1 into such a list); args.label_smoothing /
+VLG_LABEL_SMOOTHING = eps in [0, 1), its label_smoothing=; args.box_overlap / VLG_BOX_OVERLAP = iou (default) or giou, the
+overlap term 1 - GIoU, which has a gradient for boxes that do not touch.  They change the training objective AND the loss
+validate() reports; the validation metrics' NLL and IoU stay the plain figures.
+
 Generation knobs of generate_sequence in layout mode (a keyword argument wins over them; csrc/decode.hip, DESIGN.md
 "Generation"): args.gen_temperature / VLG_GEN_TEMPERATURE (0 = argmax; > 0 samples from softmax(logits / temperature)),
 args.gen_top_k / VLG_GEN_TOP_K (0 = every class, else only the k largest logits), args.gen_seed / VLG_GEN_SEED (default
@@ -82,7 +89,7 @@ import torch.distributed as dist
 from vlg.data import BATCH_KEYS, BucketedClipLoader, ClipLoader, synthetic_clips, to_device
 from vlg.dp import GradReducer, bucket_ranges
 from vlg.optim import decayed_lr
-from vlg.spec import ADAM_BETA1, ADAM_LR, SEED, LayoutConfig
+from vlg.spec import ADAM_BETA1, ADAM_LR, N_CLASSES, SEED, LayoutConfig, loss_options
 
 
 class AverageMeter(object):
@@ -179,6 +186,33 @@ def dropout_knobs(args) -> Dict[str, object]:
     return {"dropout": p, "dropout_seed": seed + int(getattr(args, "rank", 0) or 0)}
 
 
+def loss_knobs(args) -> Dict[str, object]:
+    """the engine's loss-option keyword arguments from args / environment (module docstring): {} with all of them off, so an
+    engine without the options is never handed one; else those that are on among {class_weights, label_smoothing,
+    box_overlap}.  Refuses what LayoutEngine refuses (vlg.spec.loss_options), before any engine exists."""
+    weights = getattr(args, "class_weights", None)
+    if weights is None:
+        weights = os.environ.get("VLG_CLASS_WEIGHTS") or None
+    if isinstance(weights, str):
+        try:
+            weights = [float(x) for x in weights.split(",")]
+        except ValueError:
+            raise ValueError("VLG_CLASS_WEIGHTS must be %d comma-separated floats, got %r" % (N_CLASSES, weights)) from None
+    eps = getattr(args, "label_smoothing", None)
+    if eps is None:
+        eps = os.environ.get("VLG_LABEL_SMOOTHING", 0.0)
+    overlap = str(getattr(args, "box_overlap", None) or os.environ.get("VLG_BOX_OVERLAP", "iou")).lower()
+    weights, eps, overlap = loss_options(weights, eps, overlap, N_CLASSES)
+    knobs: Dict[str, object] = {}
+    if weights is not None:
+        knobs["class_weights"] = weights
+    if eps > 0.0:
+        knobs["label_smoothing"] = eps
+    if overlap != "iou":
+        knobs["box_overlap"] = overlap
+    return knobs
+
+
 def recipe_kwargs(knobs: Dict[str, object]) -> Dict[str, object]:
     """the recipe's engine keyword arguments - only those that are on, so an engine factory without them is never handed one"""
     return {k: knobs[k] for k in ("weight_decay", "warmup_steps", "ema_decay", "ema_warmup") if knobs.get(k)}
@@ -235,7 +269,7 @@ def get_layout_engine(args, cfg: Optional[LayoutConfig] = None, engine_factory: 
                               precision=precision,
                               padded_slots=bool(_knob(args, "variable_n", "VLG_VARIABLE_N", 0)),   # fixed-N feeds hold no padded slots
                               clip_grad=knobs["clip_grad"], skip_nonfinite=knobs["skip_nonfinite"], **recipe_kwargs(knobs),
-                              **dropout_knobs(args), **clip_cache_knob(args))
+                              **dropout_knobs(args), **clip_cache_knob(args), **loss_knobs(args))
     else:
         engine = engine_factory(cfg, args)
     if knobs["lr_decay"]:                            # guarded from the start, so a checkpoint's lr and skip count are resumed
@@ -429,6 +463,9 @@ class Trainer:
         self.reducer = None
         if self.image_mode and self.dropout:
             raise ValueError("VLG_DROPOUT is a knob of the layout-token step; VLG_MODEL=gridnet has no dropout")
+        if loss_knobs(args) and self.image_mode:                # (out-of-range values raise here too)
+            raise ValueError("VLG_CLASS_WEIGHTS / VLG_LABEL_SMOOTHING / VLG_BOX_OVERLAP are knobs of the layout-token step; "
+                             "VLG_MODEL=gridnet's losses have no options")
         if self.image_mode:
             self.engine = _ImageModel(args, self.cfg.B)
             if self.distributed:                                # replaces DDP(gridnet), trainer.py:113: bucket per grid column

@@ -36,7 +36,7 @@ from .slabs import SlabBuckets
 from .hip import (EPI_A_BF16, EPI_B_BF16, EPI_BIAS, EPI_DGELU, EPI_GELU, EPI_NONE, EPI_OUT_BF16, EPI_RESID,
                   call, ptr)
 from .spec import (ADAM_BETA1, ADAM_BETA2, ADAM_EPS, ADAM_LR, BOX_DIM, IOU_EPS, LN_EPS, LOSS_W_CE,
-                   LOSS_W_REG, LOSS_W_STRUCT, SMOOTH_L1_BETA, LayoutConfig, param_layout)
+                   LOSS_W_REG, LOSS_W_STRUCT, SMOOTH_L1_BETA, LayoutConfig, loss_options, param_layout)
 
 
 def init_params(cfg: LayoutConfig, seed: int) -> Dict[str, torch.Tensor]:
@@ -89,7 +89,7 @@ class LayoutEngine(AdamSurface):
                  lr: float = ADAM_LR, beta1: float = ADAM_BETA1, precision: str = "fp32", padded_slots: bool = True,
                  clip_grad: float = 0.0, skip_nonfinite: bool = False, weight_decay: float = 0.0, warmup_steps: int = 0,
                  ema_decay: float = 0.0, ema_warmup: bool = False, dropout: float = 0.0, dropout_seed: int = 0,
-                 clip_cache: bool = False):
+                 clip_cache: bool = False, class_weights=None, label_smoothing: float = 0.0, box_overlap: str = "iou"):
         """clip_grad > 0 clips the gradient to that global L2 norm (torch.nn.utils.clip_grad_norm_'s rule); skip_nonfinite
         leaves parameters, moments and step count untouched when the gradient holds inf or NaN.  Either one - or a call
         of set_lr - turns on the GUARDED optimiser step (vlg/optim.py), eager and captured alike; with both off and
@@ -120,8 +120,16 @@ class LayoutEngine(AdamSurface):
         guarded optimiser then skips.  Not combined with VLG_OVERLAP_WGRAD=1.
         clip_cache = True (off by default; it matters with attention = "clip" alone): rollout() from a prompt shorter than
         the window runs its grow steps through the K/V-cached step of per-clip attention (vlg_attention_clip_step) instead of
-        re-encoding the window per grown frame.  Off, rollout(cache=True) raises with per-clip attention, as before."""
+        re-encoding the window per grown frame.  Off, rollout(cache=True) raises with per-clip attention, as before.
+        Loss options (DESIGN.md "Loss options"; all off by default, and then the step launches vlg_layout_loss as ever; with
+        any of them on, vlg_layout_loss_ext in its place - one launch either way): class_weights = n_classes floats, finite
+        and >= 0 with at least one > 0, the weight= of F.cross_entropy (uploaded once; the CE mean then divides by the summed
+        weight of the valid targets, per rank under data parallelism); label_smoothing in [0, 1), its label_smoothing=;
+        box_overlap = "giou" makes the overlap term mean(1 - GIoU), which has a gradient for boxes that do not touch.
+        Fixed at construction; checkpoints do not carry them.  forward() - validation included - returns this configured
+        objective; accumulate_metrics / evaluate_rollout keep reporting the plain NLL and IoU."""
         cfg.validate()
+        weights, self.label_smoothing, self.box_overlap = loss_options(class_weights, label_smoothing, box_overlap, cfg.n_classes)
         self.clip_cache = bool(clip_cache)
         self.dropout = float(dropout)
         if not 0.0 <= self.dropout < 1.0:
@@ -158,6 +166,8 @@ class LayoutEngine(AdamSurface):
             self.drop_step = torch.zeros(1, dtype=torch.int32, device=device)
         self.layout, self.n_params = param_layout(cfg)
         f32 = dict(dtype=torch.float32, device=device)
+        self.class_weights = None if weights is None else torch.tensor(weights, **f32)
+        self._loss_ext = weights is not None or self.label_smoothing > 0.0 or self.box_overlap != "iou"
         self.params = torch.zeros(self.n_params, **f32)
         # 4 extra floats after the last parameter hold the loss scalars, so they travel inside the
         # first gradient bucket of the data-parallel all-reduce (vlg/dp.py)
@@ -502,10 +512,16 @@ class LayoutEngine(AdamSurface):
         s = self._stream()
         self._encode_window(batch, B, T, N, drop=self._dropped, final=True)
         self._linear(self.xf, self.pw("head_w"), self.p("head_b"), self.out, M, cfg.n_out, d, EPI_BIAS)
-        self._timed("loss", 0.0, "vlg_layout_loss", ptr(self.out), cfg.n_out, ptr(batch["tgt_class"]), ptr(batch["tgt_box"]),
-                    ptr(batch["valid"]), ptr(self.dout), ptr(self.loss_out), ptr(self.loss_scratch), B, T, N,
-                    cfg.n_classes, SMOOTH_L1_BETA, IOU_EPS, LOSS_W_REG, LOSS_W_STRUCT, LOSS_W_CE, s,
-                    nbytes=(2.0 * 4 * cfg.n_out + 8 + 16 + 4) * M)
+        targets = (ptr(self.out), cfg.n_out, ptr(batch["tgt_class"]), ptr(batch["tgt_box"]), ptr(batch["valid"]))
+        outs = (ptr(self.dout), ptr(self.loss_out), ptr(self.loss_scratch), B, T, N, cfg.n_classes, SMOOTH_L1_BETA, IOU_EPS,
+                LOSS_W_REG, LOSS_W_STRUCT, LOSS_W_CE)
+        nbytes = (2.0 * 4 * cfg.n_out + 8 + 16 + 4) * M
+        if self._loss_ext:                            # any option on: the same kernel body with the options compiled in
+            self._timed("loss", 0.0, "vlg_layout_loss_ext", *targets, ptr(self.class_weights), *outs, self.label_smoothing,
+                        hip.LOSS_GIOU if self.box_overlap == "giou" else 0, s,
+                        nbytes=nbytes + (12.0 * M if self.class_weights is not None else 0.0))
+        else:
+            self._timed("loss", 0.0, "vlg_layout_loss", *targets, *outs, s, nbytes=nbytes)
         return self.loss_out
 
     def _encode(self, cls, box, time_emb, w, attn, B: int, T: int, N: int, drop: bool = False, final: bool = False, ldc=None) -> None:

@@ -61,6 +61,8 @@ SIGNATURES = {
     "vlg_attention_clip_step_bf16": (I, [P, P, P, L, I, I, I, I, L, P]),
     "vlg_layout_loss_scratch": (I, []),
     "vlg_layout_loss": (I, [P, I, P, P, P, P, P, P, I, I, I, I, F, F, F, F, F, P]),
+    # (out, ld, tgt_class, tgt_box, valid, class_weight | NULL, dout, loss_out, scratch, B, T, N, C, beta, iou_eps, 3 weights, eps, flags, stream)
+    "vlg_layout_loss_ext": (I, [P, I, P, P, P, P, P, P, P, I, I, I, I, F, F, F, F, F, F, I, P]),
     "vlg_head_last_frame": (I, [P, P, P, P, P, P, I, I, I, I, I, F, P]),
     "vlg_head_frame": (I, [P, P, P, P, P, P, I, I, I, I, I, I, F, P]),
     "vlg_layout_decode": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, c_uint64, I, P]),
@@ -128,6 +130,7 @@ DIAG_SIGNATURES = {
     "vlg_debug_set_gemm_bk": (None, [I]),
     "vlg_debug_set_gemm_run": (None, [I]),
 }
+LOSS_GIOU = 1                          # vlg_layout_loss_ext flags (VLG_LOSS_GIOU)
 CEPI_BIAS, CEPI_RESID, CEPI_PRELU, CEPI_DPRELU, CEPI_ACCUM, CEPI_CIN4 = 1, 2, 4, 8, 16, 32
 CONV_PRECISIONS = ("fp32", "bf16")     # 3x3 convolutions: fp32 MFMA (conv.hip) or bf16-operand MFMA (conv_bf16.hip)
 

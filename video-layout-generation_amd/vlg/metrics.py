@@ -78,3 +78,27 @@ class MetricsRecord:
                 "confusion": conf,
             })
         return out
+
+
+def balanced_class_weights(counts, power: float = 0.5, row: int = 0) -> List[float]:
+    """Class weights for LayoutEngine(class_weights=) / VLG_CLASS_WEIGHTS from per-class target counts n_c (host only):
+    w_c proportional to n_c ** -power for the classes that occur (power 0: all equal; 1: inverse frequency; the default
+    0.5 lies between), the largest of those weights for a class that does not occur, and the whole scaled so that
+    sum_c n_c w_c == sum_c n_c - the weighted cross entropy's denominator is then the valid count's, and the loss stays
+    on the scale of the unweighted one.
+    `counts` is a sequence of n_classes counts, one dict of MetricsRecord.summary() (its confusion matrix's row sums are
+    the target counts), or a MetricsRecord itself, whose row `row` is read."""
+    if isinstance(counts, MetricsRecord):
+        counts = counts.summary()[row]
+    if isinstance(counts, dict):
+        counts = [sum(r) for r in counts["confusion"]]
+    n = [float(c) for c in counts]
+    if not n or not all(math.isfinite(c) and c >= 0.0 for c in n) or not any(c > 0.0 for c in n):
+        raise ValueError("balanced_class_weights needs finite counts >= 0 with at least one > 0, got %r" % (n,))
+    if not math.isfinite(power) or power < 0.0:
+        raise ValueError("power must be finite and >= 0, got %r" % (power,))
+    raw = [c ** -power if c > 0.0 else 0.0 for c in n]
+    top = max(raw)
+    raw = [r if c > 0.0 else top for r, c in zip(raw, n)]
+    scale = sum(n) / sum(c * r for c, r in zip(n, raw))
+    return [r * scale for r in raw]

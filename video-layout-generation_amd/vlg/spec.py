@@ -98,7 +98,35 @@ class LayoutConfig:
                 "loss": "40*smoothL1(beta=%g)+20*(1-IoU)+10*CE" % SMOOTH_L1_BETA}
 
 
-def param_shapes(cfg: LayoutConfig) -> "OrderedDict[str, Tuple[int, ...]]":
+BOX_OVERLAPS = ("iou", "giou")
+
+
+def loss_options(class_weights=None, label_smoothing: float = 0.0, box_overlap: str = "iou", n_classes: int = N_CLASSES):
+    """The layout loss's options, checked on the host (LayoutEngine and trainer.loss_knobs refuse the same things):
+    (weights as a list of n_classes floats or None, label smoothing, overlap term).  class_weights: n_classes numbers, all
+    finite and >= 0, at least one > 0; label_smoothing in [0, 1); box_overlap "iou" or "giou".  ValueError otherwise."""
+    weights = None
+    if class_weights is not None:
+        try:
+            weights = [float(w) for w in class_weights]
+        except (TypeError, ValueError):
+            raise ValueError("class_weights must be a sequence of %d numbers, got %r" % (n_classes, class_weights)) from None
+        if len(weights) != n_classes:
+            raise ValueError("class_weights must hold %d values (one per class), got %d" % (n_classes, len(weights)))
+        if not all(math.isfinite(w) and w >= 0.0 for w in weights) or not any(w > 0.0 for w in weights):
+            raise ValueError("class_weights must be finite and >= 0 with at least one > 0, got %r" % (weights,))
+    try:
+        eps = float(label_smoothing)
+    except (TypeError, ValueError):
+        raise ValueError("label_smoothing must be a number in [0, 1), got %r" % (label_smoothing,)) from None
+    if not 0.0 <= eps < 1.0:                            # (also refuses NaN)
+        raise ValueError("label_smoothing must be in [0, 1), got %r" % (label_smoothing,))
+    if box_overlap not in BOX_OVERLAPS:
+        raise ValueError("box_overlap must be one of %s, got %r" % (BOX_OVERLAPS, box_overlap))
+    return weights, eps, box_overlap
+
+
+def param_shapes(cfg: LayoutConfig) ->"OrderedDict[str, Tuple[int, ...]]":
     """Names and shapes of every trainable tensor, in flat-buffer order.
 
     The order is chosen for the backward pass: the tensors whose gradients are
