@@ -394,6 +394,36 @@ int vlg_layout_decode_append(const float* out_last, int64_t* cls, float* box, fl
                              int B, int T, int N, int n_classes, int pos, int steps, int step,
                              float temperature, int top_k, uint64_t seed, int keep_padded, void* stream);
 
+/* ------------------------------------------------------------------ scheduled sampling (csrc/decode.hip)
+ * SELF-ORACLE (tests/sched_ref.py restates it); DESIGN.md, "Scheduled sampling".  Builds the inputs of a training step's
+ * second pass from the true inputs and the first pass's outputs: every input token is either the truth or the model's own
+ * decoded prediction of it.
+ *   out       [B*N*T, ld] fp32: logits | raw box of an evaluation forward on the true inputs, INTERNAL row order
+ *             m = (b*N + n)*T + t; row m predicts frame t + 1.  Rows with t = T-1 feed nothing and are NOT read.
+ *   cls, box  the true inputs, (B,T,N) int64 / (B,T,N,4) fp32, public order, only read
+ *   mix_cls, mix_box  the mixed inputs, same shapes; every element is written, each by exactly one thread (plain stores)
+ *   step      int32 in DEVICE memory: the step counter k, read when the kernel runs (a captured graph advances it by
+ *             replaying vlg_dropout_step_advance on it)
+ * Input token i = (b*T + t)*N + n keeps the truth when t == 0 or cls[i] >= n_classes (a padded slot: id and box stay).
+ * Every other token is replaced iff (x >> 8) < thr(k), x = first word of Philox4x32-10 on counter (i, k, 1, 0) under key
+ * (seed & 0xffffffff, seed >> 32);  thr(k) = thr_max when ramp_steps == 0, else
+ * (uint64)thr_max * min(k + 1, ramp_steps) / ramp_steps (integer division).  thr_max = round(eps_max * 2^24)
+ * (vlg_sched_plan is the one place this rule lives): 0 never replaces, 2^24 always does.
+ * A replaced token takes, from row (b*N + n)*T + (t-1) of out: class = vlg_layout_decode's rule for a slot that is not
+ * padded (one device function serves all three entries), its u drawn from counter (i, k, 0, 0); box = sigmoid(raw).
+ *
+ * vlg_sched_plan (host only; thr_host is a HOST pointer): VLG_ERR_SHAPE unless 0 <= eps_max <= 1 (NaN refused).
+ * vlg_layout_mix_inputs refuses before anything is enqueued.  VLG_ERR_SHAPE: B, T or N < 1, B*T*N >= 2^31 (the token is
+ * a 32-bit counter word), n_classes < 1 or n_classes + 4 > 32, ld < n_classes + 4, thr_max > 2^24, ramp_steps < 0,
+ * temperature < 0 or not finite, top_k < 0 or > n_classes, a NULL pointer, or mix_cls / mix_box overlapping each other
+ * or any of out, cls, box, step.  VLG_ERR_ALIGN: out, box, mix_box not 16-byte, cls, mix_cls not 8-byte, step not 4-byte
+ * aligned.  Algorithmic bytes: 4 * (n_classes + 4) * B*N*(T-1) read of out, 2 * 24 * B*T*N of tokens. */
+int vlg_sched_plan(double eps_max, uint32_t* thr_host);
+int vlg_layout_mix_inputs(const float* out, int ld, const int64_t* cls, const float* box,
+                          int64_t* mix_cls, float* mix_box, const int* step,
+                          int B, int T, int N, int n_classes, uint32_t thr_max, int ramp_steps,
+                          float temperature, int top_k, uint64_t seed, void* stream);
+
 /* ------------------------------------------------------------------ validation metrics (csrc/metrics.hip)
  * Scores head outputs against targets and ADDS the result to a running record in device memory: `counts` (int64 slots,
  * vlg_layout_metrics_counts(n_classes) of them) and `sums` (double slots, vlg_layout_metrics_sums(n_classes)).  One launch,

@@ -13,6 +13,8 @@
 //     vector store; no atomics, no state.
 // vlg_layout_decode_append  the same step while the history is shorter than the window: the decoding rule is one device
 //     function (decode_token) for both; the new frame is written at its position of the window in place, nothing slides.
+// vlg_layout_mix_inputs  scheduled sampling: the inputs of a training step's second pass, per token the truth or the
+//     model's own prediction decoded by the same decode_token from the first pass's outputs (end of this file).
 #include "common.h"
 
 #define HL_BLOCK 256
@@ -122,9 +124,10 @@ extern "C" int vlg_head_last_frame(const float* x, const float* gamma, const flo
 }
 
 // ---------------------------------------------------------------------------------------------------------- decoding
-// Philox4x32-10 (Salmon et al., Random123): first output word of counter (c0, c1, 0, 0) under key (k0, k1)
-__device__ __forceinline__ uint32_t philox_first(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1) {
-    uint32_t c2 = 0u, c3 = 0u;
+// Philox4x32-10 (Salmon et al., Random123): first output word of counter (c0, c1, c2, 0) under key (k0, k1).  c2 names the
+// stream: 0 = the class draw of decode_token, 1 = the scheduled-sampling coin
+__device__ __forceinline__ uint32_t philox_first(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1, uint32_t c2 = 0u) {
+    uint32_t c3 = 0u;
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
@@ -135,7 +138,7 @@ __device__ __forceinline__ uint32_t philox_first(uint32_t c0, uint32_t c1, uint3
     return c0;
 }
 
-// The decoding rule, written once for the sliding step and the appending one.  l: token r's [logits | raw box] (the logits
+// The decoding rule, written once for the sliding step, the appending one and the scheduled-sampling mix.  l: token r's [logits | raw box] (the logits
 // become the running sums); prev / prev_box: the token's class and box in the newest frame of the history.
 __device__ __forceinline__ void decode_token(float* l, int C, int64_t prev, const float* __restrict__ prev_box, int64_t r, int step,
                                              float temperature, int top_k, uint32_t k0, uint32_t k1, int keep_padded,
@@ -317,5 +320,75 @@ extern "C" int vlg_layout_decode_append(const float* out_last, int64_t* cls, flo
     hipLaunchKernelGGL(layout_decode_append_kernel, grid, block, 0, (hipStream_t)stream, out_last, cls, box, valid, gen_cls,
                        gen_box, frame_cls, frame_box, B, T, N, n_classes, pos, steps, step, temperature, top_k,
                        (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), keep_padded);
+    return vlg_last_error();
+}
+
+// ------------------------------------------------------------------------------------------------ scheduled sampling
+// The inputs of a training step's second pass: per input token the truth or the model's own decoded prediction of it
+// (rule: include/vlg_hip.h, "scheduled sampling").  The grid walks `out` in its own row order m = (b*N + n)*T + t, 64 rows
+// per block, staged in LDS as decode_stage does (rows with t = T-1 feed nothing and are not loaded).  The thread that holds
+// row (r, t), t < T-1, decides input token (b, t+1, n): coin, then decode_token on its row, or the truth; the thread that
+// holds row (r, T-1) copies the token of frame 0.  So every token is written by exactly one thread, with plain vector
+// stores.  Launch-bound: 4*(C+4) bytes per row read, 2 * 24 bytes per token moved.
+__global__ __launch_bounds__(DEC_BLOCK) void layout_mix_inputs_kernel(
+    const float* __restrict__ out, int ld, const int64_t* __restrict__ cls, const float* __restrict__ box,
+    int64_t* __restrict__ mix_cls, float* __restrict__ mix_box, const int* __restrict__ step_ptr, int64_t M, int T, int N, int C,
+    uint32_t thr_max, int ramp_steps, float temperature, int top_k, uint32_t k0, uint32_t k1) {
+    __shared__ float rows[DEC_BLOCK][DEC_LD];
+    const int tid = threadIdx.x, n_out = C + 4;
+    const int64_t m_first = (int64_t)blockIdx.x * DEC_BLOCK;
+    const int here = (int)(M - m_first < DEC_BLOCK ? M - m_first : DEC_BLOCK);
+    for (int e = tid; e < here * n_out; e += DEC_BLOCK) {
+        const int row = e / n_out, col = e - row * n_out;
+        const int64_t m = m_first + row;
+        if (m % T != T - 1) rows[row][col] = out[m * ld + col];
+    }
+    __syncthreads();
+    if (tid >= here) return;
+    const int64_t m = m_first + tid, r = m / T;
+    const int t = (int)(m - r * T), b = (int)(r / N), n = (int)(r - (int64_t)b * N);
+    const int t_in = t == T - 1 ? 0 : t + 1;                      // the input token this thread writes
+    const int64_t i = ((int64_t)b * T + t_in) * N + n;
+    int64_t c = cls[i];
+    float4 bx = ld4(box + 4 * i);
+    if (t_in > 0 && c < C) {
+        const int k = *step_ptr;
+        const int64_t kk = (int64_t)k + 1;
+        const uint32_t thr = ramp_steps == 0 ? thr_max
+                                             : (uint32_t)((uint64_t)thr_max * (uint64_t)(kk < ramp_steps ? kk : ramp_steps) / (uint64_t)ramp_steps);
+        if ((philox_first((uint32_t)i, (uint32_t)k, k0, k1, 1u) >> 8) < thr)
+            decode_token(rows[tid], C, c, box + 4 * i, i, k, temperature, top_k, k0, k1, 0, c, bx);
+    }
+    mix_cls[i] = c;
+    st4(mix_box + 4 * i, bx);
+}
+
+extern "C" int vlg_sched_plan(double eps_max, uint32_t* thr_host) {
+    if (!(eps_max >= 0.0 && eps_max <= 1.0) || thr_host == nullptr) return VLG_ERR_SHAPE;
+    *thr_host = (uint32_t)__builtin_floor(eps_max * 16777216.0 + 0.5);
+    return 0;
+}
+
+extern "C" int vlg_layout_mix_inputs(const float* out, int ld, const int64_t* cls, const float* box, int64_t* mix_cls,
+                                     float* mix_box, const int* step, int B, int T, int N, int n_classes, uint32_t thr_max,
+                                     int ramp_steps, float temperature, int top_k, uint64_t seed, void* stream) {
+    if (B < 1 || T < 1 || N < 1 || n_classes < 1 || n_classes + 4 > HL_MAX_OUT || ld < n_classes + 4) return VLG_ERR_SHAPE;
+    if (!(temperature >= 0.f) || !(temperature <= 3.0e38f)) return VLG_ERR_SHAPE;      // negative, inf or NaN
+    if (top_k < 0 || top_k > n_classes || thr_max > (1u << 24) || ramp_steps < 0) return VLG_ERR_SHAPE;
+    const int64_t M = (int64_t)B * N * T;
+    if (M > 0x7fffffffLL) return VLG_ERR_SHAPE;                                         // the Philox counter word is the token index
+    if (!out || !cls || !box || !mix_cls || !mix_box || !step) return VLG_ERR_SHAPE;
+    // inputs are only read and outputs only written: any overlap between the two groups, or of the two outputs, is refused
+    const void* in_p[4] = {out, cls, box, step};
+    const int64_t in_n[4] = {((M - 1) * ld + n_classes + 4) * 4, M * 8, M * 16, 4};
+    for (int i = 0; i < 4; ++i)
+        if (dec_overlap(in_p[i], in_n[i], mix_cls, M * 8) || dec_overlap(in_p[i], in_n[i], mix_box, M * 16)) return VLG_ERR_SHAPE;
+    if (dec_overlap(mix_cls, M * 8, mix_box, M * 16)) return VLG_ERR_SHAPE;
+    if (!vlg_aligned16(out) || !vlg_aligned16(box) || !vlg_aligned16(mix_box) || !vlg_aligned8(cls) || !vlg_aligned8(mix_cls) ||
+        (reinterpret_cast<uintptr_t>(step) & 3u)) return VLG_ERR_ALIGN;
+    const dim3 grid((unsigned)((M + DEC_BLOCK - 1) / DEC_BLOCK)), block(DEC_BLOCK);
+    hipLaunchKernelGGL(layout_mix_inputs_kernel, grid, block, 0, (hipStream_t)stream, out, ld, cls, box, mix_cls, mix_box, step, M,
+                       T, N, n_classes, thr_max, ramp_steps, temperature, top_k, (uint32_t)(seed & 0xffffffffu),
+                       (uint32_t)(seed >> 32));
     return vlg_last_error();
 }

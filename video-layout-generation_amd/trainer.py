@@ -44,6 +44,14 @@ the embedding and the two residual branches of every layer in training steps onl
 averaged weights stay evaluation; VLG_DROPOUT_SEED (default args.seed) seeds the stateless mask, and data-parallel rank r
 uses seed + r so that ranks draw different masks.
 
+Scheduled sampling in layout mode (off by default; csrc/decode.hip, DESIGN.md "Scheduled sampling"): args.sched_sampling /
+VLG_SCHED_SAMPLING = eps_max in [0, 1] makes every training step run an evaluation forward on the true inputs first and then
+train on inputs in which each token of a frame after the first that is not padded is, with probability eps_max, the model's
+own decoded prediction of it; targets stay the true ones.  VLG_SCHED_RAMP_STEPS (0) ramps the probability linearly over
+that many training steps, VLG_SCHED_TEMPERATURE (0 = argmax) / VLG_SCHED_TOP_K (0 = every class) decode as generation does,
+VLG_SCHED_SEED (default args.seed) seeds coins and draws, and data-parallel rank r uses seed + r.  validate(), generation
+and the averaged weights are untouched.
+
 Loss options in layout mode (all off by default; csrc/loss.hip, DESIGN.md "Loss options"): args.class_weights /
 VLG_CLASS_WEIGHTS = 20 comma-separated floats, finite and >= 0 with at least one > 0, the weight= of F.cross_entropy
 (vlg.metrics.balanced_class_weights turns the confusion matrix of VLG_VAL_METRICS=1 into such a list); args.label_smoothing /
@@ -186,6 +194,33 @@ def dropout_knobs(args) -> Dict[str, object]:
     return {"dropout": p, "dropout_seed": seed + int(getattr(args, "rank", 0) or 0)}
 
 
+def sched_knobs(args) -> Dict[str, object]:
+    """the engine's scheduled-sampling keyword arguments from args / environment (module docstring): {} with
+    args.sched_sampling / VLG_SCHED_SAMPLING unset, so an engine without the option is never handed one; else
+    {sched_sampling, sched_ramp_steps, sched_temperature, sched_top_k, sched_seed}, the seed offset by the data-parallel
+    rank.  Refuses what LayoutEngine refuses, before any engine exists."""
+    eps = getattr(args, "sched_sampling", None)
+    if eps is None:
+        eps = os.environ.get("VLG_SCHED_SAMPLING") or None
+    if eps is None:
+        return {}
+    eps = float(eps)
+    if not 0.0 <= eps <= 1.0:                           # (also refuses NaN)
+        raise ValueError("VLG_SCHED_SAMPLING must be in [0, 1], got %r" % eps)
+    ramp = _knob(args, "sched_ramp_steps", "VLG_SCHED_RAMP_STEPS", 0)
+    if not 0 <= ramp < 2 ** 31:
+        raise ValueError("VLG_SCHED_RAMP_STEPS must be in [0, 2^31), got %r" % ramp)
+    temperature = _knob_float(args, "sched_temperature", "VLG_SCHED_TEMPERATURE", 0.0)
+    top_k = _knob(args, "sched_top_k", "VLG_SCHED_TOP_K", 0)
+    if not (temperature >= 0.0 and temperature != float("inf")) or not 0 <= top_k <= N_CLASSES:
+        raise ValueError("VLG_SCHED_TEMPERATURE must be finite and >= 0, VLG_SCHED_TOP_K in [0, %d]" % N_CLASSES)
+    seed = _knob(args, "sched_seed", "VLG_SCHED_SEED", int(getattr(args, "seed", SEED)))
+    if not 0 <= seed < 2 ** 63:
+        raise ValueError("VLG_SCHED_SEED must be in [0, 2^63), got %r" % seed)
+    return {"sched_sampling": eps, "sched_ramp_steps": ramp, "sched_temperature": temperature, "sched_top_k": top_k,
+            "sched_seed": seed + int(getattr(args, "rank", 0) or 0)}
+
+
 def loss_knobs(args) -> Dict[str, object]:
     """the engine's loss-option keyword arguments from args / environment (module docstring): {} with all of them off, so an
     engine without the options is never handed one; else those that are on among {class_weights, label_smoothing,
@@ -269,7 +304,7 @@ def get_layout_engine(args, cfg: Optional[LayoutConfig] = None, engine_factory: 
                               precision=precision,
                               padded_slots=bool(_knob(args, "variable_n", "VLG_VARIABLE_N", 0)),   # fixed-N feeds hold no padded slots
                               clip_grad=knobs["clip_grad"], skip_nonfinite=knobs["skip_nonfinite"], **recipe_kwargs(knobs),
-                              **dropout_knobs(args), **clip_cache_knob(args), **loss_knobs(args))
+                              **dropout_knobs(args), **clip_cache_knob(args), **loss_knobs(args), **sched_knobs(args))
     else:
         engine = engine_factory(cfg, args)
     if knobs["lr_decay"]:                            # guarded from the start, so a checkpoint's lr and skip count are resumed
@@ -463,6 +498,8 @@ class Trainer:
         self.reducer = None
         if self.image_mode and self.dropout:
             raise ValueError("VLG_DROPOUT is a knob of the layout-token step; VLG_MODEL=gridnet has no dropout")
+        if sched_knobs(args) and self.image_mode:               # (out-of-range values raise here too)
+            raise ValueError("VLG_SCHED_SAMPLING is a knob of the layout-token step; VLG_MODEL=gridnet has no token inputs to sample")
         if loss_knobs(args) and self.image_mode:                # (out-of-range values raise here too)
             raise ValueError("VLG_CLASS_WEIGHTS / VLG_LABEL_SMOOTHING / VLG_BOX_OVERLAP are knobs of the layout-token step; "
                              "VLG_MODEL=gridnet's losses have no options")

@@ -89,7 +89,9 @@ class LayoutEngine(AdamSurface):
                  lr: float = ADAM_LR, beta1: float = ADAM_BETA1, precision: str = "fp32", padded_slots: bool = True,
                  clip_grad: float = 0.0, skip_nonfinite: bool = False, weight_decay: float = 0.0, warmup_steps: int = 0,
                  ema_decay: float = 0.0, ema_warmup: bool = False, dropout: float = 0.0, dropout_seed: int = 0,
-                 clip_cache: bool = False, class_weights=None, label_smoothing: float = 0.0, box_overlap: str = "iou"):
+                 clip_cache: bool = False, class_weights=None, label_smoothing: float = 0.0, box_overlap: str = "iou",
+                 sched_sampling: Optional[float] = None, sched_ramp_steps: int = 0, sched_temperature: float = 0.0,
+                 sched_top_k: int = 0, sched_seed: int = 0):
         """clip_grad > 0 clips the gradient to that global L2 norm (torch.nn.utils.clip_grad_norm_'s rule); skip_nonfinite
         leaves parameters, moments and step count untouched when the gradient holds inf or NaN.  Either one - or a call
         of set_lr - turns on the GUARDED optimiser step (vlg/optim.py), eager and captured alike; with both off and
@@ -127,8 +129,29 @@ class LayoutEngine(AdamSurface):
         weight of the valid targets, per rank under data parallelism); label_smoothing in [0, 1), its label_smoothing=;
         box_overlap = "giou" makes the overlap term mean(1 - GIoU), which has a gradient for boxes that do not touch.
         Fixed at construction; checkpoints do not carry them.  forward() - validation included - returns this configured
-        objective; accumulate_metrics / evaluate_rollout keep reporting the plain NLL and IoU."""
+        objective; accumulate_metrics / evaluate_rollout keep reporting the plain NLL and IoU.
+        Scheduled sampling (DESIGN.md "Scheduled sampling"; rule: include/vlg_hip.h): sched_sampling = None is off - nothing
+        allocated, no launch changed; a float eps_max in [0, 1] turns it on.  forward_backward / train_step /
+        capture_train_step then run PASS 1, the evaluation forward on the true inputs (forward()'s launches minus the loss, no
+        dropout), one launch of vlg_layout_mix_inputs, which replaces each input token of a frame t >= 1 that is not padded
+        with the model's own decoded prediction of it (class by the decoding rule of rollout() under sched_temperature /
+        sched_top_k, box = sigmoid(raw)) with probability eps_max - ramped linearly over the first sched_ramp_steps training
+        steps when that is > 0 - and PASS 2, the training step as ever on the mixed inputs and the TRUE targets; no gradient
+        flows through the replaced inputs.  Coins and draws are stateless Philox functions of (token, step) under sched_seed;
+        the step is a device counter of its own (sched_step / set_sched_step), advanced once per training forward+backward
+        as dropout's is.  sched_inputs() shows the mixed inputs of the last training step.  Everything that evaluates -
+        forward(), rollout(), evaluate_rollout(), accumulate_metrics(), ema_weights() - is untouched."""
         cfg.validate()
+        self._sched = None
+        if sched_sampling is not None:
+            eps, ramp, temp, top_k = float(sched_sampling), int(sched_ramp_steps), float(sched_temperature), int(sched_top_k)
+            if not 0.0 <= eps <= 1.0:                    # (also refuses NaN)
+                raise ValueError("sched_sampling must be None or in [0, 1], got %r" % (sched_sampling,))
+            if ramp < 0 or ramp >= 2 ** 31:
+                raise ValueError("sched_ramp_steps must be in [0, 2^31), got %r" % (sched_ramp_steps,))
+            if not (math.isfinite(temp) and temp >= 0.0) or not 0 <= top_k <= cfg.n_classes:
+                raise ValueError("sched_temperature must be finite and >= 0, sched_top_k in [0, %d]" % cfg.n_classes)
+            self._sched = (eps, ramp, temp, top_k, int(sched_seed) & 0xFFFFFFFFFFFFFFFF)
         weights, self.label_smoothing, self.box_overlap = loss_options(class_weights, label_smoothing, box_overlap, cfg.n_classes)
         self.clip_cache = bool(clip_cache)
         self.dropout = float(dropout)
@@ -164,6 +187,13 @@ class LayoutEngine(AdamSurface):
             hip.check(hip.load().vlg_dropout_plan(self.dropout, ctypes.byref(thr), ctypes.byref(scale)), "vlg_dropout_plan")
             self._drop = (thr.value, scale.value, int(dropout_seed) & 0xFFFFFFFFFFFFFFFF)
             self.drop_step = torch.zeros(1, dtype=torch.int32, device=device)
+        # scheduled sampling: (thr_max, ramp_steps, temperature, top_k, seed) for the mix kernel + its own device step counter
+        self.sched_counter = None
+        if self._sched is not None:
+            thr = ctypes.c_uint32()
+            hip.check(hip.load().vlg_sched_plan(self._sched[0], ctypes.byref(thr)), "vlg_sched_plan")
+            self._sched = (thr.value,) + self._sched[1:]
+            self.sched_counter = torch.zeros(1, dtype=torch.int32, device=device)
         self.layout, self.n_params = param_layout(cfg)
         f32 = dict(dtype=torch.float32, device=device)
         self.class_weights = None if weights is None else torch.tensor(weights, **f32)
@@ -254,6 +284,8 @@ class LayoutEngine(AdamSurface):
             sd["ema"] = self.optim.ema.cpu().clone()
         if self._drop is not None:               # (knob off: the checkpoint is what it was without the option)
             sd["dropout_step"] = self.dropout_step
+        if self._sched is not None:
+            sd["sched_step"] = self.sched_step
         return sd
 
     def load_state_dict(self, sd: Dict[str, object]) -> None:
@@ -269,6 +301,32 @@ class LayoutEngine(AdamSurface):
         self.optim.set_step(int(sd["step"]))
         if self._drop is not None and sd.get("dropout_step") is not None:
             self.set_dropout_step(int(sd["dropout_step"]))
+        if self._sched is not None and sd.get("sched_step") is not None:
+            self.set_sched_step(int(sd["sched_step"]))
+
+    @property
+    def sched_step(self) -> int:
+        """the scheduled-sampling step counter k the next training step will read (a host read: it waits for the device)"""
+        if self._sched is None:
+            raise RuntimeError("sched_step needs an engine built with sched_sampling")
+        return int(self.sched_counter.item())
+
+    def set_sched_step(self, k: int) -> None:
+        if self._sched is None:
+            raise RuntimeError("set_sched_step needs an engine built with sched_sampling")
+        if not 0 <= int(k) < 2 ** 31:
+            raise ValueError("scheduled-sampling step must be in [0, 2^31), got %r" % (k,))
+        self.sched_counter.fill_(int(k))
+
+    def sched_inputs(self) -> tuple:
+        """(slot_class (B,T,N) int64, slot_box (B,T,N,4) fp32): views of the mixed inputs the last training step's second pass read"""
+        if self._sched is None:
+            raise RuntimeError("sched_inputs needs an engine built with sched_sampling")
+        if getattr(self, "_mixed_shape", None) is None:
+            raise RuntimeError("sched_inputs shows the last training step: there has been none")
+        B, T, N = self._mixed_shape
+        M = B * T * N
+        return self.mix_cls[:M].view(B, T, N), self.mix_box[:M].view(B, T, N, BOX_DIM)
 
     @property
     def dropout_step(self) -> int:
@@ -320,6 +378,12 @@ class LayoutEngine(AdamSurface):
                 raise ValueError("dropout: %d rows do not fit the mask's 32-bit row counter" % M)
             self.ybranch = torch.empty(M, d, **f32)       # proj / ff2 output (+ bias) on its way into a dropout site
             self.ddrop = torch.empty(M, d, **f32)         # gradient of that output: select(dx) of the site's layer-norm backward
+        if self._sched is not None:
+            if M >= 2 ** 31:
+                raise ValueError("scheduled sampling: %d tokens do not fit the coin's 32-bit token counter" % M)
+            self.mix_cls = torch.empty(M, dtype=torch.int64, device=self.device)      # the second pass's inputs
+            self.mix_box = torch.empty(M, BOX_DIM, **f32)
+            self._mixed_shape = None
         self.loss_scratch = torch.zeros(lib.vlg_layout_loss_scratch(), **f32)
         # validation metrics (vlg_layout_metrics): per-block partial sums and the ticket, zero between launches
         self.metrics_scratch = torch.zeros(lib.vlg_layout_metrics_scratch(), dtype=torch.float64, device=self.device)
@@ -503,15 +567,36 @@ class LayoutEngine(AdamSurface):
         Evaluation on a dropout engine too: only forward_backward / train_step drop."""
         return self._forward(batch, padded_slots, False)
 
-    def _forward(self, batch: Dict[str, torch.Tensor], padded_slots: Optional[bool], train: bool) -> torch.Tensor:
-        cfg, d = self.cfg, self.cfg.d
+    def _predict(self, batch: Dict[str, torch.Tensor], padded_slots: Optional[bool], train: bool) -> tuple:
+        """the forward's launches up to the loss: the window through the final norm, then the head into self.out"""
         B, T, N, M = self._check_batch(batch)
         self._masked = self.padded_slots if padded_slots is None else bool(padded_slots)
         self._shape = (B, T, N, M)
         self._dropped = bool(train) and self._drop is not None and not self._on_ema    # this forward's choice; its backward follows it
-        s = self._stream()
         self._encode_window(batch, B, T, N, drop=self._dropped, final=True)
-        self._linear(self.xf, self.pw("head_w"), self.p("head_b"), self.out, M, cfg.n_out, d, EPI_BIAS)
+        self._linear(self.xf, self.pw("head_w"), self.p("head_b"), self.out, M, self.cfg.n_out, self.cfg.d, EPI_BIAS)
+        return B, T, N, M
+
+    def _mix_inputs(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """Scheduled sampling, pass 1 and the mix: the evaluation forward on the true inputs (no dropout, no loss launch), then
+        vlg_layout_mix_inputs builds the second pass's inputs from self.out.  Returns the batch the training pass runs on:
+        slot_class / slot_box are the engine's mixed buffers, targets and valid the caller's."""
+        self._not_on_ema("a scheduled-sampling training step")
+        cfg = self.cfg
+        B, T, N, M = self._predict(batch, None, False)
+        thr_max, ramp, temperature, top_k, seed = self._sched
+        self._timed("sched_mix", 0.0, "vlg_layout_mix_inputs", ptr(self.out), cfg.n_out, ptr(batch["slot_class"]), ptr(batch["slot_box"]),
+                    ptr(self.mix_cls), ptr(self.mix_box), ptr(self.sched_counter), B, T, N, cfg.n_classes, thr_max, ramp,
+                    temperature, top_k, seed, self._stream(), nbytes=4.0 * cfg.n_out * B * N * (T - 1) + 2.0 * 24 * M)
+        self._mixed_shape = (B, T, N)
+        mixed = dict(batch)
+        mixed["slot_class"], mixed["slot_box"] = self.mix_cls[:M].view(B, T, N), self.mix_box[:M].view(B, T, N, BOX_DIM)
+        return mixed
+
+    def _forward(self, batch: Dict[str, torch.Tensor], padded_slots: Optional[bool], train: bool) -> torch.Tensor:
+        cfg = self.cfg
+        B, T, N, M = self._predict(batch, padded_slots, train)
+        s = self._stream()
         targets = (ptr(self.out), cfg.n_out, ptr(batch["tgt_class"]), ptr(batch["tgt_box"]), ptr(batch["valid"]))
         outs = (ptr(self.dout), ptr(self.loss_out), ptr(self.loss_scratch), B, T, N, cfg.n_classes, SMOOTH_L1_BETA, IOU_EPS,
                 LOSS_W_REG, LOSS_W_STRUCT, LOSS_W_CE)
@@ -692,8 +777,12 @@ class LayoutEngine(AdamSurface):
         self.buckets.close(s, then=(lambda: reducer.ready("embed")) if reducer is not None else None)
 
     def forward_backward(self, batch: Dict[str, torch.Tensor], reducer=None) -> torch.Tensor:
+        if self._sched is not None:                   # scheduled sampling: pass 1 + the mix; the step below is pass 2
+            batch = self._mix_inputs(batch)
         loss = self._forward(batch, None, True)       # (a training forward: the one place dropout is applied)
         self.backward(batch, reducer)
+        if self._sched is not None:                   # the next training step flips new coins (replayed by a captured graph)
+            self._timed("sched_step", 0.0, "vlg_dropout_step_advance", ptr(self.sched_counter), self._stream(), nbytes=8.0)
         return loss
 
     def train_step(self, batch: Dict[str, torch.Tensor], reducer=None) -> torch.Tensor:
@@ -756,7 +845,7 @@ class LayoutEngine(AdamSurface):
         keep = (self.params.clone(), self.exp_avg.clone(), self.exp_avg_sq.clone(), counter.clone(), self.step_count)
         # the recipe's state moves with the two capture passes too: the average, its bf16 copy, the outputs of ext
         more = [t for t in (self.optim.ema, self.optim.ema_shadow, self.optim.guard.ext if self.optim.guard is not None else None,
-                            self.drop_step) if t is not None]
+                            self.drop_step, self.sched_counter) if t is not None]
         kept_more = [t.clone() for t in more]
         def restore():
             self.params.copy_(keep[0]); self.exp_avg.copy_(keep[1]); self.exp_avg_sq.copy_(keep[2])

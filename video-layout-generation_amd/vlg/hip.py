@@ -67,6 +67,9 @@ SIGNATURES = {
     "vlg_head_frame": (I, [P, P, P, P, P, P, I, I, I, I, I, I, F, P]),
     "vlg_layout_decode": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, c_uint64, I, P]),
     "vlg_layout_decode_append": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, I, c_uint64, I, P]),
+    "vlg_sched_plan": (I, [c_double, P]),                        # host only: (eps_max, uint32* thr_max)
+    # (out, ld, cls, box, mix_cls, mix_box, step, B, T, N, C, thr_max, ramp_steps, temperature, top_k, seed, stream)
+    "vlg_layout_mix_inputs": (I, [P, I, P, P, P, P, P, I, I, I, I, c_uint32, I, F, I, c_uint64, P]),
     "vlg_layout_metrics_counts": (I, [I]),
     "vlg_layout_metrics_sums": (I, [I]),
     "vlg_layout_metrics_scratch": (I, []),
