@@ -344,6 +344,36 @@ int vlg_attention_clip_step(const float* qkv, const float* valid, float* o,
 int vlg_attention_clip_step_bf16(const vlg_bf16* qkv, const float* valid, vlg_bf16* o,
                                  int64_t B, int T, int N, int d, int p, int64_t ldo, void* stream);
 
+/* ------------------------------------------------------------------ frame attention (option attention = "factored")
+ * Softmax attention INSIDE a frame, per (clip, head): token (t, n) attends to the tokens (t, m) of its own frame with
+ * valid[(b*T + t)*N + m] > 0 (valid may be NULL: all), and to itself - the per-clip rule for padded slots, unchanged: a
+ * padded slot is never a key except its own.  Not causal in n; nothing crosses frames.  SELF-ORACLE: clip_attention of the
+ * CPU specification on the B*T one-frame clips.  The odd layers of attention = "factored" (even layers: vlg_attention_fwd /
+ * _bwd / _step, causal along time per slot), so all mixing along time stays causal.
+ * The entries are the per-clip ones with that visibility rule: the same buffers, row order, scale, head layout, lse and
+ * delta layouts (log2 domain), fp64 score path of the fp32 step, bf16 rounding points, one owner per gradient element (no
+ * atomics; a clip's bits depend neither on B nor on the run), shape contract (T*N a multiple of 32) and refusals - the
+ * argument lists and the host front end are shared, and a refused call enqueues nothing.  A token that sees only itself
+ * returns its V row bit for bit.
+ * What the frame-local walk reads: a query-owner block the key tiles from the first token of its first frame to the last
+ * token of its last frame, a key-owner block the query tiles of its own frames.  vlg_attention_frame_step reads the rows of
+ * position p ALONE - q, k and v of the N tokens (p, n) - and valid[:, p]: rows of every other position, EARLIER ones
+ * included, and their valid entries may hold anything, NaN included.  It needs no cache: generation calls it on the q k v
+ * rows the projection just wrote at position p. */
+int vlg_attention_frame_fwd(const float* qkv, const float* valid, float* out, float* lse,
+                            int64_t B, int T, int N, int d, void* stream);
+int vlg_attention_frame_bwd(const float* qkv, const float* valid, const float* out, const float* dout, const float* lse,
+                            float* delta, float* dqkv, int64_t B, int T, int N, int d, void* stream);
+int vlg_attention_frame_fwd_bf16(const vlg_bf16* qkv, const float* valid, vlg_bf16* out, float* lse,
+                                 int64_t B, int T, int N, int d, void* stream);
+int vlg_attention_frame_bwd_bf16(const vlg_bf16* qkv, const float* valid, const vlg_bf16* out, const vlg_bf16* dout,
+                                 const float* lse, float* delta, vlg_bf16* dqkv,
+                                 int64_t B, int T, int N, int d, void* stream);
+int vlg_attention_frame_step(const float* qkv, const float* valid, float* o,
+                             int64_t B, int T, int N, int d, int p, int64_t ldo, void* stream);
+int vlg_attention_frame_step_bf16(const vlg_bf16* qkv, const float* valid, vlg_bf16* o,
+                                  int64_t B, int T, int N, int d, int p, int64_t ldo, void* stream);
+
 /* ------------------------------------------------------------------ generation (csrc/decode.hip)
  * The forward-only tail of an autoregressive rollout (reference src/trainer.py:453-476 rolls its pixel model out the same
  * way: predict, argmax, append, slide).  SELF-ORACLE (tests/decode_ref.py); rule and rooflines: DESIGN.md, "Generation".

@@ -5,7 +5,7 @@ One child process per tree and round, alternating A B A B ..., never two at a ti
 tree, rolls out (32,16,64), d = 256, 4 layers from a full T-frame prompt in fp32 and bf16 and reports ms per generated
 frame (host wall-clock around calls that end with the frames on the CPU, as tools/rollout_bench.py measures).  Prints per
 tree and precision the median of the rounds with their spread.  A child that fails ends the run: nothing is started after it.
-VLG_ATTENTION=clip in the environment rolls out with per-clip attention (default: per-slot)."""
+VLG_ATTENTION=clip | factored in the environment rolls out with per-clip / factored attention (default: per-slot)."""
 import json
 import os
 import subprocess

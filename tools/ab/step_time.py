@@ -1,5 +1,5 @@
 """Whole-step time of the in-tree engine with whatever libvlg VLG_HIP_LIB names (one process per variant, same box);
-VLG_ATTENTION=clip times the step with per-clip attention."""
+VLG_ATTENTION=clip | factored times the step with per-clip / factored attention, VLG_PRECISION=bf16 in that mode."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "video-layout-generation_amd")]
@@ -9,7 +9,7 @@ from vlg.engine import LayoutEngine
 from vlg.spec import LayoutConfig, SEED
 dev = torch.device("cuda:0")
 cfg = LayoutConfig(B=32, T=16, N=64, d=256, n_layers=4, attention=os.environ.get("VLG_ATTENTION", "slot"))
-eng = LayoutEngine(cfg, dev, seed=SEED)
+eng = LayoutEngine(cfg, dev, seed=SEED, precision=os.environ.get("VLG_PRECISION", "fp32"))
 batch = to_device(synthetic_clips(cfg.B, cfg.T, cfg.N, seed=SEED), dev)
 res = []
 for rnd in range(6):

@@ -3,7 +3,7 @@
 launches + vlg_head_last_frame + vlg_layout_decode, no host wait inside the loop) against the host loop it replaced
 (restated here from forward() + outputs_btn(): training forward with the loss on dummy targets, argmax / sigmoid / cat in
 torch, two copies to the CPU per frame), alternately in one process on the same prompt, fp32 and bf16.
-    python tools/rollout_bench.py [B] [T] [N] [d] [--layers L] [--steps S] [--attention slot|clip] [--prompt P] [--no-cache]
+    python tools/rollout_bench.py [B] [T] [N] [d] [--layers L] [--steps S] [--attention slot|clip|factored] [--prompt P] [--no-cache]
                                   [--clip-cache]
 --prompt P (1 <= P < T) measures the short-prompt rollout instead: the prompt pass on its own (steps = 1), and --steps
 frames (default T - P: the history grows to the window) with the cached grow step and with the re-encoding one

@@ -60,6 +60,27 @@
 // the matrix pipe waits for; not kept.
 // bf16, measured at (32, 16, 64), d = 256 (tools/clip_attn_bench.py --bf16, alternated with the fp32 kernels): forward 54 us = 336
 // TFLOP/s, backward 155 us = 295 TFLOP/s algorithmic (0.13 / 0.12 of the 2.5 PF bf16 peak; fp32 in the same run 185 / 643 us).
+//
+// FRAME-LOCAL INSTANTIATIONS (option attention = "factored", its odd layers; vlg_attention_frame_*): the four templates take a
+// compile-time flag FRAME.  false is the block-causal code above, unchanged.  true is attention INSIDE a frame - the same
+// walk, the same policies, lse / delta layouts and rounding points, with three rules exchanged (stated once in Python and
+// checked by brute force: tests/frame_walk.py, tests/test_frame_walk_cpu.py):
+//   visibility      FRAME_VISIBLE: the key's frame code EQUALS the query's frame, or the key is the query itself.  A padded
+//                   slot's code carries CINVALID as before, so it equals no frame: never a key except its own.
+//   tile ranges     from the frames alone.  A query-owner block walks the key tiles from the one holding the first token of
+//                   its first frame (frame_first_tile) to the one holding the last token of its last frame (clip_key_tiles,
+//                   as before); a key-owner block walks the query tiles of exactly that range of ITS frames; the step walks
+//                   the tiles of frame p and stages zeros for whatever they hold of other frames - it loads no row and no
+//                   valid entry of another position, earlier ones included.
+//   classification  FRAME_TILE_HIDDEN: none of the tile's frames is among the wave's; FRAME_TILE_ELEMENTWISE: valid is given,
+//                   or the tile or the wave's own 32 tokens hold a frame boundary; whole otherwise (then both are one frame).
+// Work per (clip, head): N^2 T pairs.  Every block of a frame-local launch walks the tiles of its own one or two frames, so
+// there is no longest block to deal first: the launch keeps the grid and the block -> token map of the block-causal one
+// ((clip, head) fastest, so the blocks resident together read neighbouring rows), and that order decides nothing.
+// Measured at (32, 16, 64), d = 256 (tools/clip_attn_bench.py --frame --bf16): forward 46 us fp32 / 17 us bf16, backward 158 /
+// 57 us, step 19 / 5.4 us at every p.  At N^2 T pairs these are bandwidth kernels with a short matrix body (the forward's
+// ideal is 14 us of fp32 MFMA, 21 us of HBM): a block stages four tiles and each wave computes two, too short a walk for the
+// prefetch to hide anything - the forward moves its bytes at 2.9 TB/s (DESIGN.md "Factored space-time attention").
 #include <initializer_list>
 #include "common.h"
 #include "gemm_tile.h"
@@ -85,6 +106,9 @@ __device__ __forceinline__ int clip_frame_code(const float* __restrict__ valid, 
 }
 // (macros, not functions: an inlined bool function compiles the || differently, and the fp32 kernels' code stays as tuned)
 #define CLIP_VISIBLE(fr, tq, s_reg, s_own) ((fr) <= (tq) || (s_reg) == (s_own))
+// frame-local: the key's frame code IS the query's frame (tests/frame_walk.py: visible).  FRAME is a template constant
+#define FRAME_VISIBLE(fr, tq, s_reg, s_own) ((fr) == (tq) || (s_reg) == (s_own))
+#define CLIP_SEES(FRAME, fr, tq, s_reg, s_own) ((FRAME) ? FRAME_VISIBLE(fr, tq, s_reg, s_own) : CLIP_VISIBLE(fr, tq, s_reg, s_own))
 // register r of a 32x32 C/D tile, lane half h  ->  its row
 __device__ __forceinline__ int clip_crow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
@@ -108,6 +132,13 @@ __device__ __forceinline__ int clip_first_query_tile(int kb0, int N) { return ((
 #define CLIP_TILE_ELEMENTWISE(valid, k0, N, tq_min) ((valid) != nullptr || ((k0) + CKT - 1) / (N) > (tq_min))
 // ... and of a wave's 32 keys (first frame tk_min) against the 32-query tile at q0: hidden if every query is in an earlier frame
 #define CLIP_QUERY_TILE_HIDDEN(q0, N, tk_min) (((q0) + CKT - 1) / (N) < (tk_min))
+// Frame-local (tests/frame_walk.py: first_tile, end_tile, classify).  The first tile of an owner block's walk - query owners'
+// key tiles and key owners' query tiles alike - holds the first token of the block's first frame; the walk ends with
+// clip_key_tiles.  A 32-token tile at k0 against a wave whose 32 owner tokens lie in frames t_min .. t_max:
+__device__ __forceinline__ int frame_first_tile(int s0, int N) { return ((s0 / N) * N) / CKT; }
+#define FRAME_TILE_HIDDEN(k0, N, t_min, t_max) (((k0) + CKT - 1) / (N) < (t_min) || (k0) / (N) > (t_max))
+#define FRAME_TILE_ELEMENTWISE(valid, k0, N, t_min, t_max)                                                                \
+    ((valid) != nullptr || (k0) / (N) != ((k0) + CKT - 1) / (N) || (t_min) != (t_max))
 // register r of a 32x32 C/D tile, lane half h  ->  row (r & 3) + 8 (r >> 2) + 4 h: the four registers 4g .. 4g+3 are rows
 // 8g + 4h .. + 3, i.e. ONE float4 at offset 8g + 4h of a 32-entry per-row table
 __device__ __forceinline__ void rows16(float (&v)[16], const float* tab, int h) {
@@ -400,7 +431,8 @@ struct ClipBf16 {
 // One key tile of a query owner's walk, staged as Ks (row-major K), Vt (transposed V) and kfr (the keys' frame codes): the
 // scores, the mask, the online softmax and O += P . V.  The forward and the generation step share it.  It reads the walk's
 // names from the scope it stands in: qf (the wave's scored Q fragment), valid, k0 (the tile's first key token), N, the
-// lane's query token sq and its frame tq, the wave's first query frame tq_min, the running m_run / l_run / o, turn, w, l31, h.
+// lane's query token sq and its frame tq, the wave's first and last query frame tq_min / tq_max and the template's FRAME
+// (tq_max is read by the frame-local classification alone), the running m_run / l_run / o, turn, w, l31, h.
 // (a macro for the reason CLIP_VISIBLE is one: the forward's code stays as tuned)
 // SCORES declares and fills st, the tile's log2-domain scores; PFIX is appended to every probability exp2(st - m): the forward
 // takes the MFMA scores and no fix, the fp32 generation step exact scores with their rounding remainder (ClipF32::step_scores).
@@ -410,11 +442,11 @@ struct ClipBf16 {
 #define CLIP_FWD_TILE(P, Ks, Vt, kfr, SCORES, PFIX)                                                                      \
     {                                                                                                                    \
         SCORES                                                                                                           \
-        if (CLIP_TILE_ELEMENTWISE(valid, k0, N, tq_min)) {                                                               \
+        if (FRAME ? FRAME_TILE_ELEMENTWISE(valid, k0, N, tq_min, tq_max) : CLIP_TILE_ELEMENTWISE(valid, k0, N, tq_min)) {  \
             int fr[16];                                                                                                  \
             rows16i(fr, kfr, h);                                                                                         \
             _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                             \
-                st[r] = CLIP_VISIBLE(fr[r], tq, k0 + clip_crow(r, h), sq) ? st[r] : -INFINITY;                           \
+                st[r] = CLIP_SEES(FRAME, fr[r], tq, k0 + clip_crow(r, h), sq) ? st[r] : -INFINITY;                       \
             }                                                                                                            \
         }                                                                                                                \
         float tmax = st[0];                                                                                              \
@@ -431,7 +463,7 @@ struct ClipBf16 {
         if (__any(alpha != 1.0f)) P::rescale(turn, o, alpha, w, l31, h);      /* O by its query's factor */              \
         P::contract32(o, p, Vt, l31, h);                             /* O[query][dim] += P[query][key] V[key][dim] */    \
     }
-template <typename P>
+template <typename P, bool FRAME>
 __global__ __launch_bounds__(256, 3) void attn_clip_fwd_kernel(const typename P::elem* __restrict__ qkv, const float* __restrict__ valid,
                                                             typename P::elem* __restrict__ out, float* __restrict__ lse, int T, int N, int d) {
     __shared__ __attribute__((aligned(16))) typename P::elem Ks[CKT * P::LDR];
@@ -455,6 +487,7 @@ __global__ __launch_bounds__(256, 3) void attn_clip_fwd_kernel(const typename P:
     const int64_t qrow = wact ? clip_row(b, sq, T, N) : 0;
     typename P::Frag qf;
     if (wact) P::frag_load_scored(qf, qkv + qrow * ld + hh * CHD + 32 * h);
+    const int jfirst = FRAME ? frame_first_tile(q0, N) : 0;          // frame-local: from the block's first frame on
     const int ntiles = clip_key_tiles(q0, nq, N, S);
     const int tok = tid >> 3, c = tid & 7;
     auto tile_load = [&](int j, typename P::Stage& kn, typename P::Stage& vn, int& fr) __attribute__((always_inline)) {
@@ -466,12 +499,12 @@ __global__ __launch_bounds__(256, 3) void attn_clip_fwd_kernel(const typename P:
     };
     typename P::Stage kn, vn;
     int frn;
-    tile_load(0, kn, vn, frn);
+    tile_load(jfirst, kn, vn, frn);
     float m_run = -INFINITY, l_run = 0.f;
     f32x16 o[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { o[0][r] = 0.f; o[1][r] = 0.f; }
-    for (int j = 0; j < ntiles; ++j) {
+    for (int j = jfirst; j < ntiles; ++j) {
         __syncthreads();                                             // the previous tile is consumed
         P::stage_rows(Ks, tok, c, kn);
         P::stage_transposed(Vt, tok, c, vn);
@@ -479,7 +512,7 @@ __global__ __launch_bounds__(256, 3) void attn_clip_fwd_kernel(const typename P:
         __syncthreads();
         if (j + 1 < ntiles) tile_load(j + 1, kn, vn, frn);           // in flight under this tile's MFMAs
         const int k0 = j * CKT;
-        if (!wact || CLIP_TILE_HIDDEN(k0, N, tq_max)) continue;
+        if (!wact || (FRAME ? FRAME_TILE_HIDDEN(k0, N, tq_min, tq_max) : CLIP_TILE_HIDDEN(k0, N, tq_max))) continue;
         CLIP_FWD_TILE(P, Ks, Vt, kfr, CLIP_SCORES_MFMA(P, Ks), )
     }
     if (!wact) return;
@@ -500,13 +533,15 @@ __global__ __launch_bounds__(256, 3) void attn_clip_fwd_kernel(const typename P:
 // block's unscaled queries), handed to the shared softmax as the nearest fp32 value and a remainder that corrects P.
 // Tokens from (pos + 1) N on - the tail of the last key tile - belong to later frames: their rows and their valid are NOT
 // read (they may hold NaN); the images get zeros and a frame code no query sees, so P = 0 meets V = 0.
+// Frame-local (FRAME): the keys are the tokens of frame pos alone, kbeg <= s < kend - the walk starts at the tile holding
+// kbeg, and what the first and last tile hold of OTHER frames, earlier ones included, is treated as the tail above is.
 template <typename P>
 struct ClipStepTiles {
     typename P::elem Ks[CKT * P::LDR];
     typename P::elem Vt[CHD * P::LDT];
     int kfr[CKT];
 };
-template <typename P>
+template <typename P, bool FRAME>
 __global__ __launch_bounds__(256, P::STEP_EXACT ? 1 : 2) void attn_clip_step_kernel(const typename P::elem* __restrict__ qkv, const float* __restrict__ valid,
                                                              typename P::elem* __restrict__ out, int T, int N, int d, int pos,
                                                              int64_t ldo) {
@@ -524,7 +559,7 @@ __global__ __launch_bounds__(256, P::STEP_EXACT ? 1 : 2) void attn_clip_step_ker
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l31 = lane & 31, h = lane >> 5;
     const int nlive = N - n0 < CKT ? N - n0 : CKT;
     const int64_t ld = 3 * (int64_t)d;
-    const int tq = pos, tq_min = pos;
+    const int tq = pos, tq_min = pos, tq_max = pos;
     const int sq = pos * N + n0 + (l31 < nlive ? l31 : nlive - 1);
     typename P::Frag qf;
     P::frag_load_scored(qf, qkv + clip_row(b, sq, T, N) * ld + hh * CHD + 32 * h);
@@ -535,8 +570,10 @@ __global__ __launch_bounds__(256, P::STEP_EXACT ? 1 : 2) void attn_clip_step_ker
         P::stage_rows(Qs, qt, tid & 7, P::stage_load(qkv + clip_row(b, sr, T, N) * ld + hh * CHD, tid & 7));
     }
     const int kend = (pos + 1) * N;                                  // the keys: tokens s < kend
-    const int ntiles = (kend + CKT - 1) / CKT;
-    const int jlo = (w * ntiles) / 4, jhi = ((w + 1) * ntiles) / 4;  // this wave's tiles; at most (ntiles + 3) / 4 of them
+    const int kbeg = FRAME ? pos * N : 0;                            // ... frame-local: kbeg <= s
+    const int jt0 = FRAME ? kbeg / CKT : 0;                          // the first tile that holds a key
+    const int ntiles = (kend + CKT - 1) / CKT - jt0;
+    const int jlo = jt0 + (w * ntiles) / 4, jhi = jt0 + ((w + 1) * ntiles) / 4;  // this wave's tiles; at most (ntiles + 3) / 4 of them
     typename P::elem* Ks = tiles[w].Ks;
     typename P::elem* Vt = tiles[w].Vt;
     int* kfr = tiles[w].kfr;
@@ -550,7 +587,7 @@ __global__ __launch_bounds__(256, P::STEP_EXACT ? 1 : 2) void attn_clip_step_ker
             kn[i] = P::stage_zero();
             vn[i] = P::stage_zero();
             frn[i] = CINVALID + T;
-            if (sk < kend) {
+            if (sk < kend && (!FRAME || sk >= kbeg)) {
                 const typename P::elem* p = qkv + clip_row(b, sk, T, N) * ld + hh * CHD;
                 kn[i] = P::stage_load(p + d, c);
                 vn[i] = P::stage_load(p + 2 * d, c);
@@ -558,7 +595,7 @@ __global__ __launch_bounds__(256, P::STEP_EXACT ? 1 : 2) void attn_clip_step_ker
             }
         }
     };
-    tile_load(jlo < jhi ? jlo : ntiles);                             // (no tile: zeros, never staged)
+    tile_load(jlo < jhi ? jlo : jt0 + ntiles);                       // (no tile: zeros, never staged)
     float m_run = -INFINITY, l_run = 0.f;
     f32x16 o[2];
 #pragma unroll
@@ -613,7 +650,7 @@ __global__ __launch_bounds__(256, P::STEP_EXACT ? 1 : 2) void attn_clip_step_ker
 }
 
 // ------------------------------------------------------------------------------------------- backward, query owner (dQ)
-template <typename P>
+template <typename P, bool FRAME>
 __global__ __launch_bounds__(256, P::DQ_WAVES) void attn_clip_dq_kernel(const typename P::elem* __restrict__ qkv,
                                                                         const float* __restrict__ valid,
                                                                         const typename P::elem* __restrict__ out,
@@ -656,6 +693,7 @@ __global__ __launch_bounds__(256, P::DQ_WAVES) void attn_clip_dq_kernel(const ty
         lse_q = lse[li];
         if (h == 0) delta[li] = del_q;                               // the key-owner kernel reads it
     }
+    const int jfirst = FRAME ? frame_first_tile(q0, N) : 0;
     const int ntiles = clip_key_tiles(q0, nq, N, S);
     const int tok = tid >> 3, c = tid & 7;
     auto tile_load = [&](int j, typename P::Stage& kn, typename P::Stage& vn, int& fr) __attribute__((always_inline)) {
@@ -667,11 +705,11 @@ __global__ __launch_bounds__(256, P::DQ_WAVES) void attn_clip_dq_kernel(const ty
     };
     typename P::Stage kn, vn;
     int frn;
-    tile_load(0, kn, vn, frn);
+    tile_load(jfirst, kn, vn, frn);
     f32x16 dq[2];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { dq[0][r] = 0.f; dq[1][r] = 0.f; }
-    for (int j = 0; j < ntiles; ++j) {
+    for (int j = jfirst; j < ntiles; ++j) {
         __syncthreads();
         P::stage_rows(Ks, tok, c, kn);
         P::stage_transposed(Kt, tok, c, kn);
@@ -680,19 +718,19 @@ __global__ __launch_bounds__(256, P::DQ_WAVES) void attn_clip_dq_kernel(const ty
         __syncthreads();
         if (j + 1 < ntiles) tile_load(j + 1, kn, vn, frn);
         const int k0 = j * CKT;
-        if (!wact || CLIP_TILE_HIDDEN(k0, N, tq_max)) continue;
+        if (!wact || (FRAME ? FRAME_TILE_HIDDEN(k0, N, tq_min, tq_max) : CLIP_TILE_HIDDEN(k0, N, tq_max))) continue;
         float ds[16];
         {
             const f32x16 st = P::dot64(Ks, l31, h, qf);              // S^T
 #pragma unroll
             for (int r = 0; r < 16; ++r) ds[r] = __builtin_amdgcn_exp2f(P::log2_score(st[r]) - lse_q);      // P^T
         }
-        if (CLIP_TILE_ELEMENTWISE(valid, k0, N, tq_min)) {
+        if (FRAME ? FRAME_TILE_ELEMENTWISE(valid, k0, N, tq_min, tq_max) : CLIP_TILE_ELEMENTWISE(valid, k0, N, tq_min)) {
             int fr[16];
             rows16i(fr, kfr, h);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                ds[r] = CLIP_VISIBLE(fr[r], tq, k0 + clip_crow(r, h), sq) ? ds[r] : 0.f;
+                ds[r] = CLIP_SEES(FRAME, fr[r], tq, k0 + clip_crow(r, h), sq) ? ds[r] : 0.f;
             }
         }
         {
@@ -709,7 +747,7 @@ __global__ __launch_bounds__(256, P::DQ_WAVES) void attn_clip_dq_kernel(const ty
 // --------------------------------------------------------------------------------------- backward, key owner (dK, dV)
 // S = Q . K^T and dP = dO . V^T with the key on the lane and the tile's queries on registers: lse, delta and the frame of a
 // query come from 32-entry tables staged with the tile
-template <typename P>
+template <typename P, bool FRAME>
 __global__ __launch_bounds__(256, 2) void attn_clip_dkv_kernel(const typename P::elem* __restrict__ qkv, const float* __restrict__ valid,
                                                             const typename P::elem* __restrict__ dout, const float* __restrict__ lse,
                                                             const float* __restrict__ delta, typename P::elem* __restrict__ dqkv,
@@ -733,7 +771,7 @@ __global__ __launch_bounds__(256, 2) void attn_clip_dkv_kernel(const typename P:
     P::own_rows(rows, b, kb0, nk, T, N);
     const bool wact = 32 * w < nk;
     const int sk = kb0 + 32 * w + l31;
-    const int tk_min = (kb0 + 32 * w) / N;
+    const int tk_min = (kb0 + 32 * w) / N, tk_max = wact ? (kb0 + 32 * w + 31) / N : -1;    // (tk_max: frame-local alone)
     const int64_t krow = wact ? clip_row(b, sk, T, N) : 0;
     int kfr_own = 0;                                                 // this lane's key: frame (+ CINVALID if padded)
     typename P::Frag kf, vf;
@@ -742,8 +780,8 @@ __global__ __launch_bounds__(256, 2) void attn_clip_dkv_kernel(const typename P:
         P::frag_load(kf, qkv + krow * ld + d + hh * CHD + 32 * h);   // the scale rides on the Q rows (stage_rows_scored)
         P::frag_load(vf, qkv + krow * ld + 2 * d + hh * CHD + 32 * h);
     }
-    const int jfirst = clip_first_query_tile(kb0, N);
-    const int ntiles = S / CKT;
+    const int jfirst = clip_first_query_tile(kb0, N);                // (= frame_first_tile: the block's first frame, either way)
+    const int ntiles = FRAME ? clip_key_tiles(kb0, nk, N, S) : S / CKT;     // frame-local: through the block's last frame
     const int tok = tid >> 3, c = tid & 7;
     const int64_t lbase = (b * heads + hh) * (int64_t)S;
     auto tile_load = [&](int j, typename P::Stage& qn, typename P::Stage& gn, float& ls, float& dl, int& fr)
@@ -773,7 +811,7 @@ __global__ __launch_bounds__(256, 2) void attn_clip_dkv_kernel(const typename P:
         __syncthreads();
         if (j + 1 < ntiles) tile_load(j + 1, qn, gn, lsn, dln, frn);
         const int q0 = j * CKT;
-        if (!wact || CLIP_QUERY_TILE_HIDDEN(q0, N, tk_min)) continue;
+        if (!wact || (FRAME ? FRAME_TILE_HIDDEN(q0, N, tk_min, tk_max) : CLIP_QUERY_TILE_HIDDEN(q0, N, tk_min))) continue;
         float p[16], ds[16];
         {
             const f32x16 s = P::dot64(Qs, l31, h, kf);               // S[query (r, h)][key l31]
@@ -784,7 +822,7 @@ __global__ __launch_bounds__(256, 2) void attn_clip_dkv_kernel(const typename P:
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int query = q0 + clip_crow(r, h);
-                const bool ok = CLIP_VISIBLE(kfr_own, fr[r], query, sk);
+                const bool ok = CLIP_SEES(FRAME, kfr_own, fr[r], query, sk);
                 p[r] = ok ? __builtin_amdgcn_exp2f(P::log2_score(s[r]) - ls[r]) : 0.f;
             }
         }
@@ -827,28 +865,28 @@ static dim3 clip_grid(int64_t B, int T, int N, int d) {
     return dim3((unsigned)(B * (d / CHD)), (unsigned)((T * N + CQB - 1) / CQB));
 }
 
-template <typename P>
+template <typename P, bool FRAME>
 static int clip_fwd(const typename P::elem* qkv, const float* valid, typename P::elem* out, float* lse, int64_t B, int T, int N,
                     int d, void* stream) {
     if (const int rc = clip_args(B, T, N, d, {qkv, out}, {lse})) return rc;
-    hipLaunchKernelGGL(attn_clip_fwd_kernel<P>, clip_grid(B, T, N, d), dim3(256), 0, (hipStream_t)stream, qkv, valid, out, lse,
+    hipLaunchKernelGGL((attn_clip_fwd_kernel<P, FRAME>), clip_grid(B, T, N, d), dim3(256), 0, (hipStream_t)stream, qkv, valid, out, lse,
                        T, N, d);
     return vlg_last_error();
 }
-template <typename P>
+template <typename P, bool FRAME>
 static int clip_bwd(const typename P::elem* qkv, const float* valid, const typename P::elem* out, const typename P::elem* dout,
                     const float* lse, float* delta, typename P::elem* dqkv, int64_t B, int T, int N, int d, void* stream) {
     if (const int rc = clip_args(B, T, N, d, {qkv, out, dout, dqkv}, {lse, delta})) return rc;
     const dim3 grid = clip_grid(B, T, N, d);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(attn_clip_dq_kernel<P>, grid, dim3(256), 0, s, qkv, valid, out, dout, lse, delta, dqkv, T, N, d);
-    hipLaunchKernelGGL(attn_clip_dkv_kernel<P>, grid, dim3(256), 0, s, qkv, valid, dout, lse, delta, dqkv, T, N, d);
+    hipLaunchKernelGGL((attn_clip_dq_kernel<P, FRAME>), grid, dim3(256), 0, s, qkv, valid, out, dout, lse, delta, dqkv, T, N, d);
+    hipLaunchKernelGGL((attn_clip_dkv_kernel<P, FRAME>), grid, dim3(256), 0, s, qkv, valid, dout, lse, delta, dqkv, T, N, d);
     return vlg_last_error();
 }
 
 // one block per (clip, head) x 32 queries of frame p.  The pointers: 16 bytes fp32, 8 bytes bf16 (its stores are 8 bytes wide,
 // so its rows must keep that: ldo a multiple of 4 elements)
-template <typename P>
+template <typename P, bool FRAME>
 static int clip_step(const typename P::elem* qkv, const float* valid, typename P::elem* o, int64_t B, int T, int N, int d, int p,
                      int64_t ldo, void* stream) {
     if (const int rc = clip_check(B, T, N, d)) return rc;
@@ -857,34 +895,68 @@ static int clip_step(const typename P::elem* qkv, const float* valid, typename P
     for (const void* t : {(const void*)qkv, (const void*)o})
         if (t == nullptr || !(wide ? vlg_aligned16(t) : vlg_aligned8(t))) return VLG_ERR_ALIGN;
     if (!wide && (ldo % 4) != 0) return VLG_ERR_ALIGN;
-    hipLaunchKernelGGL(attn_clip_step_kernel<P>, dim3((unsigned)(B * (d / CHD)), (unsigned)((N + CKT - 1) / CKT)), dim3(256), 0,
+    hipLaunchKernelGGL((attn_clip_step_kernel<P, FRAME>), dim3((unsigned)(B * (d / CHD)), (unsigned)((N + CKT - 1) / CKT)), dim3(256), 0,
                        (hipStream_t)stream, qkv, valid, o, T, N, d, p, ldo);
     return vlg_last_error();
 }
 
+// This file is compiled twice: as itself it instantiates the block-causal kernels, and through attention_frame.hip
+// (VLG_ATTENTION_FRAME_TU) the frame-local ones.  Two translation units, because the instantiations of one unit share the
+// module-wide lowering of their LDS variables: with the frame-local key-owner kernel beside it, the block-causal one came
+// out with a different prologue.  Apart, the block-causal code objects are instruction for instruction what they were.
+#ifndef VLG_ATTENTION_FRAME_TU
 extern "C" int vlg_attention_clip_step(const float* qkv, const float* valid, float* o, int64_t B, int T, int N, int d, int p,
                                        int64_t ldo, void* stream) {
-    return clip_step<ClipF32>(qkv, valid, o, B, T, N, d, p, ldo, stream);
+    return clip_step<ClipF32, false>(qkv, valid, o, B, T, N, d, p, ldo, stream);
 }
 extern "C" int vlg_attention_clip_step_bf16(const vlg_bf16* qkv, const float* valid, vlg_bf16* o, int64_t B, int T, int N, int d,
                                             int p, int64_t ldo, void* stream) {
-    return clip_step<ClipBf16>(reinterpret_cast<const bf16_t*>(qkv), valid, reinterpret_cast<bf16_t*>(o), B, T, N, d, p, ldo, stream);
+    return clip_step<ClipBf16, false>(reinterpret_cast<const bf16_t*>(qkv), valid, reinterpret_cast<bf16_t*>(o), B, T, N, d, p, ldo, stream);
 }
 extern "C" int vlg_attention_clip_fwd(const float* qkv, const float* valid, float* out, float* lse, int64_t B, int T, int N,
                                       int d, void* stream) {
-    return clip_fwd<ClipF32>(qkv, valid, out, lse, B, T, N, d, stream);
+    return clip_fwd<ClipF32, false>(qkv, valid, out, lse, B, T, N, d, stream);
 }
 extern "C" int vlg_attention_clip_bwd(const float* qkv, const float* valid, const float* out, const float* dout,
                                       const float* lse, float* delta, float* dqkv, int64_t B, int T, int N, int d, void* stream) {
-    return clip_bwd<ClipF32>(qkv, valid, out, dout, lse, delta, dqkv, B, T, N, d, stream);
+    return clip_bwd<ClipF32, false>(qkv, valid, out, dout, lse, delta, dqkv, B, T, N, d, stream);
 }
 extern "C" int vlg_attention_clip_fwd_bf16(const vlg_bf16* qkv, const float* valid, vlg_bf16* out, float* lse, int64_t B, int T,
                                            int N, int d, void* stream) {
-    return clip_fwd<ClipBf16>(reinterpret_cast<const bf16_t*>(qkv), valid, reinterpret_cast<bf16_t*>(out), lse, B, T, N, d, stream);
+    return clip_fwd<ClipBf16, false>(reinterpret_cast<const bf16_t*>(qkv), valid, reinterpret_cast<bf16_t*>(out), lse, B, T, N, d, stream);
 }
 extern "C" int vlg_attention_clip_bwd_bf16(const vlg_bf16* qkv, const float* valid, const vlg_bf16* out, const vlg_bf16* dout,
                                            const float* lse, float* delta, vlg_bf16* dqkv, int64_t B, int T, int N, int d,
                                            void* stream) {
-    return clip_bwd<ClipBf16>(reinterpret_cast<const bf16_t*>(qkv), valid, reinterpret_cast<const bf16_t*>(out),
+    return clip_bwd<ClipBf16, false>(reinterpret_cast<const bf16_t*>(qkv), valid, reinterpret_cast<const bf16_t*>(out),
                               reinterpret_cast<const bf16_t*>(dout), lse, delta, reinterpret_cast<bf16_t*>(dqkv), B, T, N, d, stream);
 }
+#else
+// frame-local attention (attention = "factored", odd layers): the argument lists and the host front end of the entries above
+extern "C" int vlg_attention_frame_step(const float* qkv, const float* valid, float* o, int64_t B, int T, int N, int d, int p,
+                                       int64_t ldo, void* stream) {
+    return clip_step<ClipF32, true>(qkv, valid, o, B, T, N, d, p, ldo, stream);
+}
+extern "C" int vlg_attention_frame_step_bf16(const vlg_bf16* qkv, const float* valid, vlg_bf16* o, int64_t B, int T, int N, int d,
+                                            int p, int64_t ldo, void* stream) {
+    return clip_step<ClipBf16, true>(reinterpret_cast<const bf16_t*>(qkv), valid, reinterpret_cast<bf16_t*>(o), B, T, N, d, p, ldo, stream);
+}
+extern "C" int vlg_attention_frame_fwd(const float* qkv, const float* valid, float* out, float* lse, int64_t B, int T, int N,
+                                      int d, void* stream) {
+    return clip_fwd<ClipF32, true>(qkv, valid, out, lse, B, T, N, d, stream);
+}
+extern "C" int vlg_attention_frame_bwd(const float* qkv, const float* valid, const float* out, const float* dout,
+                                      const float* lse, float* delta, float* dqkv, int64_t B, int T, int N, int d, void* stream) {
+    return clip_bwd<ClipF32, true>(qkv, valid, out, dout, lse, delta, dqkv, B, T, N, d, stream);
+}
+extern "C" int vlg_attention_frame_fwd_bf16(const vlg_bf16* qkv, const float* valid, vlg_bf16* out, float* lse, int64_t B, int T,
+                                           int N, int d, void* stream) {
+    return clip_fwd<ClipBf16, true>(reinterpret_cast<const bf16_t*>(qkv), valid, reinterpret_cast<bf16_t*>(out), lse, B, T, N, d, stream);
+}
+extern "C" int vlg_attention_frame_bwd_bf16(const vlg_bf16* qkv, const float* valid, const vlg_bf16* out, const vlg_bf16* dout,
+                                           const float* lse, float* delta, vlg_bf16* dqkv, int64_t B, int T, int N, int d,
+                                           void* stream) {
+    return clip_bwd<ClipBf16, true>(reinterpret_cast<const bf16_t*>(qkv), valid, reinterpret_cast<const bf16_t*>(out),
+                              reinterpret_cast<const bf16_t*>(dout), lse, delta, reinterpret_cast<bf16_t*>(dqkv), B, T, N, d, stream);
+}
+#endif

@@ -67,6 +67,9 @@ slot that is padded (reserved class id) in the window's last frame padded in eve
 args.gen_clip_cache / VLG_GEN_CLIP_CACHE = 1 (off by default; an engine knob, LayoutEngine(clip_cache=True)): with
 VLG_ATTENTION=clip a prompt shorter than the window grows through the K/V-cached step (vlg_attention_clip_step) instead of
 re-encoding the window per grown frame.
+args.attention / VLG_ATTENTION = slot (default) | clip | factored picks the encoder's attention (vlg/spec.py LayoutConfig):
+factored alternates slot's per-slot causal layers (even) with attention across the slots of one frame (odd layers;
+vlg_attention_frame_*); same parameters and checkpoints as the others, T*N a multiple of 32, grown frames cached by default.
 
 Validation metrics in layout mode (csrc/metrics.hip, vlg/metrics.py, DESIGN.md "Validation metrics"): args.val_metrics /
 VLG_VAL_METRICS = 1 makes validate() also score every batch on the device - class accuracy, top-k accuracy, NLL, mean IoU,
@@ -286,7 +289,8 @@ def layout_config(args) -> LayoutConfig:
     return LayoutConfig(B=max(int(args.batch_size) // gpus, 1), T=_knob(args, "n_frames", "VLG_FRAMES", 16),
                         N=_knob(args, "n_slots", "VLG_SLOTS", 64), d=_knob(args, "d_model", "VLG_DMODEL", 256),
                         n_layers=_knob(args, "n_layers", "VLG_LAYERS", 4),
-                        # "slot" (default): causal attention along T per slot; "clip": block-causal over all slots of a clip
+                        # "slot" (default): causal attention along T per slot; "clip": block-causal over all slots of a clip;
+                        # "factored": slot's layers (even) alternating with attention inside a frame (odd)
                         attention=str(getattr(args, "attention", None) or os.environ.get("VLG_ATTENTION", "slot")))
 
 

@@ -112,7 +112,9 @@ class LayoutEngine(AdamSurface):
                     three bf16 terms, six bf16 MFMAs per product block (csrc/gemm_split.hip).
         The residual stream and its gradient, layer-norm statistics, softmax, losses, weight gradients, Adam and the
         master weights are fp32 in all three.  attention = "clip" follows the storage: its bf16 entry points under "bf16"
-        (bf16 MFMA, fp32 scores and softmax statistics), the fp32 kernels otherwise (bf16_mfma included).
+        (bf16 MFMA, fp32 scores and softmax statistics), the fp32 kernels otherwise (bf16_mfma included).  So do the odd
+        layers of attention = "factored" (vlg_attention_frame_*: attention across the slots of one frame; the even layers are
+        "slot"'s launches) - the mode changes the per-layer attention launch and nothing else in the step.
         dropout = p in [0, 1) (0 = off: nothing allocated, no launch changed): inverted dropout on the embedding and on
         the two residual branches of every layer (2L + 1 sites; rule and sites: include/vlg_hip.h, "dropout"), fused into
         the step's layer-norm launches.  Only forward_backward / train_step / capture_train_step apply it; a bare
@@ -390,6 +392,9 @@ class LayoutEngine(AdamSurface):
         if cfg.attention == "clip":       # per query and head: log-sum-exp of every layer (saved for backward), <dO, O> scratch
             self.lse = torch.empty(L, cfg.n_heads * M, **f32)
             self.delta = torch.empty(cfg.n_heads * M, **f32)
+        elif cfg.n_frame_layers:          # "factored": the odd layers alone keep one (layer l: row l // 2); delta once
+            self.lse = torch.empty(cfg.n_frame_layers, cfg.n_heads * M, **f32)
+            self.delta = torch.empty(cfg.n_heads * M, **f32)
         # partial-sum ("slab") arenas: floats needed by the embedding, a layer-norm, and each weight-gradient shape
         emb_len = self.layout["l0.ln1_g"][0]
         need = [lib.vlg_embed_bwd_slabs() * emb_len, lib.vlg_layernorm_bwd_slabs(M) * 2 * d]
@@ -488,8 +493,18 @@ class LayoutEngine(AdamSurface):
             then()
         self.wbuckets.add(arena, stride, n_slabs, self.grads.data_ptr() + 4 * self.layout[wname][0], stride, s)
 
+    def _lse(self, l: int) -> torch.Tensor:
+        return self.lse[l // 2 if self.cfg.attention == "factored" else l]
+
     def _attn_fwd(self, l: int, batch, B, T, N, M) -> None:
+        """the attention launch of layer l: per slot along time, per clip, or - the odd layers of "factored" - inside a frame"""
         d, s = self.cfg.d, self._stream()
+        if self.cfg.frame_layer(l):
+            e = self.qkv.element_size()                             # N^2 T (query, key) pairs per clip
+            self._timed("attn_frame_fwd", 4.0 * B * d * N * N * T, "vlg_attention_frame_fwd" + self._sfx, ptr(self.qkv[l]),
+                        ptr(batch["valid"]) if self._masked else 0, ptr(self.att[l]), ptr(self._lse(l)), B, T, N, d, s,
+                        nbytes=4.0 * e * M * d)
+            return
         if self.cfg.attention == "clip":
             fl = 4.0 * B * d * N * N * T * (T + 1) / 2.0            # visible (query, key) pairs x 2 products x 2 x head dim, all heads
             e = self.qkv.element_size()                             # qkv read, out written; the fp32 lse is negligible
@@ -502,6 +517,12 @@ class LayoutEngine(AdamSurface):
 
     def _attn_bwd(self, l: int, batch, B, T, N, M) -> None:
         d, s = self.cfg.d, self._stream()
+        if self.cfg.frame_layer(l):
+            e = self.qkv.element_size()                             # algorithmic: 2.5 x the forward, as per clip
+            self._timed("attn_frame_bwd", 2.5 * 4.0 * B * d * N * N * T, "vlg_attention_frame_bwd" + self._sfx, ptr(self.qkv[l]),
+                        ptr(batch["valid"]) if self._masked else 0, ptr(self.att[l]), ptr(self.dh), ptr(self._lse(l)),
+                        ptr(self.delta), ptr(self.dqkv), B, T, N, d, s, nbytes=7.0 * e * M * d)
+            return
         if self.cfg.attention == "clip":
             fl = 2.5 * 4.0 * B * d * N * N * T * (T + 1) / 2.0       # ALGORITHMIC: 5 products against the forward's 2 (the two-kernel
                                                                      # backward recomputes S and dP: 7 are executed)
@@ -909,7 +930,9 @@ class LayoutEngine(AdamSurface):
         and the qkv projection writes its rows into the cache with ldc = T*3d.  As many launches as on the window (1 + 7 per
         layer), on 1/T of its rows.  Per-slot attention: vlg_attention_step.  Per-clip attention (clip_cache): the N queries of
         frame p against every slot of the frames <= p, vlg_attention_clip_step, masked by the window's `valid` when
-        self._masked - its frame p is what the previous vlg_layout_decode_append wrote."""
+        self._masked - its frame p is what the previous vlg_layout_decode_append wrote.  Factored attention: even layers
+        vlg_attention_step against the cache, odd layers vlg_attention_frame_step on the q k v rows the projection just wrote
+        at position p (no cache behind it; masked as per-clip's is)."""
         d, T, L = self.cfg.d, self.cfg.T, self.cfg.n_layers
         g, BN, s = self._grow_buffers(), B * N, self._stream()
         h, one = [g["h"]] * L, lambda name: [g[name]] * L
@@ -926,8 +949,13 @@ class LayoutEngine(AdamSurface):
             self._timed("attn_step", 0.0, "vlg_attention_step" + self._sfx, ptr(self.qkv[l]), ptr(g["att"]), BN, T, d, p, d, s,
                         nbytes=self.qkv.element_size() * BN * d * (2.0 * (p + 1) + 2.0))
 
-        self._encode(g["cls"], g["box"], self.p("time_emb")[p], w, attn_clip if self.cfg.attention == "clip" else attn, B, 1, N,
-                     ldc=T * 3 * d)
+        def attn_frame(l):                                          # q, k, v and o rows of frame p alone: no cache behind it
+            self._timed("attn_frame_step", 4.0 * B * d * N * N, "vlg_attention_frame_step" + self._sfx, ptr(self.qkv[l]),
+                        ptr(valid) if self._masked else 0, ptr(g["att"]), B, T, N, d, p, d, s,
+                        nbytes=self.qkv.element_size() * BN * d * 4.0 + (4.0 * BN if self._masked else 0.0))
+
+        per_layer = lambda l: (attn_frame if self.cfg.frame_layer(l) else attn_clip if self.cfg.attention == "clip" else attn)(l)
+        self._encode(g["cls"], g["box"], self.p("time_emb")[p], w, per_layer, B, 1, N, ldc=T * 3 * d)
         return w.x[L]
 
     def rollout(self, slot_class: torch.Tensor, slot_box: torch.Tensor, steps: int = 8, temperature: float = 0.0,
@@ -949,7 +977,8 @@ class LayoutEngine(AdamSurface):
         frame's B*N rows only, against the keys and values self.qkv[l] already holds for the earlier positions
         (_encode_step; vlg_attention_step, or with per-clip attention vlg_attention_clip_step under the window's valid).
         Per-clip attention has the cached step only in an engine built with clip_cache=True: without the option it
-        re-encodes the window per grown frame and cache=True raises.  cache=False always re-encodes.  Once the window is
+        re-encodes the window per grown frame and cache=True raises.  Factored attention is cached by default: even layers
+        vlg_attention_step, odd layers vlg_attention_frame_step on the newest frame's own rows.  cache=False always re-encodes.  Once the window is
         full the steps are the sliding ones above, from the same buffers.
         No loss, no targets, no host wait inside the loop (one before it with per-clip attention: the mask decision)."""
         cfg, d = self.cfg, self.cfg.d
@@ -987,7 +1016,7 @@ class LayoutEngine(AdamSurface):
             torch.lt(win[0][0], cfg.n_classes, out=win[0][2])
         # per-clip attention: masks are decided ONCE, here (the only host wait of the call), on the prompt's real frames.  Later
         # frames are masked by the decode kernels' valid; they never gain a padded slot the prompt did not have
-        self._masked = cfg.attention == "clip" and (self.padded_slots or bool((win[0][2][:, :P] == 0).any()))
+        self._masked = cfg.attention in ("clip", "factored") and (self.padded_slots or bool((win[0][2][:, :P] == 0).any()))
         gen_cls = torch.empty(B, steps, N, dtype=torch.int64, device=self.device)
         gen_box = torch.empty(B, steps, N, BOX_DIM, dtype=torch.float32, device=self.device)
         logits = torch.empty(steps, BN, cfg.n_out, dtype=torch.float32, device=self.device)

@@ -59,6 +59,12 @@ SIGNATURES = {
     "vlg_attention_clip_bwd_bf16": (I, [P, P, P, P, P, P, P, L, I, I, I, P]),
     "vlg_attention_clip_step": (I, [P, P, P, L, I, I, I, I, L, P]),      # (qkv, valid, o, B, T, N, d, p, ldo, stream)
     "vlg_attention_clip_step_bf16": (I, [P, P, P, L, I, I, I, I, L, P]),
+    "vlg_attention_frame_fwd": (I, [P, P, P, P, L, I, I, I, P]),         # attention inside a frame: the per-clip argument lists
+    "vlg_attention_frame_bwd": (I, [P, P, P, P, P, P, P, L, I, I, I, P]),
+    "vlg_attention_frame_fwd_bf16": (I, [P, P, P, P, L, I, I, I, P]),
+    "vlg_attention_frame_bwd_bf16": (I, [P, P, P, P, P, P, P, L, I, I, I, P]),
+    "vlg_attention_frame_step": (I, [P, P, P, L, I, I, I, I, L, P]),
+    "vlg_attention_frame_step_bf16": (I, [P, P, P, L, I, I, I, I, L, P]),
     "vlg_layout_loss_scratch": (I, []),
     "vlg_layout_loss": (I, [P, I, P, P, P, P, P, P, I, I, I, I, F, F, F, F, F, P]),
     # (out, ld, tgt_class, tgt_box, valid, class_weight | NULL, dout, loss_out, scratch, B, T, N, C, beta, iou_eps, 3 weights, eps, flags, stream)

@@ -53,7 +53,9 @@ class LayoutConfig:
     n_layers: int = 4
     n_classes: int = N_CLASSES
     # "slot": causal attention along T independently per (clip, slot) - the default the headline is quoted on;
-    # "clip": block-causal attention over all T*N tokens of a clip (token (t, n) sees every slot of frames <= t)
+    # "clip": block-causal attention over all T*N tokens of a clip (token (t, n) sees every slot of frames <= t);
+    # "factored": divided space-time attention - even layers are "slot"'s, odd layers attend across the slots of one frame
+    # (not causal in n, nothing crosses frames).  Same parameters and checkpoints as the other two; n_layers = 1 is "slot"
     attention: str = "slot"
 
     @property
@@ -85,19 +87,29 @@ class LayoutConfig:
             raise ValueError("T must be one of 4, 8, 16, 32 (temporal tile held by one wavefront)")
         if self.N < 1 or self.B < 1 or self.n_layers < 1:
             raise ValueError("B, N, n_layers must be >= 1")
-        if self.attention not in ("slot", "clip"):
-            raise ValueError("attention must be 'slot' or 'clip'")
-        if self.attention == "clip" and (self.T * self.N) % 32 != 0:
-            raise ValueError("attention='clip' needs T*N to be a multiple of 32 (32-token MFMA tiles)")
+        if self.attention not in ATTENTION_MODES:
+            raise ValueError("attention must be 'slot', 'clip' or 'factored'")
+        if self.attention in ("clip", "factored") and (self.T * self.N) % 32 != 0:
+            raise ValueError("attention=%r needs T*N to be a multiple of 32 (32-token MFMA tiles)" % self.attention)
+
+    def frame_layer(self, l: int) -> bool:
+        """whether layer l attends inside a frame (the odd layers of "factored") instead of along time per slot"""
+        return self.attention == "factored" and l % 2 == 1
+
+    @property
+    def n_frame_layers(self) -> int:
+        return self.n_layers // 2 if self.attention == "factored" else 0
 
     def describe(self) -> Dict[str, object]:
         return {"B": self.B, "T": self.T, "N": self.N, "d": self.d, "layers": self.n_layers,
                 "heads": self.n_heads, "d_ff": self.d_ff, "classes": self.n_classes,
-                "attention": ("causal-temporal-per-slot" if self.attention == "slot"
-                              else "block-causal-per-clip (every slot of frames <= t)"), "box": "cxcywh-sigmoid",
+                "attention": {"slot": "causal-temporal-per-slot", "clip": "block-causal-per-clip (every slot of frames <= t)",
+                              "factored": "factored-space-time (even layers causal-temporal-per-slot, odd layers every slot "
+                                          "of the token's own frame)"}[self.attention], "box": "cxcywh-sigmoid",
                 "loss": "40*smoothL1(beta=%g)+20*(1-IoU)+10*CE" % SMOOTH_L1_BETA}
 
 
+ATTENTION_MODES = ("slot", "clip", "factored")
 BOX_OVERLAPS = ("iou", "giou")
 
 
@@ -180,6 +192,9 @@ def step_flops(cfg: LayoutConfig) -> Dict[str, float]:
     if cfg.attention == "clip":                                # allowed (query, key) pairs per clip: N^2 T (T + 1) / 2
         attn_fwd = 4.0 * cfg.B * d * cfg.N * cfg.N * cfg.T * (cfg.T + 1) / 2.0
     head_fwd = 2.0 * M * d * cfg.n_out
+    if cfg.attention == "factored":                            # odd layers: N^2 T pairs per clip, inside the frames
+        frame_fwd = 4.0 * cfg.B * d * cfg.N * cfg.N * cfg.T
+        attn_fwd += (frame_fwd - attn_fwd) * cfg.n_frame_layers / cfg.n_layers      # the mean over the layers
     fwd = cfg.n_layers * (per_layer_fwd + attn_fwd) + head_fwd
     # backward = 2 x forward for the projections; attention backward = 2.5 x its forward (5 products against 2)
     return {"gemm_fwd_per_layer": per_layer_fwd, "fwd": fwd, "fwd_bwd": 3.0 * fwd + 0.5 * cfg.n_layers * attn_fwd}
