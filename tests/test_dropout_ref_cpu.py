@@ -171,6 +171,18 @@ def test_knobs_parse_and_offset_the_seed_by_rank(workdir, monkeypatch):
         trainer.dropout_knobs(reference_args(workdir / "e"))
 
 
+def test_dropout_rule_is_stated_once_and_names_its_caller():
+    """vlg.spec.dropout_options: what LayoutEngine (keyword) and trainer.dropout_knobs (environment variable) both call"""
+    from vlg.spec import dropout_options
+    assert dropout_options(0) == 0.0 and dropout_options(0.1) == 0.1 and dropout_options("0.25", "VLG_DROPOUT") == 0.25
+    assert dropout_options(math.nextafter(1.0, 0.0)) < 1.0
+    for bad in (-0.1, 1.0, 1.5, float("nan"), -1e-9):
+        with pytest.raises(ValueError, match=r"^dropout must be in \[0, 1\)"):
+            dropout_options(bad)
+        with pytest.raises(ValueError, match=r"^VLG_DROPOUT must be in \[0, 1\)"):
+            dropout_options(bad, "VLG_DROPOUT")
+
+
 def test_trainer_refuses_out_of_range_dropout_at_construction(workdir):
     from trainer import Trainer
     with pytest.raises(ValueError, match="VLG_DROPOUT"):

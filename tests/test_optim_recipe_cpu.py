@@ -163,6 +163,18 @@ def test_recipe_knobs_from_args_and_environment(workdir, monkeypatch):
             optim_knobs(reference_args(workdir / "exp", **bad))
 
 
+def test_recipe_rule_is_stated_once_and_names_its_caller():
+    """vlg.spec.recipe_options: what FlatAdam (keywords) and trainer.optim_knobs (environment variables) both call"""
+    from vlg.spec import recipe_options
+    assert recipe_options() == (0.0, 0, 0.0) and recipe_options(0.1, 500, 0.999) == (0.1, 500, 0.999)
+    env = ("VLG_WEIGHT_DECAY", "VLG_WARMUP_STEPS", "VLG_EMA_DECAY")
+    for bad in (dict(ema_decay=1.0), dict(ema_decay=-0.1), dict(ema_decay=float("nan")), dict(weight_decay=-1.0), dict(warmup_steps=-1)):
+        with pytest.raises(ValueError, match="weight_decay and warmup_steps must be >= 0, ema_decay in"):
+            recipe_options(**bad)
+        with pytest.raises(ValueError, match="VLG_WEIGHT_DECAY and VLG_WARMUP_STEPS must be >= 0, VLG_EMA_DECAY in"):
+            recipe_options(names=env, **bad)
+
+
 # ----------------------------------------------------------------------------- FlatAdam's host side, on a stub
 class _StubLib:
     def vlg_grad_sumsq_blocks(self, n):

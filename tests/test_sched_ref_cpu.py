@@ -136,6 +136,28 @@ def test_sched_knobs(monkeypatch):
                 sched_knobs(_args())
 
 
+def test_sched_and_decode_rules_are_stated_once_and_name_their_caller():
+    """vlg.spec.sched_options / decode_options: what LayoutEngine and rollout (keywords) and trainer.sched_knobs (environment
+    variables) all call"""
+    from vlg.spec import decode_options, sched_options
+    assert sched_options(0.25) == (0.25, 0, 0.0, 0) and sched_options("1", 2 ** 31 - 1, 0.7, NC, NC) == (1.0, 2 ** 31 - 1, 0.7, NC)
+    assert decode_options(0, 0) == (0.0, 0) and decode_options(1.5, NC, NC) == (1.5, NC)
+    env = tuple(SCHED_ENV[:4])
+    for kw, name in ((dict(eps_max=1.5), "sched_sampling"), (dict(eps_max=-0.1), "sched_sampling"),
+                     (dict(eps_max=float("nan")), "sched_sampling"), (dict(eps_max=0.5, ramp_steps=-1), "sched_ramp_steps"),
+                     (dict(eps_max=0.5, ramp_steps=2 ** 31), "sched_ramp_steps"), (dict(eps_max=0.5, temperature=-1.0), "sched_temperature"),
+                     (dict(eps_max=0.5, temperature=float("inf")), "sched_temperature"),
+                     (dict(eps_max=0.5, temperature=float("nan")), "sched_temperature"), (dict(eps_max=0.5, top_k=NC + 1), "sched_top_k"),
+                     (dict(eps_max=0.5, top_k=-1), "sched_top_k")):
+        with pytest.raises(ValueError, match=name):
+            sched_options(n_classes=NC, **kw)
+        with pytest.raises(ValueError, match="VLG_" + name.upper()):
+            sched_options(n_classes=NC, names=env, **kw)
+    for temperature, top_k in ((-1e-9, 0), (float("inf"), 0), (float("nan"), 0), (0.0, -1), (0.0, NC + 1)):
+        with pytest.raises(ValueError, match=r"^temperature must be finite and >= 0, top_k in \[0, %d\]" % NC):
+            decode_options(temperature, top_k, NC)
+
+
 def test_near_draws_of_the_kernel_cases_stay_under_one_percent():
     """the exact seeds and shapes tests/test_hip_sched_mix.py samples with: draws whose u * S lies within 1e-5 * S of a
     cumulative boundary are excused there, and must stay under 1 % of the draws (the project's cap)"""

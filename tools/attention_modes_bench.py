@@ -10,11 +10,10 @@ import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "video-layout-generation_amd")]
 import torch
+from vlg.attention import MODES, cached_by_default
 from vlg.data import synthetic_clips, to_device
 from vlg.engine import LayoutEngine
 from vlg.spec import LayoutConfig, SEED
-
-MODES = ("slot", "clip", "factored")
 
 
 def opt(name, default):
@@ -39,7 +38,7 @@ batch = to_device(synthetic_clips(B, T, N, seed=SEED), dev)
 pc, pb = batch["slot_class"][:, :1].contiguous(), batch["slot_box"][:, :1].contiguous()
 for precision in ("fp32", "bf16"):
     engines = {m: LayoutEngine(LayoutConfig(B=B, T=T, N=N, d=d, n_layers=L, attention=m), dev, seed=SEED, precision=precision,
-                               padded_slots=False, clip_cache=(m == "clip")) for m in MODES}
+                               padded_slots=False, clip_cache=not cached_by_default(m)) for m in MODES}
     roll = lambda e, steps: [t.cpu() for t in e.rollout(pc, pb, steps=steps)]
     for e in engines.values():
         for _ in range(3):

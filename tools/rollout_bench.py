@@ -15,6 +15,7 @@ import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "video-layout-generation_amd")]
 import torch
+from vlg.attention import cached_by_default
 from vlg.data import synthetic_clips, to_device
 from vlg.engine import LayoutEngine
 from vlg.spec import LayoutConfig
@@ -118,9 +119,9 @@ if "--prompt" in sys.argv:
     P = int(opt("--prompt", 2))
     if not 1 <= P < T:
         sys.exit("--prompt takes 1 <= P < T")
-    clip_cache = "--clip-cache" in sys.argv and cfg.attention == "clip"
-    prompt_bench(cfg, dev, cls, box, P, int(opt("--steps", T - P)),
-                 "--no-cache" not in sys.argv and (cfg.attention != "clip" or clip_cache), clip_cache)
+    cached = cached_by_default(cfg.attention)
+    clip_cache = "--clip-cache" in sys.argv and not cached
+    prompt_bench(cfg, dev, cls, box, P, int(opt("--steps", T - P)), "--no-cache" not in sys.argv and (cached or clip_cache), clip_cache)
     sys.exit(0)
 paths = {"host loop": host_loop, "rollout()": device_path}
 for precision in ("fp32", "bf16"):

@@ -29,47 +29,37 @@ VLG_LR_DECAY = 1 honours --lr_decay_step / --lr_decay_gamma (epochs; the referen
 they stay ignored unless asked for).  Any of them switches the engine to its guarded step; the train log line then also
 shows the gradient norm and the number of skipped steps.
 
-The training recipe on that step (all off by default; vlg/optim.py, DESIGN.md "Training recipe"): args.weight_decay /
-VLG_WEIGHT_DECAY = decoupled weight decay (AdamW) on the weight matrices (layout mode) or convolution weights (pixel mode);
-args.warmup_steps / VLG_WARMUP_STEPS = linear learning-rate warm-up over that many applied steps - it composes with
-VLG_LR_DECAY: the epoch's rate is written into the device record as before and the warm-up scales it on the device;
-args.ema_decay / VLG_EMA_DECAY = an exponential moving average of the weights with that decay, args.ema_warmup /
-VLG_EMA_WARMUP = 1 ramps the decay as min(d, (1 + step) / (10 + step)); args.ema_eval / VLG_EMA_EVAL (default 1, read only
+The training recipe on that step (all off by default; what each does: FlatAdam in vlg/optim.py, DESIGN.md "Training recipe";
+what is legal: vlg.spec.recipe_options): args.weight_decay / VLG_WEIGHT_DECAY, on the weight matrices (layout mode) or
+convolution weights (pixel mode); args.warmup_steps / VLG_WARMUP_STEPS - it composes with VLG_LR_DECAY: the epoch's rate is
+written into the device record as before and the warm-up scales it on the device; args.ema_decay / VLG_EMA_DECAY and
+args.ema_warmup / VLG_EMA_WARMUP = 1, the weights' moving average; args.ema_eval / VLG_EMA_EVAL (default 1, read only
 when the average is on): layout mode's validate(), generate_sequence() and evaluate_rollout() run on the averaged weights
 (LayoutEngine.ema_weights()).  save_checkpoint adds 'gridnet_ema', the averaged model in 'gridnet''s format; --resume
 restores the average through 'optimizer'.
 
-Dropout in layout mode (off by default; csrc/dropout.hip, DESIGN.md "Dropout"): args.dropout / VLG_DROPOUT = p in [0, 1) drops
-the embedding and the two residual branches of every layer in training steps only - validate(), generation and the
-averaged weights stay evaluation; VLG_DROPOUT_SEED (default args.seed) seeds the stateless mask, and data-parallel rank r
-uses seed + r so that ranks draw different masks.
+The three options below are LayoutEngine's keyword arguments of the same names - its docstring says what each does, and
+vlg/spec.py (dropout_options, sched_options, loss_options) which values are legal; here only how they are asked for.
 
-Scheduled sampling in layout mode (off by default; csrc/decode.hip, DESIGN.md "Scheduled sampling"): args.sched_sampling /
-VLG_SCHED_SAMPLING = eps_max in [0, 1] makes every training step run an evaluation forward on the true inputs first and then
-train on inputs in which each token of a frame after the first that is not padded is, with probability eps_max, the model's
-own decoded prediction of it; targets stay the true ones.  VLG_SCHED_RAMP_STEPS (0) ramps the probability linearly over
-that many training steps, VLG_SCHED_TEMPERATURE (0 = argmax) / VLG_SCHED_TOP_K (0 = every class) decode as generation does,
-VLG_SCHED_SEED (default args.seed) seeds coins and draws, and data-parallel rank r uses seed + r.  validate(), generation
-and the averaged weights are untouched.
+Dropout in layout mode (off by default; DESIGN.md "Dropout"): args.dropout / VLG_DROPOUT = p; VLG_DROPOUT_SEED (default
+args.seed) seeds the stateless mask, and data-parallel rank r uses seed + r so that ranks draw different masks.
 
-Loss options in layout mode (all off by default; csrc/loss.hip, DESIGN.md "Loss options"): args.class_weights /
-VLG_CLASS_WEIGHTS = 20 comma-separated floats, finite and >= 0 with at least one > 0, the weight= of F.cross_entropy
-(vlg.metrics.balanced_class_weights turns the confusion matrix of VLG_VAL_METRICS=1 into such a list); args.label_smoothing /
-VLG_LABEL_SMOOTHING = eps in [0, 1), its label_smoothing=; args.box_overlap / VLG_BOX_OVERLAP = iou (default) or giou, the
-overlap term 1 - GIoU, which has a gradient for boxes that do not touch.  They change the training objective AND the loss
-validate() reports; the validation metrics' NLL and IoU stay the plain figures.
+Scheduled sampling in layout mode (off by default; DESIGN.md "Scheduled sampling"): args.sched_sampling / VLG_SCHED_SAMPLING
+= eps_max, VLG_SCHED_RAMP_STEPS (0), VLG_SCHED_TEMPERATURE (0 = argmax) / VLG_SCHED_TOP_K (0 = every class), VLG_SCHED_SEED
+(default args.seed; data-parallel rank r uses seed + r).
+
+Loss options in layout mode (all off by default; DESIGN.md "Loss options"): args.class_weights / VLG_CLASS_WEIGHTS = 20
+comma-separated floats (vlg.metrics.balanced_class_weights turns the confusion matrix of VLG_VAL_METRICS=1 into such a
+list); args.label_smoothing / VLG_LABEL_SMOOTHING; args.box_overlap / VLG_BOX_OVERLAP = iou (default) or giou.
 
 Generation knobs of generate_sequence in layout mode (a keyword argument wins over them; csrc/decode.hip, DESIGN.md
 "Generation"): args.gen_temperature / VLG_GEN_TEMPERATURE (0 = argmax; > 0 samples from softmax(logits / temperature)),
 args.gen_top_k / VLG_GEN_TOP_K (0 = every class, else only the k largest logits), args.gen_seed / VLG_GEN_SEED (default
 args.seed; the same seed, prompt and weights give the same sequence), args.gen_keep_padded / VLG_GEN_KEEP_PADDED = 1 keeps a
 slot that is padded (reserved class id) in the window's last frame padded in every generated frame.
-args.gen_clip_cache / VLG_GEN_CLIP_CACHE = 1 (off by default; an engine knob, LayoutEngine(clip_cache=True)): with
-VLG_ATTENTION=clip a prompt shorter than the window grows through the K/V-cached step (vlg_attention_clip_step) instead of
-re-encoding the window per grown frame.
-args.attention / VLG_ATTENTION = slot (default) | clip | factored picks the encoder's attention (vlg/spec.py LayoutConfig):
-factored alternates slot's per-slot causal layers (even) with attention across the slots of one frame (odd layers;
-vlg_attention_frame_*); same parameters and checkpoints as the others, T*N a multiple of 32, grown frames cached by default.
+args.gen_clip_cache / VLG_GEN_CLIP_CACHE = 1 (off by default) is the engine knob LayoutEngine(clip_cache=True).
+args.attention / VLG_ATTENTION = slot (default) | clip | factored picks the encoder's attention: the kinds of attention, the
+layers each mode gives them to and which modes cache grown frames by default are stated in vlg/attention.py.
 
 Validation metrics in layout mode (csrc/metrics.hip, vlg/metrics.py, DESIGN.md "Validation metrics"): args.val_metrics /
 VLG_VAL_METRICS = 1 makes validate() also score every batch on the device - class accuracy, top-k accuracy, NLL, mean IoU,
@@ -100,7 +90,8 @@ import torch.distributed as dist
 from vlg.data import BATCH_KEYS, BucketedClipLoader, ClipLoader, synthetic_clips, to_device
 from vlg.dp import GradReducer, bucket_ranges
 from vlg.optim import decayed_lr
-from vlg.spec import ADAM_BETA1, ADAM_LR, N_CLASSES, SEED, LayoutConfig, loss_options
+from vlg.spec import (ADAM_BETA1, ADAM_LR, N_CLASSES, SEED, LayoutConfig, dropout_options, loss_options, recipe_options,
+                      sched_options)
 
 
 class AverageMeter(object):
@@ -168,11 +159,9 @@ def optim_knobs(args) -> Dict[str, object]:
     knobs = {"clip_grad": max(_knob_float(args, "clip_grad", "VLG_CLIP_GRAD", 0.0), 0.0),
              "skip_nonfinite": bool(_knob(args, "skip_nonfinite", "VLG_SKIP_NONFINITE", 0)),
              "lr_decay": os.environ.get("VLG_LR_DECAY", "0") == "1"}
-    weight_decay = _knob_float(args, "weight_decay", "VLG_WEIGHT_DECAY", 0.0)
-    warmup_steps = _knob(args, "warmup_steps", "VLG_WARMUP_STEPS", 0)
-    ema_decay = _knob_float(args, "ema_decay", "VLG_EMA_DECAY", 0.0)
-    if weight_decay < 0.0 or warmup_steps < 0 or not 0.0 <= ema_decay < 1.0:
-        raise ValueError("VLG_WEIGHT_DECAY and VLG_WARMUP_STEPS must be >= 0, VLG_EMA_DECAY in [0, 1)")
+    weight_decay, warmup_steps, ema_decay = recipe_options(
+        _knob_float(args, "weight_decay", "VLG_WEIGHT_DECAY", 0.0), _knob(args, "warmup_steps", "VLG_WARMUP_STEPS", 0),
+        _knob_float(args, "ema_decay", "VLG_EMA_DECAY", 0.0), names=("VLG_WEIGHT_DECAY", "VLG_WARMUP_STEPS", "VLG_EMA_DECAY"))
     if weight_decay > 0.0:
         knobs["weight_decay"] = weight_decay
     if warmup_steps > 0:
@@ -183,45 +172,38 @@ def optim_knobs(args) -> Dict[str, object]:
     return knobs
 
 
+def _rank_seed(args, name: str, env: str) -> int:
+    """an option's seed (default args.seed) in [0, 2^63), offset by the data-parallel rank so that ranks draw differently"""
+    seed = _knob(args, name, env, int(getattr(args, "seed", SEED)))
+    if not 0 <= seed < 2 ** 63:
+        raise ValueError("%s must be in [0, 2^63), got %r" % (env, seed))
+    return seed + int(getattr(args, "rank", 0) or 0)
+
+
 def dropout_knobs(args) -> Dict[str, object]:
     """the engine's dropout keyword arguments from args / environment (module docstring): {} with the knob off, so an
-    engine without the option is never handed one; else {dropout, dropout_seed}, the seed offset by the data-parallel rank."""
-    p = _knob_float(args, "dropout", "VLG_DROPOUT", 0.0)
-    if not 0.0 <= p < 1.0:                              # (also refuses NaN)
-        raise ValueError("VLG_DROPOUT must be in [0, 1), got %r" % p)
-    seed = _knob(args, "dropout_seed", "VLG_DROPOUT_SEED", int(getattr(args, "seed", SEED)))
-    if not 0 <= seed < 2 ** 63:
-        raise ValueError("VLG_DROPOUT_SEED must be in [0, 2^63), got %r" % seed)
-    if p == 0.0:
-        return {}
-    return {"dropout": p, "dropout_seed": seed + int(getattr(args, "rank", 0) or 0)}
+    engine without the option is never handed one; else {dropout, dropout_seed}.  The rule is LayoutEngine's:
+    vlg.spec.dropout_options, before any engine exists."""
+    p = dropout_options(_knob_float(args, "dropout", "VLG_DROPOUT", 0.0), "VLG_DROPOUT")
+    seed = _rank_seed(args, "dropout_seed", "VLG_DROPOUT_SEED")
+    return {"dropout": p, "dropout_seed": seed} if p else {}
 
 
 def sched_knobs(args) -> Dict[str, object]:
     """the engine's scheduled-sampling keyword arguments from args / environment (module docstring): {} with
     args.sched_sampling / VLG_SCHED_SAMPLING unset, so an engine without the option is never handed one; else
-    {sched_sampling, sched_ramp_steps, sched_temperature, sched_top_k, sched_seed}, the seed offset by the data-parallel
-    rank.  Refuses what LayoutEngine refuses, before any engine exists."""
+    {sched_sampling, sched_ramp_steps, sched_temperature, sched_top_k, sched_seed}.  The rule is LayoutEngine's:
+    vlg.spec.sched_options, before any engine exists."""
     eps = getattr(args, "sched_sampling", None)
     if eps is None:
         eps = os.environ.get("VLG_SCHED_SAMPLING") or None
     if eps is None:
         return {}
-    eps = float(eps)
-    if not 0.0 <= eps <= 1.0:                           # (also refuses NaN)
-        raise ValueError("VLG_SCHED_SAMPLING must be in [0, 1], got %r" % eps)
-    ramp = _knob(args, "sched_ramp_steps", "VLG_SCHED_RAMP_STEPS", 0)
-    if not 0 <= ramp < 2 ** 31:
-        raise ValueError("VLG_SCHED_RAMP_STEPS must be in [0, 2^31), got %r" % ramp)
-    temperature = _knob_float(args, "sched_temperature", "VLG_SCHED_TEMPERATURE", 0.0)
-    top_k = _knob(args, "sched_top_k", "VLG_SCHED_TOP_K", 0)
-    if not (temperature >= 0.0 and temperature != float("inf")) or not 0 <= top_k <= N_CLASSES:
-        raise ValueError("VLG_SCHED_TEMPERATURE must be finite and >= 0, VLG_SCHED_TOP_K in [0, %d]" % N_CLASSES)
-    seed = _knob(args, "sched_seed", "VLG_SCHED_SEED", int(getattr(args, "seed", SEED)))
-    if not 0 <= seed < 2 ** 63:
-        raise ValueError("VLG_SCHED_SEED must be in [0, 2^63), got %r" % seed)
-    return {"sched_sampling": eps, "sched_ramp_steps": ramp, "sched_temperature": temperature, "sched_top_k": top_k,
-            "sched_seed": seed + int(getattr(args, "rank", 0) or 0)}
+    names = ("sched_sampling", "sched_ramp_steps", "sched_temperature", "sched_top_k")
+    values = sched_options(eps, _knob(args, "sched_ramp_steps", "VLG_SCHED_RAMP_STEPS", 0),
+                           _knob_float(args, "sched_temperature", "VLG_SCHED_TEMPERATURE", 0.0),
+                           _knob(args, "sched_top_k", "VLG_SCHED_TOP_K", 0), N_CLASSES, tuple("VLG_" + n.upper() for n in names))
+    return dict(zip(names, values), sched_seed=_rank_seed(args, "sched_seed", "VLG_SCHED_SEED"))
 
 
 def loss_knobs(args) -> Dict[str, object]:
@@ -288,9 +270,7 @@ def layout_config(args) -> LayoutConfig:
     gpus = max(int(getattr(args, "gpus", 1) or 1), 1)
     return LayoutConfig(B=max(int(args.batch_size) // gpus, 1), T=_knob(args, "n_frames", "VLG_FRAMES", 16),
                         N=_knob(args, "n_slots", "VLG_SLOTS", 64), d=_knob(args, "d_model", "VLG_DMODEL", 256),
-                        n_layers=_knob(args, "n_layers", "VLG_LAYERS", 4),
-                        # "slot" (default): causal attention along T per slot; "clip": block-causal over all slots of a clip;
-                        # "factored": slot's layers (even) alternating with attention inside a frame (odd)
+                        n_layers=_knob(args, "n_layers", "VLG_LAYERS", 4),     # (the attention modes: vlg/attention.py)
                         attention=str(getattr(args, "attention", None) or os.environ.get("VLG_ATTENTION", "slot")))
 
 
@@ -740,9 +720,7 @@ class Trainer:
         (B,steps,N) and boxes (B,steps,N,4) on the CPU.  A prompt shorter than T (the reference's generate_sequence starts
         from two observed frames) grows to T with a K/V cache where the engine has one (LayoutEngine.rollout).
         temperature / top_k / seed / keep_padded: None takes the generation knob from args or the environment
-        (generation_knobs; module docstring).  temperature 0 is the argmax; > 0 samples from softmax(logits / temperature)
-        over the top_k largest logits (0 = all), reproducibly per (seed, token, step); keep_padded keeps a slot that is
-        padded (reserved class id) in the window's last frame padded, with its box.  An engine with rollout()
+        (generation_knobs; the module docstring says what each does).  An engine with rollout()
         (vlg.engine.LayoutEngine) generates on the device, without a host wait per frame, and the result is copied to the
         CPU once; any other engine runs the host loop, which can only take the argmax of a full T-frame prompt."""
         if self.image_mode:

@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import functools
 import math
 import os
 import types
@@ -30,13 +31,19 @@ from typing import Dict, Optional
 import torch
 
 from . import hip
+from .attention import MODES, cached_by_default, layer_kinds, lse_rows
 from .metrics import MetricsRecord
 from .optim import AdamSurface, FlatAdam, build_decay_mask, decays_matrix
 from .slabs import SlabBuckets
 from .hip import (EPI_A_BF16, EPI_B_BF16, EPI_BIAS, EPI_DGELU, EPI_GELU, EPI_NONE, EPI_OUT_BF16, EPI_RESID,
                   call, ptr)
 from .spec import (ADAM_BETA1, ADAM_BETA2, ADAM_EPS, ADAM_LR, BOX_DIM, IOU_EPS, LN_EPS, LOSS_W_CE,
-                   LOSS_W_REG, LOSS_W_STRUCT, SMOOTH_L1_BETA, LayoutConfig, loss_options, param_layout)
+                   LOSS_W_REG, LOSS_W_STRUCT, SMOOTH_L1_BETA, LayoutConfig, decode_options, dropout_options, loss_options,
+                   param_layout, sched_options)
+
+# the int32 device step counters: checkpoint key (= the advance launch's timer family, = the property that reads it) -> the
+# option an engine needs to have one
+STEP_COUNTERS = {"dropout_step": "dropout > 0", "sched_step": "sched_sampling"}
 
 
 def init_params(cfg: LayoutConfig, seed: int) -> Dict[str, torch.Tensor]:
@@ -96,12 +103,10 @@ class LayoutEngine(AdamSurface):
         leaves parameters, moments and step count untouched when the gradient holds inf or NaN.  Either one - or a call
         of set_lr - turns on the GUARDED optimiser step (vlg/optim.py), eager and captured alike; with both off and
         set_lr never called, the step's launches are exactly those of an engine without these options.
-        The recipe (vlg/optim.py; each off at 0, any of them turns the guarded step on): weight_decay = decoupled decay
-        (torch.optim.AdamW) on the weight matrices - every tensor whose name ends in _w; not biases, layer-norm gains and
-        biases, cls_emb or time_emb; warmup_steps = linear learning-rate warm-up over that many APPLIED steps, scaling
-        whatever set_lr wrote; ema_decay = an exponential moving average of the weights (ema_warmup: decay
-        min(d, (1 + step) / (10 + step))), kept by the Adam launch, in the bf16 mode with its own bf16 copy:
-        `with engine.ema_weights():` evaluates and generates on it.
+        The recipe (FlatAdam in vlg/optim.py says what each does, vlg.spec.recipe_options what is legal; each off at 0, any of
+        them turns the guarded step on): weight_decay falls on the weight matrices - every tensor whose name ends in _w; not
+        biases, layer-norm gains and biases, cls_emb or time_emb; warmup_steps; ema_decay / ema_warmup, the weights' moving
+        average (in the bf16 mode with its own bf16 copy): `with engine.ema_weights():` evaluates and generates on it.
         precision:
         "fp32"      exact-fp32 MFMA projections, every tensor fp32 (parity 1e-4);
         "bf16"      BASELINE.json configs[2]: bf16 MFMA projections (fp32 accumulate) AND the activations that only
@@ -111,10 +116,9 @@ class LayoutEngine(AdamSurface):
         "fp32x3"    fp32 tensors and fp32-grade projections on the bf16 matrix cores: every operand split exactly into
                     three bf16 terms, six bf16 MFMAs per product block (csrc/gemm_split.hip).
         The residual stream and its gradient, layer-norm statistics, softmax, losses, weight gradients, Adam and the
-        master weights are fp32 in all three.  attention = "clip" follows the storage: its bf16 entry points under "bf16"
-        (bf16 MFMA, fp32 scores and softmax statistics), the fp32 kernels otherwise (bf16_mfma included).  So do the odd
-        layers of attention = "factored" (vlg_attention_frame_*: attention across the slots of one frame; the even layers are
-        "slot"'s launches) - the mode changes the per-layer attention launch and nothing else in the step.
+        master weights are fp32 in all three.  Every attention kind (vlg/attention.py) follows the storage: its bf16 entry
+        points under "bf16" (per clip: bf16 MFMA, fp32 scores and softmax statistics), the fp32 kernels otherwise (bf16_mfma
+        included); cfg.attention changes the per-layer attention launch and nothing else in the step.
         dropout = p in [0, 1) (0 = off: nothing allocated, no launch changed): inverted dropout on the embedding and on
         the two residual branches of every layer (2L + 1 sites; rule and sites: include/vlg_hip.h, "dropout"), fused into
         the step's layer-norm launches.  Only forward_backward / train_step / capture_train_step apply it; a bare
@@ -122,43 +126,35 @@ class LayoutEngine(AdamSurface):
         evaluation.  The mask is a stateless Philox function of (row, column, site, step) under dropout_seed; the step is a
         device counter (dropout_step / set_dropout_step) advanced once per training forward+backward, whether or not the
         guarded optimiser then skips.  Not combined with VLG_OVERLAP_WGRAD=1.
-        clip_cache = True (off by default; it matters with attention = "clip" alone): rollout() from a prompt shorter than
-        the window runs its grow steps through the K/V-cached step of per-clip attention (vlg_attention_clip_step) instead of
-        re-encoding the window per grown frame.  Off, rollout(cache=True) raises with per-clip attention, as before.
-        Loss options (DESIGN.md "Loss options"; all off by default, and then the step launches vlg_layout_loss as ever; with
-        any of them on, vlg_layout_loss_ext in its place - one launch either way): class_weights = n_classes floats, finite
-        and >= 0 with at least one > 0, the weight= of F.cross_entropy (uploaded once; the CE mean then divides by the summed
-        weight of the valid targets, per rank under data parallelism); label_smoothing in [0, 1), its label_smoothing=;
-        box_overlap = "giou" makes the overlap term mean(1 - GIoU), which has a gradient for boxes that do not touch.
+        clip_cache = True (off by default; it matters with attention = "clip" alone): rollout()'s grown frames take the
+        K/V-cached step with per-clip attention too (rollout's docstring).
+        Loss options (DESIGN.md "Loss options"; legal values: vlg.spec.loss_options; all off by default, and then the step
+        launches vlg_layout_loss as ever; with any of them on, vlg_layout_loss_ext in its place - one launch either way):
+        class_weights = the weight= of F.cross_entropy (uploaded once; the CE mean then divides by the summed weight of the
+        valid targets, per rank under data parallelism); label_smoothing = its label_smoothing=; box_overlap = "giou" makes
+        the overlap term mean(1 - GIoU), which has a gradient for boxes that do not touch.
         Fixed at construction; checkpoints do not carry them.  forward() - validation included - returns this configured
         objective; accumulate_metrics / evaluate_rollout keep reporting the plain NLL and IoU.
-        Scheduled sampling (DESIGN.md "Scheduled sampling"; rule: include/vlg_hip.h): sched_sampling = None is off - nothing
-        allocated, no launch changed; a float eps_max in [0, 1] turns it on.  forward_backward / train_step /
-        capture_train_step then run PASS 1, the evaluation forward on the true inputs (forward()'s launches minus the loss, no
-        dropout), one launch of vlg_layout_mix_inputs, which replaces each input token of a frame t >= 1 that is not padded
-        with the model's own decoded prediction of it (class by the decoding rule of rollout() under sched_temperature /
-        sched_top_k, box = sigmoid(raw)) with probability eps_max - ramped linearly over the first sched_ramp_steps training
-        steps when that is > 0 - and PASS 2, the training step as ever on the mixed inputs and the TRUE targets; no gradient
-        flows through the replaced inputs.  Coins and draws are stateless Philox functions of (token, step) under sched_seed;
-        the step is a device counter of its own (sched_step / set_sched_step), advanced once per training forward+backward
-        as dropout's is.  sched_inputs() shows the mixed inputs of the last training step.  Everything that evaluates -
-        forward(), rollout(), evaluate_rollout(), accumulate_metrics(), ema_weights() - is untouched."""
+        Scheduled sampling (DESIGN.md "Scheduled sampling"; rule: include/vlg_hip.h; legal values: vlg.spec.sched_options):
+        sched_sampling = None is off - nothing allocated, no launch changed; a float eps_max turns it on.  forward_backward /
+        train_step / capture_train_step then run PASS 1 and the mix (_mix_inputs), which replaces each input token of a frame
+        t >= 1 that is not padded with the model's own decoded prediction of it (class by the decoding rule of rollout()
+        under sched_temperature / sched_top_k, box = sigmoid(raw)) with probability eps_max - ramped linearly over the first
+        sched_ramp_steps training steps when that is > 0 - and PASS 2, the training step as ever on the mixed inputs and the
+        TRUE targets; no gradient flows through the replaced inputs.  Coins and draws are stateless Philox functions of
+        (token, step) under sched_seed; the step is a device counter of its own (sched_step / set_sched_step), advanced as
+        dropout's is.  sched_inputs() shows the last training step's mixed inputs.  Whatever evaluates is untouched."""
         cfg.validate()
-        self._sched = None
-        if sched_sampling is not None:
-            eps, ramp, temp, top_k = float(sched_sampling), int(sched_ramp_steps), float(sched_temperature), int(sched_top_k)
-            if not 0.0 <= eps <= 1.0:                    # (also refuses NaN)
-                raise ValueError("sched_sampling must be None or in [0, 1], got %r" % (sched_sampling,))
-            if ramp < 0 or ramp >= 2 ** 31:
-                raise ValueError("sched_ramp_steps must be in [0, 2^31), got %r" % (sched_ramp_steps,))
-            if not (math.isfinite(temp) and temp >= 0.0) or not 0 <= top_k <= cfg.n_classes:
-                raise ValueError("sched_temperature must be finite and >= 0, sched_top_k in [0, %d]" % cfg.n_classes)
-            self._sched = (eps, ramp, temp, top_k, int(sched_seed) & 0xFFFFFFFFFFFFFFFF)
+        self._sched = None if sched_sampling is None else sched_options(    # (the option rules: vlg/spec.py, the trainer's *_knobs call them too)
+            sched_sampling, sched_ramp_steps, sched_temperature, sched_top_k, cfg.n_classes) + (int(sched_seed) & 0xFFFFFFFFFFFFFFFF,)
         weights, self.label_smoothing, self.box_overlap = loss_options(class_weights, label_smoothing, box_overlap, cfg.n_classes)
         self.clip_cache = bool(clip_cache)
-        self.dropout = float(dropout)
-        if not 0.0 <= self.dropout < 1.0:
-            raise ValueError("dropout must be in [0, 1), got %r" % (dropout,))
+        self.dropout = dropout_options(dropout)
+        # vlg/attention.py: every layer's attention kind and lse row; of the mode as a whole, whether a layer takes `valid` and
+        # whether a short prompt's grown frames have a cached step
+        self.attn = layer_kinds(cfg.attention, cfg.n_layers)
+        self._lse_row, self._per_clip = lse_rows(self.attn), any(k.per_clip for k in MODES[cfg.attention])
+        self._cacheable = self.clip_cache or cached_by_default(cfg.attention)
         if self.dropout > 0.0 and os.environ.get("VLG_OVERLAP_WGRAD", "0") == "1":
             raise ValueError("VLG_OVERLAP_WGRAD=1 together with dropout=%g is not supported: the side stream's hazard "
                              "tracking does not cover the dropout gradient buffer" % self.dropout)
@@ -182,20 +178,21 @@ class LayoutEngine(AdamSurface):
         if device.type != "cuda":
             raise hip.HipError("LayoutEngine needs a HIP device (got %s); there is no CPU path" % device)
         self.cfg, self.device = cfg, device
+        self._counters: Dict[str, torch.Tensor] = {}     # STEP_COUNTERS key -> the counter, for the options that are on
         # dropout: (thr, scale, seed) for the kernels + the device step counter, or None with the knob off
-        self._drop, self.drop_step, self._dropped = None, None, False
+        self._drop, self._dropped = None, False
         if self.dropout > 0.0:
             thr, scale = ctypes.c_uint32(), ctypes.c_float()
             hip.check(hip.load().vlg_dropout_plan(self.dropout, ctypes.byref(thr), ctypes.byref(scale)), "vlg_dropout_plan")
             self._drop = (thr.value, scale.value, int(dropout_seed) & 0xFFFFFFFFFFFFFFFF)
-            self.drop_step = torch.zeros(1, dtype=torch.int32, device=device)
+            self._counters["dropout_step"] = torch.zeros(1, dtype=torch.int32, device=device)
         # scheduled sampling: (thr_max, ramp_steps, temperature, top_k, seed) for the mix kernel + its own device step counter
-        self.sched_counter = None
         if self._sched is not None:
             thr = ctypes.c_uint32()
             hip.check(hip.load().vlg_sched_plan(self._sched[0], ctypes.byref(thr)), "vlg_sched_plan")
             self._sched = (thr.value,) + self._sched[1:]
-            self.sched_counter = torch.zeros(1, dtype=torch.int32, device=device)
+            self._counters["sched_step"] = torch.zeros(1, dtype=torch.int32, device=device)
+        self.drop_step, self.sched_counter = self._counters.get("dropout_step"), self._counters.get("sched_step")
         self.layout, self.n_params = param_layout(cfg)
         f32 = dict(dtype=torch.float32, device=device)
         self.class_weights = None if weights is None else torch.tensor(weights, **f32)
@@ -284,10 +281,7 @@ class LayoutEngine(AdamSurface):
               "layout": {k: (o, tuple(s)) for k, (o, s) in self.layout.items()}}
         if self.optim.ema is not None:
             sd["ema"] = self.optim.ema.cpu().clone()
-        if self._drop is not None:               # (knob off: the checkpoint is what it was without the option)
-            sd["dropout_step"] = self.dropout_step
-        if self._sched is not None:
-            sd["sched_step"] = self.sched_step
+        sd.update((key, self._read_step(key)) for key in self._counters)    # (option off: no key, the checkpoint it always was)
         return sd
 
     def load_state_dict(self, sd: Dict[str, object]) -> None:
@@ -301,24 +295,33 @@ class LayoutEngine(AdamSurface):
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.optim.set_step(int(sd["step"]))
-        if self._drop is not None and sd.get("dropout_step") is not None:
-            self.set_dropout_step(int(sd["dropout_step"]))
-        if self._sched is not None and sd.get("sched_step") is not None:
-            self.set_sched_step(int(sd["sched_step"]))
+        for key in self._counters:
+            if sd.get(key) is not None:
+                self._set_step(key, int(sd[key]))
 
-    @property
-    def sched_step(self) -> int:
-        """the scheduled-sampling step counter k the next training step will read (a host read: it waits for the device)"""
-        if self._sched is None:
-            raise RuntimeError("sched_step needs an engine built with sched_sampling")
-        return int(self.sched_counter.item())
+    def _step_counter(self, key: str, who: str) -> torch.Tensor:
+        if key not in self._counters:
+            raise RuntimeError("%s needs an engine built with %s" % (who, STEP_COUNTERS[key]))
+        return self._counters[key]
 
-    def set_sched_step(self, k: int) -> None:
-        if self._sched is None:
-            raise RuntimeError("set_sched_step needs an engine built with sched_sampling")
+    def _read_step(self, key: str) -> int:
+        """the step k the next training step will read from that counter (a host read: it waits for the device)"""
+        return int(self._step_counter(key, key).item())
+
+    def _set_step(self, key: str, k: int) -> None:
+        counter = self._step_counter(key, "set_" + key)
         if not 0 <= int(k) < 2 ** 31:
-            raise ValueError("scheduled-sampling step must be in [0, 2^31), got %r" % (k,))
-        self.sched_counter.fill_(int(k))
+            raise ValueError("%s must be in [0, 2^31), got %r" % (key, k))
+        counter.fill_(int(k))
+
+    def _advance_step(self, key: str, stream: int) -> None:
+        """the next training step draws anew (a captured graph advances by replaying this launch)"""
+        self._timed(key, 0.0, "vlg_dropout_step_advance", ptr(self._counters[key]), stream, nbytes=8.0)
+
+    sched_step = property(lambda self: self._read_step("sched_step"), doc="the scheduled-sampling counter: _read_step")
+    dropout_step = property(lambda self: self._read_step("dropout_step"), doc="the dropout counter: _read_step")
+    set_sched_step = functools.partialmethod(_set_step, "sched_step")
+    set_dropout_step = functools.partialmethod(_set_step, "dropout_step")
 
     def sched_inputs(self) -> tuple:
         """(slot_class (B,T,N) int64, slot_box (B,T,N,4) fp32): views of the mixed inputs the last training step's second pass read"""
@@ -329,20 +332,6 @@ class LayoutEngine(AdamSurface):
         B, T, N = self._mixed_shape
         M = B * T * N
         return self.mix_cls[:M].view(B, T, N), self.mix_box[:M].view(B, T, N, BOX_DIM)
-
-    @property
-    def dropout_step(self) -> int:
-        """the dropout step counter k the next training step will read (a host read: it waits for the device)"""
-        if self._drop is None:
-            raise RuntimeError("dropout_step needs an engine built with dropout > 0")
-        return int(self.drop_step.item())
-
-    def set_dropout_step(self, k: int) -> None:
-        if self._drop is None:
-            raise RuntimeError("set_dropout_step needs an engine built with dropout > 0")
-        if not 0 <= int(k) < 2 ** 31:
-            raise ValueError("dropout step must be in [0, 2^31), got %r" % (k,))
-        self.drop_step.fill_(int(k))
 
     def optimizer_state(self) -> Dict[str, object]:
         """Adam state for the checkpoint's 'optimizer' entry (flat tensors, CPU)."""
@@ -389,11 +378,9 @@ class LayoutEngine(AdamSurface):
         self.loss_scratch = torch.zeros(lib.vlg_layout_loss_scratch(), **f32)
         # validation metrics (vlg_layout_metrics): per-block partial sums and the ticket, zero between launches
         self.metrics_scratch = torch.zeros(lib.vlg_layout_metrics_scratch(), dtype=torch.float64, device=self.device)
-        if cfg.attention == "clip":       # per query and head: log-sum-exp of every layer (saved for backward), <dO, O> scratch
-            self.lse = torch.empty(L, cfg.n_heads * M, **f32)
-            self.delta = torch.empty(cfg.n_heads * M, **f32)
-        elif cfg.n_frame_layers:          # "factored": the odd layers alone keep one (layer l: row l // 2); delta once
-            self.lse = torch.empty(cfg.n_frame_layers, cfg.n_heads * M, **f32)
+        n_clip = sum(k.per_clip for k in self.attn)
+        if n_clip:      # per query and head: log-sum-exp of every per-clip layer (saved for backward; row: _lse), <dO, O> scratch once
+            self.lse = torch.empty(n_clip, cfg.n_heads * M, **f32)
             self.delta = torch.empty(cfg.n_heads * M, **f32)
         # partial-sum ("slab") arenas: floats needed by the embedding, a layer-norm, and each weight-gradient shape
         emb_len = self.layout["l0.ln1_g"][0]
@@ -494,45 +481,28 @@ class LayoutEngine(AdamSurface):
         self.wbuckets.add(arena, stride, n_slabs, self.grads.data_ptr() + 4 * self.layout[wname][0], stride, s)
 
     def _lse(self, l: int) -> torch.Tensor:
-        return self.lse[l // 2 if self.cfg.attention == "factored" else l]
+        return self.lse[self._lse_row[l]]
 
     def _attn_fwd(self, l: int, batch, B, T, N, M) -> None:
-        """the attention launch of layer l: per slot along time, per clip, or - the odd layers of "factored" - inside a frame"""
-        d, s = self.cfg.d, self._stream()
-        if self.cfg.frame_layer(l):
-            e = self.qkv.element_size()                             # N^2 T (query, key) pairs per clip
-            self._timed("attn_frame_fwd", 4.0 * B * d * N * N * T, "vlg_attention_frame_fwd" + self._sfx, ptr(self.qkv[l]),
-                        ptr(batch["valid"]) if self._masked else 0, ptr(self.att[l]), ptr(self._lse(l)), B, T, N, d, s,
-                        nbytes=4.0 * e * M * d)
-            return
-        if self.cfg.attention == "clip":
-            fl = 4.0 * B * d * N * N * T * (T + 1) / 2.0            # visible (query, key) pairs x 2 products x 2 x head dim, all heads
-            e = self.qkv.element_size()                             # qkv read, out written; the fp32 lse is negligible
-            self._timed("attn_clip_fwd", fl, "vlg_attention_clip_fwd" + self._sfx, ptr(self.qkv[l]),
-                        ptr(batch["valid"]) if self._masked else 0, ptr(self.att[l]), ptr(self.lse[l]), B, T, N, d, s,
-                        nbytes=4.0 * e * M * d)
-            return
-        self._timed("attn_fwd", 0.0, "vlg_attention_fwd" + self._sfx, ptr(self.qkv[l]), ptr(self.att[l]), B * N, T, d, s,
-                    nbytes=4.0 * self.qkv.element_size() * M * d)
+        """the attention launch of layer l, by its kind (vlg/attention.py): per slot along time, per clip, or inside a frame"""
+        k, d, s = self.attn[l], self.cfg.d, self._stream()
+        nb = 4.0 * self.qkv.element_size() * M * d          # qkv read, out written; the fp32 lse is negligible
+        if k.per_clip:      # flops: visible (query, key) pairs x 2 products x 2 x head dim, all heads
+            self._timed(k.family + "_fwd", 4.0 * B * d * k.pairs(T, N), k.stem + "_fwd" + self._sfx, ptr(self.qkv[l]),
+                        ptr(batch["valid"]) if self._masked else 0, ptr(self.att[l]), ptr(self._lse(l)), B, T, N, d, s, nbytes=nb)
+        else:
+            self._timed(k.family + "_fwd", 0.0, k.stem + "_fwd" + self._sfx, ptr(self.qkv[l]), ptr(self.att[l]), B * N, T, d, s, nbytes=nb)
 
     def _attn_bwd(self, l: int, batch, B, T, N, M) -> None:
-        d, s = self.cfg.d, self._stream()
-        if self.cfg.frame_layer(l):
-            e = self.qkv.element_size()                             # algorithmic: 2.5 x the forward, as per clip
-            self._timed("attn_frame_bwd", 2.5 * 4.0 * B * d * N * N * T, "vlg_attention_frame_bwd" + self._sfx, ptr(self.qkv[l]),
+        k, d, s = self.attn[l], self.cfg.d, self._stream()
+        nb = 7.0 * self.qkv.element_size() * M * d          # qkv, out, dout read, dqkv written (+ qkv, dout again)
+        if k.per_clip:      # ALGORITHMIC flops: 5 products against the forward's 2 (the two-kernel backward recomputes S and dP: 7 are executed)
+            self._timed(k.family + "_bwd", 2.5 * 4.0 * B * d * k.pairs(T, N), k.stem + "_bwd" + self._sfx, ptr(self.qkv[l]),
                         ptr(batch["valid"]) if self._masked else 0, ptr(self.att[l]), ptr(self.dh), ptr(self._lse(l)),
-                        ptr(self.delta), ptr(self.dqkv), B, T, N, d, s, nbytes=7.0 * e * M * d)
-            return
-        if self.cfg.attention == "clip":
-            fl = 2.5 * 4.0 * B * d * N * N * T * (T + 1) / 2.0       # ALGORITHMIC: 5 products against the forward's 2 (the two-kernel
-                                                                     # backward recomputes S and dP: 7 are executed)
-            e = self.qkv.element_size()                             # qkv, out, dout read, dqkv written (+ qkv, dout again)
-            self._timed("attn_clip_bwd", fl, "vlg_attention_clip_bwd" + self._sfx, ptr(self.qkv[l]),
-                        ptr(batch["valid"]) if self._masked else 0, ptr(self.att[l]), ptr(self.dh), ptr(self.lse[l]),
-                        ptr(self.delta), ptr(self.dqkv), B, T, N, d, s, nbytes=7.0 * e * M * d)
-            return
-        self._timed("attn_bwd", 0.0, "vlg_attention_bwd" + self._sfx, ptr(self.qkv[l]), ptr(self.dh), ptr(self.dqkv), B * N, T, d, s,
-                    nbytes=7.0 * self.qkv.element_size() * M * d)
+                        ptr(self.delta), ptr(self.dqkv), B, T, N, d, s, nbytes=nb)
+        else:
+            self._timed(k.family + "_bwd", 0.0, k.stem + "_bwd" + self._sfx, ptr(self.qkv[l]), ptr(self.dh), ptr(self.dqkv), B * N, T, d, s,
+                        nbytes=nb)
 
     def _ln_fwd(self, x, gname, y, stat, M):
         d = self.cfg.d
@@ -584,8 +554,7 @@ class LayoutEngine(AdamSurface):
     def forward(self, batch: Dict[str, torch.Tensor], padded_slots: Optional[bool] = None) -> torch.Tensor:
         """Forward + fused loss (the loss kernel also leaves d(total)/d(out) in self.dout).
         Returns the device tensor {total, smooth_l1, iou, ce}.  padded_slots overrides the engine's setting for this
-        forward and the backward that follows it: a rollout window can hold padded slots where training batches never do.
-        Evaluation on a dropout engine too: only forward_backward / train_step drop."""
+        forward and the backward that follows it: a rollout window can hold padded slots where training batches never do."""
         return self._forward(batch, padded_slots, False)
 
     def _predict(self, batch: Dict[str, torch.Tensor], padded_slots: Optional[bool], train: bool) -> tuple:
@@ -782,8 +751,8 @@ class LayoutEngine(AdamSurface):
             close("l%d" % l)
         join()
         self._backward_tail(batch, B, T, N, M, reducer)
-        if self._dropped:            # the next training step draws new masks (a captured graph advances by replaying this launch)
-            self._timed("dropout_step", 0.0, "vlg_dropout_step_advance", ptr(self.drop_step), s, nbytes=8.0)
+        if self._dropped:            # the next training step draws new masks
+            self._advance_step("dropout_step", s)
 
     def _backward_tail(self, batch, B, T, N, M, reducer) -> None:
         cfg, d = self.cfg, self.cfg.d
@@ -802,8 +771,8 @@ class LayoutEngine(AdamSurface):
             batch = self._mix_inputs(batch)
         loss = self._forward(batch, None, True)       # (a training forward: the one place dropout is applied)
         self.backward(batch, reducer)
-        if self._sched is not None:                   # the next training step flips new coins (replayed by a captured graph)
-            self._timed("sched_step", 0.0, "vlg_dropout_step_advance", ptr(self.sched_counter), self._stream(), nbytes=8.0)
+        if self._sched is not None:                   # the next training step flips new coins
+            self._advance_step("sched_step", self._stream())
         return loss
 
     def train_step(self, batch: Dict[str, torch.Tensor], reducer=None) -> torch.Tensor:
@@ -863,17 +832,16 @@ class LayoutEngine(AdamSurface):
         static = {k: example_batch[k].clone() for k in ("slot_class", "slot_box", "tgt_class", "tgt_box", "valid")}
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
-        keep = (self.params.clone(), self.exp_avg.clone(), self.exp_avg_sq.clone(), counter.clone(), self.step_count)
-        # the recipe's state moves with the two capture passes too: the average, its bf16 copy, the outputs of ext
-        more = [t for t in (self.optim.ema, self.optim.ema_shadow, self.optim.guard.ext if self.optim.guard is not None else None,
-                            self.drop_step, self.sched_counter) if t is not None]
-        kept_more = [t.clone() for t in more]
+        # what the two capture passes move: parameters, moments, the optimiser's scalars, the recipe's state (the average, its
+        # bf16 copy, the outputs of ext) and the options' step counters
+        moved = [t for t in (self.params, self.exp_avg, self.exp_avg_sq, counter, self.optim.ema, self.optim.ema_shadow,
+                             self.optim.guard.ext if self.optim.guard is not None else None, *self._counters.values()) if t is not None]
+        kept, kept_steps = [t.clone() for t in moved], self.step_count
         def restore():
-            self.params.copy_(keep[0]); self.exp_avg.copy_(keep[1]); self.exp_avg_sq.copy_(keep[2])
-            counter.copy_(keep[3]); self.step_count = keep[4]
-            self._refresh_shadow()
-            for t, k in zip(more, kept_more):
+            for t, k in zip(moved, kept):
                 t.copy_(k)
+            self.step_count = kept_steps
+            self._refresh_shadow()
 
         with torch.cuda.stream(side):            # warm-up on a side stream, as stream capture requires
             self.train_step(static)
@@ -928,34 +896,29 @@ class LayoutEngine(AdamSurface):
         into the cache and returns the compact residual stream [B*N, d] leaving the last layer.  _encode with T = 1 and
         time_emb[p] on the compact set: the residual stream ping-pongs between xa and xb, one h and one stat serve every norm,
         and the qkv projection writes its rows into the cache with ldc = T*3d.  As many launches as on the window (1 + 7 per
-        layer), on 1/T of its rows.  Per-slot attention: vlg_attention_step.  Per-clip attention (clip_cache): the N queries of
-        frame p against every slot of the frames <= p, vlg_attention_clip_step, masked by the window's `valid` when
-        self._masked - its frame p is what the previous vlg_layout_decode_append wrote.  Factored attention: even layers
-        vlg_attention_step against the cache, odd layers vlg_attention_frame_step on the q k v rows the projection just wrote
-        at position p (no cache behind it; masked as per-clip's is)."""
+        layer), on 1/T of its rows.  Attention is the _step entry point of the layer's kind (vlg/attention.py): the queries of
+        frame p against the keys of the frames the kind sees (FRAME: the rows the projection just wrote, no cache behind it);
+        a per-clip kind is masked by the window's `valid` when self._masked - its frame p is what the previous
+        vlg_layout_decode_append wrote."""
         d, T, L = self.cfg.d, self.cfg.T, self.cfg.n_layers
         g, BN, s = self._grow_buffers(), B * N, self._stream()
         h, one = [g["h"]] * L, lambda name: [g[name]] * L
         w = types.SimpleNamespace(x=[g["xa"], g["xb"]] * L, h1=h, h2=h, qkv=[self.qkv[l].view(-1)[p * 3 * d:] for l in range(L)],
                                   att=one("att"), xmid=one("xmid"), u=one("u"), gl=one("gl"), stats=[g["stat"]] * (2 * L))
 
-        def attn_clip(l):
-            e = self.qkv.element_size()                             # q and o rows of the frame, k and v of p + 1 frames
-            self._timed("attn_clip_step", 4.0 * B * d * N * N * (p + 1), "vlg_attention_clip_step" + self._sfx, ptr(self.qkv[l]),
-                        ptr(valid) if self._masked else 0, ptr(g["att"]), B, T, N, d, p, d, s,
-                        nbytes=e * BN * d * (2.0 * (p + 1) + 2.0) + (4.0 * BN * (p + 1) if self._masked else 0.0))
-
         def attn(l):
-            self._timed("attn_step", 0.0, "vlg_attention_step" + self._sfx, ptr(self.qkv[l]), ptr(g["att"]), BN, T, d, p, d, s,
-                        nbytes=self.qkv.element_size() * BN * d * (2.0 * (p + 1) + 2.0))
+            k = self.attn[l]
+            frames = k.step_frames(p)           # q and o rows of frame p, k and v of the frames behind it (FRAME: its own alone)
+            nb = self.qkv.element_size() * BN * d * (2.0 * frames + 2.0)
+            if k.per_clip:
+                self._timed(k.family + "_step", 4.0 * B * d * k.step_pairs(N, p), k.stem + "_step" + self._sfx, ptr(self.qkv[l]),
+                            ptr(valid) if self._masked else 0, ptr(g["att"]), B, T, N, d, p, d, s,
+                            nbytes=nb + (4.0 * BN * frames if self._masked else 0.0))
+            else:
+                self._timed(k.family + "_step", 0.0, k.stem + "_step" + self._sfx, ptr(self.qkv[l]), ptr(g["att"]), BN, T, d, p, d, s,
+                            nbytes=nb)
 
-        def attn_frame(l):                                          # q, k, v and o rows of frame p alone: no cache behind it
-            self._timed("attn_frame_step", 4.0 * B * d * N * N, "vlg_attention_frame_step" + self._sfx, ptr(self.qkv[l]),
-                        ptr(valid) if self._masked else 0, ptr(g["att"]), B, T, N, d, p, d, s,
-                        nbytes=self.qkv.element_size() * BN * d * 4.0 + (4.0 * BN if self._masked else 0.0))
-
-        per_layer = lambda l: (attn_frame if self.cfg.frame_layer(l) else attn_clip if self.cfg.attention == "clip" else attn)(l)
-        self._encode(g["cls"], g["box"], self.p("time_emb")[p], w, per_layer, B, 1, N, ldc=T * 3 * d)
+        self._encode(g["cls"], g["box"], self.p("time_emb")[p], w, attn, B, 1, N, ldc=T * 3 * d)
         return w.x[L]
 
     def rollout(self, slot_class: torch.Tensor, slot_box: torch.Tensor, steps: int = 8, temperature: float = 0.0,
@@ -975,11 +938,9 @@ class LayoutEngine(AdamSurface):
         pass encodes that window once, reads frame P-1 (vlg_head_frame) and appends in place (vlg_layout_decode_append).
         Each further frame until the window is full is a CACHED step (cache None or True): the encoder runs on the newest
         frame's B*N rows only, against the keys and values self.qkv[l] already holds for the earlier positions
-        (_encode_step; vlg_attention_step, or with per-clip attention vlg_attention_clip_step under the window's valid).
-        Per-clip attention has the cached step only in an engine built with clip_cache=True: without the option it
-        re-encodes the window per grown frame and cache=True raises.  Factored attention is cached by default: even layers
-        vlg_attention_step, odd layers vlg_attention_frame_step on the newest frame's own rows.  cache=False always re-encodes.  Once the window is
-        full the steps are the sliding ones above, from the same buffers.
+        (_encode_step).  Which modes are cached by default: vlg/attention.py - per-clip attention only in an engine built with
+        clip_cache=True: without the option it re-encodes the window per grown frame and cache=True raises.  cache=False
+        always re-encodes.  Once the window is full the steps are the sliding ones above, from the same buffers.
         No loss, no targets, no host wait inside the loop (one before it with per-clip attention: the mask decision)."""
         cfg, d = self.cfg, self.cfg.d
         if slot_class.dim() != 3 or tuple(slot_box.shape) != tuple(slot_class.shape) + (BOX_DIM,):
@@ -989,7 +950,7 @@ class LayoutEngine(AdamSurface):
         M, BN = B * T * N, B * N
         if not 1 <= P <= T:
             raise ValueError("prompt has %d frames, the engine's window takes 1 to T=%d" % (P, T))
-        if cache and cfg.attention == "clip" and not self.clip_cache:
+        if cache and not self._cacheable:
             raise ValueError("cache=True: the cached step of per-clip attention is an option, LayoutEngine(clip_cache=True) / "
                              "VLG_GEN_CLIP_CACHE=1 (without it cache=None re-encodes the window)")
         if M > self.capacity:
@@ -1000,9 +961,8 @@ class LayoutEngine(AdamSurface):
         steps, top_k = int(steps), int(top_k)
         if steps < 1:
             raise ValueError("steps must be >= 1")
-        if not (math.isfinite(temperature) and temperature >= 0.0) or not 0 <= top_k <= cfg.n_classes:
-            raise ValueError("temperature must be finite and >= 0, top_k in [0, %d]" % cfg.n_classes)
-        cached = P < T and (cfg.attention != "clip" or self.clip_cache) and (cache is None or bool(cache))
+        decode_options(temperature, top_k, cfg.n_classes)
+        cached = P < T and self._cacheable and (cache is None or bool(cache))
         win = [(c[:M].view(B, T, N), b[:M].view(B, T, N, BOX_DIM), v[:M].view(B, T, N)) for c, b, v in self._windows()]
         if P == T:
             win[0][0].copy_(slot_class)
@@ -1016,7 +976,7 @@ class LayoutEngine(AdamSurface):
             torch.lt(win[0][0], cfg.n_classes, out=win[0][2])
         # per-clip attention: masks are decided ONCE, here (the only host wait of the call), on the prompt's real frames.  Later
         # frames are masked by the decode kernels' valid; they never gain a padded slot the prompt did not have
-        self._masked = cfg.attention in ("clip", "factored") and (self.padded_slots or bool((win[0][2][:, :P] == 0).any()))
+        self._masked = self._per_clip and (self.padded_slots or bool((win[0][2][:, :P] == 0).any()))
         gen_cls = torch.empty(B, steps, N, dtype=torch.int64, device=self.device)
         gen_box = torch.empty(B, steps, N, BOX_DIM, dtype=torch.float32, device=self.device)
         logits = torch.empty(steps, BN, cfg.n_out, dtype=torch.float32, device=self.device)

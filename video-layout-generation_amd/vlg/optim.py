@@ -26,7 +26,7 @@ import torch
 
 from . import hip
 from .hip import call, ptr
-from .spec import ADAM_BETA2, ADAM_EPS
+from .spec import ADAM_BETA2, ADAM_EPS, recipe_options
 
 # slots of ctl (VLG_CTL_* in include/vlg_hip.h)
 STEP_SIZE, SQRT_BC2, STEP, APPLY, GRAD_MULT, GRAD_NORM, LR, SKIPPED, CLIP_COEF, CTL_FLOATS = 0, 1, 2, 3, 4, 5, 6, 7, 8, 16
@@ -171,10 +171,8 @@ class FlatAdam:
                  warmup_steps: int = 0, ema_decay: float = 0.0, ema_warmup: bool = False,
                  decay_mask: Optional[torch.Tensor] = None, ema_shadow: bool = False):
         self.n, self.device, self.shadow = int(n), device, shadow
-        self.weight_decay, self.warmup_steps = float(weight_decay), int(warmup_steps)
-        self.ema_decay, self.ema_warmup = float(ema_decay), bool(ema_warmup)
-        if self.weight_decay < 0.0 or self.warmup_steps < 0 or not 0.0 <= self.ema_decay < 1.0:
-            raise ValueError("weight_decay and warmup_steps must be >= 0 and ema_decay in [0, 1)")
+        self.weight_decay, self.warmup_steps, self.ema_decay = recipe_options(weight_decay, warmup_steps, ema_decay)
+        self.ema_warmup = bool(ema_warmup)
         self.ema: Optional[torch.Tensor] = None
         self.ema_shadow: Optional[torch.Tensor] = None
         self.decay_mask: Optional[torch.Tensor] = None

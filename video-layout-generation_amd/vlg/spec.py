@@ -20,6 +20,8 @@ import math
 from collections import OrderedDict
 from typing import Dict, Tuple
 
+from .attention import FRAME, MODES, layer_kinds
+
 # ---- reference-real constants -------------------------------------------------
 N_CLASSES = 20                  # reference src/models/gridnet.py:9 (seg_out = 20), trainer.py:31-52
 LOSS_W_REG = 40.0               # reference src/trainer.py:248  (L1 term  * 40)
@@ -52,10 +54,8 @@ class LayoutConfig:
     d: int = 256                # token width
     n_layers: int = 4
     n_classes: int = N_CLASSES
-    # "slot": causal attention along T independently per (clip, slot) - the default the headline is quoted on;
-    # "clip": block-causal attention over all T*N tokens of a clip (token (t, n) sees every slot of frames <= t);
-    # "factored": divided space-time attention - even layers are "slot"'s, odd layers attend across the slots of one frame
-    # (not causal in n, nothing crosses frames).  Same parameters and checkpoints as the other two; n_layers = 1 is "slot"
+    # vlg/attention.py MODES: "slot" - the default the headline is quoted on -, "clip", or "factored" (divided space-time
+    # attention).  Same parameters and checkpoints in all three; "factored" with n_layers = 1 is "slot"
     attention: str = "slot"
 
     @property
@@ -89,16 +89,16 @@ class LayoutConfig:
             raise ValueError("B, N, n_layers must be >= 1")
         if self.attention not in ATTENTION_MODES:
             raise ValueError("attention must be 'slot', 'clip' or 'factored'")
-        if self.attention in ("clip", "factored") and (self.T * self.N) % 32 != 0:
+        if any(k.per_clip for k in MODES[self.attention]) and (self.T * self.N) % 32 != 0:
             raise ValueError("attention=%r needs T*N to be a multiple of 32 (32-token MFMA tiles)" % self.attention)
 
     def frame_layer(self, l: int) -> bool:
         """whether layer l attends inside a frame (the odd layers of "factored") instead of along time per slot"""
-        return self.attention == "factored" and l % 2 == 1
+        return layer_kinds(self.attention, l + 1)[l] is FRAME
 
     @property
     def n_frame_layers(self) -> int:
-        return self.n_layers // 2 if self.attention == "factored" else 0
+        return layer_kinds(self.attention, self.n_layers).count(FRAME)
 
     def describe(self) -> Dict[str, object]:
         return {"B": self.B, "T": self.T, "N": self.N, "d": self.d, "layers": self.n_layers,
@@ -109,7 +109,7 @@ class LayoutConfig:
                 "loss": "40*smoothL1(beta=%g)+20*(1-IoU)+10*CE" % SMOOTH_L1_BETA}
 
 
-ATTENTION_MODES = ("slot", "clip", "factored")
+ATTENTION_MODES = tuple(MODES)            # "slot", "clip", "factored": vlg/attention.py
 BOX_OVERLAPS = ("iou", "giou")
 
 
@@ -136,6 +136,41 @@ def loss_options(class_weights=None, label_smoothing: float = 0.0, box_overlap: 
     if box_overlap not in BOX_OVERLAPS:
         raise ValueError("box_overlap must be one of %s, got %r" % (BOX_OVERLAPS, box_overlap))
     return weights, eps, box_overlap
+
+
+# The other options' rules, in loss_options' shape: checked on the host, normalised values back or ValueError.  `names` are
+# what the message calls the values - LayoutEngine and FlatAdam pass their keywords, the trainer its environment variables.
+def dropout_options(p, name: str = "dropout") -> float:
+    """dropout probability in [0, 1); 0 is off"""
+    if not 0.0 <= float(p) < 1.0:                       # (also refuses NaN)
+        raise ValueError("%s must be in [0, 1), got %r" % (name, p))
+    return float(p)
+
+
+def decode_options(temperature, top_k, n_classes: int = N_CLASSES, names=("temperature", "top_k")):
+    """the decoding rule's knobs (rollout, scheduled sampling): temperature finite and >= 0 (0 = argmax), top_k in
+    [0, n_classes] (0 = every class)"""
+    if not (math.isfinite(temperature) and temperature >= 0.0) or not 0 <= int(top_k) <= n_classes:
+        raise ValueError("%s must be finite and >= 0, %s in [0, %d]" % (names + (n_classes,)))
+    return float(temperature), int(top_k)
+
+
+def sched_options(eps_max, ramp_steps=0, temperature=0.0, top_k=0, n_classes: int = N_CLASSES,
+                  names=("sched_sampling", "sched_ramp_steps", "sched_temperature", "sched_top_k")):
+    """scheduled sampling, once it is on: (eps_max in [0, 1], ramp_steps in [0, 2^31), temperature, top_k as decode_options)"""
+    if not 0.0 <= float(eps_max) <= 1.0:                # (also refuses NaN)
+        raise ValueError("%s must be in [0, 1], got %r" % (names[0], eps_max))
+    if not 0 <= int(ramp_steps) < 2 ** 31:
+        raise ValueError("%s must be in [0, 2^31), got %r" % (names[1], ramp_steps))
+    return (float(eps_max), int(ramp_steps)) + decode_options(float(temperature), top_k, n_classes, names[2:])
+
+
+def recipe_options(weight_decay=0.0, warmup_steps=0, ema_decay=0.0, names=("weight_decay", "warmup_steps", "ema_decay")):
+    """the optimiser recipe: (weight_decay >= 0, warmup_steps >= 0, ema_decay in [0, 1)); each is off at 0"""
+    weight_decay, warmup_steps, ema_decay = float(weight_decay), int(warmup_steps), float(ema_decay)
+    if weight_decay < 0.0 or warmup_steps < 0 or not 0.0 <= ema_decay < 1.0:
+        raise ValueError("%s and %s must be >= 0, %s in [0, 1)" % tuple(names))
+    return weight_decay, warmup_steps, ema_decay
 
 
 def param_shapes(cfg: LayoutConfig) ->"OrderedDict[str, Tuple[int, ...]]":
@@ -188,13 +223,11 @@ def step_flops(cfg: LayoutConfig) -> Dict[str, float]:
     """Algorithmic FLOPs of one training step (Spec N)."""
     M, d = cfg.tokens, cfg.d
     per_layer_fwd = 24.0 * M * d * d            # QKV 6 + proj 2 + FFN 16  (x M d^2)
-    attn_fwd = 4.0 * cfg.B * cfg.N * cfg.T * cfg.T * d / 2.0   # causal half
-    if cfg.attention == "clip":                                # allowed (query, key) pairs per clip: N^2 T (T + 1) / 2
-        attn_fwd = 4.0 * cfg.B * d * cfg.N * cfg.N * cfg.T * (cfg.T + 1) / 2.0
+    # a layer's attention by its kind: 4 d flop per visible (query, key) pair - per slot the causal half T^2 / 2, as ever
+    kinds = [4.0 * cfg.B * d * k.pairs(cfg.T, cfg.N) if k.per_clip else 4.0 * cfg.B * cfg.N * cfg.T * cfg.T * d / 2.0
+             for k in layer_kinds(cfg.attention, cfg.n_layers)]
+    attn_fwd = kinds[0] + sum(f - kinds[0] for f in kinds) / cfg.n_layers       # the mean over the layers
     head_fwd = 2.0 * M * d * cfg.n_out
-    if cfg.attention == "factored":                            # odd layers: N^2 T pairs per clip, inside the frames
-        frame_fwd = 4.0 * cfg.B * d * cfg.N * cfg.N * cfg.T
-        attn_fwd += (frame_fwd - attn_fwd) * cfg.n_frame_layers / cfg.n_layers      # the mean over the layers
     fwd = cfg.n_layers * (per_layer_fwd + attn_fwd) + head_fwd
     # backward = 2 x forward for the projections; attention backward = 2.5 x its forward (5 products against 2)
     return {"gemm_fwd_per_layer": per_layer_fwd, "fwd": fwd, "fwd_bwd": 3.0 * fwd + 0.5 * cfg.n_layers * attn_fwd}
