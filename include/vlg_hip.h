@@ -504,6 +504,58 @@ int vlg_layout_metrics(const float* out, int ld, const int64_t* tgt_class, const
                        int tgt_T, int t0, int64_t* counts, double* sums, void* scratch,
                        int B, int T, int N, int n_classes, int top_k, float iou_thr, float iou_eps, void* stream);
 
+/* ------------------------------------------------------------------ rasterised layouts (csrc/raster.hip)
+ * Draws layouts - the slots of a frame as (class, cx, cy, w, h) - into label maps, and counts a confusion matrix of two
+ * label maps.  SELF-ORACLE (tests/raster_ref.py restates the definition in fp32 numpy; every quantity below is ONE
+ * correctly rounded fp32 operation, so the device matches it exactly); DESIGN.md, "Rasterised layouts".
+ *
+ * vlg_layout_rasterize
+ *   inputs    cls (B,T_buf,N) int64, box (B,T_buf,N,4) fp32 cxcywh, valid (B,T_buf,N) fp32 or NULL, public order.  Frames
+ *             t0 .. t0+T-1 of every clip are drawn into labels (B,T,H,W); the clip is read in place, as vlg_layout_metrics
+ *             reads its targets
+ *   drawn     a slot is drawn iff (valid == NULL or valid != 0) and 0 <= cls < n_classes and all four box values are
+ *             finite and w > 0 and h > 0
+ *   edges     in pixel units, one rounded fp32 operation per step:  hw = 0.5f*w;  X0 = (cx - hw) * (float)W;
+ *             X1 = (cx + hw) * (float)W;  Y0, Y1 likewise from cy, h, H.  (Contracting cx - 0.5f*w into an fma changes
+ *             nothing: 0.5f*w is exact.  No other step has the fma shape.)
+ *   coverage  pixel (y,x) is covered iff X0 <= x + 0.5f < X1 and Y0 <= y + 0.5f < Y1: centres decide, left/top edges are
+ *             inclusive, right/bottom exclusive.  Nothing is clamped: a box that hangs over the border is clipped by the
+ *             image, a box thinner than a pixel may cover no centre
+ *   winner    of a pixel: the covering drawn slot with the smallest (area, n), area = w*h one rounded multiplication; the
+ *             lower slot index wins equal areas; small objects lie on top
+ *   label     what = VLG_RASTER_CLASS: the winner's class; VLG_RASTER_SLOT: its slot index n; no winner: `background`
+ *   out_kind  VLG_LABEL_U8 (1 B per pixel, what vlg_label_confusion reads), VLG_LABEL_I64 (the dtype of a cross-entropy
+ *             target), VLG_LABEL_F32 (the dtype of the pixel model's segmentation input)
+ * Worked example (H = 8, W = 16, background 20): slot 0 = class 3, box (.5,.5,.5,.5); slot 1 = class 5, box
+ * (.5,.5,.25,.25); slot 2 = class 7, box (.25,.5,.25,.25).  Rows 2 and 5 are 20 x4, 3 x8, 20 x4; rows 3 and 4 are
+ * 20 20 7 7 7 7 5 5 5 5 3 3 20 20 20 20; every other row is background.
+ * Refusals, all before anything is enqueued.  VLG_ERR_SHAPE: B, T, N or H < 1; t0 < 0 or t0 + T > T_buf; N > 1024;
+ * n_classes < 1 or > 255; W < 16 or W % 16 != 0; H or W > 16384; background outside [0, 255]; an unknown out_kind or what;
+ * what = SLOT with U8 and N > 255; a NULL cls, box or labels; labels overlapping an input.  VLG_ERR_ALIGN: box or labels
+ * not 16-byte aligned, cls not 8-byte aligned, valid not 4-byte aligned.
+ * Writes: every element of labels exactly once, by one thread, with plain vector stores; nothing else.  No atomics, no
+ * scratch, no block waits for another.
+ *
+ * vlg_label_confusion
+ *   pred, truth  (B,T,hw) uint8 label maps.  counts: per_frame ? T : 1 rows of n_labels*n_labels + 1 int64, ADDED TO
+ *   pixel (b,t,i) goes to row t (row 0 without per_frame) and adds 1 to [truth*n_labels + pred] - the orientation of
+ *   VLG_MET_CONF - or, if either label is >= n_labels, to the row's last slot (IGNORED).  Per launch the rows grow by
+ *   exactly B*T*hw in total.  Per-block LDS histogram; non-zero bins leave as 64-bit integer atomics, as vlg_layout_metrics'
+ *   counts do: exact whatever the schedule, no scratch.
+ * VLG_ERR_SHAPE: n_labels outside [1, 32]; hw < 16 or hw % 16 != 0; B*T*hw >= 2^31; B or T < 1; a NULL pointer; per_frame
+ * with T > 65535 (the frame is a grid dimension).
+ * VLG_ERR_ALIGN: the maps not 16-byte aligned or counts not 8-byte aligned.  A refused call enqueues nothing. */
+#define VLG_LABEL_U8     0
+#define VLG_LABEL_I64    1
+#define VLG_LABEL_F32    2
+#define VLG_RASTER_CLASS 0
+#define VLG_RASTER_SLOT  1
+int vlg_layout_rasterize(const int64_t* cls, const float* box, const float* valid, void* labels,
+                         int B, int T_buf, int t0, int T, int N, int n_classes, int H, int W,
+                         int out_kind, int what, int background, void* stream);
+int vlg_label_confusion(const uint8_t* pred, const uint8_t* truth, int64_t* counts,
+                        int B, int T, int64_t hw, int n_labels, int per_frame, void* stream);
+
 /* ------------------------------------------------------------------ reductions */
 int vlg_reduce_slabs(const float* slabs, int64_t slab_stride, int n_slabs,
                      float* dst, int64_t len, void* stream);

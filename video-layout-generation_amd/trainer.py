@@ -68,6 +68,12 @@ one host read per pass; the returned dict gains those keys.  args.val_topk / VLG
 accuracy, args.val_iou_thr / VLG_VAL_IOU_THR (0.5) the IoU threshold; evaluate_rollout uses the same two.  Off (the default)
 validate() returns {"loss": ...} as before.
 
+Pixel score of rollouts in layout mode (csrc/raster.hip, vlg/raster.py, DESIGN.md "Rasterised layouts"): args.val_pixels /
+VLG_VAL_PIXELS = HxW (off by default; legal sizes: vlg.raster.raster_options) makes evaluate_rollout also draw the decoded
+frames and the frames that really followed as H x W class maps on the device and score them pixel by pixel: each
+horizon's dict gains pixel_miou, pixel_accuracy, pixel_per_class_iou and pixel_background_iou.  render_layout() draws any
+layout into label maps, also as the float maps the pixel model's generate_sequence takes.
+
 Repairs of reference defects, all stated: gradients are overwritten each
 step (A-5 zero_grad), the train log line uses the `loss` key (A-6), one checkpoint schema
 {'epoch','arch','gridnet','optimizer'} for save/--ckpt/--resume (A-1,A-8,A-9), `.model` exists
@@ -90,6 +96,7 @@ import torch.distributed as dist
 from vlg.data import BATCH_KEYS, BucketedClipLoader, ClipLoader, synthetic_clips, to_device
 from vlg.dp import GradReducer, bucket_ranges
 from vlg.optim import decayed_lr
+from vlg.raster import parse_size, raster_options
 from vlg.spec import (ADAM_BETA1, ADAM_LR, N_CLASSES, SEED, LayoutConfig, dropout_options, loss_options, recipe_options,
                       sched_options)
 
@@ -258,6 +265,18 @@ def metrics_knobs(args) -> Dict[str, object]:
     return {"on": bool(_knob(args, "val_metrics", "VLG_VAL_METRICS", 0)),
             "top_k": _knob(args, "val_topk", "VLG_VAL_TOPK", 5),
             "iou_thr": _knob_float(args, "val_iou_thr", "VLG_VAL_IOU_THR", 0.5)}
+
+
+def pixel_knobs(args) -> Dict[str, object]:
+    """{size: (H, W)} of the rollouts' pixel score in layout mode from args.val_pixels / VLG_VAL_PIXELS = "HxW" (module
+    docstring); {} with the knob off (unset, empty or 0).  An (H, W) pair is taken as it is; a size the rasteriser does not
+    take raises ValueError here."""
+    v = getattr(args, "val_pixels", None)
+    if v is None:
+        v = os.environ.get("VLG_VAL_PIXELS", "")
+    if v in ("", "0", 0, False):
+        return {}
+    return {"size": raster_options(parse_size(v) if isinstance(v, str) else v, None, N_CLASSES)[0]}
 
 
 def epoch_lr(args, epoch: int) -> float:
@@ -786,7 +805,9 @@ class Trainer:
         seed / keep_padded are the generation knobs of generate_sequence (None = from args or the environment);
         val_topk / val_iou_thr the metric's (None = metrics_knobs).  A step is scored on the model's distribution at that
         step (arg-max, rank and NLL of the logits, box = sigmoid(raw)), also when the history was sampled.
-        Returns a list of S summary dicts (vlg/metrics.py), one per horizon step."""
+        Returns a list of S summary dicts (vlg/metrics.py), one per horizon step.  With the pixel knob on (pixel_knobs) the
+        decoded frames and the true ones are also drawn and compared pixel by pixel (LayoutEngine.evaluate_rollout's
+        pixel_record), and each dict gains pixel_miou, pixel_accuracy, pixel_per_class_iou and pixel_background_iou."""
         if self.image_mode or not hasattr(self.engine, "evaluate_rollout"):
             raise ValueError("evaluate_rollout needs the layout engine with evaluate_rollout() (vlg.engine.LayoutEngine: the "
                              "vlg_layout_metrics kernel); %s has none" % type(self.engine).__name__)
@@ -795,14 +816,40 @@ class Trainer:
             if given is not None:
                 knobs[name] = type(knobs[name])(given)
         mk = metrics_knobs(self.args)
+        pk, pixels = pixel_knobs(self.args), {}
+        if pk:
+            P = self.cfg.T if prompt_frames is None else int(prompt_frames)
+            pixels = {"pixel_record": self.engine.pixel_record(max(1, clip_class.shape[1] - P)), "pixel_size": pk["size"]}
         with self._eval_weights():
             record = self.engine.evaluate_rollout(
                 clip_class.to(self.device).contiguous(), clip_box.to(self.device).contiguous(),
                 top_k=mk["top_k"] if val_topk is None else int(val_topk),
                 iou_thr=mk["iou_thr"] if val_iou_thr is None else float(val_iou_thr),
                 temperature=knobs["temperature"], sample_top_k=knobs["top_k"], seed=knobs["seed"], keep_padded=knobs["keep_padded"],
-                prompt_frames=prompt_frames)
-        return record.summary()
+                prompt_frames=prompt_frames, **pixels)
+        out = record.summary()
+        if pk:
+            for s, p in zip(out, pixels["pixel_record"].summary()):
+                s.update(pixel_miou=p["miou"], pixel_accuracy=p["pixel_accuracy"], pixel_per_class_iou=p["per_class_iou"],
+                         pixel_background_iou=p["background_iou"])
+        return out
+
+    def render_layout(self, slot_class, slot_box, size=None, valid=None, what: str = "class", dtype=torch.float32):
+        """Layout mode: draw layouts into label maps on the device (LayoutEngine.rasterize) and return them on the CPU.
+        slot_class (B,T,N) / slot_box (B,T,N,4) / valid (B,T,N) or None, CPU or device tensors; size = (H, W), None takes
+        the pixel knob's (pixel_knobs).  Returns (B,T,H,W) of `dtype`: with the default float32, [:, t:t+1] is a
+        segmentation-id argument of the pixel model's generate_sequence; what = "slot" gives slot indices instead of
+        classes."""
+        if self.image_mode or not hasattr(self.engine, "rasterize"):
+            raise ValueError("render_layout needs the layout engine with rasterize() (vlg.engine.LayoutEngine: the "
+                             "vlg_layout_rasterize kernel); %s has none" % type(self.engine).__name__)
+        if size is None:
+            size = pixel_knobs(self.args).get("size")
+            if size is None:
+                raise ValueError("render_layout needs size=(H, W) or the pixel knob (args.val_pixels / VLG_VAL_PIXELS=HxW)")
+        v = None if valid is None else valid.to(self.device, torch.float32).contiguous()
+        return self.engine.rasterize(slot_class.to(self.device).contiguous(), slot_box.to(self.device).contiguous(), size,
+                                     valid=v, what=what, dtype=dtype).cpu()
 
     def eval_generate_sequence(self, img1, img2, seg1, seg2):
         """main.py:64-67 entry (reference src/trainer.py:429-451): read two frames and two segmentation-id maps from

@@ -33,6 +33,7 @@ import torch
 from . import hip
 from .attention import MODES, cached_by_default, layer_kinds, lse_rows
 from .metrics import MetricsRecord
+from .raster import MAX_SLOTS, WHATS, PixelRecord, raster_options
 from .optim import AdamSurface, FlatAdam, build_decay_mask, decays_matrix
 from .slabs import SlabBuckets
 from .hip import (EPI_A_BF16, EPI_B_BF16, EPI_BIAS, EPI_DGELU, EPI_GELU, EPI_NONE, EPI_OUT_BF16, EPI_RESID,
@@ -1038,7 +1039,7 @@ class LayoutEngine(AdamSurface):
     def evaluate_rollout(self, clip_class: torch.Tensor, clip_box: torch.Tensor, record: Optional[MetricsRecord] = None,
                          top_k: int = 5, iou_thr: float = 0.5, return_logits: bool = False, temperature: float = 0.0,
                          sample_top_k: int = 0, seed: int = 0, keep_padded: bool = False, prompt_frames: Optional[int] = None,
-                         cache: Optional[bool] = None):
+                         cache: Optional[bool] = None, pixel_record: Optional[PixelRecord] = None, pixel_size=None):
         """Score a rollout against the frames that really followed.  clip_class (B,P+S,N) int64 and clip_box (B,P+S,N,4)
         fp32 are device tensors: the first P = prompt_frames frames (None: T; 1 <= P <= T; `cache` as rollout takes it) are
         the prompt, rollout(..., steps=S) generates S frames under the sampling knobs (temperature, sample_top_k =
@@ -1049,6 +1050,11 @@ class LayoutEngine(AdamSurface):
         A step is scored on the model's DISTRIBUTION at that step - arg-max, rank and NLL of its logits, box =
         sigmoid(raw) - not on the class that was drawn: with temperature > 0 the history the model conditions on is
         sampled, the score is still that of the logits.
+        pixel_record (engine.pixel_record(S)) with pixel_size = (H, W) adds the score of the frames that were actually
+        DRAWN and fed back: the decoded gen_cls / gen_box and frames P .. P+S-1 of the clip (read in place) are rasterised
+        as uint8 class maps into two engine-owned buffers, and one vlg_label_confusion launch adds horizon step i to row i
+        of the pixel record - three more launches, no host wait; the token record and the return value are what they are
+        without it.
         Returns the record, or (record, gen_cls, gen_box, logits) with return_logits."""
         cfg = self.cfg
         if clip_class.dim() != 3 or tuple(clip_box.shape) != tuple(clip_class.shape) + (BOX_DIM,):
@@ -1067,12 +1073,84 @@ class LayoutEngine(AdamSurface):
             record = self.metrics_record(S)
         elif record.rows < S:
             raise ValueError("the record has %d rows, the rollout %d steps" % (record.rows, S))
+        size = self._check_pixels(pixel_record, S, pixel_size) if pixel_record is not None else None
         gen_cls, gen_box, logits = self.rollout(clip_class[:, :P], clip_box[:, :P], steps=S, temperature=temperature,
                                                 top_k=sample_top_k, seed=seed, keep_padded=keep_padded, return_logits=True,
                                                 cache=cache)
         for i in range(S):
             self._metrics(logits[i], cfg.n_out, clip_class, clip_box, None, TS, P + i, record, i, B, 1, N, top_k, iou_thr)
+        if pixel_record is not None:
+            self._score_pixels(gen_cls, gen_box, clip_class, clip_box, P, pixel_record, size)
         return (record, gen_cls, gen_box, logits) if return_logits else record
+
+    # --------------------------------------------------------------------- rasterised layouts
+    _LABEL_KINDS = {torch.uint8: hip.LABEL_U8, torch.int64: hip.LABEL_I64, torch.float32: hip.LABEL_F32}
+
+    def pixel_record(self, rows: int = 1) -> PixelRecord:
+        """A zeroed PixelRecord (vlg/raster.py) on the engine's device, `rows` independent rows."""
+        return PixelRecord(self.cfg.n_classes, rows, self.device)
+
+    def rasterize(self, slot_class: torch.Tensor, slot_box: torch.Tensor, size, valid: Optional[torch.Tensor] = None,
+                  frames: Optional[tuple] = None, dtype: torch.dtype = torch.int64, what: str = "class",
+                  background: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Draw layouts into label maps on the device: one launch of vlg_layout_rasterize (definition: include/vlg_hip.h),
+        no host wait.  slot_class (B,T,N) int64, slot_box (B,T,N,4) fp32 and valid (B,T,N) fp32 or None are contiguous
+        device tensors and are read in place; frames = (t0, T') draws frames t0 .. t0+T'-1 only.  Returns (B,T',H,W) of
+        `dtype` - uint8 (what the pixel score reads), int64 (a cross-entropy target) or float32 (the pixel model's
+        segmentation input) - holding per pixel the class of the smallest covering slot (what = "class") or its slot index
+        ("slot"), and `background` where there is none (None: n_classes for classes, N for slots).  `out` is written if
+        given (same shape and dtype, contiguous).  Legal sizes: vlg.raster.raster_options."""
+        if slot_class.dim() != 3 or tuple(slot_box.shape) != tuple(slot_class.shape) + (BOX_DIM,):
+            raise ValueError("rasterize takes slot_class (B,T,N) and slot_box (B,T,N,4)")
+        B, Tb, N = slot_class.shape
+        if what not in WHATS:
+            raise ValueError("what must be one of %s, got %r" % (WHATS, what))
+        if dtype not in self._LABEL_KINDS:
+            raise ValueError("dtype must be torch.uint8, torch.int64 or torch.float32, got %r" % (dtype,))
+        if not 1 <= N <= MAX_SLOTS or (what == "slot" and dtype == torch.uint8 and N > 255):
+            raise ValueError("rasterize draws 1 to %d slots per frame (slot indices as uint8: at most 255), got %d" % (MAX_SLOTS, N))
+        (H, W), bg = raster_options(size, (self.cfg.n_classes if what == "class" else N) if background is None else background,
+                                    self.cfg.n_classes)
+        t0, T = (0, Tb) if frames is None else (int(frames[0]), int(frames[1]))
+        if T < 1 or t0 < 0 or t0 + T > Tb:
+            raise ValueError("frames = (t0, T) must lie inside the clip's %d frames, got %r" % (Tb, frames))
+        tensors = [(slot_class, torch.int64, "slot_class", (B, Tb, N)), (slot_box, torch.float32, "slot_box", (B, Tb, N, BOX_DIM))]
+        if valid is not None:
+            tensors.append((valid, torch.float32, "valid", (B, Tb, N)))
+        for t, dt, name, shape in tensors:
+            if t.dtype != dt or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError("%s must be a contiguous %s HIP tensor of shape %s" % (name, dt, shape))
+        if out is None:
+            out = torch.empty(B, T, H, W, dtype=dtype, device=self.device)
+        elif out.dtype != dtype or tuple(out.shape) != (B, T, H, W) or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("out must be a contiguous %s HIP tensor of shape %s" % (dtype, (B, T, H, W)))
+        self._timed("raster", 0.0, "vlg_layout_rasterize", ptr(slot_class), ptr(slot_box), ptr(valid), ptr(out), B, Tb, t0, T,
+                    N, self.cfg.n_classes, H, W, self._LABEL_KINDS[dtype], WHATS.index(what), bg, self._stream(),
+                    nbytes=float(out.numel() * out.element_size()) + 28.0 * B * T * N)
+        return out
+
+    def _check_pixels(self, record, S: int, size) -> tuple:
+        C = self.cfg.n_classes
+        if not isinstance(record, PixelRecord) or record.n_classes != C or not record.counts.is_cuda:
+            raise ValueError("pixel_record must be a PixelRecord of %d classes on %s (engine.pixel_record())" % (C, self.device))
+        if record.rows < S:
+            raise ValueError("the pixel record has %d rows, the rollout %d steps" % (record.rows, S))
+        if size is None:
+            raise ValueError("a pixel record needs pixel_size=(H, W)")
+        return raster_options(size, None, C)[0]
+
+    def _score_pixels(self, gen_cls, gen_box, clip_class, clip_box, P: int, record: PixelRecord, size: tuple) -> None:
+        """evaluate_rollout's pixel score: three launches, no host wait"""
+        B, S, N = gen_cls.shape
+        key = (B, S) + size
+        if getattr(self, "_pixel_maps_key", None) != key:                 # the two label buffers, allocated on first use
+            self._pixel_maps = torch.empty((2,) + key, dtype=torch.uint8, device=self.device)
+            self._pixel_maps_key = key
+        drawn, truth = self._pixel_maps[0], self._pixel_maps[1]
+        self.rasterize(gen_cls, gen_box, size, dtype=torch.uint8, out=drawn)
+        self.rasterize(clip_class, clip_box, size, frames=(P, S), dtype=torch.uint8, out=truth)
+        self._timed("confusion", 0.0, "vlg_label_confusion", ptr(drawn), ptr(truth), ptr(record.counts), B, S,
+                    size[0] * size[1], record.n_labels, 1, self._stream(), nbytes=2.0 * drawn.numel())
 
     # ---------------------------------------------------------------- public views
     def outputs_btn(self) -> tuple:

@@ -80,6 +80,8 @@ SIGNATURES = {
     "vlg_layout_metrics_sums": (I, [I]),
     "vlg_layout_metrics_scratch": (I, []),
     "vlg_layout_metrics": (I, [P, I, P, P, P, I, I, P, P, P, I, I, I, I, I, F, F, P]),
+    "vlg_layout_rasterize": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P]),
+    "vlg_label_confusion": (I, [P, P, P, I, I, L, I, I, P]),
     "vlg_reduce_slabs": (I, [P, L, I, P, L, P]),
     "vlg_reduce_slabs_table": (I, [P, I, I, P]),
     "vlg_sum_partials_table": (I, [P, I, P]),
@@ -140,6 +142,8 @@ DIAG_SIGNATURES = {
     "vlg_debug_set_gemm_run": (None, [I]),
 }
 LOSS_GIOU = 1                          # vlg_layout_loss_ext flags (VLG_LOSS_GIOU)
+LABEL_U8, LABEL_I64, LABEL_F32 = 0, 1, 2   # vlg_layout_rasterize out_kind (VLG_LABEL_*)
+RASTER_CLASS, RASTER_SLOT = 0, 1           # ... and what (VLG_RASTER_*)
 CEPI_BIAS, CEPI_RESID, CEPI_PRELU, CEPI_DPRELU, CEPI_ACCUM, CEPI_CIN4 = 1, 2, 4, 8, 16, 32
 CONV_PRECISIONS = ("fp32", "bf16")     # 3x3 convolutions: fp32 MFMA (conv.hip) or bf16-operand MFMA (conv_bf16.hip)
 
