@@ -165,6 +165,23 @@ def test_temporal_attention_exact(H, dev, T, d, n_seq, bf16):
     assert bool(torch.isnan(heads(dq4, 3)[s, h, :i + 1, 1:]).all()), "dk / dv of frames <= the poisoned one not all NaN"
 
 
+@pytest.mark.parametrize("bf16", [False, True], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("d,n_seq", [(64, 5), (192, 3)])
+def test_temporal_attention_first_block_is_t16(H, dev, d, n_seq, bf16):
+    """Bit for bit: the MFMA scheme is one body over T / 16 query blocks, so frames 0..15 of a T = 32 sequence get what the
+    T = 16 kernel computes on those frames alone - the output, and with dout = 0 on frames 16..31 (the later query block
+    then adds exact zeros to dk, dv of the first key tile) also dq, dk, dv."""
+    qkv, do = _attn_inputs(32, d, n_seq, seed=32 + d + n_seq, bf16=bf16)
+    do[:, 16:] = 0
+    o32, dq32 = _attn_run(H, dev, qkv, do, bf16)
+    o16, dq16 = _attn_run(H, dev, qkv[:, :16], do[:, :16], bf16)
+    first = lambda x: x.view(n_seq, 32, -1)[:, :16].reshape(n_seq * 16, -1)
+    assert torch.equal(first(o32), o16), "output of frames 0..15 at T = 32 differs from T = 16"
+    for i, name in enumerate(("dq", "dk", "dv")):
+        sl = slice(i * d, (i + 1) * d)
+        assert torch.equal(first(dq32)[:, sl], dq16[:, sl]), "%s of frames 0..15 at T = 32 differs from T = 16" % name
+
+
 # ------------------------------------------------------------------------------------------------ per-clip attention fp32
 def _to_rows(t):
     """(B,T,N,C) -> the internal row order (b, n, t)"""
