@@ -454,6 +454,57 @@ int vlg_layout_mix_inputs(const float* out, int ld, const int64_t* cls, const fl
                           int B, int T, int N, int n_classes, uint32_t thr_max, int ramp_steps,
                           float temperature, int top_k, uint64_t seed, void* stream);
 
+/* ------------------------------------------------------------------ augmentation (csrc/augment.hip)
+ * SELF-ORACLE (tests/augment_ref.py restates it); DESIGN.md, "Augmentation".  Builds the batch a training step runs on
+ * from the caller's batch: per clip a horizontal flip, a zoom about the image centre and a shift, per input token a
+ * jitter, per track (one slot of one clip, all its frames) a drop.  One launch.
+ *   cls, box        the inputs slot_class (B,T,N) int64 / slot_box (B,T,N,4) fp32 (cx, cy, w, h), public order, only read
+ *   tgt_box, valid  the targets' boxes (B,T,N,4) fp32 and valid (B,T,N) fp32, only read.  tgt_class has no part in it:
+ *                   the step keeps reading the caller's
+ *   aug_cls, aug_box, aug_tgt_box, aug_valid   the augmented batch, same shapes; every element is written, each by exactly
+ *                   one thread (plain vector stores)
+ *   step            int32 in DEVICE memory: the step counter k, read when the kernel runs (a captured graph advances it by
+ *                   replaying vlg_dropout_step_advance on it)
+ * Token i = (b*T + t)*N + n, track r = b*N + n.  W(c0,c1,c2,c3) = the four words of Philox4x32-10 on that counter under key
+ * (seed & 0xffffffff, seed >> 32);  v(x) = (float)(x >> 8) * 2^-23 - 1, in [-1, 1) and exact in fp32;
+ * coin(x, thr) = (x >> 8) < thr with thr = round(p * 2^24) (vlg_augment_plan is the one place this rounding lives): 0 never
+ * wins, 2^24 always does.  Counter word c2 names the stream: 2, 3, 4 here, clear of the 0 and 1 of csrc/decode.hip.
+ *   clip draw   (x0..x3) = W(b, k, 2, 0):  flip = coin(x0, thr_flip), s = 1 + zoom * v(x1), tx = shift * v(x2), ty = shift * v(x3)
+ *   track draw  drop = coin(first word of W(r, k, 3, 0), thr_drop)
+ *   token draw  (inputs only, only when jitter > 0)  (y0..y3) = W(i, k, 4, 0):  jx = jitter * v(y0), jy = jitter * v(y1),
+ *               jw = 1 + jitter * v(y2), jh = 1 + jitter * v(y3)
+ * The box map on (cx, cy, w, h).  EVERY operation is rounded to fp32 and nothing is fused: the device code of this function
+ * is compiled with floating-point contraction off.  max(a, c) below means a > c ? a : c and min(a, c) means a < c ? a : c
+ * (c the constant), so a NaN coordinate becomes the constant.
+ *   1. flip: cx = 1 - cx
+ *   2. the geometric stage, only if zoom > 0 || shift > 0 || jitter > 0 (ONE decision for the whole launch):
+ *        cx = ((cx - 0.5) * s + 0.5) + tx;  cy = ((cy - 0.5) * s + 0.5) + ty;  w = w * s;  h = h * s
+ *        an input box with jitter > 0:  cx = cx + jx;  cy = cy + jy;  w = w * jw;  h = h * jh
+ *        crop to the image, x axis:  x0 = max(cx - 0.5 * w, 0);  x1 = min(cx + 0.5 * w, 1);  w = max(x1 - x0, 2^-10);
+ *        cx = min(max(0.5 * (x0 + x1), 0), 1);  the y axis likewise with cy, h.  A box pushed wholly outside becomes a
+ *        sliver on the border, never NaN or a negative size
+ *   3. geometric stage off: a box that is not flipped is copied bit for bit, also where the data's own boxes stick out
+ * Per token:
+ *   input, dropped track   class n_classes and a zero box in all T frames (whatever the tokens held), aug_valid = 0 in all T
+ *   input, padded token    (cls[i] >= n_classes, track kept) class and box copied untouched - the convention of rollout
+ *                          and scheduled sampling
+ *   input, otherwise       class copied, box = the map with jitter
+ *   target                 aug_tgt_box[i] = the map WITHOUT jitter when valid[i] > 0, else a bit copy
+ *   aug_valid[i]           drop ? 0 : valid[i].  valid[b,t,n] is both the key mask of input token (t,n) in the per-clip
+ *                          attention kinds and the loss mask of the target of (t,n): only whole tracks are ever invalidated
+ *
+ * vlg_augment_plan (host only; thr_host is a HOST pointer): VLG_ERR_SHAPE unless 0 <= p <= 1 (NaN refused).
+ * vlg_layout_augment refuses before anything is enqueued.  VLG_ERR_SHAPE: B, T or N < 1, B*T*N >= 2^31 (the token is a
+ * 32-bit counter word), n_classes < 1, thr_flip or thr_drop > 2^24, zoom or shift outside [0, 0.5] or jitter outside
+ * [0, 0.25] (NaN and inf refused), a NULL pointer, or one of the four outputs overlapping any other buffer.  VLG_ERR_ALIGN:
+ * a box pointer not 16-byte, a class pointer not 8-byte, valid, aug_valid or step not 4-byte aligned.
+ * Algorithmic bytes: 88 per token (8 + 16 + 16 + 4 read, the same written): a launch-bound pass, 2.9 MB at (32,16,64). */
+int vlg_augment_plan(double p, uint32_t* thr_host);
+int vlg_layout_augment(const int64_t* cls, const float* box, const float* tgt_box, const float* valid,
+                       int64_t* aug_cls, float* aug_box, float* aug_tgt_box, float* aug_valid, const int* step,
+                       int B, int T, int N, int n_classes, uint32_t thr_flip, uint32_t thr_drop,
+                       float zoom, float shift, float jitter, uint64_t seed, void* stream);
+
 /* ------------------------------------------------------------------ validation metrics (csrc/metrics.hip)
  * Scores head outputs against targets and ADDS the result to a running record in device memory: `counts` (int64 slots,
  * vlg_layout_metrics_counts(n_classes) of them) and `sums` (double slots, vlg_layout_metrics_sums(n_classes)).  One launch,

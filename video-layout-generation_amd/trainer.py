@@ -38,8 +38,9 @@ when the average is on): layout mode's validate(), generate_sequence() and evalu
 (LayoutEngine.ema_weights()).  save_checkpoint adds 'gridnet_ema', the averaged model in 'gridnet''s format; --resume
 restores the average through 'optimizer'.
 
-The three options below are LayoutEngine's keyword arguments of the same names - its docstring says what each does, and
-vlg/spec.py (dropout_options, sched_options, loss_options) which values are legal; here only how they are asked for.
+The four options below are LayoutEngine's keyword arguments of the same names - its docstring says what each does, and
+vlg/spec.py (dropout_options, sched_options, augment_options, loss_options) which values are legal; here only how they are
+asked for.
 
 Dropout in layout mode (off by default; DESIGN.md "Dropout"): args.dropout / VLG_DROPOUT = p; VLG_DROPOUT_SEED (default
 args.seed) seeds the stateless mask, and data-parallel rank r uses seed + r so that ranks draw different masks.
@@ -47,6 +48,14 @@ args.seed) seeds the stateless mask, and data-parallel rank r uses seed + r so t
 Scheduled sampling in layout mode (off by default; DESIGN.md "Scheduled sampling"): args.sched_sampling / VLG_SCHED_SAMPLING
 = eps_max, VLG_SCHED_RAMP_STEPS (0), VLG_SCHED_TEMPERATURE (0 = argmax) / VLG_SCHED_TOP_K (0 = every class), VLG_SCHED_SEED
 (default args.seed; data-parallel rank r uses seed + r).
+
+Augmentation in layout mode (off by default; DESIGN.md "Augmentation"; legal values: vlg.spec.augment_options):
+args.aug_flip / VLG_AUG_FLIP = the probability of a horizontal flip per CLIP, args.aug_zoom / VLG_AUG_ZOOM and args.aug_shift /
+VLG_AUG_SHIFT = the per-clip zoom about the centre (1 +- zoom) and shift (+- shift of the image), args.aug_jitter /
+VLG_AUG_JITTER = the per-token jitter of the input boxes, args.aug_drop / VLG_AUG_DROP = the probability of dropping a track;
+any of them set turns the option on, inside the step (captured steps included), and the ones not set count as 0.
+VLG_AUG_SEED (default args.seed; data-parallel rank r uses seed + r).  With VLG_AUG_FLIP set the device's per-clip flip
+REPLACES the host's per-batch coin (_flip, the reference's src/trainer.py:199-206); with it unset _flip runs as ever.
 
 Loss options in layout mode (all off by default; DESIGN.md "Loss options"): args.class_weights / VLG_CLASS_WEIGHTS = 20
 comma-separated floats (vlg.metrics.balanced_class_weights turns the confusion matrix of VLG_VAL_METRICS=1 into such a
@@ -97,8 +106,8 @@ from vlg.data import BATCH_KEYS, BucketedClipLoader, ClipLoader, synthetic_clips
 from vlg.dp import GradReducer, bucket_ranges
 from vlg.optim import decayed_lr
 from vlg.raster import parse_size, raster_options
-from vlg.spec import (ADAM_BETA1, ADAM_LR, N_CLASSES, SEED, LayoutConfig, dropout_options, loss_options, recipe_options,
-                      sched_options)
+from vlg.spec import (ADAM_BETA1, ADAM_LR, N_CLASSES, SEED, LayoutConfig, augment_options, dropout_options, loss_options,
+                      recipe_options, sched_options)
 
 
 class AverageMeter(object):
@@ -213,6 +222,29 @@ def sched_knobs(args) -> Dict[str, object]:
     return dict(zip(names, values), sched_seed=_rank_seed(args, "sched_seed", "VLG_SCHED_SEED"))
 
 
+AUG_KNOBS = ("aug_flip", "aug_zoom", "aug_shift", "aug_jitter", "aug_drop")
+
+
+def augment_knobs(args) -> Dict[str, object]:
+    """the engine's augmentation keyword arguments from args / environment (module docstring): {} with none of
+    args.aug_* / VLG_AUG_FLIP, VLG_AUG_ZOOM, VLG_AUG_SHIFT, VLG_AUG_JITTER, VLG_AUG_DROP set, so an engine without the option
+    is never handed one; else all five (a knob that is not set is 0.0) and aug_seed.  The rule is LayoutEngine's:
+    vlg.spec.augment_options, before any engine exists."""
+    asked = []
+    for name in AUG_KNOBS:
+        v = getattr(args, name, None)
+        asked.append(v if v is not None else (os.environ.get("VLG_" + name.upper()) or None))
+    if all(v is None for v in asked):
+        return {}
+    values = augment_options(*asked, names=tuple("VLG_" + n.upper() for n in AUG_KNOBS))
+    return dict(zip(AUG_KNOBS, values), aug_seed=_rank_seed(args, "aug_seed", "VLG_AUG_SEED"))
+
+
+def device_flip(args) -> bool:
+    """whether the engine's per-clip flip stands in for the host's per-batch one (Trainer._flip): args.aug_flip / VLG_AUG_FLIP set"""
+    return getattr(args, "aug_flip", None) is not None or bool(os.environ.get("VLG_AUG_FLIP"))
+
+
 def loss_knobs(args) -> Dict[str, object]:
     """the engine's loss-option keyword arguments from args / environment (module docstring): {} with all of them off, so an
     engine without the options is never handed one; else those that are on among {class_weights, label_smoothing,
@@ -307,7 +339,8 @@ def get_layout_engine(args, cfg: Optional[LayoutConfig] = None, engine_factory: 
                               precision=precision,
                               padded_slots=bool(_knob(args, "variable_n", "VLG_VARIABLE_N", 0)),   # fixed-N feeds hold no padded slots
                               clip_grad=knobs["clip_grad"], skip_nonfinite=knobs["skip_nonfinite"], **recipe_kwargs(knobs),
-                              **dropout_knobs(args), **clip_cache_knob(args), **loss_knobs(args), **sched_knobs(args))
+                              **dropout_knobs(args), **clip_cache_knob(args), **loss_knobs(args), **sched_knobs(args),
+                              **augment_knobs(args))
     else:
         engine = engine_factory(cfg, args)
     if knobs["lr_decay"]:                            # guarded from the start, so a checkpoint's lr and skip count are resumed
@@ -503,6 +536,10 @@ class Trainer:
             raise ValueError("VLG_DROPOUT is a knob of the layout-token step; VLG_MODEL=gridnet has no dropout")
         if sched_knobs(args) and self.image_mode:               # (out-of-range values raise here too)
             raise ValueError("VLG_SCHED_SAMPLING is a knob of the layout-token step; VLG_MODEL=gridnet has no token inputs to sample")
+        if augment_knobs(args) and self.image_mode:             # (out-of-range values raise here too)
+            raise ValueError("VLG_AUG_* are knobs of the layout-token step; VLG_MODEL=gridnet flips its frames in vlg_prep_input")
+        # the HIP engine flips per clip: the host's per-batch _flip stands down (an injected engine is handed no aug_* knob)
+        self.device_flip = device_flip(args) and engine_factory is None
         if loss_knobs(args) and self.image_mode:                # (out-of-range values raise here too)
             raise ValueError("VLG_CLASS_WEIGHTS / VLG_LABEL_SMOOTHING / VLG_BOX_OVERLAP are knobs of the layout-token step; "
                              "VLG_MODEL=gridnet's losses have no options")
@@ -589,7 +626,8 @@ class Trainer:
                 flip = random.random() < 0.5
                 batch = to_device(batch, self.device, self.engine.keys)
             else:
-                batch = to_device(self._flip(batch), self.device)     # H2D, reference src/trainer.py:184-187
+                # H2D, reference src/trainer.py:184-187 (with VLG_AUG_FLIP the engine flips per clip on the device instead)
+                batch = to_device(batch if self.device_flip else self._flip(batch), self.device)
             load_time = time() - end
             end = time()
             self.global_step += 1

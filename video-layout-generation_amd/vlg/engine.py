@@ -40,11 +40,11 @@ from .hip import (EPI_A_BF16, EPI_B_BF16, EPI_BIAS, EPI_DGELU, EPI_GELU, EPI_NON
                   call, ptr)
 from .spec import (ADAM_BETA1, ADAM_BETA2, ADAM_EPS, ADAM_LR, BOX_DIM, IOU_EPS, LN_EPS, LOSS_W_CE,
                    LOSS_W_REG, LOSS_W_STRUCT, SMOOTH_L1_BETA, LayoutConfig, decode_options, dropout_options, loss_options,
-                   param_layout, sched_options)
+                   augment_options, param_layout, sched_options)
 
 # the int32 device step counters: checkpoint key (= the advance launch's timer family, = the property that reads it) -> the
 # option an engine needs to have one
-STEP_COUNTERS = {"dropout_step": "dropout > 0", "sched_step": "sched_sampling"}
+STEP_COUNTERS = {"dropout_step": "dropout > 0", "sched_step": "sched_sampling", "augment_step": "an aug_* option"}
 
 
 def init_params(cfg: LayoutConfig, seed: int) -> Dict[str, torch.Tensor]:
@@ -99,7 +99,9 @@ class LayoutEngine(AdamSurface):
                  ema_decay: float = 0.0, ema_warmup: bool = False, dropout: float = 0.0, dropout_seed: int = 0,
                  clip_cache: bool = False, class_weights=None, label_smoothing: float = 0.0, box_overlap: str = "iou",
                  sched_sampling: Optional[float] = None, sched_ramp_steps: int = 0, sched_temperature: float = 0.0,
-                 sched_top_k: int = 0, sched_seed: int = 0):
+                 sched_top_k: int = 0, sched_seed: int = 0, aug_flip: Optional[float] = None, aug_zoom: Optional[float] = None,
+                 aug_shift: Optional[float] = None, aug_jitter: Optional[float] = None, aug_drop: Optional[float] = None,
+                 aug_seed: int = 0):
         """clip_grad > 0 clips the gradient to that global L2 norm (torch.nn.utils.clip_grad_norm_'s rule); skip_nonfinite
         leaves parameters, moments and step count untouched when the gradient holds inf or NaN.  Either one - or a call
         of set_lr - turns on the GUARDED optimiser step (vlg/optim.py), eager and captured alike; with both off and
@@ -144,8 +146,21 @@ class LayoutEngine(AdamSurface):
         sched_ramp_steps training steps when that is > 0 - and PASS 2, the training step as ever on the mixed inputs and the
         TRUE targets; no gradient flows through the replaced inputs.  Coins and draws are stateless Philox functions of
         (token, step) under sched_seed; the step is a device counter of its own (sched_step / set_sched_step), advanced as
-        dropout's is.  sched_inputs() shows the last training step's mixed inputs.  Whatever evaluates is untouched."""
+        dropout's is.  sched_inputs() shows the last training step's mixed inputs.  Whatever evaluates is untouched.
+        Augmentation (DESIGN.md "Augmentation"; rule: include/vlg_hip.h; legal values: vlg.spec.augment_options): with aug_flip,
+        aug_zoom, aug_shift, aug_jitter and aug_drop all None it is off - nothing allocated, no launch changed; any of them
+        given, 0.0 included, turns it on and the missing ones count as 0.  forward_backward / train_step / capture_train_step
+        then FIRST build the batch they train on in engine-owned buffers (_augment, one launch; the caller's tensors are only
+        read): per clip a flip with probability aug_flip, a zoom about the centre by 1 +- aug_zoom and a shift by +- aug_shift
+        of the image, per input token a box jitter of +- aug_jitter, per track a drop with probability aug_drop, which pads the
+        track's inputs and takes its targets out of the loss.  Scheduled sampling then runs both passes on that batch.  Draws
+        are stateless Philox functions of (clip | track | token, step) under aug_seed; the step is a device counter of its own
+        (augment_step / set_augment_step).  augmented_batch() shows the last training step's batch.  Whatever evaluates is
+        untouched.  aug_drop > 0 needs padded_slots = True with a per-clip attention kind: their unmasked kernels would
+        attend to the dropped slots."""
         cfg.validate()
+        given = (aug_flip, aug_zoom, aug_shift, aug_jitter, aug_drop)
+        self._aug = None if all(v is None for v in given) else augment_options(*given) + (int(aug_seed) & 0xFFFFFFFFFFFFFFFF,)
         self._sched = None if sched_sampling is None else sched_options(    # (the option rules: vlg/spec.py, the trainer's *_knobs call them too)
             sched_sampling, sched_ramp_steps, sched_temperature, sched_top_k, cfg.n_classes) + (int(sched_seed) & 0xFFFFFFFFFFFFFFFF,)
         weights, self.label_smoothing, self.box_overlap = loss_options(class_weights, label_smoothing, box_overlap, cfg.n_classes)
@@ -165,6 +180,9 @@ class LayoutEngine(AdamSurface):
         # that its batches never hold any (fixed-N feeds), so the kernels skip the per-key validity masks
         self.padded_slots = bool(padded_slots)
         self._masked = self.padded_slots             # this forward's choice; its backward follows it
+        if self._aug is not None and self._aug[4] > 0.0 and self._per_clip and not self.padded_slots:
+            raise ValueError("aug_drop=%g with attention=%r needs padded_slots=True: the unmasked per-clip kernels would attend "
+                             "to the dropped slots" % (self._aug[4], cfg.attention))
         self.precision = precision
         self.gemm_flags = {"fp32": 0, "fp32x3": hip.EPI_SPLIT3}.get(precision, hip.EPI_BF16)
         self.bf16_store = precision == "bf16"
@@ -193,7 +211,15 @@ class LayoutEngine(AdamSurface):
             hip.check(hip.load().vlg_sched_plan(self._sched[0], ctypes.byref(thr)), "vlg_sched_plan")
             self._sched = (thr.value,) + self._sched[1:]
             self._counters["sched_step"] = torch.zeros(1, dtype=torch.int32, device=device)
+        # augmentation: (thr_flip, zoom, shift, jitter, thr_drop, seed) for the augment kernel + its own device step counter
+        if self._aug is not None:
+            thr = [ctypes.c_uint32(), ctypes.c_uint32()]
+            for t, p in zip(thr, (self._aug[0], self._aug[4])):
+                hip.check(hip.load().vlg_augment_plan(p, ctypes.byref(t)), "vlg_augment_plan")
+            self._aug = (thr[0].value,) + self._aug[1:4] + (thr[1].value, self._aug[5])
+            self._counters["augment_step"] = torch.zeros(1, dtype=torch.int32, device=device)
         self.drop_step, self.sched_counter = self._counters.get("dropout_step"), self._counters.get("sched_step")
+        self.aug_counter = self._counters.get("augment_step")
         self.layout, self.n_params = param_layout(cfg)
         f32 = dict(dtype=torch.float32, device=device)
         self.class_weights = None if weights is None else torch.tensor(weights, **f32)
@@ -321,7 +347,9 @@ class LayoutEngine(AdamSurface):
 
     sched_step = property(lambda self: self._read_step("sched_step"), doc="the scheduled-sampling counter: _read_step")
     dropout_step = property(lambda self: self._read_step("dropout_step"), doc="the dropout counter: _read_step")
+    augment_step = property(lambda self: self._read_step("augment_step"), doc="the augmentation counter: _read_step")
     set_sched_step = functools.partialmethod(_set_step, "sched_step")
+    set_augment_step = functools.partialmethod(_set_step, "augment_step")
     set_dropout_step = functools.partialmethod(_set_step, "dropout_step")
 
     def sched_inputs(self) -> tuple:
@@ -333,6 +361,18 @@ class LayoutEngine(AdamSurface):
         B, T, N = self._mixed_shape
         M = B * T * N
         return self.mix_cls[:M].view(B, T, N), self.mix_box[:M].view(B, T, N, BOX_DIM)
+
+    def augmented_batch(self) -> Dict[str, torch.Tensor]:
+        """{slot_class (B,T,N) int64, slot_box (B,T,N,4), tgt_box (B,T,N,4), valid (B,T,N) fp32}: views of the batch the last
+        training step ran on (before scheduled sampling mixed its inputs; tgt_class is the caller's own)"""
+        if self._aug is None:
+            raise RuntimeError("augmented_batch needs an engine built with an aug_* option")
+        if getattr(self, "_aug_shape", None) is None:
+            raise RuntimeError("augmented_batch shows the last training step: there has been none")
+        B, T, N = self._aug_shape
+        M = B * T * N
+        return {"slot_class": self.aug_cls[:M].view(B, T, N), "slot_box": self.aug_box[:M].view(B, T, N, BOX_DIM),
+                "tgt_box": self.aug_tgt_box[:M].view(B, T, N, BOX_DIM), "valid": self.aug_valid[:M].view(B, T, N)}
 
     def optimizer_state(self) -> Dict[str, object]:
         """Adam state for the checkpoint's 'optimizer' entry (flat tensors, CPU)."""
@@ -376,6 +416,13 @@ class LayoutEngine(AdamSurface):
             self.mix_cls = torch.empty(M, dtype=torch.int64, device=self.device)      # the second pass's inputs
             self.mix_box = torch.empty(M, BOX_DIM, **f32)
             self._mixed_shape = None
+        if self._aug is not None:
+            if M >= 2 ** 31:
+                raise ValueError("augmentation: %d tokens do not fit the draws' 32-bit token counter" % M)
+            self.aug_cls = torch.empty(M, dtype=torch.int64, device=self.device)      # the batch a training step runs on
+            self.aug_box, self.aug_tgt_box = torch.empty(M, BOX_DIM, **f32), torch.empty(M, BOX_DIM, **f32)
+            self.aug_valid = torch.empty(M, **f32)
+            self._aug_shape = None
         self.loss_scratch = torch.zeros(lib.vlg_layout_loss_scratch(), **f32)
         # validation metrics (vlg_layout_metrics): per-block partial sums and the ticket, zero between launches
         self.metrics_scratch = torch.zeros(lib.vlg_layout_metrics_scratch(), dtype=torch.float64, device=self.device)
@@ -567,6 +614,19 @@ class LayoutEngine(AdamSurface):
         self._encode_window(batch, B, T, N, drop=self._dropped, final=True)
         self._linear(self.xf, self.pw("head_w"), self.p("head_b"), self.out, M, self.cfg.n_out, self.cfg.d, EPI_BIAS)
         return B, T, N, M
+
+    def _augment(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """Augmentation: vlg_layout_augment builds the batch this training step runs on from the caller's, which is only read.
+        Returns it: slot_class / slot_box / tgt_box / valid are the engine's buffers, tgt_class the caller's."""
+        self._not_on_ema("an augmenting training step")
+        B, T, N, M = self._check_batch(batch)
+        thr_flip, zoom, shift, jitter, thr_drop, seed = self._aug
+        self._timed("augment", 0.0, "vlg_layout_augment", ptr(batch["slot_class"]), ptr(batch["slot_box"]), ptr(batch["tgt_box"]),
+                    ptr(batch["valid"]), ptr(self.aug_cls), ptr(self.aug_box), ptr(self.aug_tgt_box), ptr(self.aug_valid),
+                    ptr(self.aug_counter), B, T, N, self.cfg.n_classes, thr_flip, thr_drop, zoom, shift, jitter, seed,
+                    self._stream(), nbytes=88.0 * M)
+        self._aug_shape = (B, T, N)
+        return dict(batch, **self.augmented_batch())
 
     def _mix_inputs(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """Scheduled sampling, pass 1 and the mix: the evaluation forward on the true inputs (no dropout, no loss launch), then
@@ -768,12 +828,16 @@ class LayoutEngine(AdamSurface):
         self.buckets.close(s, then=(lambda: reducer.ready("embed")) if reducer is not None else None)
 
     def forward_backward(self, batch: Dict[str, torch.Tensor], reducer=None) -> torch.Tensor:
+        if self._aug is not None:                     # augmentation first: everything below runs on the augmented batch
+            batch = self._augment(batch)
         if self._sched is not None:                   # scheduled sampling: pass 1 + the mix; the step below is pass 2
             batch = self._mix_inputs(batch)
         loss = self._forward(batch, None, True)       # (a training forward: the one place dropout is applied)
         self.backward(batch, reducer)
         if self._sched is not None:                   # the next training step flips new coins
             self._advance_step("sched_step", self._stream())
+        if self._aug is not None:                     # the next training step draws anew
+            self._advance_step("augment_step", self._stream())
         return loss
 
     def train_step(self, batch: Dict[str, torch.Tensor], reducer=None) -> torch.Tensor:

@@ -76,6 +76,9 @@ SIGNATURES = {
     "vlg_sched_plan": (I, [c_double, P]),                        # host only: (eps_max, uint32* thr_max)
     # (out, ld, cls, box, mix_cls, mix_box, step, B, T, N, C, thr_max, ramp_steps, temperature, top_k, seed, stream)
     "vlg_layout_mix_inputs": (I, [P, I, P, P, P, P, P, I, I, I, I, c_uint32, I, F, I, c_uint64, P]),
+    "vlg_augment_plan": (I, [c_double, P]),                      # host only: (p, uint32* thr)
+    # (cls, box, tgt_box, valid, aug_cls, aug_box, aug_tgt_box, aug_valid, step, B, T, N, C, thr_flip, thr_drop, zoom, shift, jitter, seed, stream)
+    "vlg_layout_augment": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, c_uint32, c_uint32, F, F, F, c_uint64, P]),
     "vlg_layout_metrics_counts": (I, [I]),
     "vlg_layout_metrics_sums": (I, [I]),
     "vlg_layout_metrics_scratch": (I, []),

@@ -165,6 +165,26 @@ def sched_options(eps_max, ramp_steps=0, temperature=0.0, top_k=0, n_classes: in
     return (float(eps_max), int(ramp_steps)) + decode_options(float(temperature), top_k, n_classes, names[2:])
 
 
+AUG_BOUNDS = {"flip": 1.0, "zoom": 0.5, "shift": 0.5, "jitter": 0.25, "drop": 1.0}      # upper bounds; drop's is open
+
+
+def augment_options(flip=None, zoom=None, shift=None, jitter=None, drop=None,
+                    names=("aug_flip", "aug_zoom", "aug_shift", "aug_jitter", "aug_drop")):
+    """augmentation, once it is on (any knob given; a missing one counts as 0): (flip in [0, 1], zoom in [0, 0.5], shift in
+    [0, 0.5], jitter in [0, 0.25], drop in [0, 1)) as floats"""
+    out = []
+    for key, value, name in zip(("flip", "zoom", "shift", "jitter", "drop"), (flip, zoom, shift, jitter, drop), names):
+        try:
+            x = 0.0 if value is None else float(value)
+        except (TypeError, ValueError):
+            raise ValueError("%s must be a number, got %r" % (name, value)) from None
+        hi = AUG_BOUNDS[key]
+        if not (0.0 <= x < hi if key == "drop" else 0.0 <= x <= hi):       # (also refuses NaN)
+            raise ValueError("%s must be in [0, %g%s, got %r" % (name, hi, ")" if key == "drop" else "]", value))
+        out.append(x)
+    return tuple(out)
+
+
 def recipe_options(weight_decay=0.0, warmup_steps=0, ema_decay=0.0, names=("weight_decay", "warmup_steps", "ema_decay")):
     """the optimiser recipe: (weight_decay >= 0, warmup_steps >= 0, ema_decay in [0, 1)); each is off at 0"""
     weight_decay, warmup_steps, ema_decay = float(weight_decay), int(warmup_steps), float(ema_decay)
