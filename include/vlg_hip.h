@@ -297,6 +297,38 @@ int vlg_layout_loss_ext(const float* out, int ld, const int64_t* tgt_class, cons
                         int B, int T, int N, int n_classes, float beta, float iou_eps,
                         float w_reg, float w_iou, float w_ce, float label_smoothing, int flags, void* stream);
 
+/* ------------------------------------------------------------------ Gaussian box head (csrc/box_nll.hip)
+ * SELF-ORACLE (tests/boxhead_ref.py restates it in fp64); DESIGN.md, "Gaussian box head".  With the option
+ * LayoutConfig(box_head="gaussian") a head-output row holds [0,C) logits | [C,C+4) raw mean | [C+4,C+8) raw scale |
+ * [C+8,C+12) padding.  For token row m = (b*N + n)*T + t, targets at src = (b*T + t)*N + n as the loss kernel reads them:
+ *   mu_k    = sigmoid(out[m, C+k])                  a CONSTANT here: no gradient reaches the mean, which the smooth-L1
+ *                                                   and IoU terms keep training exactly as they did
+ *   g_k     = sigmoid(out[m, C+4+k]),  s_k = s_min + (s_max - s_min) g_k,  sigma_k = exp(s_k)
+ *   e_k     = (tgt_k - mu_k) exp(-s_k)
+ *   nll_m   = 1/4 sum_k (e_k^2 / 2 + s_k + ln(2 pi) / 2)
+ *   cover_m = 1/4 sum_k [ |tgt_k - mu_k| <= sigma_k ]          (a calibrated head reads 0.683)
+ *   cnt = max(sum valid, 1),  box_nll = 1/cnt sum_m valid_m nll_m,  box_cover = 1/cnt sum_m valid_m cover_m
+ *   dout[m, C+4+k] = w_nll valid_m/cnt 1/4 (1 - e_k^2) (s_max - s_min) g_k (1 - g_k),   dout[m, C+8 .. C+11] = 0
+ * out / dout are [rows, ld], ld >= C+12 and a multiple of 4.  READ: out[m, C .. C+8), tgt_box, valid - nothing else (the
+ * logits and the padding columns may hold anything, NaN included).  WRITTEN: dout[m, C+4 .. C+12) and nothing else of
+ * dout - the loss launch wrote [0, C+4) - with plain vector stores.
+ * loss_io is 8 floats.  The launch writes [4] = box_nll, [5] = box_cover, [6] = [7] = 0 and [0] = [0] + w_nll * box_nll,
+ * once.  THE RULE: call it once, in stream order, after the vlg_layout_loss[_ext] launch that wrote [0..3].
+ * An invalid token is multiplied by its valid flag, as in the loss kernel: a finite row with valid == 0 contributes
+ * exact zeros; a NON-FINITE mean, scale or target of an invalid token still makes its gradient row and both sums NaN.
+ * scratch: >= vlg_layout_box_nll_scratch() floats of its OWN (not the loss launch's), 16-byte aligned, zeroed once by the
+ * caller; scratch[1] is the ticket by which the last block folds the per-block partials in block order, and is left zero.
+ * No float atomics: two launches on the same inputs agree bit for bit.  Every block forms the valid count itself.
+ * VLG_ERR_SHAPE, nothing enqueued: n_classes != 20, B, T or N < 1, ld < C+12 or not a multiple of 4, !(s_min < s_max) or
+ * either not finite, w_nll negative or not finite.  VLG_ERR_ALIGN: out, dout, tgt_box, valid or scratch NULL or not
+ * 16-byte aligned, loss_io NULL.  52 B in and 32 B out per token: bound by the launch, not by bytes. */
+#define VLG_BOX_S_MIN (-7.0f)   /* the bounds the DECODING entries below use for log sigma; vlg.spec.BOX_S_MIN / BOX_S_MAX */
+#define VLG_BOX_S_MAX (0.0f)
+int vlg_layout_box_nll_scratch(void);
+int vlg_layout_box_nll(const float* out, int ld, const float* tgt_box, const float* valid, float* dout, float* loss_io,
+                       float* scratch, int B, int T, int N, int n_classes, float s_min, float s_max, float w_nll,
+                       void* stream);
+
 /* ------------------------------------------------------------------ per-clip attention (option attention = "clip")
  * Block-causal softmax attention over ALL T*N tokens of a clip, per (clip, head): token (t, n) attends to every slot of
  * frames <= t; slots with valid == 0 (valid may be NULL: none) are never keys, except for themselves.  SELF-ORACLE
@@ -423,6 +455,31 @@ int vlg_layout_decode_append(const float* out_last, int64_t* cls, float* box, fl
                              int64_t* gen_cls, float* gen_box, int64_t* frame_cls, float* frame_box,
                              int B, int T, int N, int n_classes, int pos, int steps, int step,
                              float temperature, int top_k, uint64_t seed, int keep_padded, void* stream);
+/* The two steps above with a row stride and a SAMPLED box (the Gaussian box head): the argument lists of vlg_layout_decode /
+ * vlg_layout_decode_append plus `ld` after out_last - the row stride of out_last in floats, ld >= n_classes + 4 and a
+ * multiple of 4 - and `box_temperature` after top_k.  One front end and one kernel body serve both pairs; box sampling is a
+ * compile-time parameter of it, and the plain entries are the ld = n_classes + 4, box_temperature = 0 calls.
+ *   box    box_temperature == 0: sigmoid(raw), exactly as above (the kernel instantiation of the plain entries).
+ *          box_temperature = tau > 0 (needs ld >= n_classes + 8 and n_classes + 8 <= 32, else VLG_ERR_SHAPE): out_last rows
+ *          are [logits | raw mean | raw scale | ...];  (x0, x1, x2, x3) = all four words of Philox4x32-10 on counter
+ *          (b*N + n, step, 5, 0) under the call's key (streams 0 and 1 are the class draw and the scheduled-sampling coin,
+ *          2 to 4 augmentation's);  u_i = (x_i >> 8) * 2^-24 + 2^-25 evaluated in fp32 as the class draw's u (so u may round
+ *          to 1.0, which gives z = 0);  z0 = sqrt(-2 ln u0) cos(2 pi u1), z1 = sqrt(-2 ln u0) sin(2 pi u1), z2, z3 likewise
+ *          from u2, u3;  mu_k = sigmoid(raw mean_k), sigma_k = exp(VLG_BOX_S_MIN + (VLG_BOX_S_MAX - VLG_BOX_S_MIN)
+ *          sigmoid(raw scale_k));  box_k = min(max(mu_k + tau sigma_k z_k, 0), 1).
+ *   class  untouched: the same counter (b*N + n, step, 0, 0), the same rule.
+ *   A slot kept by keep_padded keeps its box.  Columns >= n_classes + 8 (tau == 0: >= n_classes + 4) are never read.  A draw
+ *   is a function of (token, step, seed) alone.
+ * Refusals as the plain entries, plus VLG_ERR_SHAPE for a bad ld and for box_temperature negative, NaN or infinite. */
+int vlg_layout_decode_ext(const float* out_last, int ld, const int64_t* cls_in, const float* box_in,
+                          int64_t* cls_out, float* box_out, float* valid_out, int64_t* gen_cls, float* gen_box,
+                          int B, int T, int N, int n_classes, int steps, int step,
+                          float temperature, int top_k, float box_temperature, uint64_t seed, int keep_padded, void* stream);
+int vlg_layout_decode_append_ext(const float* out_last, int ld, int64_t* cls, float* box, float* valid,
+                                 int64_t* gen_cls, float* gen_box, int64_t* frame_cls, float* frame_box,
+                                 int B, int T, int N, int n_classes, int pos, int steps, int step,
+                                 float temperature, int top_k, float box_temperature, uint64_t seed, int keep_padded,
+                                 void* stream);
 
 /* ------------------------------------------------------------------ scheduled sampling (csrc/decode.hip)
  * SELF-ORACLE (tests/sched_ref.py restates it); DESIGN.md, "Scheduled sampling".  Builds the inputs of a training step's

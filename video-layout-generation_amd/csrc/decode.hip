@@ -13,9 +13,14 @@
 //     vector store; no atomics, no state.
 // vlg_layout_decode_append  the same step while the history is shorter than the window: the decoding rule is one device
 //     function (decode_token) for both; the new frame is written at its position of the window in place, nothing slides.
+// vlg_layout_decode_ext / vlg_layout_decode_append_ext  the two steps with a row stride for out_last and, with
+//     box_temperature > 0, a box DRAWN from the Gaussian box head's N(mu, (tau sigma)^2) (Box-Muller on the four words of
+//     one more Philox call, stream 5): a compile-time parameter of the same kernels and of decode_token, so the instantiation
+//     behind the plain entries keeps the rule it always had.
 // vlg_layout_mix_inputs  scheduled sampling: the inputs of a training step's second pass, per token the truth or the
 //     model's own prediction decoded by the same decode_token from the first pass's outputs (end of this file).
 #include "common.h"
+#include "layernorm_rows.h"        // philox4x32_10: all four words of a counter
 
 #define HL_BLOCK 256
 #define HL_WAVES (HL_BLOCK / 64)
@@ -138,17 +143,42 @@ __device__ __forceinline__ uint32_t philox_first(uint32_t c0, uint32_t c1, uint3
     return c0;
 }
 
+// u of one Philox word, as the class draw forms it: fp32 throughout (not exact above 2^23; may round to 1.0)
+__device__ __forceinline__ float philox_u(uint32_t x) {
+    return (float)(x >> 8) * 5.9604644775390625e-08f + 2.98023223876953125e-08f;                   // 2^-24, 2^-25
+}
+
 // The decoding rule, written once for the sliding step, the appending one and the scheduled-sampling mix.  l: token r's [logits | raw box] (the logits
 // become the running sums); prev / prev_box: the token's class and box in the newest frame of the history.
+// BOX (the Gaussian box head, vlg_layout_decode_ext with box_temperature = tau > 0): l holds [logits | raw mean | raw scale]
+// and the box is drawn, box_k = clamp(mu_k + tau sigma_k z_k, 0, 1), z = Box-Muller on the four words of counter
+// (r, step, 5, 0); the class draw is untouched.  BOX = false is the rule as it always was, instruction for instruction.
+template <bool BOX>
 __device__ __forceinline__ void decode_token(float* l, int C, int64_t prev, const float* __restrict__ prev_box, int64_t r, int step,
                                              float temperature, int top_k, uint32_t k0, uint32_t k1, int keep_padded,
-                                             int64_t& cls, float4& box) {
+                                             int64_t& cls, float4& box, float box_tau = 0.f) {
     if (keep_padded && prev >= C) {                        // a padded slot stays padded, box and all
         cls = prev;
         box = ld4(prev_box);
     } else {
         box = make_float4(1.0f / (1.0f + expf(-l[C])), 1.0f / (1.0f + expf(-l[C + 1])),
                           1.0f / (1.0f + expf(-l[C + 2])), 1.0f / (1.0f + expf(-l[C + 3])));
+        if constexpr (BOX) {
+            uint32_t x[4];
+            philox4x32_10((uint32_t)r, (uint32_t)step, 5u, 0u, k0, k1, x);
+            const float rad0 = sqrtf(-2.0f * logf(philox_u(x[0]))), ang0 = 6.28318530717958648f * philox_u(x[1]);
+            const float rad1 = sqrtf(-2.0f * logf(philox_u(x[2]))), ang1 = 6.28318530717958648f * philox_u(x[3]);
+            const float z[4] = {rad0 * cosf(ang0), rad0 * sinf(ang0), rad1 * cosf(ang1), rad1 * sinf(ang1)};
+            const float mu[4] = {box.x, box.y, box.z, box.w};
+            float bx[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float g = 1.0f / (1.0f + expf(-l[C + 4 + k]));
+                const float sigma = expf(VLG_BOX_S_MIN + (VLG_BOX_S_MAX - VLG_BOX_S_MIN) * g);
+                bx[k] = fminf(fmaxf(mu[k] + box_tau * sigma * z[k], 0.f), 1.f);
+            }
+            box = make_float4(bx[0], bx[1], bx[2], bx[3]);
+        }
         int pick = 0;
         if (temperature == 0.f) {
             float best = l[0];
@@ -174,7 +204,7 @@ __device__ __forceinline__ void decode_token(float* l, int C, int64_t prev, cons
                 l[c] = cum;
             }
             const uint32_t x0 = philox_first((uint32_t)r, (uint32_t)step, k0, k1);
-            const float u = (float)(x0 >> 8) * 5.9604644775390625e-08f + 2.98023223876953125e-08f;    // 2^-24, 2^-25
+            const float u = philox_u(x0);
             const float thr = u * cum;                     // cum = S
             pick = -1;
             int last_kept = 0;
@@ -189,32 +219,34 @@ __device__ __forceinline__ void decode_token(float* l, int C, int64_t prev, cons
     }
 }
 
-// stage the block's rows of out_last in LDS; returns the number of tokens of this block
-__device__ __forceinline__ int decode_stage(float (*rows)[DEC_LD], const float* __restrict__ out_last, int64_t BN, int n_out) {
+// stage the first n_out columns of the block's rows of out_last (row stride ld) in LDS; returns the number of tokens of this block
+__device__ __forceinline__ int decode_stage(float (*rows)[DEC_LD], const float* __restrict__ out_last, int ld, int64_t BN, int n_out) {
     const int tid = threadIdx.x;
     const int64_t r_first = (int64_t)blockIdx.x * DEC_BLOCK;
     const int here = (int)(BN - r_first < DEC_BLOCK ? BN - r_first : DEC_BLOCK);
-    for (int e = tid; e < here * n_out; e += DEC_BLOCK) rows[e / n_out][e % n_out] = out_last[r_first * n_out + e];
+    for (int e = tid; e < here * n_out; e += DEC_BLOCK) rows[e / n_out][e % n_out] = out_last[(r_first + e / n_out) * ld + e % n_out];
     __syncthreads();
     return here;
 }
 
+template <bool BOX>
 __global__ __launch_bounds__(DEC_BLOCK) void layout_decode_kernel(
-    const float* __restrict__ out_last, const int64_t* __restrict__ cls_in, const float* __restrict__ box_in,
+    const float* __restrict__ out_last, int ld, const int64_t* __restrict__ cls_in, const float* __restrict__ box_in,
     int64_t* __restrict__ cls_out, float* __restrict__ box_out, float* __restrict__ valid_out,
     int64_t* __restrict__ gen_cls, float* __restrict__ gen_box, int B, int T, int N, int C, int steps, int step,
-    float temperature, int top_k, uint32_t k0, uint32_t k1, int keep_padded) {
+    float temperature, int top_k, uint32_t k0, uint32_t k1, int keep_padded, float box_tau) {
     __shared__ float rows[DEC_BLOCK][DEC_LD];
     const int tid = threadIdx.x;
     const int64_t BN = (int64_t)B * N, r_first = (int64_t)blockIdx.x * DEC_BLOCK;
-    const int here = decode_stage(rows, out_last, BN, C + 4);
+    const int here = decode_stage(rows, out_last, ld, BN, C + (BOX ? 8 : 4));
     if (tid < here) {
         const int64_t r = r_first + tid;
         const int b = (int)(r / N), n = (int)(r % N);
         const int64_t last = ((int64_t)b * T + (T - 1)) * N + n;
         int64_t cls;
         float4 box;
-        decode_token(rows[tid], C, cls_in[last], box_in + 4 * last, r, step, temperature, top_k, k0, k1, keep_padded, cls, box);
+        decode_token<BOX>(rows[tid], C, cls_in[last], box_in + 4 * last, r, step, temperature, top_k, k0, k1, keep_padded, cls, box,
+                          box_tau);
         const int64_t g = ((int64_t)b * steps + step) * N + n;
         gen_cls[g] = cls;
         st4(gen_box + 4 * g, box);
@@ -238,19 +270,31 @@ static inline bool dec_overlap(const void* a, int64_t na, const void* b, int64_t
     return a != nullptr && b != nullptr && pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
 }
 
-extern "C" int vlg_layout_decode(const float* out_last, const int64_t* cls_in, const float* box_in, int64_t* cls_out,
-                                 float* box_out, float* valid_out, int64_t* gen_cls, float* gen_box, int B, int T, int N,
-                                 int n_classes, int steps, int step, float temperature, int top_k, uint64_t seed,
-                                 int keep_padded, void* stream) {
+// what the _ext entries add to the refusals: the row stride, and the box temperature with the columns it needs.  Returns the
+// number of columns of a row the kernel reads
+// (ext: an _ext entry, whose ld must be a multiple of 4; the plain entries pass ld = n_classes + 4, whatever that is)
+static inline int dec_box_columns(int n_classes, int ld, float box_temperature, bool ext) {
+    if (ld < n_classes + 4 || (ext && (ld & 3))) return 0;
+    if (!(box_temperature >= 0.f) || !(box_temperature <= 3.0e38f)) return 0;           // negative, inf or NaN
+    if (box_temperature == 0.f) return n_classes + 4;
+    return (ld >= n_classes + 8 && n_classes + 8 <= HL_MAX_OUT) ? n_classes + 8 : 0;
+}
+
+static int decode_front(bool ext, const float* out_last, int ld, const int64_t* cls_in, const float* box_in, int64_t* cls_out,
+                        float* box_out, float* valid_out, int64_t* gen_cls, float* gen_box, int B, int T, int N,
+                        int n_classes, int steps, int step, float temperature, int top_k, float box_temperature,
+                        uint64_t seed, int keep_padded, void* stream) {
     if (B < 1 || T < 1 || N < 1 || n_classes < 1 || n_classes + 4 > HL_MAX_OUT) return VLG_ERR_SHAPE;
     if (!(temperature >= 0.f) || !(temperature <= 3.0e38f)) return VLG_ERR_SHAPE;      // negative, inf or NaN
     if (top_k < 0 || top_k > n_classes || steps < 1 || step < 0 || step >= steps) return VLG_ERR_SHAPE;
+    const int cols = dec_box_columns(n_classes, ld, box_temperature, ext);
+    if (cols == 0) return VLG_ERR_SHAPE;
     const int64_t BN = (int64_t)B * N, M = BN * T;
     if (BN > 0x7fffffffLL) return VLG_ERR_SHAPE;                                        // the Philox counter word is the token index
     if (!out_last || !cls_in || !box_in || !cls_out || !box_out || !gen_cls || !gen_box) return VLG_ERR_SHAPE;
     // inputs are only read and outputs only written: any overlap between the two groups is refused
     const void* in_p[3] = {out_last, cls_in, box_in};
-    const int64_t in_n[3] = {BN * (n_classes + 4) * 4, M * 8, M * 16};
+    const int64_t in_n[3] = {((BN - 1) * ld + cols) * 4, M * 8, M * 16};
     const void* out_p[5] = {cls_out, box_out, valid_out, gen_cls, gen_box};
     const int64_t out_n[5] = {M * 8, M * 16, M * 4, BN * steps * 8, BN * steps * 16};
     for (int i = 0; i < 3; ++i)
@@ -260,32 +304,56 @@ extern "C" int vlg_layout_decode(const float* out_last, const int64_t* cls_in, c
         !vlg_aligned8(cls_in) || !vlg_aligned8(cls_out) || !vlg_aligned8(gen_cls) ||
         (reinterpret_cast<uintptr_t>(valid_out) & 3u)) return VLG_ERR_ALIGN;
     const dim3 grid((unsigned)((BN + DEC_BLOCK - 1) / DEC_BLOCK)), block(DEC_BLOCK);
-    hipLaunchKernelGGL(layout_decode_kernel, grid, block, 0, (hipStream_t)stream, out_last, cls_in, box_in, cls_out, box_out,
-                       valid_out, gen_cls, gen_box, B, T, N, n_classes, steps, step, temperature, top_k,
-                       (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), keep_padded);
+    const uint32_t k0 = (uint32_t)(seed & 0xffffffffu), k1 = (uint32_t)(seed >> 32);
+    if (box_temperature > 0.f)
+        hipLaunchKernelGGL(layout_decode_kernel<true>, grid, block, 0, (hipStream_t)stream, out_last, ld, cls_in, box_in, cls_out,
+                           box_out, valid_out, gen_cls, gen_box, B, T, N, n_classes, steps, step, temperature, top_k, k0, k1,
+                           keep_padded, box_temperature);
+    else
+        hipLaunchKernelGGL(layout_decode_kernel<false>, grid, block, 0, (hipStream_t)stream, out_last, ld, cls_in, box_in, cls_out,
+                           box_out, valid_out, gen_cls, gen_box, B, T, N, n_classes, steps, step, temperature, top_k, k0, k1,
+                           keep_padded, 0.f);
     return vlg_last_error();
+}
+
+extern "C" int vlg_layout_decode_ext(const float* out_last, int ld, const int64_t* cls_in, const float* box_in, int64_t* cls_out,
+                                     float* box_out, float* valid_out, int64_t* gen_cls, float* gen_box, int B, int T, int N,
+                                     int n_classes, int steps, int step, float temperature, int top_k, float box_temperature,
+                                     uint64_t seed, int keep_padded, void* stream) {
+    return decode_front(true, out_last, ld, cls_in, box_in, cls_out, box_out, valid_out, gen_cls, gen_box, B, T, N, n_classes, steps,
+                        step, temperature, top_k, box_temperature, seed, keep_padded, stream);
+}
+
+// the ld = n_classes + 4, box_temperature = 0 call of the same front end
+extern "C" int vlg_layout_decode(const float* out_last, const int64_t* cls_in, const float* box_in, int64_t* cls_out,
+                                 float* box_out, float* valid_out, int64_t* gen_cls, float* gen_box, int B, int T, int N,
+                                 int n_classes, int steps, int step, float temperature, int top_k, uint64_t seed,
+                                 int keep_padded, void* stream) {
+    return decode_front(false, out_last, n_classes + 4, cls_in, box_in, cls_out, box_out, valid_out, gen_cls, gen_box, B, T, N,
+                        n_classes, steps, step, temperature, top_k, 0.f, seed, keep_padded, stream);
 }
 
 // ---------------------------------------------------------------------------------------- decoding, growing history
 // The same step while the history is shorter than the window: nothing slides.  Thread i decodes token i from the newest
 // frame pos - 1 and writes frame pos of the window in place, the generated frame and a compact copy of it (the next
 // step's embedding input).  64 B per token out; no other element of any buffer is touched.
+template <bool BOX>
 __global__ __launch_bounds__(DEC_BLOCK) void layout_decode_append_kernel(
-    const float* __restrict__ out_last, int64_t* __restrict__ cls, float* __restrict__ box, float* __restrict__ valid,
+    const float* __restrict__ out_last, int ld, int64_t* __restrict__ cls, float* __restrict__ box, float* __restrict__ valid,
     int64_t* __restrict__ gen_cls, float* __restrict__ gen_box, int64_t* __restrict__ frame_cls, float* __restrict__ frame_box,
     int B, int T, int N, int C, int pos, int steps, int step, float temperature, int top_k, uint32_t k0, uint32_t k1,
-    int keep_padded) {
+    int keep_padded, float box_tau) {
     __shared__ float rows[DEC_BLOCK][DEC_LD];
     const int tid = threadIdx.x;
     const int64_t BN = (int64_t)B * N, r_first = (int64_t)blockIdx.x * DEC_BLOCK;
-    const int here = decode_stage(rows, out_last, BN, C + 4);
+    const int here = decode_stage(rows, out_last, ld, BN, C + (BOX ? 8 : 4));
     if (tid >= here) return;
     const int64_t r = r_first + tid;
     const int b = (int)(r / N), n = (int)(r % N);
     const int64_t newest = ((int64_t)b * T + (pos - 1)) * N + n, at = newest + N;
     int64_t c;
     float4 bx;
-    decode_token(rows[tid], C, cls[newest], box + 4 * newest, r, step, temperature, top_k, k0, k1, keep_padded, c, bx);
+    decode_token<BOX>(rows[tid], C, cls[newest], box + 4 * newest, r, step, temperature, top_k, k0, k1, keep_padded, c, bx, box_tau);
     const int64_t g = ((int64_t)b * steps + step) * N + n;
     gen_cls[g] = c;
     st4(gen_box + 4 * g, bx);
@@ -296,20 +364,22 @@ __global__ __launch_bounds__(DEC_BLOCK) void layout_decode_append_kernel(
     st4(frame_box + 4 * r, bx);
 }
 
-extern "C" int vlg_layout_decode_append(const float* out_last, int64_t* cls, float* box, float* valid, int64_t* gen_cls,
-                                        float* gen_box, int64_t* frame_cls, float* frame_box, int B, int T, int N,
-                                        int n_classes, int pos, int steps, int step, float temperature, int top_k,
-                                        uint64_t seed, int keep_padded, void* stream) {
+static int decode_append_front(bool ext, const float* out_last, int ld, int64_t* cls, float* box, float* valid, int64_t* gen_cls,
+                               float* gen_box, int64_t* frame_cls, float* frame_box, int B, int T, int N,
+                               int n_classes, int pos, int steps, int step, float temperature, int top_k, float box_temperature,
+                               uint64_t seed, int keep_padded, void* stream) {
     if (B < 1 || T < 1 || N < 1 || n_classes < 1 || n_classes + 4 > HL_MAX_OUT) return VLG_ERR_SHAPE;
     if (!(temperature >= 0.f) || !(temperature <= 3.0e38f)) return VLG_ERR_SHAPE;      // negative, inf or NaN
     if (top_k < 0 || top_k > n_classes || steps < 1 || step < 0 || step >= steps) return VLG_ERR_SHAPE;
     if (pos < 1 || pos >= T) return VLG_ERR_SHAPE;
+    const int cols = dec_box_columns(n_classes, ld, box_temperature, ext);
+    if (cols == 0) return VLG_ERR_SHAPE;
     const int64_t BN = (int64_t)B * N, M = BN * T;
     if (BN > 0x7fffffffLL) return VLG_ERR_SHAPE;                                        // the Philox counter word is the token index
     if (!out_last || !cls || !box || !gen_cls || !gen_box || !frame_cls || !frame_box) return VLG_ERR_SHAPE;
     // the window is updated in place (frame pos - 1 read, frame pos written); every other pair of buffers must be disjoint
     const void* p[8] = {out_last, cls, box, valid, gen_cls, gen_box, frame_cls, frame_box};
-    const int64_t n[8] = {BN * (n_classes + 4) * 4, M * 8, M * 16, M * 4, BN * steps * 8, BN * steps * 16, BN * 8, BN * 16};
+    const int64_t n[8] = {((BN - 1) * ld + cols) * 4, M * 8, M * 16, M * 4, BN * steps * 8, BN * steps * 16, BN * 8, BN * 16};
     for (int i = 0; i < 8; ++i)
         for (int j = i + 1; j < 8; ++j)
             if (dec_overlap(p[i], n[i], p[j], n[j])) return VLG_ERR_SHAPE;
@@ -317,10 +387,33 @@ extern "C" int vlg_layout_decode_append(const float* out_last, int64_t* cls, flo
         !vlg_aligned8(cls) || !vlg_aligned8(gen_cls) || !vlg_aligned8(frame_cls) ||
         (reinterpret_cast<uintptr_t>(valid) & 3u)) return VLG_ERR_ALIGN;
     const dim3 grid((unsigned)((BN + DEC_BLOCK - 1) / DEC_BLOCK)), block(DEC_BLOCK);
-    hipLaunchKernelGGL(layout_decode_append_kernel, grid, block, 0, (hipStream_t)stream, out_last, cls, box, valid, gen_cls,
-                       gen_box, frame_cls, frame_box, B, T, N, n_classes, pos, steps, step, temperature, top_k,
-                       (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), keep_padded);
+    const uint32_t k0 = (uint32_t)(seed & 0xffffffffu), k1 = (uint32_t)(seed >> 32);
+    if (box_temperature > 0.f)
+        hipLaunchKernelGGL(layout_decode_append_kernel<true>, grid, block, 0, (hipStream_t)stream, out_last, ld, cls, box, valid,
+                           gen_cls, gen_box, frame_cls, frame_box, B, T, N, n_classes, pos, steps, step, temperature, top_k, k0, k1,
+                           keep_padded, box_temperature);
+    else
+        hipLaunchKernelGGL(layout_decode_append_kernel<false>, grid, block, 0, (hipStream_t)stream, out_last, ld, cls, box, valid,
+                           gen_cls, gen_box, frame_cls, frame_box, B, T, N, n_classes, pos, steps, step, temperature, top_k, k0, k1,
+                           keep_padded, 0.f);
     return vlg_last_error();
+}
+
+extern "C" int vlg_layout_decode_append_ext(const float* out_last, int ld, int64_t* cls, float* box, float* valid,
+                                            int64_t* gen_cls, float* gen_box, int64_t* frame_cls, float* frame_box, int B, int T,
+                                            int N, int n_classes, int pos, int steps, int step, float temperature, int top_k,
+                                            float box_temperature, uint64_t seed, int keep_padded, void* stream) {
+    return decode_append_front(true, out_last, ld, cls, box, valid, gen_cls, gen_box, frame_cls, frame_box, B, T, N, n_classes, pos,
+                               steps, step, temperature, top_k, box_temperature, seed, keep_padded, stream);
+}
+
+// the ld = n_classes + 4, box_temperature = 0 call of the same front end
+extern "C" int vlg_layout_decode_append(const float* out_last, int64_t* cls, float* box, float* valid, int64_t* gen_cls,
+                                        float* gen_box, int64_t* frame_cls, float* frame_box, int B, int T, int N,
+                                        int n_classes, int pos, int steps, int step, float temperature, int top_k,
+                                        uint64_t seed, int keep_padded, void* stream) {
+    return decode_append_front(false, out_last, n_classes + 4, cls, box, valid, gen_cls, gen_box, frame_cls, frame_box, B, T, N,
+                               n_classes, pos, steps, step, temperature, top_k, 0.f, seed, keep_padded, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ scheduled sampling
@@ -357,7 +450,7 @@ __global__ __launch_bounds__(DEC_BLOCK) void layout_mix_inputs_kernel(
         const uint32_t thr = ramp_steps == 0 ? thr_max
                                              : (uint32_t)((uint64_t)thr_max * (uint64_t)(kk < ramp_steps ? kk : ramp_steps) / (uint64_t)ramp_steps);
         if ((philox_first((uint32_t)i, (uint32_t)k, k0, k1, 1u) >> 8) < thr)
-            decode_token(rows[tid], C, c, box + 4 * i, i, k, temperature, top_k, k0, k1, 0, c, bx);
+            decode_token<false>(rows[tid], C, c, box + 4 * i, i, k, temperature, top_k, k0, k1, 0, c, bx);
     }
     mix_cls[i] = c;
     st4(mix_box + 4 * i, bx);

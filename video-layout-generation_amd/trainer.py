@@ -61,6 +61,13 @@ Loss options in layout mode (all off by default; DESIGN.md "Loss options"): args
 comma-separated floats (vlg.metrics.balanced_class_weights turns the confusion matrix of VLG_VAL_METRICS=1 into such a
 list); args.label_smoothing / VLG_LABEL_SMOOTHING; args.box_overlap / VLG_BOX_OVERLAP = iou (default) or giou.
 
+Gaussian box head in layout mode (off by default; csrc/box_nll.hip, DESIGN.md "Gaussian box head"; box_knobs):
+args.box_head / VLG_BOX_HEAD = point (default) | gaussian gives the model four learned box scales beside the four means and
+one NLL launch behind the loss launch; args.box_nll_weight / VLG_BOX_NLL_WEIGHT (default 1) weighs that term, and is refused
+with the point head; validate() then adds box_nll and box_cover to its result.  args.gen_box_temperature /
+VLG_GEN_BOX_TEMPERATURE joins the generation knobs below: > 0 draws every generated box from the predicted distribution
+(refused with the point head).
+
 Generation knobs of generate_sequence in layout mode (a keyword argument wins over them; csrc/decode.hip, DESIGN.md
 "Generation"): args.gen_temperature / VLG_GEN_TEMPERATURE (0 = argmax; > 0 samples from softmax(logits / temperature)),
 args.gen_top_k / VLG_GEN_TOP_K (0 = every class, else only the k largest logits), args.gen_seed / VLG_GEN_SEED (default
@@ -107,7 +114,7 @@ from vlg.dp import GradReducer, bucket_ranges
 from vlg.optim import decayed_lr
 from vlg.raster import parse_size, raster_options
 from vlg.spec import (ADAM_BETA1, ADAM_LR, N_CLASSES, SEED, LayoutConfig, augment_options, dropout_options, loss_options,
-                      recipe_options, sched_options)
+                      recipe_options, sched_options, box_options, box_temperature_options)
 
 
 class AverageMeter(object):
@@ -272,6 +279,20 @@ def loss_knobs(args) -> Dict[str, object]:
     return knobs
 
 
+def box_knobs(args) -> Dict[str, object]:
+    """the Gaussian box head's knobs from args / environment (DESIGN.md "Gaussian box head"): {} with args.box_head /
+    VLG_BOX_HEAD unset or "point", so a config and an engine without the option are never handed one; else {box_head:
+    "gaussian", box_nll_weight} (args.box_nll_weight / VLG_BOX_NLL_WEIGHT, default 1).  box_head goes to LayoutConfig
+    (layout_config), box_nll_weight to the engine.  Refuses what they refuse (vlg.spec.box_options) - VLG_BOX_NLL_WEIGHT
+    with the point head included - before any engine exists."""
+    head = str(getattr(args, "box_head", None) or os.environ.get("VLG_BOX_HEAD") or "point").lower()
+    weight = getattr(args, "box_nll_weight", None)
+    if weight is None:
+        weight = os.environ.get("VLG_BOX_NLL_WEIGHT") or None
+    head, weight = box_options(head, weight, names=("VLG_BOX_HEAD", "VLG_BOX_NLL_WEIGHT"))
+    return {"box_head": head, "box_nll_weight": weight} if head == "gaussian" else {}
+
+
 def recipe_kwargs(knobs: Dict[str, object]) -> Dict[str, object]:
     """the recipe's engine keyword arguments - only those that are on, so an engine factory without them is never handed one"""
     return {k: knobs[k] for k in ("weight_decay", "warmup_steps", "ema_decay", "ema_warmup") if knobs.get(k)}
@@ -279,11 +300,19 @@ def recipe_kwargs(knobs: Dict[str, object]) -> Dict[str, object]:
 
 def generation_knobs(args) -> Dict[str, object]:
     """{temperature, top_k, seed, keep_padded} of generate_sequence in layout mode, from args / environment (module
-    docstring): argmax, every class, the run's seed, padded slots decoded like any other - unless asked otherwise."""
-    return {"temperature": _knob_float(args, "gen_temperature", "VLG_GEN_TEMPERATURE", 0.0),
-            "top_k": _knob(args, "gen_top_k", "VLG_GEN_TOP_K", 0),
-            "seed": _knob(args, "gen_seed", "VLG_GEN_SEED", int(getattr(args, "seed", SEED))),
-            "keep_padded": bool(_knob(args, "gen_keep_padded", "VLG_GEN_KEEP_PADDED", 0))}
+    docstring): argmax, every class, the run's seed, padded slots decoded like any other - unless asked otherwise.
+    args.gen_box_temperature / VLG_GEN_BOX_TEMPERATURE, where set, joins as box_temperature (the Gaussian box head's box
+    draw; refused here with the point head: vlg.spec.box_temperature_options); unset, the dict is the one it always was."""
+    knobs = {"temperature": _knob_float(args, "gen_temperature", "VLG_GEN_TEMPERATURE", 0.0),
+             "top_k": _knob(args, "gen_top_k", "VLG_GEN_TOP_K", 0),
+             "seed": _knob(args, "gen_seed", "VLG_GEN_SEED", int(getattr(args, "seed", SEED))),
+             "keep_padded": bool(_knob(args, "gen_keep_padded", "VLG_GEN_KEEP_PADDED", 0))}
+    tau = getattr(args, "gen_box_temperature", None)
+    if tau is None:
+        tau = os.environ.get("VLG_GEN_BOX_TEMPERATURE") or None
+    if tau is not None:
+        knobs["box_temperature"] = box_temperature_options(tau, box_knobs(args).get("box_head", "point"), "VLG_GEN_BOX_TEMPERATURE")
+    return knobs
 
 
 def clip_cache_knob(args) -> Dict[str, object]:
@@ -322,7 +351,8 @@ def layout_config(args) -> LayoutConfig:
     return LayoutConfig(B=max(int(args.batch_size) // gpus, 1), T=_knob(args, "n_frames", "VLG_FRAMES", 16),
                         N=_knob(args, "n_slots", "VLG_SLOTS", 64), d=_knob(args, "d_model", "VLG_DMODEL", 256),
                         n_layers=_knob(args, "n_layers", "VLG_LAYERS", 4),     # (the attention modes: vlg/attention.py)
-                        attention=str(getattr(args, "attention", None) or os.environ.get("VLG_ATTENTION", "slot")))
+                        attention=str(getattr(args, "attention", None) or os.environ.get("VLG_ATTENTION", "slot")),
+                        **{k: v for k, v in box_knobs(args).items() if k == "box_head"})
 
 
 def get_layout_engine(args, cfg: Optional[LayoutConfig] = None, engine_factory: Optional[Callable] = None):
@@ -340,7 +370,7 @@ def get_layout_engine(args, cfg: Optional[LayoutConfig] = None, engine_factory: 
                               padded_slots=bool(_knob(args, "variable_n", "VLG_VARIABLE_N", 0)),   # fixed-N feeds hold no padded slots
                               clip_grad=knobs["clip_grad"], skip_nonfinite=knobs["skip_nonfinite"], **recipe_kwargs(knobs),
                               **dropout_knobs(args), **clip_cache_knob(args), **loss_knobs(args), **sched_knobs(args),
-                              **augment_knobs(args))
+                              **augment_knobs(args), **{k: v for k, v in box_knobs(args).items() if k == "box_nll_weight"})
     else:
         engine = engine_factory(cfg, args)
     if knobs["lr_decay"]:                            # guarded from the start, so a checkpoint's lr and skip count are resumed
@@ -551,8 +581,9 @@ class Trainer:
         else:
             self.engine = get_layout_engine(args, self.cfg, engine_factory)
             if self.distributed:                                # replaces the DDP wrappers, trainer.py:113,115
-                self.reducer = GradReducer(self.engine.grads_ext,
-                                           bucket_ranges(self.engine.layout, self.engine.n_params, self.cfg.n_layers))
+                self.reducer = GradReducer(self.engine.grads_ext,       # (the loss scalars' tail: LayoutConfig.loss_tail)
+                                           bucket_ranges(self.engine.layout, self.engine.n_params, self.cfg.n_layers,
+                                                         tail_extra=self.cfg.loss_tail))
         self.device = self.engine.device
         self.gridnet = self.model = _ModelHandle(self.engine)   # reference attr `gridnet`; main.py:65 wants `.model`
         self.optim = optim_knobs(args)
@@ -673,6 +704,8 @@ class Trainer:
         self.args.logger.info("Validation started")
         self.gridnet.eval()
         val_loss = AverageMeter()
+        box_head = not self.image_mode and getattr(self.cfg, "gaussian_box", False)
+        box_nll, box_cover = AverageMeter(), AverageMeter()
         mk = metrics_knobs(self.args)
         record = None
         if mk["on"] and not self.image_mode:
@@ -690,7 +723,10 @@ class Trainer:
             if self.image_mode:
                 loss = self.engine.eval_loss(batch).clone()
             else:
-                loss = self.engine.forward(batch)[0:1].clone()      # forward only, reference src/trainer.py:320-333
+                scalars = self.engine.forward(batch)                # forward only, reference src/trainer.py:320-333
+                loss = scalars[0:1].clone()
+                if box_head:                                        # the Gaussian box head's {box_nll, box_cover}
+                    box = scalars[4:6].clone()
                 if record is not None:                              # one launch, adds to the device record; no host wait
                     self.engine.accumulate_metrics(batch, record, top_k=mk["top_k"], iou_thr=mk["iou_thr"])
             size = torch.tensor([float(batch[keys[0]].shape[0])], device=loss.device)
@@ -698,6 +734,12 @@ class Trainer:
             self.sync([loss, size], mean=False)                     # size-weighted SUM, trainer.py:336-338
             loss.div_(size)                                         # / GLOBAL clip count (see module docstring)
             val_loss.update(loss.item(), size.item())
+            if box_head:                                            # the same size-weighted mean over the ranks
+                box.mul_(float(batch[keys[0]].shape[0]))            # (size is the global count by now)
+                self.sync([box], mean=False)
+                box.div_(size)
+                box_nll.update(box[0].item(), size.item())
+                box_cover.update(box[1].item(), size.item())
             comp_time = time() - end
             end = time()
             if int(self.args.rank) == 0 and i % int(self.args.print_freq) == 0:
@@ -710,8 +752,12 @@ class Trainer:
             self.args.logger.info("Epoch [{epoch:d}/{tot_epoch:d}] loss [{loss:.4f}] ".format(
                 epoch=self.epoch, tot_epoch=int(self.args.epochs), loss=val_loss.avg))
             self.writer.add_scalar("val/loss", val_loss.avg, self.epoch)                # trainer.py:377
+        extra = {"box_nll": box_nll.avg, "box_cover": box_cover.avg} if box_head else {}
+        if box_head and int(self.args.rank) == 0:
+            self.writer.add_scalar("val/box_nll", box_nll.avg, self.epoch)
+            self.writer.add_scalar("val/box_cover", box_cover.avg, self.epoch)
         if record is None:
-            return {"loss": val_loss.avg}                                               # trainer.py:379
+            return dict({"loss": val_loss.avg}, **extra)                                # trainer.py:379
         record.all_reduce(lambda tensors: self.sync(tensors, mean=False))               # counts and sums are additive
         summary = record.summary()[0]                                                   # the pass's one read of the record
         if int(self.args.rank) == 0:
@@ -723,7 +769,7 @@ class Trainer:
             for key in ("accuracy", "mean_iou", "nll", "iou_hit"):
                 if summary[key] is not None:
                     self.writer.add_scalar("val/" + key, summary[key], self.epoch)
-        return dict(summary, loss=val_loss.avg)
+        return dict(summary, loss=val_loss.avg, **extra)
 
     def sync(self, tensors, mean=True):
         """Synchronize all tensors given using mean or sum (reference src/trainer.py:381-386)."""
@@ -864,7 +910,8 @@ class Trainer:
                 top_k=mk["top_k"] if val_topk is None else int(val_topk),
                 iou_thr=mk["iou_thr"] if val_iou_thr is None else float(val_iou_thr),
                 temperature=knobs["temperature"], sample_top_k=knobs["top_k"], seed=knobs["seed"], keep_padded=knobs["keep_padded"],
-                prompt_frames=prompt_frames, **pixels)
+                prompt_frames=prompt_frames, **pixels,
+                **({"box_temperature": knobs["box_temperature"]} if "box_temperature" in knobs else {}))
         out = record.summary()
         if pk:
             for s, p in zip(out, pixels["pixel_record"].summary()):

@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import dataclasses
 import functools
 import math
 import os
@@ -40,7 +41,8 @@ from .hip import (EPI_A_BF16, EPI_B_BF16, EPI_BIAS, EPI_DGELU, EPI_GELU, EPI_NON
                   call, ptr)
 from .spec import (ADAM_BETA1, ADAM_BETA2, ADAM_EPS, ADAM_LR, BOX_DIM, IOU_EPS, LN_EPS, LOSS_W_CE,
                    LOSS_W_REG, LOSS_W_STRUCT, SMOOTH_L1_BETA, LayoutConfig, decode_options, dropout_options, loss_options,
-                   augment_options, param_layout, sched_options)
+                   augment_options, param_layout, sched_options, BOX_HEAD_EXTRA, BOX_S_MAX, BOX_S_MIN, box_options,
+                   box_temperature_options)
 
 # the int32 device step counters: checkpoint key (= the advance launch's timer family, = the property that reads it) -> the
 # option an engine needs to have one
@@ -61,6 +63,9 @@ def init_params(cfg: LayoutConfig, seed: int) -> Dict[str, torch.Tensor]:
     out: Dict[str, torch.Tensor] = {}
     for name, (_, shape) in layout.items():
         base = name.split(".")[-1]
+        grown = cfg.gaussian_box and name in ("head_w", "head_b")
+        if grown:                                        # draw the point head's rows, in its order and shapes; append below
+            shape = (shape[0] - BOX_HEAD_EXTRA,) + tuple(shape[1:])
         if base in ("cls_emb", "time_emb"):
             t = torch.randn(shape, generator=g, dtype=torch.float32)
         elif base.endswith("_g"):
@@ -71,6 +76,8 @@ def init_params(cfg: LayoutConfig, seed: int) -> Dict[str, torch.Tensor]:
             t = (torch.rand(shape, generator=g, dtype=torch.float32) * 2 - 1) * (1.0 / math.sqrt(shape[1]))
         else:
             t = (torch.rand(shape, generator=g, dtype=torch.float32) * 2 - 1) * (1.0 / math.sqrt(fan_in[name]))
+        if grown:       # the scale and padding rows start at zero: sigma = exp((BOX_S_MIN + BOX_S_MAX) / 2); the padding rows stay there
+            t = torch.cat([t, t.new_zeros((BOX_HEAD_EXTRA,) + tuple(shape[1:]))], dim=0)
         out[name] = t
     return out
 
@@ -101,7 +108,7 @@ class LayoutEngine(AdamSurface):
                  sched_sampling: Optional[float] = None, sched_ramp_steps: int = 0, sched_temperature: float = 0.0,
                  sched_top_k: int = 0, sched_seed: int = 0, aug_flip: Optional[float] = None, aug_zoom: Optional[float] = None,
                  aug_shift: Optional[float] = None, aug_jitter: Optional[float] = None, aug_drop: Optional[float] = None,
-                 aug_seed: int = 0):
+                 aug_seed: int = 0, box_nll_weight: float = 1.0):
         """clip_grad > 0 clips the gradient to that global L2 norm (torch.nn.utils.clip_grad_norm_'s rule); skip_nonfinite
         leaves parameters, moments and step count untouched when the gradient holds inf or NaN.  Either one - or a call
         of set_lr - turns on the GUARDED optimiser step (vlg/optim.py), eager and captured alike; with both off and
@@ -157,8 +164,17 @@ class LayoutEngine(AdamSurface):
         are stateless Philox functions of (clip | track | token, step) under aug_seed; the step is a device counter of its own
         (augment_step / set_augment_step).  augmented_batch() shows the last training step's batch.  Whatever evaluates is
         untouched.  aug_drop > 0 needs padded_slots = True with a per-clip attention kind: their unmasked kernels would
-        attend to the dropped slots."""
+        attend to the dropped slots.
+        Gaussian box head (DESIGN.md "Gaussian box head"; rule: include/vlg_hip.h; legal values: vlg.spec.box_options): it is the
+        MODEL's option, LayoutConfig(box_head="gaussian") - with "point" nothing is allocated and no launch changes.  The head
+        then predicts four per-coordinate scales beside the four means (n_out = n_classes + 12), one vlg_layout_box_nll launch
+        follows the loss launch of every forward - training, validation, captured, scheduled sampling's pass 2 - and adds
+        box_nll_weight times the Gaussian negative log-likelihood of the target box to the total; its gradient reaches the scale
+        outputs only (the mean is detached).  forward() then returns 8 scalars {total, smooth_l1, iou, ce, box_nll, box_cover,
+        0, 0}, and rollout() / evaluate_rollout() take box_temperature to DRAW boxes.  box_nll_weight other than 1.0 is legal only
+        with that head."""
         cfg.validate()
+        self.box_nll_weight = box_options(cfg.box_head, box_nll_weight)[1]
         given = (aug_flip, aug_zoom, aug_shift, aug_jitter, aug_drop)
         self._aug = None if all(v is None for v in given) else augment_options(*given) + (int(aug_seed) & 0xFFFFFFFFFFFFFFFF,)
         self._sched = None if sched_sampling is None else sched_options(    # (the option rules: vlg/spec.py, the trainer's *_knobs call them too)
@@ -225,9 +241,9 @@ class LayoutEngine(AdamSurface):
         self.class_weights = None if weights is None else torch.tensor(weights, **f32)
         self._loss_ext = weights is not None or self.label_smoothing > 0.0 or self.box_overlap != "iou"
         self.params = torch.zeros(self.n_params, **f32)
-        # 4 extra floats after the last parameter hold the loss scalars, so they travel inside the
-        # first gradient bucket of the data-parallel all-reduce (vlg/dp.py)
-        self.grads_ext = torch.zeros(self.n_params + 4, **f32)
+        # cfg.loss_tail (4; 8 with the Gaussian box head) extra floats after the last parameter hold the loss scalars, so they
+        # travel inside the first gradient bucket of the data-parallel all-reduce (vlg.dp.bucket_ranges(tail_extra=cfg.loss_tail))
+        self.grads_ext = torch.zeros(self.n_params + cfg.loss_tail, **f32)
         self.grads = self.grads_ext[:self.n_params]
         # bf16 mode: a bf16 copy of the weights feeds the projections (the Adam kernel refreshes it with every update)
         self.params_bf16 = torch.zeros(self.n_params, dtype=torch.bfloat16, device=device) if self.bf16_store else None
@@ -239,7 +255,7 @@ class LayoutEngine(AdamSurface):
         self.load_params(init_params(cfg, seed))
         self._wgrad_plans: Dict[tuple, tuple] = {}
         self._alloc_workspace(cfg.tokens)
-        self.loss_out = self.grads_ext[self.n_params:]   # {total, smooth_l1, iou, ce}
+        self.loss_out = self.grads_ext[self.n_params:]   # {total, smooth_l1, iou, ce}; Gaussian box head: + {box_nll, box_cover, 0, 0}
         self.timer = None                            # optional KernelTimer (bench.py roofline leg)
 
     # ------------------------------------------------------------------ parameters
@@ -292,6 +308,10 @@ class LayoutEngine(AdamSurface):
         """(the moving average, where there is one, restarts from the loaded parameters)"""
         self._not_on_ema("load_params")
         for name in self.layout:
+            if self.cfg.gaussian_box and name in ("head_w", "head_b") and tensors[name].shape[0] == self.cfg.n_out - BOX_HEAD_EXTRA:
+                raise ValueError("%s has %d rows, a point head's; this engine's Gaussian box head has %d - "
+                                 "vlg.spec.grow_box_head(tensors, cfg) pads a point-head checkpoint with the zero rows"
+                                 % (name, tensors[name].shape[0], self.cfg.n_out))
             self.view(self.params, name).copy_(tensors[name].to(torch.float32))
         self._refresh_shadow()
         self.optim.seed_ema(self.params)
@@ -313,7 +333,11 @@ class LayoutEngine(AdamSurface):
 
     def load_state_dict(self, sd: Dict[str, object]) -> None:
         if tuple(sd["params"].shape) != (self.n_params,):
-            raise ValueError("checkpoint has %d parameters, model has %d" % (sd["params"].numel(), self.n_params))
+            hint = ""
+            if self.cfg.gaussian_box and sd["params"].numel() == param_layout(dataclasses.replace(self.cfg, box_head="point"))[1]:
+                hint = (" (a point-head checkpoint: load its named parameters through vlg.spec.grow_box_head(tensors, cfg) "
+                        "and load_params)")
+            raise ValueError("checkpoint has %d parameters, model has %d%s" % (sd["params"].numel(), self.n_params, hint))
         self._not_on_ema("load_state_dict")
         self.params.copy_(sd["params"])
         self._refresh_shadow()
@@ -424,6 +448,8 @@ class LayoutEngine(AdamSurface):
             self.aug_valid = torch.empty(M, **f32)
             self._aug_shape = None
         self.loss_scratch = torch.zeros(lib.vlg_layout_loss_scratch(), **f32)
+        if cfg.gaussian_box:                              # the NLL launch's own partials and ticket, zero between launches
+            self.box_nll_scratch = torch.zeros(lib.vlg_layout_box_nll_scratch(), **f32)
         # validation metrics (vlg_layout_metrics): per-block partial sums and the ticket, zero between launches
         self.metrics_scratch = torch.zeros(lib.vlg_layout_metrics_scratch(), dtype=torch.float64, device=self.device)
         n_clip = sum(k.per_clip for k in self.attn)
@@ -601,7 +627,8 @@ class LayoutEngine(AdamSurface):
     # --------------------------------------------------------------------- forward
     def forward(self, batch: Dict[str, torch.Tensor], padded_slots: Optional[bool] = None) -> torch.Tensor:
         """Forward + fused loss (the loss kernel also leaves d(total)/d(out) in self.dout).
-        Returns the device tensor {total, smooth_l1, iou, ce}.  padded_slots overrides the engine's setting for this
+        Returns the device tensor {total, smooth_l1, iou, ce} - with the Gaussian box head 8 floats, + {box_nll, box_cover, 0, 0},
+        and the total includes box_nll_weight * box_nll.  padded_slots overrides the engine's setting for this
         forward and the backward that follows it: a rollout window can hold padded slots where training batches never do."""
         return self._forward(batch, padded_slots, False)
 
@@ -658,6 +685,10 @@ class LayoutEngine(AdamSurface):
                         nbytes=nbytes + (12.0 * M if self.class_weights is not None else 0.0))
         else:
             self._timed("loss", 0.0, "vlg_layout_loss", *targets, *outs, s, nbytes=nbytes)
+        if cfg.gaussian_box:        # the scale columns' gradient, the padding columns' zeros, loss_out[4..7], and the total's NLL share
+            self._timed("box_nll", 0.0, "vlg_layout_box_nll", ptr(self.out), cfg.n_out, ptr(batch["tgt_box"]), ptr(batch["valid"]),
+                        ptr(self.dout), ptr(self.loss_out), ptr(self.box_nll_scratch), B, T, N, cfg.n_classes, BOX_S_MIN,
+                        BOX_S_MAX, self.box_nll_weight, s, nbytes=(52.0 + 32.0) * M)
         return self.loss_out
 
     def _encode(self, cls, box, time_emb, w, attn, B: int, T: int, N: int, drop: bool = False, final: bool = False, ldc=None) -> None:
@@ -988,7 +1019,7 @@ class LayoutEngine(AdamSurface):
 
     def rollout(self, slot_class: torch.Tensor, slot_box: torch.Tensor, steps: int = 8, temperature: float = 0.0,
                 top_k: int = 0, seed: int = 0, keep_padded: bool = False, return_logits: bool = False,
-                cache: Optional[bool] = None) -> tuple:
+                cache: Optional[bool] = None, box_temperature: float = 0.0) -> tuple:
         """Autoregressive generation on the device from a prompt of P frames, 1 <= P <= T: slot_class (B,P,N) int64 and
         slot_box (B,P,N,4) fp32 are device tensors and are not modified.  Returns DEVICE tensors gen_cls (B,steps,N) int64,
         gen_box (B,steps,N,4) fp32 and, with return_logits, the (steps, B*N, n_out) buffer of each step's [logits | raw box].
@@ -1006,8 +1037,14 @@ class LayoutEngine(AdamSurface):
         (_encode_step).  Which modes are cached by default: vlg/attention.py - per-clip attention only in an engine built with
         clip_cache=True: without the option it re-encodes the window per grown frame and cache=True raises.  cache=False
         always re-encodes.  Once the window is full the steps are the sliding ones above, from the same buffers.
-        No loss, no targets, no host wait inside the loop (one before it with per-clip attention: the mask decision)."""
+        No loss, no targets, no host wait inside the loop (one before it with per-clip attention: the mask decision).
+        box_temperature (the Gaussian box head; ValueError when > 0 on a point-head engine): 0 keeps the mean box sigmoid(raw);
+        tau > 0 DRAWS every generated box, box_k = clamp(mu_k + tau sigma_k z_k, 0, 1), z a stateless Philox normal of (token,
+        step) under `seed` on a stream of its own - the class draw is what it is without it.  A Gaussian-head engine decodes
+        through vlg_layout_decode_ext / vlg_layout_decode_append_ext (row stride n_out) in every step kind, sliding, cached and
+        re-encoded alike; a point-head engine's launches are what they always were."""
         cfg, d = self.cfg, self.cfg.d
+        box_tau = box_temperature_options(box_temperature, cfg.box_head)
         if slot_class.dim() != 3 or tuple(slot_box.shape) != tuple(slot_class.shape) + (BOX_DIM,):
             raise ValueError("rollout takes slot_class (B,P,N) and slot_box (B,P,N,4)")
         B, P, N = slot_class.shape
@@ -1050,6 +1087,8 @@ class LayoutEngine(AdamSurface):
         head = (ptr(self.p("lnf_g")), ptr(self.p("lnf_b")), ptr(self.p("head_w")), ptr(self.p("head_b")))
         head_kw = dict(nbytes=4.0 * BN * (d + cfg.n_out) + 4.0 * cfg.n_out * d)
         knobs = (float(temperature), top_k, int(seed) & 0xFFFFFFFFFFFFFFFF, int(bool(keep_padded)), s)
+        # the Gaussian head's rows are [logits | raw mean | raw scale | padding]: the _ext entries take the stride and the box draw
+        ext, dec_ld, dec_tau = ("_ext", (cfg.n_out,), (box_tau,)) if cfg.gaussian_box else ("", (), ())
         cur = 0                                                     # the window buffer that holds the history
         for i, (encoder, t_read, pos) in enumerate(grow_schedule(P, T, steps, cached)):
             (cls, box, valid), (ncls, nbox, nvalid) = win[cur], win[cur ^ 1]
@@ -1061,12 +1100,12 @@ class LayoutEngine(AdamSurface):
             self._timed("head_last", 2.0 * BN * cfg.n_out * d, "vlg_head_frame" if frame else "vlg_head_last_frame", ptr(x), *head,
                         ptr(logits[i]), B, Tx, N, d, cfg.n_out, *frame, LN_EPS, s, **head_kw)
             if pos is not None:                                     # append in place; the window does not move
-                self._timed("decode", 0.0, "vlg_layout_decode_append", ptr(logits[i]), ptr(cls), ptr(box), ptr(valid), ptr(gen_cls),
-                            ptr(gen_box), ptr(grow["cls"]), ptr(grow["box"]), B, T, N, cfg.n_classes, pos, steps, i, *knobs,
-                            nbytes=4.0 * BN * cfg.n_out + 3.0 * 28 * BN)
+                self._timed("decode", 0.0, "vlg_layout_decode_append" + ext, ptr(logits[i]), *dec_ld, ptr(cls), ptr(box), ptr(valid),
+                            ptr(gen_cls), ptr(gen_box), ptr(grow["cls"]), ptr(grow["box"]), B, T, N, cfg.n_classes, pos, steps, i,
+                            *knobs[:2], *dec_tau, *knobs[2:], nbytes=4.0 * BN * cfg.n_out + 3.0 * 28 * BN)
                 continue
-            self._timed("decode", 0.0, "vlg_layout_decode", ptr(logits[i]), ptr(cls), ptr(box), ptr(ncls), ptr(nbox),
-                        ptr(nvalid), ptr(gen_cls), ptr(gen_box), B, T, N, cfg.n_classes, steps, i, *knobs,
+            self._timed("decode", 0.0, "vlg_layout_decode" + ext, ptr(logits[i]), *dec_ld, ptr(cls), ptr(box), ptr(ncls), ptr(nbox),
+                        ptr(nvalid), ptr(gen_cls), ptr(gen_box), B, T, N, cfg.n_classes, steps, i, *knobs[:2], *dec_tau, *knobs[2:],
                         nbytes=4.0 * BN * cfg.n_out + 2.0 * 28 * M)
             cur ^= 1
         return (gen_cls, gen_box, logits) if return_logits else (gen_cls, gen_box)
@@ -1103,11 +1142,12 @@ class LayoutEngine(AdamSurface):
     def evaluate_rollout(self, clip_class: torch.Tensor, clip_box: torch.Tensor, record: Optional[MetricsRecord] = None,
                          top_k: int = 5, iou_thr: float = 0.5, return_logits: bool = False, temperature: float = 0.0,
                          sample_top_k: int = 0, seed: int = 0, keep_padded: bool = False, prompt_frames: Optional[int] = None,
-                         cache: Optional[bool] = None, pixel_record: Optional[PixelRecord] = None, pixel_size=None):
+                         cache: Optional[bool] = None, pixel_record: Optional[PixelRecord] = None, pixel_size=None,
+                         box_temperature: float = 0.0):
         """Score a rollout against the frames that really followed.  clip_class (B,P+S,N) int64 and clip_box (B,P+S,N,4)
         fp32 are device tensors: the first P = prompt_frames frames (None: T; 1 <= P <= T; `cache` as rollout takes it) are
         the prompt, rollout(..., steps=S) generates S frames under the sampling knobs (temperature, sample_top_k =
-        rollout's top_k, seed, keep_padded), and step i's [logits | raw box]
+        rollout's top_k, seed, keep_padded, and box_temperature - the Gaussian box head's box draw), and step i's [logits | raw box]
         are scored against frame P+i of the clip into row i of `record` (a fresh S-row record if None; a given one is
         added to): S launches of vlg_layout_metrics reading the clip in place, no host wait.  top_k and iou_thr are the
         METRIC's (top-k accuracy, IoU hit).  A truth slot with the reserved class id is unscored.
@@ -1140,7 +1180,7 @@ class LayoutEngine(AdamSurface):
         size = self._check_pixels(pixel_record, S, pixel_size) if pixel_record is not None else None
         gen_cls, gen_box, logits = self.rollout(clip_class[:, :P], clip_box[:, :P], steps=S, temperature=temperature,
                                                 top_k=sample_top_k, seed=seed, keep_padded=keep_padded, return_logits=True,
-                                                cache=cache)
+                                                cache=cache, box_temperature=box_temperature)
         for i in range(S):
             self._metrics(logits[i], cfg.n_out, clip_class, clip_box, None, TS, P + i, record, i, B, 1, N, top_k, iou_thr)
         if pixel_record is not None:

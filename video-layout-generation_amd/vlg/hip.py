@@ -69,6 +69,12 @@ SIGNATURES = {
     "vlg_layout_loss": (I, [P, I, P, P, P, P, P, P, I, I, I, I, F, F, F, F, F, P]),
     # (out, ld, tgt_class, tgt_box, valid, class_weight | NULL, dout, loss_out, scratch, B, T, N, C, beta, iou_eps, 3 weights, eps, flags, stream)
     "vlg_layout_loss_ext": (I, [P, I, P, P, P, P, P, P, P, I, I, I, I, F, F, F, F, F, F, I, P]),
+    "vlg_layout_box_nll_scratch": (I, []),
+    # (out, ld, tgt_box, valid, dout, loss_io, scratch, B, T, N, C, s_min, s_max, w_nll, stream)
+    "vlg_layout_box_nll": (I, [P, I, P, P, P, P, P, I, I, I, I, F, F, F, P]),
+    # the plain decode entries + ld after out_last and box_temperature after top_k
+    "vlg_layout_decode_ext": (I, [P, I, P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, F, c_uint64, I, P]),
+    "vlg_layout_decode_append_ext": (I, [P, I, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, I, F, c_uint64, I, P]),
     "vlg_head_last_frame": (I, [P, P, P, P, P, P, I, I, I, I, I, F, P]),
     "vlg_head_frame": (I, [P, P, P, P, P, P, I, I, I, I, I, I, F, P]),
     "vlg_layout_decode": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, c_uint64, I, P]),

@@ -43,6 +43,13 @@ SMOOTH_L1_BETA = 0.1            # boxes are normalised to [0,1]; beta=0.1 exerci
 IOU_EPS = 1e-7
 LN_EPS = 1e-5
 BOX_DIM = 4                     # (cx, cy, w, h), all in [0,1]
+# the Gaussian box head (LayoutConfig.box_head = "gaussian"; DESIGN.md "Gaussian box head"): log sigma = BOX_S_MIN +
+# (BOX_S_MAX - BOX_S_MIN) * sigmoid(raw scale), so sigma lies in [e^-7, 1] on boxes normalised to [0, 1]
+# (VLG_BOX_S_MIN / VLG_BOX_S_MAX of include/vlg_hip.h are the same numbers for the decoding kernels)
+BOX_S_MIN = -7.0
+BOX_S_MAX = 0.0
+BOX_HEADS = ("point", "gaussian")
+BOX_HEAD_EXTRA = 8              # columns a Gaussian head appends to a head-output row: 4 raw scales + 4 of padding
 
 
 @dataclasses.dataclass(frozen=True)
@@ -57,6 +64,10 @@ class LayoutConfig:
     # vlg/attention.py MODES: "slot" - the default the headline is quoted on -, "clip", or "factored" (divided space-time
     # attention).  Same parameters and checkpoints in all three; "factored" with n_layers = 1 is "slot"
     attention: str = "slot"
+    # "point": the box is sigmoid(raw), as ever.  "gaussian": four learned per-coordinate scales beside the four means - the
+    # head-output row grows to [logits | raw mean | raw scale | 4 of padding] (the padding keeps n_out a multiple of 8, which
+    # the reduced-precision projections need of N) and head_w / head_b gain those rows; nothing else changes
+    box_head: str = "point"
 
     @property
     def n_heads(self) -> int:
@@ -74,7 +85,18 @@ class LayoutConfig:
 
     @property
     def n_out(self) -> int:
-        return self.n_classes + BOX_DIM
+        return self.n_classes + BOX_DIM + (BOX_HEAD_EXTRA if self.box_head == "gaussian" else 0)
+
+    @property
+    def gaussian_box(self) -> bool:
+        return self.box_head == "gaussian"
+
+    @property
+    def loss_tail(self) -> int:
+        """floats of loss scalars behind the flat gradient (they ride in the first data-parallel bucket): {total, smooth_l1,
+        iou, ce}, with the Gaussian head + {box_nll, box_cover, 0, 0}.  THE definition: the engine's gradient buffer,
+        loss_out and bucket_ranges' tail_extra all take it"""
+        return 8 if self.gaussian_box else 4
 
     @property
     def tokens(self) -> int:
@@ -89,6 +111,8 @@ class LayoutConfig:
             raise ValueError("B, N, n_layers must be >= 1")
         if self.attention not in ATTENTION_MODES:
             raise ValueError("attention must be 'slot', 'clip' or 'factored'")
+        if self.box_head not in BOX_HEADS:
+            raise ValueError("box_head must be one of %s, got %r" % (BOX_HEADS, self.box_head))
         if any(k.per_clip for k in MODES[self.attention]) and (self.T * self.N) % 32 != 0:
             raise ValueError("attention=%r needs T*N to be a multiple of 32 (32-token MFMA tiles)" % self.attention)
 
@@ -101,6 +125,12 @@ class LayoutConfig:
         return layer_kinds(self.attention, self.n_layers).count(FRAME)
 
     def describe(self) -> Dict[str, object]:
+        d = self._describe()
+        if self.gaussian_box:       # (only with the option on: the default's line does not change)
+            d["box_head"] = "gaussian (log sigma in [%g, %g], detached mean)" % (BOX_S_MIN, BOX_S_MAX)
+        return d
+
+    def _describe(self) -> Dict[str, object]:
         return {"B": self.B, "T": self.T, "N": self.N, "d": self.d, "layers": self.n_layers,
                 "heads": self.n_heads, "d_ff": self.d_ff, "classes": self.n_classes,
                 "attention": {"slot": "causal-temporal-per-slot", "clip": "block-causal-per-clip (every slot of frames <= t)",
@@ -136,6 +166,53 @@ def loss_options(class_weights=None, label_smoothing: float = 0.0, box_overlap: 
     if box_overlap not in BOX_OVERLAPS:
         raise ValueError("box_overlap must be one of %s, got %r" % (BOX_OVERLAPS, box_overlap))
     return weights, eps, box_overlap
+
+
+def box_options(box_head: str = "point", box_nll_weight=None, names=("box_head", "box_nll_weight")):
+    """The box head's options, in loss_options' shape: (box_head, weight of the NLL term in the total).  box_head "point" or
+    "gaussian"; box_nll_weight finite and >= 0, and anything but its default 1.0 (None counts as the default) is legal ONLY
+    with the Gaussian head - the point head has no such term.  ValueError otherwise."""
+    if box_head not in BOX_HEADS:
+        raise ValueError("%s must be one of %s, got %r" % (names[0], BOX_HEADS, box_head))
+    try:
+        w = 1.0 if box_nll_weight is None else float(box_nll_weight)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a number, got %r" % (names[1], box_nll_weight)) from None
+    if box_head != "gaussian" and w != 1.0:             # (NaN != 1.0 too)
+        raise ValueError("%s needs %s=gaussian: the point head has no scale to fit" % (names[1], names[0]))
+    if not (math.isfinite(w) and w >= 0.0):
+        raise ValueError("%s must be finite and >= 0, got %r" % (names[1], box_nll_weight))
+    return box_head, w
+
+
+def box_temperature_options(box_temperature, box_head: str = "point", name: str = "box_temperature") -> float:
+    """the box draw's temperature of rollout / evaluate_rollout: finite and >= 0 (0 = the mean box); > 0 needs the Gaussian head"""
+    try:
+        tau = float(box_temperature)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a number, got %r" % (name, box_temperature)) from None
+    if not (math.isfinite(tau) and tau >= 0.0):
+        raise ValueError("%s must be finite and >= 0, got %r" % (name, box_temperature))
+    if tau > 0.0 and box_head != "gaussian":
+        raise ValueError("%s > 0 needs box_head=gaussian: the point head predicts no scale to draw from" % name)
+    return tau
+
+
+def grow_box_head(tensors, cfg: "LayoutConfig"):
+    """The named parameters of a POINT-head checkpoint -> the dict a Gaussian-head engine of `cfg` loads: head_w / head_b
+    padded with the zero rows init_params gives a Gaussian head (sigma starts at exp((BOX_S_MIN + BOX_S_MAX) / 2)), every
+    other tensor passed through.  Fits a scale head onto a trained model."""
+    import torch
+    if not cfg.gaussian_box:
+        raise ValueError("grow_box_head takes the Gaussian-head config the result is for (box_head=%r)" % cfg.box_head)
+    point = cfg.n_classes + BOX_DIM
+    out = dict(tensors)
+    for name, want in (("head_w", (point, cfg.d)), ("head_b", (point,))):
+        t = tensors[name]
+        if tuple(t.shape) != want:
+            raise ValueError("grow_box_head: %s has shape %s, a point head of this config has %s" % (name, tuple(t.shape), want))
+        out[name] = torch.cat([t, t.new_zeros((BOX_HEAD_EXTRA,) + tuple(t.shape[1:]))], dim=0)
+    return out
 
 
 # The other options' rules, in loss_options' shape: checked on the host, normalised values back or ValueError.  `names` are
