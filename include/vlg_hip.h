@@ -406,6 +406,20 @@ int vlg_attention_frame_step(const float* qkv, const float* valid, float* o,
 int vlg_attention_frame_step_bf16(const vlg_bf16* qkv, const float* valid, vlg_bf16* o,
                                   int64_t B, int T, int N, int d, int p, int64_t ldo, void* stream);
 
+/* ------------------------------------------------------------------ random draws (csrc/philox.h)
+ * Every draw of generation, scheduled sampling, augmentation and the Gaussian box head below is a word of Philox4x32-10 on
+ * counter (index, step, stream, 0) under key (seed & 0xffffffff, seed >> 32).  `stream` keeps the draws of one (index, step)
+ * apart; this is the one table of them, and a new kind of draw takes a new entry.  The rules below name them by number.
+ * The dropout mask above is not in it: its third counter word is its SITE, and its own seed keeps it apart from these. */
+enum vlg_rng_stream {
+    VLG_RNG_CLASS_DRAW   = 0,   /* u of a sampled class: vlg_layout_decode*, and a replaced token of vlg_layout_mix_inputs */
+    VLG_RNG_SCHED_COIN   = 1,   /* scheduled sampling: truth or prediction */
+    VLG_RNG_CLIP_DRAW    = 2,   /* augmentation, per clip: flip, zoom, shift */
+    VLG_RNG_TRACK_DROP   = 3,   /* augmentation, per track: drop */
+    VLG_RNG_TOKEN_JITTER = 4,   /* augmentation, per input token: jitter */
+    VLG_RNG_BOX_NORMAL   = 5    /* the sampled box of vlg_layout_decode*_ext */
+};
+
 /* ------------------------------------------------------------------ generation (csrc/decode.hip)
  * The forward-only tail of an autoregressive rollout (reference src/trainer.py:453-476 rolls its pixel model out the same
  * way: predict, argmax, append, slide).  SELF-ORACLE (tests/decode_ref.py); rule and rooflines: DESIGN.md, "Generation".
@@ -462,9 +476,8 @@ int vlg_layout_decode_append(const float* out_last, int64_t* cls, float* box, fl
  *   box    box_temperature == 0: sigmoid(raw), exactly as above (the kernel instantiation of the plain entries).
  *          box_temperature = tau > 0 (needs ld >= n_classes + 8 and n_classes + 8 <= 32, else VLG_ERR_SHAPE): out_last rows
  *          are [logits | raw mean | raw scale | ...];  (x0, x1, x2, x3) = all four words of Philox4x32-10 on counter
- *          (b*N + n, step, 5, 0) under the call's key (streams 0 and 1 are the class draw and the scheduled-sampling coin,
- *          2 to 4 augmentation's);  u_i = (x_i >> 8) * 2^-24 + 2^-25 evaluated in fp32 as the class draw's u (so u may round
- *          to 1.0, which gives z = 0);  z0 = sqrt(-2 ln u0) cos(2 pi u1), z1 = sqrt(-2 ln u0) sin(2 pi u1), z2, z3 likewise
+ *          (b*N + n, step, 5, 0) under the call's key (stream VLG_RNG_BOX_NORMAL of enum vlg_rng_stream above);
+ *          u_i = (x_i >> 8) * 2^-24 + 2^-25 evaluated in fp32 as the class draw's u (so u may round to 1.0, which gives z = 0);  z0 = sqrt(-2 ln u0) cos(2 pi u1), z1 = sqrt(-2 ln u0) sin(2 pi u1), z2, z3 likewise
  *          from u2, u3;  mu_k = sigmoid(raw mean_k), sigma_k = exp(VLG_BOX_S_MIN + (VLG_BOX_S_MAX - VLG_BOX_S_MIN)
  *          sigmoid(raw scale_k));  box_k = min(max(mu_k + tau sigma_k z_k, 0), 1).
  *   class  untouched: the same counter (b*N + n, step, 0, 0), the same rule.
@@ -525,7 +538,7 @@ int vlg_layout_mix_inputs(const float* out, int ld, const int64_t* cls, const fl
  * Token i = (b*T + t)*N + n, track r = b*N + n.  W(c0,c1,c2,c3) = the four words of Philox4x32-10 on that counter under key
  * (seed & 0xffffffff, seed >> 32);  v(x) = (float)(x >> 8) * 2^-23 - 1, in [-1, 1) and exact in fp32;
  * coin(x, thr) = (x >> 8) < thr with thr = round(p * 2^24) (vlg_augment_plan is the one place this rounding lives): 0 never
- * wins, 2^24 always does.  Counter word c2 names the stream: 2, 3, 4 here, clear of the 0 and 1 of csrc/decode.hip.
+ * wins, 2^24 always does.  Counter word c2 names the stream: 2, 3, 4 here (enum vlg_rng_stream above, the one table).
  *   clip draw   (x0..x3) = W(b, k, 2, 0):  flip = coin(x0, thr_flip), s = 1 + zoom * v(x1), tx = shift * v(x2), ty = shift * v(x3)
  *   track draw  drop = coin(first word of W(r, k, 3, 0), thr_drop)
  *   token draw  (inputs only, only when jitter > 0)  (y0..y3) = W(i, k, 4, 0):  jx = jitter * v(y0), jy = jitter * v(y1),

@@ -20,38 +20,24 @@ jitter where valid > 0, else a bit copy.  valid: 0 on a dropped track, else copi
 import numpy as np
 import torch
 
-import decode_ref as D
+import philox_ref as P
+from philox_ref import coin, words  # noqa: F401  (words(index, k, stream, seed): the four words of counter (index, k, stream, 0))
 
-TWO24 = 1 << 24
+TWO24 = P.TWO24
 NC = 20
 F = np.float32
 MIN_SIZE = F(2.0 ** -10)
-STREAM_CLIP, STREAM_TRACK, STREAM_TOKEN = 2, 3, 4
+STREAM_CLIP, STREAM_TRACK, STREAM_TOKEN = P.CLIP_DRAW, P.TRACK_DROP, P.TOKEN_JITTER
 
 
 def threshold(p):
     """round(p * 2^24): what vlg_augment_plan computes"""
     if not 0.0 <= p <= 1.0:
         raise ValueError("a probability must be in [0, 1]")
-    return int(np.floor(np.float64(p) * TWO24 + 0.5))
+    return P.coin_threshold(p)
 
 
-def words(index, k, stream, seed):
-    """the four Philox words of counter (index, k, stream, 0) under the seed's key, uint64 arrays < 2^32"""
-    index = np.asarray(index, dtype=np.uint64)
-    z = np.zeros_like(index)
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    return D.philox4x32_10((index, z + np.uint64(k), z + np.uint64(stream), z),
-                           (z + np.uint64(seed & 0xFFFFFFFF), z + np.uint64(seed >> 32)))
-
-
-def v(x):
-    """(float)(x >> 8) * 2^-23 - 1: fp32 in [-1, 1), every step exact"""
-    return (x >> np.uint64(8)).astype(F) * F(2.0 ** -23) - F(1.0)
-
-
-def coin(x, thr):
-    return (x >> np.uint64(8)).astype(np.int64) < int(thr)
+v = P.signed32          # (float)(x >> 8) * 2^-23 - 1: fp32 in [-1, 1), every step exact
 
 
 def clip_draw(B, k, seed, thr_flip, zoom, shift):

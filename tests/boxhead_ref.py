@@ -17,9 +17,10 @@ import numpy as np
 import torch
 
 import decode_ref
+import philox_ref as P
 
 S_MIN, S_MAX = -7.0, 0.0                 # vlg.spec.BOX_S_MIN / BOX_S_MAX (the CPU test checks they agree)
-BOX_STREAM = 5                           # the Philox counter's third word of the box draw
+BOX_STREAM = P.BOX_NORMAL                # the Philox counter's third word of the box draw
 HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 EPS32 = 2.0 ** -24                       # half an fp32 ulp at 1
 
@@ -98,20 +99,12 @@ def check_nll(got_dscale, got_nll, got_cover, ref, what=""):
 
 
 # ---- sampled boxes ---------------------------------------------------------------------------------------------------------
-def uniforms32(words):
-    """u of Philox words as the kernels form it: fp32 arithmetic (x >> 8 is exact, the sum rounds above 2^23), as float64"""
-    v = (np.asarray(words, dtype=np.uint64) >> np.uint64(8)).astype(np.float32)
-    return (v * np.float32(2.0 ** -24) + np.float32(2.0 ** -25)).astype(np.float64)
+uniforms32 = P.unit32   # u of Philox words as the kernels form it: fp32 arithmetic, as float64
 
 
 def normals(tokens, step, seed):
     """(R, 4) float64: z0..z3 of every token index in `tokens` at `step` under `seed`"""
-    tokens = np.asarray(tokens, dtype=np.uint64)
-    zero = np.zeros_like(tokens)
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    x = decode_ref.philox4x32_10((tokens, zero + np.uint64(step), zero + np.uint64(BOX_STREAM), zero),
-                                 (zero + np.uint64(seed & 0xFFFFFFFF), zero + np.uint64(seed >> 32)))
-    return normals_of_words(x)
+    return normals_of_words(P.words(tokens, step, BOX_STREAM, seed))
 
 
 def normals_of_words(x):

@@ -1,42 +1,23 @@
-"""CPU restatement of the generation step (include/vlg_hip.h, vlg_layout_decode; DESIGN.md "Generation"): Philox4x32-10
-in numpy integers, the decoding rule in fp64, the window slide.  Plain module: test infrastructure, nothing collected.
+"""CPU restatement of the generation step (include/vlg_hip.h, vlg_layout_decode; DESIGN.md "Generation"): the decoding
+rule in fp64, the window slide.  Plain module: test infrastructure, nothing collected.
 
 The rule, word for word.  Box = sigmoid(raw).  temperature == 0: the first maximum of the logits.  temperature > 0: kept
 set = every class (top_k == 0) or the top_k largest raw logits, equal values ordered by lower class index first;
 z = logit / temperature, m = max z over the kept set, p = exp(z - m) on the kept set and 0 elsewhere; cum = running sum
 of p in class order, S its last value; the class is the first kept c with cum_c >= u * S, the last kept class if none.
-u = (x0 >> 8) * 2^-24 + 2^-25 with x0 the first word of Philox4x32-10 on counter (token, step, 0, 0) under key
-(seed & 0xffffffff, seed >> 32), token = b*N + n.  keep_padded: a slot whose class in the window's last frame is
+u = (x0 >> 8) * 2^-24 + 2^-25 with x0 the first word of Philox4x32-10 (tests/philox_ref.py) on counter (token, step, 0, 0)
+under key (seed & 0xffffffff, seed >> 32), token = b*N + n.  keep_padded: a slot whose class in the window's last frame is
 >= n_classes keeps that id and its box."""
 import numpy as np
 import torch
 
-M0, M1 = 0xD2511F53, 0xCD9E8D57
-W0, W1 = 0x9E3779B9, 0xBB67AE85
-_MASK = np.uint64(0xFFFFFFFF)
-_32 = np.uint64(32)
-
-
-def philox4x32_10(counter, key):
-    """counter: 4 words, key: 2 words (ints or equal-shaped integer arrays) -> the 4 output words as uint64 arrays < 2^32.
-    Random123's round: c' = [hi(M1*c2) ^ c1 ^ k0, lo(M1*c2), hi(M0*c0) ^ c3 ^ k1, lo(M0*c0)], key += (W0, W1) between rounds."""
-    c = [np.asarray(x, dtype=np.uint64) & _MASK for x in counter]
-    k = [np.asarray(x, dtype=np.uint64) & _MASK for x in key]
-    for r in range(10):
-        if r > 0:
-            k = [(k[0] + np.uint64(W0)) & _MASK, (k[1] + np.uint64(W1)) & _MASK]
-        p0, p1 = np.uint64(M0) * c[0], np.uint64(M1) * c[2]              # 32 x 32 -> 64 bits: exact in uint64
-        c = [(p1 >> _32) ^ c[1] ^ k[0], p1 & _MASK, (p0 >> _32) ^ c[3] ^ k[1], p0 & _MASK]
-    return c
+import philox_ref as P
+from philox_ref import philox4x32_10  # noqa: F401  (the generator lives in philox_ref; this name keeps working)
 
 
 def uniform(tokens, step, seed):
     """u of every token index in `tokens` at `step` under `seed`: float64, strictly inside (0, 1)"""
-    tokens = np.asarray(tokens, dtype=np.uint64)
-    zero = np.zeros_like(tokens)
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    x0 = philox4x32_10((tokens, zero + np.uint64(step), zero, zero), (zero + np.uint64(seed & 0xFFFFFFFF), zero + np.uint64(seed >> 32)))[0]
-    return (x0 >> np.uint64(8)).astype(np.float64) * 2.0 ** -24 + 2.0 ** -25
+    return P.unit64(P.words(tokens, step, P.CLASS_DRAW, seed)[0])
 
 
 def decode_step(logits64, step, temperature, top_k, seed, margin=1e-5):

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from decode_ref import philox4x32_10
+from philox_ref import philox4x32_10
 from oracle import layout_spec as O
 
 TWO32 = 2 ** 32

@@ -18,15 +18,16 @@ import numpy as np
 import torch
 
 import decode_ref as D
+import philox_ref as P
 
-TWO24 = 1 << 24
+TWO24 = P.TWO24
 
 
 def thr_max(eps_max):
     """round(eps_max * 2^24): what vlg_sched_plan computes"""
     if not 0.0 <= eps_max <= 1.0:
         raise ValueError("eps_max must be in [0, 1]")
-    return int(np.floor(np.float64(eps_max) * TWO24 + 0.5))
+    return P.coin_threshold(eps_max)
 
 
 def thr(k, thr_max_, ramp_steps):
@@ -36,23 +37,14 @@ def thr(k, thr_max_, ramp_steps):
     return int(thr_max_) * min(int(k) + 1, int(ramp_steps)) // int(ramp_steps)
 
 
-def _words(tokens, k, stream, seed):
-    """first Philox word of counter (token, k, stream, 0) under the seed's key, uint64 array < 2^32"""
-    tokens = np.asarray(tokens, dtype=np.uint64)
-    z = np.zeros_like(tokens)
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    return D.philox4x32_10((tokens, z + np.uint64(k), z + np.uint64(stream), z),
-                           (z + np.uint64(seed & 0xFFFFFFFF), z + np.uint64(seed >> 32)))[0]
-
-
 def coin_words(tokens, k, seed):
     """x >> 8 of every token's coin: 24-bit integers"""
-    return (_words(tokens, k, 1, seed) >> np.uint64(8)).astype(np.int64)
+    return P.bits24(P.words(tokens, k, P.SCHED_COIN, seed)[0])
 
 
 def draw_words(tokens, k, seed):
     """x >> 8 of every token's class draw (counter stream 0, the one decode_ref.uniform reads)"""
-    return (_words(tokens, k, 0, seed) >> np.uint64(8)).astype(np.int64)
+    return P.bits24(P.words(tokens, k, P.CLASS_DRAW, seed)[0])
 
 
 def eligible(slot_class, n_classes):

@@ -1,6 +1,6 @@
 // Augmentation of a layout batch on the device (rule: include/vlg_hip.h, "augmentation"; DESIGN.md "Augmentation").
 //
-// vlg_augment_plan    host only: probability -> the 24-bit coin threshold
+// vlg_augment_plan    host only: probability -> the 24-bit coin threshold (philox_coin_threshold, philox.h)
 // vlg_layout_augment  per clip flip / zoom / shift, per input token jitter, per track drop: one launch, the caller's batch
 //                     only read, four engine-owned buffers written
 //
@@ -9,13 +9,11 @@
 // draw by the T threads of the track (an integer-only Philox call each, no LDS, no second launch).  Launch-bound: 88 bytes
 // per token, 2.9 MB at (32,16,64).  Three compile-time variants: AUG_COPY (flip / drop only: a box that is not flipped is
 // moved as the four words it is), AUG_GEO (zoom / shift) and AUG_JIT (+ the third Philox call of the token draw).
-#include "layernorm_rows.h"         // philox4x32_10
+#include "common.h"
+#include "philox.h"
 
 #define AUG_BLOCK 256
 enum { AUG_COPY = 0, AUG_GEO = 1, AUG_JIT = 2 };
-
-// v(x): 24 bits of a Philox word as a float in [-1, 1), every step exact in fp32
-__device__ __forceinline__ float aug_v(uint32_t x) { return (float)(x >> 8) * 1.1920928955078125e-7f - 1.0f; }
 
 // One axis of the crop to the image.  max / min of the rule are the comparisons written here, so a NaN becomes the constant.
 __device__ __forceinline__ void aug_crop(float& c, float& w) {
@@ -72,24 +70,24 @@ __global__ __launch_bounds__(AUG_BLOCK) void layout_augment_kernel(
     bool flip = false, drop = false;
     float s = 1.f, tx = 0.f, ty = 0.f, jx = 0.f, jy = 0.f, jw = 1.f, jh = 1.f;
     if (MODE != AUG_COPY || thr_flip != 0u) {                      // (a zero threshold never wins: the draw is not needed)
-        philox4x32_10((uint32_t)b, k, 2u, 0u, k0, k1, x);
-        flip = (x[0] >> 8) < thr_flip;
+        philox4x32_10((uint32_t)b, k, VLG_RNG_CLIP_DRAW, 0u, k0, k1, x);
+        flip = philox_coin(x[0], thr_flip);
         if constexpr (MODE != AUG_COPY) {
-            s = 1.0f + zoom * aug_v(x[1]);
-            tx = shift * aug_v(x[2]);
-            ty = shift * aug_v(x[3]);
+            s = 1.0f + zoom * philox_signed(x[1]);
+            tx = shift * philox_signed(x[2]);
+            ty = shift * philox_signed(x[3]);
         }
     }
     if (thr_drop != 0u) {
-        philox4x32_10((uint32_t)(b * N + n), k, 3u, 0u, k0, k1, x);
-        drop = (x[0] >> 8) < thr_drop;
+        philox4x32_10((uint32_t)(b * N + n), k, VLG_RNG_TRACK_DROP, 0u, k0, k1, x);
+        drop = philox_coin(x[0], thr_drop);
     }
     if constexpr (MODE == AUG_JIT) {
-        philox4x32_10((uint32_t)i, k, 4u, 0u, k0, k1, x);
-        jx = jitter * aug_v(x[0]);
-        jy = jitter * aug_v(x[1]);
-        jw = 1.0f + jitter * aug_v(x[2]);
-        jh = 1.0f + jitter * aug_v(x[3]);
+        philox4x32_10((uint32_t)i, k, VLG_RNG_TOKEN_JITTER, 0u, k0, k1, x);
+        jx = jitter * philox_signed(x[0]);
+        jy = jitter * philox_signed(x[1]);
+        jw = 1.0f + jitter * philox_signed(x[2]);
+        jh = 1.0f + jitter * philox_signed(x[3]);
     }
 
     if (drop) {                                                    // the whole track, in every frame: reserved class, zero box
@@ -108,14 +106,10 @@ __global__ __launch_bounds__(AUG_BLOCK) void layout_augment_kernel(
 
 extern "C" int vlg_augment_plan(double p, uint32_t* thr_host) {
     if (!(p >= 0.0 && p <= 1.0) || thr_host == nullptr) return VLG_ERR_SHAPE;
-    *thr_host = (uint32_t)__builtin_floor(p * 16777216.0 + 0.5);
+    *thr_host = philox_coin_threshold(p);
     return 0;
 }
 
-static inline bool aug_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
-}
 static inline bool aug_knob_ok(float x, float bound) { return x >= 0.f && x <= bound; }      // (refuses NaN and inf)
 
 extern "C" int vlg_layout_augment(const int64_t* cls, const float* box, const float* tgt_box, const float* valid,
@@ -124,7 +118,7 @@ extern "C" int vlg_layout_augment(const int64_t* cls, const float* box, const fl
                                   float shift, float jitter, uint64_t seed, void* stream) {
     if (B < 1 || T < 1 || N < 1 || n_classes < 1) return VLG_ERR_SHAPE;
     const int64_t M = (int64_t)B * T * N;
-    if (M > 0x7fffffffLL) return VLG_ERR_SHAPE;                                         // the Philox counter word is the token index
+    if (!philox_index_fits(M)) return VLG_ERR_SHAPE;                                    // the Philox counter word is the token index
     if (thr_flip > (1u << 24) || thr_drop > (1u << 24)) return VLG_ERR_SHAPE;
     if (!aug_knob_ok(zoom, 0.5f) || !aug_knob_ok(shift, 0.5f) || !aug_knob_ok(jitter, 0.25f)) return VLG_ERR_SHAPE;
     if (!cls || !box || !tgt_box || !valid || !aug_cls || !aug_box || !aug_tgt_box || !aug_valid || !step) return VLG_ERR_SHAPE;
@@ -133,16 +127,16 @@ extern "C" int vlg_layout_augment(const int64_t* cls, const float* box, const fl
     const int64_t nb[9] = {M * 8, M * 16, M * 16, M * 4, M * 8, M * 16, M * 16, M * 4, 4};
     for (int o = 0; o < 4; ++o)
         for (int j = o + 1; j < 9; ++j)
-            if (aug_overlap(p[o], nb[o], p[j], nb[j])) return VLG_ERR_SHAPE;
+            if (vlg_overlap(p[o], nb[o], p[j], nb[j])) return VLG_ERR_SHAPE;
     if (!vlg_aligned16(box) || !vlg_aligned16(tgt_box) || !vlg_aligned16(aug_box) || !vlg_aligned16(aug_tgt_box) ||
-        !vlg_aligned8(cls) || !vlg_aligned8(aug_cls) || ((reinterpret_cast<uintptr_t>(valid) | reinterpret_cast<uintptr_t>(aug_valid) |
-                                                          reinterpret_cast<uintptr_t>(step)) & 3u)) return VLG_ERR_ALIGN;
+        !vlg_aligned8(cls) || !vlg_aligned8(aug_cls) || !vlg_aligned4(valid) || !vlg_aligned4(aug_valid) || !vlg_aligned4(step))
+        return VLG_ERR_ALIGN;
     const dim3 grid((unsigned)((M + AUG_BLOCK - 1) / AUG_BLOCK)), block(AUG_BLOCK);
-    const uint32_t k0 = (uint32_t)(seed & 0xffffffffu), k1 = (uint32_t)(seed >> 32);
+    const PhiloxKey key = philox_key(seed);
 #define AUG_LAUNCH(MODE)                                                                                                       \
     hipLaunchKernelGGL(layout_augment_kernel<MODE>, grid, block, 0, (hipStream_t)stream, cls, box, tgt_box, valid, aug_cls,   \
                        aug_box, aug_tgt_box, aug_valid, step, (int)M, T, N, n_classes, thr_flip, thr_drop, zoom, shift, jitter, \
-                       k0, k1)
+                       key.k0, key.k1)
     if (jitter > 0.f) AUG_LAUNCH(AUG_JIT);                         // one decision for the whole launch
     else if (zoom > 0.f || shift > 0.f) AUG_LAUNCH(AUG_GEO);
     else AUG_LAUNCH(AUG_COPY);

@@ -11,8 +11,8 @@
 // 52 B in and 32 B out per token - 2.8 MB at the metric shape - so the launch is bound by its latency, not by bytes.
 // Every block counts the valid slots ITSELF, as layout_loss_kernel does (the mean's denominator scales every gradient; a
 // sum of 0/1 flags is exact in fp32 in any order), with its first pass's loads already in flight.  The last block to
-// finish (an integer ticket in scratch[1], which it resets) folds the per-block partials in block order into loss_io: no
-// float atomics, the same bits from launch to launch.
+// finish (an integer ticket in scratch[1], which it resets) folds the per-block partials in a fixed order into loss_io
+// (vlg_ticket_draw / vlg_ticket_last / vlg_fold_partials, common.h): no float atomics, the same bits from launch to launch.
 #include "common.h"
 
 #define BNLL_BLOCK 256
@@ -104,28 +104,19 @@ __global__ __launch_bounds__(BNLL_BLOCK) void layout_box_nll_kernel(
     }
     s_nll = block_sum(s_nll, red);
     s_cov = block_sum(s_cov, red);
+    unsigned int* ticket = reinterpret_cast<unsigned int*>(scratch) + 1;
     if (tid == 0) {
         float* part = scratch + 4 + 4 * blockIdx.x;
         part[0] = s_nll * inv_cnt; part[1] = s_cov * inv_cnt; part[2] = 0.f; part[3] = 0.f;
-        // publish the partial (agent scope), take a ticket; the block that draws the last one sees every partial
-        __threadfence();
-        int* ticket = reinterpret_cast<int*>(scratch) + 1;
-        const int drawn = atomicAdd(ticket, 1);
-        last_sh = (drawn == (int)gridDim.x - 1) ? 1 : 0;
+        vlg_ticket_draw(ticket, &last_sh);
     }
-    __syncthreads();
-    if (last_sh && tid < 64) {
-        __threadfence();
-        float a = 0.f, b = 0.f;
-        for (int i = tid; i < (int)gridDim.x; i += 64) {           // fixed order: lane i sums blocks i, i + 64, ... ; then the shuffle tree
-            const float4 q = ld4(scratch + 4 + 4 * i);
-            a += q.x; b += q.y;
-        }
-        a = wave_sum(a); b = wave_sum(b);
+    if (vlg_ticket_last(&last_sh) && tid < 64) {
+        float acc[2];                                               // nll, coverage
+        vlg_fold_partials<2>(scratch + 4, (int)gridDim.x, tid, acc);
         if (tid == 0) {
-            loss_io[0] = loss_io[0] + w_nll * a;                    // once: the total the loss launch before this one wrote
-            loss_io[4] = a; loss_io[5] = b; loss_io[6] = 0.f; loss_io[7] = 0.f;
-            *(reinterpret_cast<int*>(scratch) + 1) = 0;             // ready for the next launch
+            loss_io[0] = loss_io[0] + w_nll * acc[0];               // once: the total the loss launch before this one wrote
+            loss_io[4] = acc[0]; loss_io[5] = acc[1]; loss_io[6] = 0.f; loss_io[7] = 0.f;
+            *ticket = 0u;                                           // ready for the next launch
         }
     }
 }
@@ -140,7 +131,7 @@ extern "C" int vlg_layout_box_nll(const float* out, int ld, const float* tgt_box
     if (!(w_nll >= 0.f) || !(w_nll <= 3.0e38f)) return VLG_ERR_SHAPE;                               // negative, inf or NaN
     if (!out || !dout || !tgt_box || !valid) return VLG_ERR_ALIGN;
     if (!vlg_aligned16(out) || !vlg_aligned16(dout) || !vlg_aligned16(tgt_box) || !vlg_aligned16(valid)) return VLG_ERR_ALIGN;
-    if (!loss_io || (reinterpret_cast<uintptr_t>(loss_io) & 3u) || !scratch || !vlg_aligned16(scratch)) return VLG_ERR_ALIGN;
+    if (!loss_io || !vlg_aligned4(loss_io) || !scratch || !vlg_aligned16(scratch)) return VLG_ERR_ALIGN;
     const int64_t M = (int64_t)B * T * N;
     int64_t blocks = (M + BNLL_BLOCK - 1) / BNLL_BLOCK;
     if (blocks > BNLL_MAX_BLOCKS) blocks = BNLL_MAX_BLOCKS;

@@ -24,7 +24,15 @@ static inline int vlg_tune_env(const char* name, int dflt) {
 #define VLG_TUNE(name, dflt) (dflt)
 #endif
 
+// host checks on the caller's pointers, shared by every front end (NULL is aligned; who refuses NULL says so itself)
 static inline bool vlg_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline bool vlg_aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+static inline bool vlg_aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+// do the byte ranges [a, a + bytes_a) and [b, b + bytes_b) share a byte?  NULL overlaps nothing.
+static inline bool vlg_overlap(const void* a, int64_t bytes_a, const void* b, int64_t bytes_b) {
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return a != nullptr && b != nullptr && pa < pb + (uintptr_t)bytes_b && pb < pa + (uintptr_t)bytes_a;
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -70,7 +78,6 @@ __device__ __forceinline__ float ld1(const float* p) { return *p; }
 __device__ __forceinline__ float ld1(const bf16_t* p) { return (float)*p; }
 __device__ __forceinline__ void st1(float* p, float v) { *p = v; }
 __device__ __forceinline__ void st1(bf16_t* p, float v) { *p = (bf16_t)v; }
-static inline bool vlg_aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 __device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
@@ -223,4 +230,41 @@ __device__ __forceinline__ float block_sum(float v, float* smem) {
         for (int i = 0; i < nw; ++i) r += smem[i];
     __syncthreads();
     return r;
+}
+
+// ------------------------------------------------------------------------------------------------- last-block protocol
+// A launch whose blocks each leave a partial in global memory and whose LAST block to finish folds them - no float atomics,
+// no second launch.  `ticket` is an integer the caller zeroed ONCE; `last_sh` is one int of the block's LDS.
+//   vlg_ticket_draw  THREAD 0 ALONE, once the block's partial is published: it stored the partial itself, or the threads that
+//                    did have fenced (__threadfence) ahead of a barrier this call is behind.  Its own fence (agent scope)
+//                    puts the partial ahead of the ticket in every other block's view; drawing the grid's last ticket
+//                    means every other block has published.
+//   vlg_ticket_last  EVERY thread of the block (it holds a barrier): true in the block that drew the last ticket, which has
+//                    fenced again and so sees every partial.  That block folds, then sets *ticket = 0 for the next launch.
+// Work that needs no answer and may drain while the fold runs goes between the two (metrics.hip's count atomics).
+__device__ __forceinline__ void vlg_ticket_draw(unsigned int* ticket, int* last_sh) {
+    __threadfence();
+    *last_sh = (atomicAdd(ticket, 1u) == gridDim.x - 1) ? 1 : 0;
+}
+__device__ __forceinline__ bool vlg_ticket_last(const int* last_sh) {
+    __syncthreads();
+    const bool last = *last_sh != 0;
+    if (last) __threadfence();
+    return last;
+}
+
+// The fold of float4 partials (one per block, the first NACC components in use) that loss.hip and box_nll.hip share: for
+// the 64 lanes of ONE wavefront of the last block.  Fixed order: lane i sums blocks i, i + 64, ... ; then the shuffle tree.
+template <int NACC>
+__device__ __forceinline__ void vlg_fold_partials(const float* partials, int blocks, int lane, float (&acc)[NACC]) {
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.f;
+    for (int i = lane; i < blocks; i += 64) {
+        const float4 q = ld4(partials + 4 * i);
+        const float e[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int k = 0; k < NACC; ++k) acc[k] += e[k];
+    }
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) acc[k] = wave_sum(acc[k]);
 }

@@ -15,12 +15,14 @@
 //     function (decode_token) for both; the new frame is written at its position of the window in place, nothing slides.
 // vlg_layout_decode_ext / vlg_layout_decode_append_ext  the two steps with a row stride for out_last and, with
 //     box_temperature > 0, a box DRAWN from the Gaussian box head's N(mu, (tau sigma)^2) (Box-Muller on the four words of
-//     one more Philox call, stream 5): a compile-time parameter of the same kernels and of decode_token, so the instantiation
-//     behind the plain entries keeps the rule it always had.
+//     one more Philox call, stream VLG_RNG_BOX_NORMAL): a compile-time parameter of the same kernels and of decode_token, so
+//     the instantiation behind the plain entries keeps the rule it always had.
 // vlg_layout_mix_inputs  scheduled sampling: the inputs of a training step's second pass, per token the truth or the
 //     model's own prediction decoded by the same decode_token from the first pass's outputs (end of this file).
+// Draws: philox.h (the generator, the word conversions, the seed's key); streams: vlg_rng_stream, include/vlg_hip.h.
+#include <type_traits>
 #include "common.h"
-#include "layernorm_rows.h"        // philox4x32_10: all four words of a counter
+#include "philox.h"
 
 #define HL_BLOCK 256
 #define HL_WAVES (HL_BLOCK / 64)
@@ -129,30 +131,12 @@ extern "C" int vlg_head_last_frame(const float* x, const float* gamma, const flo
 }
 
 // ---------------------------------------------------------------------------------------------------------- decoding
-// Philox4x32-10 (Salmon et al., Random123): first output word of counter (c0, c1, c2, 0) under key (k0, k1).  c2 names the
-// stream: 0 = the class draw of decode_token, 1 = the scheduled-sampling coin
-__device__ __forceinline__ uint32_t philox_first(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1, uint32_t c2 = 0u) {
-    uint32_t c3 = 0u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return c0;
-}
-
-// u of one Philox word, as the class draw forms it: fp32 throughout (not exact above 2^23; may round to 1.0)
-__device__ __forceinline__ float philox_u(uint32_t x) {
-    return (float)(x >> 8) * 5.9604644775390625e-08f + 2.98023223876953125e-08f;                   // 2^-24, 2^-25
-}
-
 // The decoding rule, written once for the sliding step, the appending one and the scheduled-sampling mix.  l: token r's [logits | raw box] (the logits
 // become the running sums); prev / prev_box: the token's class and box in the newest frame of the history.
 // BOX (the Gaussian box head, vlg_layout_decode_ext with box_temperature = tau > 0): l holds [logits | raw mean | raw scale]
 // and the box is drawn, box_k = clamp(mu_k + tau sigma_k z_k, 0, 1), z = Box-Muller on the four words of counter
-// (r, step, 5, 0); the class draw is untouched.  BOX = false is the rule as it always was, instruction for instruction.
+// (r, step, VLG_RNG_BOX_NORMAL, 0); the class draw is untouched.  BOX = false is the rule as it always was, instruction for
+// instruction.
 template <bool BOX>
 __device__ __forceinline__ void decode_token(float* l, int C, int64_t prev, const float* __restrict__ prev_box, int64_t r, int step,
                                              float temperature, int top_k, uint32_t k0, uint32_t k1, int keep_padded,
@@ -165,9 +149,9 @@ __device__ __forceinline__ void decode_token(float* l, int C, int64_t prev, cons
                           1.0f / (1.0f + expf(-l[C + 2])), 1.0f / (1.0f + expf(-l[C + 3])));
         if constexpr (BOX) {
             uint32_t x[4];
-            philox4x32_10((uint32_t)r, (uint32_t)step, 5u, 0u, k0, k1, x);
-            const float rad0 = sqrtf(-2.0f * logf(philox_u(x[0]))), ang0 = 6.28318530717958648f * philox_u(x[1]);
-            const float rad1 = sqrtf(-2.0f * logf(philox_u(x[2]))), ang1 = 6.28318530717958648f * philox_u(x[3]);
+            philox4x32_10((uint32_t)r, (uint32_t)step, VLG_RNG_BOX_NORMAL, 0u, k0, k1, x);
+            const float rad0 = sqrtf(-2.0f * logf(philox_unit(x[0]))), ang0 = 6.28318530717958648f * philox_unit(x[1]);
+            const float rad1 = sqrtf(-2.0f * logf(philox_unit(x[2]))), ang1 = 6.28318530717958648f * philox_unit(x[3]);
             const float z[4] = {rad0 * cosf(ang0), rad0 * sinf(ang0), rad1 * cosf(ang1), rad1 * sinf(ang1)};
             const float mu[4] = {box.x, box.y, box.z, box.w};
             float bx[4];
@@ -203,8 +187,8 @@ __device__ __forceinline__ void decode_token(float* l, int C, int64_t prev, cons
                 if ((kept >> c) & 1u) cum += expf(l[c] / temperature - m);
                 l[c] = cum;
             }
-            const uint32_t x0 = philox_first((uint32_t)r, (uint32_t)step, k0, k1);
-            const float u = philox_u(x0);
+            const uint32_t x0 = philox_word0((uint32_t)r, (uint32_t)step, VLG_RNG_CLASS_DRAW, k0, k1);
+            const float u = philox_unit(x0);
             const float thr = u * cum;                     // cum = S
             pick = -1;
             int last_kept = 0;
@@ -265,11 +249,6 @@ __global__ __launch_bounds__(DEC_BLOCK) void layout_decode_kernel(
     }
 }
 
-static inline bool dec_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return a != nullptr && b != nullptr && pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
-}
-
 // what the _ext entries add to the refusals: the row stride, and the box temperature with the columns it needs.  Returns the
 // number of columns of a row the kernel reads
 // (ext: an _ext entry, whose ld must be a multiple of 4; the plain entries pass ld = n_classes + 4, whatever that is)
@@ -280,40 +259,59 @@ static inline int dec_box_columns(int n_classes, int ld, float box_temperature, 
     return (ld >= n_classes + 8 && n_classes + 8 <= HL_MAX_OUT) ? n_classes + 8 : 0;
 }
 
+// The refusals the four decoding entries share - shape limits, temperature, top_k, steps / step, the box columns, the counter
+// range - and, for a call that passes them, what its launch needs: the grid, the seed's key, the columns of a row it reads.
+struct DecCall {
+    int64_t BN;                 // tokens of a frame
+    int cols;
+    dim3 grid;
+    PhiloxKey key;
+};
+static int decode_checks(bool ext, int ld, int B, int T, int N, int n_classes, int steps, int step, float temperature, int top_k,
+                         float box_temperature, uint64_t seed, DecCall& c) {
+    if (B < 1 || T < 1 || N < 1 || n_classes < 1 || n_classes + 4 > HL_MAX_OUT) return VLG_ERR_SHAPE;
+    if (!(temperature >= 0.f) || !(temperature <= 3.0e38f)) return VLG_ERR_SHAPE;      // negative, inf or NaN
+    if (top_k < 0 || top_k > n_classes || steps < 1 || step < 0 || step >= steps) return VLG_ERR_SHAPE;
+    c.cols = dec_box_columns(n_classes, ld, box_temperature, ext);
+    if (c.cols == 0) return VLG_ERR_SHAPE;
+    c.BN = (int64_t)B * N;
+    if (!philox_index_fits(c.BN)) return VLG_ERR_SHAPE;                                 // the Philox counter word is the token index
+    c.grid = dim3((unsigned)((c.BN + DEC_BLOCK - 1) / DEC_BLOCK));
+    c.key = philox_key(seed);
+    return 0;
+}
+// box sampling is a compile-time parameter of both kernels: the one place where the temperature picks the instantiation
+template <typename Launch>
+static int decode_launch(float box_temperature, Launch launch) {
+    if (box_temperature > 0.f) launch(std::true_type());
+    else launch(std::false_type());
+    return vlg_last_error();
+}
+
 static int decode_front(bool ext, const float* out_last, int ld, const int64_t* cls_in, const float* box_in, int64_t* cls_out,
                         float* box_out, float* valid_out, int64_t* gen_cls, float* gen_box, int B, int T, int N,
                         int n_classes, int steps, int step, float temperature, int top_k, float box_temperature,
                         uint64_t seed, int keep_padded, void* stream) {
-    if (B < 1 || T < 1 || N < 1 || n_classes < 1 || n_classes + 4 > HL_MAX_OUT) return VLG_ERR_SHAPE;
-    if (!(temperature >= 0.f) || !(temperature <= 3.0e38f)) return VLG_ERR_SHAPE;      // negative, inf or NaN
-    if (top_k < 0 || top_k > n_classes || steps < 1 || step < 0 || step >= steps) return VLG_ERR_SHAPE;
-    const int cols = dec_box_columns(n_classes, ld, box_temperature, ext);
-    if (cols == 0) return VLG_ERR_SHAPE;
-    const int64_t BN = (int64_t)B * N, M = BN * T;
-    if (BN > 0x7fffffffLL) return VLG_ERR_SHAPE;                                        // the Philox counter word is the token index
+    DecCall c;
+    const int err = decode_checks(ext, ld, B, T, N, n_classes, steps, step, temperature, top_k, box_temperature, seed, c);
+    if (err != 0) return err;
+    const int64_t BN = c.BN, M = BN * T;
     if (!out_last || !cls_in || !box_in || !cls_out || !box_out || !gen_cls || !gen_box) return VLG_ERR_SHAPE;
     // inputs are only read and outputs only written: any overlap between the two groups is refused
     const void* in_p[3] = {out_last, cls_in, box_in};
-    const int64_t in_n[3] = {((BN - 1) * ld + cols) * 4, M * 8, M * 16};
+    const int64_t in_n[3] = {((BN - 1) * ld + c.cols) * 4, M * 8, M * 16};
     const void* out_p[5] = {cls_out, box_out, valid_out, gen_cls, gen_box};
     const int64_t out_n[5] = {M * 8, M * 16, M * 4, BN * steps * 8, BN * steps * 16};
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 5; ++j)
-            if (dec_overlap(in_p[i], in_n[i], out_p[j], out_n[j])) return VLG_ERR_SHAPE;
+            if (vlg_overlap(in_p[i], in_n[i], out_p[j], out_n[j])) return VLG_ERR_SHAPE;
     if (!vlg_aligned16(out_last) || !vlg_aligned16(box_in) || !vlg_aligned16(box_out) || !vlg_aligned16(gen_box) ||
-        !vlg_aligned8(cls_in) || !vlg_aligned8(cls_out) || !vlg_aligned8(gen_cls) ||
-        (reinterpret_cast<uintptr_t>(valid_out) & 3u)) return VLG_ERR_ALIGN;
-    const dim3 grid((unsigned)((BN + DEC_BLOCK - 1) / DEC_BLOCK)), block(DEC_BLOCK);
-    const uint32_t k0 = (uint32_t)(seed & 0xffffffffu), k1 = (uint32_t)(seed >> 32);
-    if (box_temperature > 0.f)
-        hipLaunchKernelGGL(layout_decode_kernel<true>, grid, block, 0, (hipStream_t)stream, out_last, ld, cls_in, box_in, cls_out,
-                           box_out, valid_out, gen_cls, gen_box, B, T, N, n_classes, steps, step, temperature, top_k, k0, k1,
-                           keep_padded, box_temperature);
-    else
-        hipLaunchKernelGGL(layout_decode_kernel<false>, grid, block, 0, (hipStream_t)stream, out_last, ld, cls_in, box_in, cls_out,
-                           box_out, valid_out, gen_cls, gen_box, B, T, N, n_classes, steps, step, temperature, top_k, k0, k1,
-                           keep_padded, 0.f);
-    return vlg_last_error();
+        !vlg_aligned8(cls_in) || !vlg_aligned8(cls_out) || !vlg_aligned8(gen_cls) || !vlg_aligned4(valid_out)) return VLG_ERR_ALIGN;
+    return decode_launch(box_temperature, [&](auto box) {
+        hipLaunchKernelGGL(layout_decode_kernel<decltype(box)::value>, c.grid, dim3(DEC_BLOCK), 0, (hipStream_t)stream, out_last, ld,
+                           cls_in, box_in, cls_out, box_out, valid_out, gen_cls, gen_box, B, T, N, n_classes, steps, step,
+                           temperature, top_k, c.key.k0, c.key.k1, keep_padded, box_temperature);
+    });
 }
 
 extern "C" int vlg_layout_decode_ext(const float* out_last, int ld, const int64_t* cls_in, const float* box_in, int64_t* cls_out,
@@ -368,35 +366,25 @@ static int decode_append_front(bool ext, const float* out_last, int ld, int64_t*
                                float* gen_box, int64_t* frame_cls, float* frame_box, int B, int T, int N,
                                int n_classes, int pos, int steps, int step, float temperature, int top_k, float box_temperature,
                                uint64_t seed, int keep_padded, void* stream) {
-    if (B < 1 || T < 1 || N < 1 || n_classes < 1 || n_classes + 4 > HL_MAX_OUT) return VLG_ERR_SHAPE;
-    if (!(temperature >= 0.f) || !(temperature <= 3.0e38f)) return VLG_ERR_SHAPE;      // negative, inf or NaN
-    if (top_k < 0 || top_k > n_classes || steps < 1 || step < 0 || step >= steps) return VLG_ERR_SHAPE;
+    DecCall c;
+    const int err = decode_checks(ext, ld, B, T, N, n_classes, steps, step, temperature, top_k, box_temperature, seed, c);
+    if (err != 0) return err;
     if (pos < 1 || pos >= T) return VLG_ERR_SHAPE;
-    const int cols = dec_box_columns(n_classes, ld, box_temperature, ext);
-    if (cols == 0) return VLG_ERR_SHAPE;
-    const int64_t BN = (int64_t)B * N, M = BN * T;
-    if (BN > 0x7fffffffLL) return VLG_ERR_SHAPE;                                        // the Philox counter word is the token index
+    const int64_t BN = c.BN, M = BN * T;
     if (!out_last || !cls || !box || !gen_cls || !gen_box || !frame_cls || !frame_box) return VLG_ERR_SHAPE;
     // the window is updated in place (frame pos - 1 read, frame pos written); every other pair of buffers must be disjoint
     const void* p[8] = {out_last, cls, box, valid, gen_cls, gen_box, frame_cls, frame_box};
-    const int64_t n[8] = {((BN - 1) * ld + cols) * 4, M * 8, M * 16, M * 4, BN * steps * 8, BN * steps * 16, BN * 8, BN * 16};
+    const int64_t n[8] = {((BN - 1) * ld + c.cols) * 4, M * 8, M * 16, M * 4, BN * steps * 8, BN * steps * 16, BN * 8, BN * 16};
     for (int i = 0; i < 8; ++i)
         for (int j = i + 1; j < 8; ++j)
-            if (dec_overlap(p[i], n[i], p[j], n[j])) return VLG_ERR_SHAPE;
+            if (vlg_overlap(p[i], n[i], p[j], n[j])) return VLG_ERR_SHAPE;
     if (!vlg_aligned16(out_last) || !vlg_aligned16(box) || !vlg_aligned16(gen_box) || !vlg_aligned16(frame_box) ||
-        !vlg_aligned8(cls) || !vlg_aligned8(gen_cls) || !vlg_aligned8(frame_cls) ||
-        (reinterpret_cast<uintptr_t>(valid) & 3u)) return VLG_ERR_ALIGN;
-    const dim3 grid((unsigned)((BN + DEC_BLOCK - 1) / DEC_BLOCK)), block(DEC_BLOCK);
-    const uint32_t k0 = (uint32_t)(seed & 0xffffffffu), k1 = (uint32_t)(seed >> 32);
-    if (box_temperature > 0.f)
-        hipLaunchKernelGGL(layout_decode_append_kernel<true>, grid, block, 0, (hipStream_t)stream, out_last, ld, cls, box, valid,
-                           gen_cls, gen_box, frame_cls, frame_box, B, T, N, n_classes, pos, steps, step, temperature, top_k, k0, k1,
-                           keep_padded, box_temperature);
-    else
-        hipLaunchKernelGGL(layout_decode_append_kernel<false>, grid, block, 0, (hipStream_t)stream, out_last, ld, cls, box, valid,
-                           gen_cls, gen_box, frame_cls, frame_box, B, T, N, n_classes, pos, steps, step, temperature, top_k, k0, k1,
-                           keep_padded, 0.f);
-    return vlg_last_error();
+        !vlg_aligned8(cls) || !vlg_aligned8(gen_cls) || !vlg_aligned8(frame_cls) || !vlg_aligned4(valid)) return VLG_ERR_ALIGN;
+    return decode_launch(box_temperature, [&](auto box_sampled) {
+        hipLaunchKernelGGL(layout_decode_append_kernel<decltype(box_sampled)::value>, c.grid, dim3(DEC_BLOCK), 0, (hipStream_t)stream,
+                           out_last, ld, cls, box, valid, gen_cls, gen_box, frame_cls, frame_box, B, T, N, n_classes, pos, steps, step,
+                           temperature, top_k, c.key.k0, c.key.k1, keep_padded, box_temperature);
+    });
 }
 
 extern "C" int vlg_layout_decode_append_ext(const float* out_last, int ld, int64_t* cls, float* box, float* valid,
@@ -449,7 +437,7 @@ __global__ __launch_bounds__(DEC_BLOCK) void layout_mix_inputs_kernel(
         const int64_t kk = (int64_t)k + 1;
         const uint32_t thr = ramp_steps == 0 ? thr_max
                                              : (uint32_t)((uint64_t)thr_max * (uint64_t)(kk < ramp_steps ? kk : ramp_steps) / (uint64_t)ramp_steps);
-        if ((philox_first((uint32_t)i, (uint32_t)k, k0, k1, 1u) >> 8) < thr)
+        if (philox_coin(philox_word0((uint32_t)i, (uint32_t)k, VLG_RNG_SCHED_COIN, k0, k1), thr))
             decode_token<false>(rows[tid], C, c, box + 4 * i, i, k, temperature, top_k, k0, k1, 0, c, bx);
     }
     mix_cls[i] = c;
@@ -458,7 +446,7 @@ __global__ __launch_bounds__(DEC_BLOCK) void layout_mix_inputs_kernel(
 
 extern "C" int vlg_sched_plan(double eps_max, uint32_t* thr_host) {
     if (!(eps_max >= 0.0 && eps_max <= 1.0) || thr_host == nullptr) return VLG_ERR_SHAPE;
-    *thr_host = (uint32_t)__builtin_floor(eps_max * 16777216.0 + 0.5);
+    *thr_host = philox_coin_threshold(eps_max);
     return 0;
 }
 
@@ -469,19 +457,19 @@ extern "C" int vlg_layout_mix_inputs(const float* out, int ld, const int64_t* cl
     if (!(temperature >= 0.f) || !(temperature <= 3.0e38f)) return VLG_ERR_SHAPE;      // negative, inf or NaN
     if (top_k < 0 || top_k > n_classes || thr_max > (1u << 24) || ramp_steps < 0) return VLG_ERR_SHAPE;
     const int64_t M = (int64_t)B * N * T;
-    if (M > 0x7fffffffLL) return VLG_ERR_SHAPE;                                         // the Philox counter word is the token index
+    if (!philox_index_fits(M)) return VLG_ERR_SHAPE;                                    // the Philox counter word is the token index
     if (!out || !cls || !box || !mix_cls || !mix_box || !step) return VLG_ERR_SHAPE;
     // inputs are only read and outputs only written: any overlap between the two groups, or of the two outputs, is refused
     const void* in_p[4] = {out, cls, box, step};
     const int64_t in_n[4] = {((M - 1) * ld + n_classes + 4) * 4, M * 8, M * 16, 4};
     for (int i = 0; i < 4; ++i)
-        if (dec_overlap(in_p[i], in_n[i], mix_cls, M * 8) || dec_overlap(in_p[i], in_n[i], mix_box, M * 16)) return VLG_ERR_SHAPE;
-    if (dec_overlap(mix_cls, M * 8, mix_box, M * 16)) return VLG_ERR_SHAPE;
+        if (vlg_overlap(in_p[i], in_n[i], mix_cls, M * 8) || vlg_overlap(in_p[i], in_n[i], mix_box, M * 16)) return VLG_ERR_SHAPE;
+    if (vlg_overlap(mix_cls, M * 8, mix_box, M * 16)) return VLG_ERR_SHAPE;
     if (!vlg_aligned16(out) || !vlg_aligned16(box) || !vlg_aligned16(mix_box) || !vlg_aligned8(cls) || !vlg_aligned8(mix_cls) ||
-        (reinterpret_cast<uintptr_t>(step) & 3u)) return VLG_ERR_ALIGN;
+        !vlg_aligned4(step)) return VLG_ERR_ALIGN;
     const dim3 grid((unsigned)((M + DEC_BLOCK - 1) / DEC_BLOCK)), block(DEC_BLOCK);
+    const PhiloxKey key = philox_key(seed);
     hipLaunchKernelGGL(layout_mix_inputs_kernel, grid, block, 0, (hipStream_t)stream, out, ld, cls, box, mix_cls, mix_box, step, M,
-                       T, N, n_classes, thr_max, ramp_steps, temperature, top_k, (uint32_t)(seed & 0xffffffffu),
-                       (uint32_t)(seed >> 32));
+                       T, N, n_classes, thr_max, ramp_steps, temperature, top_k, key.k0, key.k1);
     return vlg_last_error();
 }

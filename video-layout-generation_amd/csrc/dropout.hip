@@ -90,17 +90,13 @@ extern "C" int vlg_dropout_plan(double p, uint32_t* thr_host, float* scale_host)
     return 0;
 }
 
-static inline bool overlaps(const void* a, const void* b, int64_t bytes_a, int64_t bytes_b) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + (uintptr_t)bytes_b && pb < pa + (uintptr_t)bytes_a;
-}
-static inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 static inline bool mask_ok(int64_t rows, int d, float scale, int site, const int* step) {
     return rows >= 1 && rows < ((int64_t)1 << 32) && ln_supports(d) && scale >= 1.0f && scale <= 4294967296.0f && site >= 0 &&
            step != nullptr;
 }
 static inline LnDrop make_drop(float* out, uint32_t thr, float scale, uint64_t seed, int site, const int* step) {
-    return LnDrop{out, step, thr, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), (uint32_t)site, scale};
+    const PhiloxKey key = philox_key(seed);
+    return LnDrop{out, step, thr, key.k0, key.k1, (uint32_t)site, scale};
 }
 
 template <typename EY>
@@ -110,12 +106,12 @@ static int dropout_add_ln_fwd(const float* y, const float* resid, const float* g
     if (!mask_ok(rows, d, scale, site, step)) return VLG_ERR_SHAPE;
     if (!y || !gamma || !beta || !x_out || !h || !mean || !rstd) return VLG_ERR_ALIGN;
     if (!vlg_aligned16(y) || !vlg_aligned16(x_out) || !vlg_aligned16(gamma) || !vlg_aligned16(beta) ||
-        !(sizeof(EY) == 4 ? vlg_aligned16(h) : vlg_aligned8(h)) || (resid && !vlg_aligned16(resid)) || !aligned4(mean) ||
-        !aligned4(rstd) || !aligned4(step)) return VLG_ERR_ALIGN;
+        !(sizeof(EY) == 4 ? vlg_aligned16(h) : vlg_aligned8(h)) || (resid && !vlg_aligned16(resid)) || !vlg_aligned4(mean) ||
+        !vlg_aligned4(rstd) || !vlg_aligned4(step)) return VLG_ERR_ALIGN;
     const int64_t nb = rows * d * 4, nh = rows * d * (int64_t)sizeof(EY);
-    if ((x_out != y && overlaps(x_out, y, nb, nb)) || overlaps(h, y, nh, nb) || overlaps(h, x_out, nh, nb) ||
-        (resid && (overlaps(resid, x_out, nb, nb) || overlaps(resid, y, nb, nb) || overlaps(resid, h, nb, nh))))
-        return VLG_ERR_SHAPE;
+    if ((x_out != y && vlg_overlap(x_out, nb, y, nb)) || vlg_overlap(h, nh, y, nb) || vlg_overlap(h, nh, x_out, nb) ||
+        vlg_overlap(resid, nb, x_out, nb) || vlg_overlap(resid, nb, y, nb) || vlg_overlap(resid, nb, h, nh))
+        return VLG_ERR_SHAPE;                                      // (a NULL resid or dres overlaps nothing)
     const dim3 grid(ln_fwd_blocks(rows)), block(LN_BLOCK);
     const LnDrop dp = make_drop(nullptr, thr, scale, seed, site, step);
 #define CALL(E, V4) hipLaunchKernelGGL((dropout_add_ln_fwd_kernel<E, V4, EY>), grid, block, 0, s, y, resid, gamma, beta, x_out, h, mean, rstd, rows, eps, dp);
@@ -148,12 +144,12 @@ static int ln_bwd_dropout(const EY* dy, const float* x, const float* mean, const
     if (slab_capacity < (int64_t)ln_bwd_blocks(rows) * slab_stride) return VLG_ERR_SHAPE;   // every block writes one slab
     if (!dy || !x || !mean || !rstd || !gamma || !dx_out || !dy_drop || !slabs) return VLG_ERR_ALIGN;
     if (!(sizeof(EY) == 4 ? vlg_aligned16(dy) : vlg_aligned8(dy)) || !vlg_aligned16(x) || !vlg_aligned16(gamma) ||
-        !vlg_aligned16(dx_out) || !vlg_aligned16(dy_drop) || (dres && !vlg_aligned16(dres)) || !aligned4(mean) ||
-        !aligned4(rstd) || !aligned4(slabs) || !aligned4(step)) return VLG_ERR_ALIGN;
+        !vlg_aligned16(dx_out) || !vlg_aligned16(dy_drop) || (dres && !vlg_aligned16(dres)) || !vlg_aligned4(mean) ||
+        !vlg_aligned4(rstd) || !vlg_aligned4(slabs) || !vlg_aligned4(step)) return VLG_ERR_ALIGN;
     const int64_t nb = rows * d * 4, ny = rows * d * (int64_t)sizeof(EY);
-    if (overlaps(dy_drop, dx_out, nb, nb) || overlaps(dy_drop, dy, nb, ny) || overlaps(dy_drop, x, nb, nb) ||
-        (dres && overlaps(dy_drop, dres, nb, nb)) || overlaps(dx_out, dy, nb, ny) || overlaps(dx_out, x, nb, nb) ||
-        (dres && dres != dx_out && overlaps(dres, dx_out, nb, nb))) return VLG_ERR_SHAPE;
+    if (vlg_overlap(dy_drop, nb, dx_out, nb) || vlg_overlap(dy_drop, nb, dy, ny) || vlg_overlap(dy_drop, nb, x, nb) ||
+        vlg_overlap(dy_drop, nb, dres, nb) || vlg_overlap(dx_out, nb, dy, ny) || vlg_overlap(dx_out, nb, x, nb) ||
+        (dres != dx_out && vlg_overlap(dres, nb, dx_out, nb))) return VLG_ERR_SHAPE;
     return ln_bwd_launch(dy, sizeof(EY) == 2, x, mean, rstd, gamma, dres, dx_out, slabs, slab_stride, rows, d,
                          make_drop(dy_drop, thr, scale, seed, site, step), s);      // the one backward kernel (layernorm.hip)
 }
@@ -176,7 +172,7 @@ extern "C" int vlg_layernorm_bwd_dropout_bf16(const vlg_bf16* dy, const float* x
 }
 
 extern "C" int vlg_dropout_step_advance(int* step, void* stream) {
-    if (step == nullptr || !aligned4(step)) return VLG_ERR_ALIGN;
+    if (step == nullptr || !vlg_aligned4(step)) return VLG_ERR_ALIGN;
     hipLaunchKernelGGL(dropout_step_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step);
     return vlg_last_error();
 }

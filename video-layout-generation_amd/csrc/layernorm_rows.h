@@ -3,6 +3,7 @@
 // kernels of dropout.hip apply to such a row.
 #pragma once
 #include "common.h"
+#include "philox.h"
 
 #define LN_BLOCK 256
 #define LN_WAVES (LN_BLOCK / 64)
@@ -70,26 +71,15 @@ static inline bool ln_supports(int d) { return d == 64 || d == 128 || d == 192 |
 
 // ------------------------------------------------------------------------------------------------------ dropout mask
 // Stateless mask (include/vlg_hip.h, "dropout"): element (row m, column c) of site s at step k is KEPT iff word c % 4 of
-// Philox4x32-10 (Salmon et al., Random123), counter (m, c / 4, s, k), key (seed lo, seed hi), is >= thr.  One call serves
-// one float4; a bit depends on (m, c, s, k, seed) alone, never on the launch geometry.
+// Philox4x32-10 (philox.h), counter (m, c / 4, s, k), key (seed lo, seed hi), is >= thr.  One call serves one float4; a bit
+// depends on (m, c, s, k, seed) alone, never on the launch geometry.  The third counter word is the SITE here, not a stream
+// of vlg_rng_stream: the mask is kept apart from those draws by its own seed.
 struct LnDrop {
     float* out;             // bwd only: dy_drop
     const int* step;        // k, read by the kernel when it runs (a captured graph advances it by replaying)
     uint32_t thr, k0, k1, site;
     float scale;
 };
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t (&x)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
-}
 
 // keep[j] of the registers RowIO<E, V4> holds of row `row`.  V4: one Philox call per float4.  Scalar layout (d < 256): a
 // lane's columns lane + 64*j lie in different float4s, so it pays one call per element and takes word c % 4 of it.

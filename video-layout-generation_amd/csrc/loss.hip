@@ -17,7 +17,8 @@
 // first store; M floats = 128 KB from L2, the same exact integer sum in every block), with its row and target loads already
 // in flight and 16 independent 16-B loads per thread outstanding (round 2's loop waited for one L2 round trip per 16 B: 17 of
 // the kernel's 26 us at M = 32 768).  The LAST block to finish (an integer ticket in scratch[1], which it resets) folds the
-// partials into loss_out[4] in block order - no float atomics, reproducible, and no second launch.
+// partials into loss_out[4] in a fixed order - no float atomics, reproducible, and no second launch (the protocol and the
+// fold: vlg_ticket_draw / vlg_ticket_last / vlg_fold_partials, common.h).
 //
 // Options (vlg_layout_loss_ext; include/vlg_hip.h, DESIGN.md "Loss options") are compile-time parameters of the ONE kernel
 // body below; vlg_layout_loss is its all-off instantiation, in which every `if constexpr` keeps the expressions above:
@@ -310,28 +311,19 @@ __global__ __launch_bounds__(LOSS_BLOCK) void layout_loss_kernel(
     s_reg = block_sum(s_reg, red);
     s_iou = block_sum(s_iou, red);
     s_ce = block_sum(s_ce, red);
+    unsigned int* ticket = reinterpret_cast<unsigned int*>(scratch) + 1;
     if (tid == 0) {
         float* part = scratch + 4 + 4 * blockIdx.x;
         part[0] = s_reg * inv_cnt; part[1] = s_iou * inv_cnt; part[2] = s_ce * (WEIGHTS ? inv_w : inv_cnt); part[3] = 0.f;
-        // publish the partial (agent scope), take a ticket; the block that draws the last one sees every partial
-        __threadfence();
-        int* ticket = reinterpret_cast<int*>(scratch) + 1;
-        const int drawn = atomicAdd(ticket, 1);
-        last_sh = (drawn == (int)gridDim.x - 1) ? 1 : 0;
+        vlg_ticket_draw(ticket, &last_sh);
     }
-    __syncthreads();
-    if (last_sh && tid < 64) {
-        __threadfence();
-        float a = 0.f, b = 0.f, c = 0.f;
-        for (int i = tid; i < (int)gridDim.x; i += 64) {           // fixed order: lane i sums blocks i, i + 64, ... ; then the shuffle tree
-            const float4 q = ld4(scratch + 4 + 4 * i);
-            a += q.x; b += q.y; c += q.z;
-        }
-        a = wave_sum(a); b = wave_sum(b); c = wave_sum(c);
+    if (vlg_ticket_last(&last_sh) && tid < 64) {
+        float acc[3];                                                // reg, iou, ce
+        vlg_fold_partials<3>(scratch + 4, (int)gridDim.x, tid, acc);
         if (tid == 0) {
-            loss_out[0] = w_reg * a + w_iou * b + w_ce * c;
-            loss_out[1] = a; loss_out[2] = b; loss_out[3] = c;
-            *(reinterpret_cast<int*>(scratch) + 1) = 0;              // ready for the next launch
+            loss_out[0] = w_reg * acc[0] + w_iou * acc[1] + w_ce * acc[2];
+            loss_out[1] = acc[0]; loss_out[2] = acc[1]; loss_out[3] = acc[2];
+            *ticket = 0u;                                            // ready for the next launch
         }
     }
 }

@@ -199,23 +199,19 @@ __global__ __launch_bounds__(MET_BLOCK) void layout_metrics_kernel(
         if ((tid & 63) == 0 && v != 0) atomicAdd(&cnt_sh[k], v);
     }
     const double tot = met_fold(acc, dred, tid);     // (its barriers also order cnt_sh)
-    // ---- sums: publish the block's partial row (agent scope), take a ticket; the last block sees every row.  This comes
-    // BEFORE the count atomics: the fence then waits for one store, and the atomics drain while the last block folds
+    // ---- sums: publish the block's partial row (agent scope), take a ticket; the last block sees every row (the protocol:
+    // vlg_ticket_draw / vlg_ticket_last, common.h).  This comes BEFORE the count atomics: the fence then waits for one
+    // store, and the atomics drain while the last block folds
     if (tid < MET_SLOTS) {
         partials[(int64_t)blockIdx.x * MET_SLOTS + tid] = tot;
         __threadfence();
     }
     __syncthreads();
-    if (tid == 0) {
-        const unsigned int drawn = atomicAdd(ticket, 1u);
-        last_sh = (drawn == gridDim.x - 1) ? 1 : 0;
-    }
+    if (tid == 0) vlg_ticket_draw(ticket, &last_sh);
     if (tid < MET_NCNT && cnt_sh[tid] != 0) atomicAdd(counts + tid, (unsigned long long)cnt_sh[tid]);
     for (int i = tid; i < C * C; i += MET_BLOCK)
         if (hist[i] != 0) atomicAdd(counts + VLG_MET_CONF + i, (unsigned long long)hist[i]);
-    __syncthreads();
-    if (last_sh) {
-        __threadfence();
+    if (vlg_ticket_last(&last_sh)) {
         // group g adds rows g, g + 8, ... in increasing order; the record's own value and all the rows a thread adds at
         // up to 256 blocks are requested before the first add (one trip to memory instead of one per row)
         const bool own = tid < VLG_MET_IOU_BY_CLASS + C;
@@ -254,7 +250,7 @@ extern "C" int vlg_layout_metrics(const float* out, int ld, const int64_t* tgt_c
     if (M > (1LL << 38)) return VLG_ERR_SHAPE;                                          // a block's counts are 32-bit
     if (!out || !tgt_box || !scratch || !sums || !tgt_class || !counts) return VLG_ERR_ALIGN;
     if (!vlg_aligned16(out) || !vlg_aligned16(tgt_box) || !vlg_aligned16(scratch) || !vlg_aligned8(sums) ||
-        !vlg_aligned8(tgt_class) || !vlg_aligned8(counts) || (reinterpret_cast<uintptr_t>(valid) & 3u)) return VLG_ERR_ALIGN;
+        !vlg_aligned8(tgt_class) || !vlg_aligned8(counts) || !vlg_aligned4(valid)) return VLG_ERR_ALIGN;
     int64_t blocks = (M + MET_TOK - 1) / MET_TOK;
     if (blocks > MET_MAX_BLOCKS) blocks = MET_MAX_BLOCKS;
     double* partials = reinterpret_cast<double*>(scratch) + 2;

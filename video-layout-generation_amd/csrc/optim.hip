@@ -423,7 +423,7 @@ extern "C" int vlg_adamw_ema_step_ctl(float* param, const float* grad, float* ex
     if (n < 4 || (n & 3) || !ctl || !ext || (ema_shadow && !ema)) return VLG_ERR_SHAPE;
     if (!vlg_aligned16(param) || !vlg_aligned16(grad) || !vlg_aligned16(exp_avg) || !vlg_aligned16(exp_avg_sq) ||
         !vlg_aligned16(ctl) || !vlg_aligned16(ext) || (shadow && !vlg_aligned8(shadow)) || (ema && !vlg_aligned16(ema)) ||
-        (ema_shadow && !vlg_aligned8(ema_shadow)) || (reinterpret_cast<uintptr_t>(decay_mask) & 3u)) return VLG_ERR_ALIGN;
+        (ema_shadow && !vlg_aligned8(ema_shadow)) || !vlg_aligned4(decay_mask)) return VLG_ERR_ALIGN;
     const dim3 grid(stream_blocks(n / 4)), block(256);
     hipStream_t s = (hipStream_t)stream;
     bf16_t* sh = reinterpret_cast<bf16_t*>(shadow);

@@ -170,12 +170,6 @@ __global__ __launch_bounds__(RAS_BLOCK) void layout_rasterize_kernel(
     }
 }
 
-static inline bool ras_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-    if (b == nullptr) return false;
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + (uintptr_t)nb && b0 < a0 + (uintptr_t)na;
-}
-
 extern "C" int vlg_layout_rasterize(const int64_t* cls, const float* box, const float* valid, void* labels,
                                     int B, int T_buf, int t0, int T, int N, int n_classes, int H, int W,
                                     int out_kind, int what, int background, void* stream) {
@@ -189,9 +183,9 @@ extern "C" int vlg_layout_rasterize(const int64_t* cls, const float* box, const 
     if (!cls || !box || !labels) return VLG_ERR_SHAPE;
     const int64_t slots = (int64_t)B * T_buf * N, pixels = (int64_t)B * T * H * W;
     const int64_t out_bytes = pixels * (out_kind == VLG_LABEL_U8 ? 1 : out_kind == VLG_LABEL_F32 ? 4 : 8);
-    if (ras_overlap(labels, out_bytes, cls, slots * 8) || ras_overlap(labels, out_bytes, box, slots * 16) ||
-        ras_overlap(labels, out_bytes, valid, slots * 4)) return VLG_ERR_SHAPE;
-    if (!vlg_aligned16(box) || !vlg_aligned16(labels) || !vlg_aligned8(cls) || (reinterpret_cast<uintptr_t>(valid) & 3u))
+    if (vlg_overlap(labels, out_bytes, cls, slots * 8) || vlg_overlap(labels, out_bytes, box, slots * 16) ||
+        vlg_overlap(labels, out_bytes, valid, slots * 4)) return VLG_ERR_SHAPE;
+    if (!vlg_aligned16(box) || !vlg_aligned16(labels) || !vlg_aligned8(cls) || !vlg_aligned4(valid))
         return VLG_ERR_ALIGN;
     const int cols = W / (out_kind == VLG_LABEL_U8 ? 16 : 4);
     int band_rows = RAS_UNITS * RAS_BLOCK / cols;        // RAS_UNITS thread units per thread: staging is paid once per band
