@@ -25,6 +25,21 @@ of its site (0, then 1 + 2l and 2 + 2l; site 0 in place on x[0]); every layer-no
 that FED it (2L, then 1 + 2l and 2l) and also leaves select(dx) in `ddrop`, which the proj / ff2 backward and the
 embedding backward read in place of dx; one counter advance ends the step.  ybranch and ddrop are fp32 in every mode.
 The masks are dropout_ref.keep_mask's, in the row order above; tests/dropout_ref.py states the rule.
+
+Options (vlg/engine.py forward_backward; each a Contract field, each restated by the *_ref module named):
+  factored   layer l takes vlg.attention.layer_kinds' kind: even layers the per-slot entries, odd layers frame_fwd / frame_bwd -
+             the clip entries' operand lists with lse[row], row = vlg.attention.lse_rows, and the clip stage functions under
+             tests/frame_walk.py's `visible` (the key's frame is the query's, or the key is the query); `valid` reaches them
+             under padded_slots; the bf16 frame kernels are the clip templates (P / dS rounding, operand_flip_slack)
+  gaussian   the head, the loss and the head's backward run at cfg.n_out = 32; a box_nll entry follows the loss
+             (boxhead_ref.box_nll_closed): scale columns of dout, zeros in the padding columns, loss_out[4:8], the total's share
+  loss       any option on: vlg_layout_loss_ext with class_weights (or NULL) after valid (loss_ext_ref.losses + autograd)
+  sched      pass 1 = the plain forward through the head (stages "pass1 ...": no dropout, no loss), "sched mix"
+             (sched_ref.mix_inputs on pass 1's out), pass 2 = the step with mix_cls / mix_box as the embedding's inputs, forward and
+             backward; targets and valid stay the truth
+  augment    "augment" first (augment_ref.augment); every later entry names aug_cls / aug_box / aug_tgt_box / aug_valid where it
+             named batch:slot_class / slot_box / tgt_box / valid; batch:tgt_class stays the caller's
+  counters   one advance per option that has a counter, after the backward, in the order dropout, sched, augment
 """
 import functools
 import math
@@ -32,8 +47,13 @@ import math
 import torch
 import torch.nn.functional as F
 
+import augment_ref
+import boxhead_ref
 import dropout_ref
+import loss_ext_ref
+import sched_ref
 from oracle import layout_spec as O
+from vlg.attention import layer_kinds, lse_rows
 
 BF = torch.bfloat16
 EPI_NONE, EPI_BIAS, EPI_GELU, EPI_RESID, EPI_DGELU, EPI_BF16 = 0, 1, 2, 4, 8, 16
@@ -44,17 +64,27 @@ PRECISIONS = ("fp32", "fp32x3", "bf16", "bf16_mfma")
 BF16_BUFFERS = ("h1", "qkv", "att", "h2", "u", "gl", "xf", "dh", "du", "dqkv")      # bf16 in memory under "bf16"
 BACKWARD_BUFFERS = ("dx", "dh", "du", "dqkv", "dout", "delta")                        # reused by the backward: snapshot per launch
 DROPOUT_BUFFERS = ("ybranch", "x[0]", "ddrop")              # rewritten within a dropout step: snapshot per launch there
+GAUSSIAN_BUFFERS = ("loss_out",)                            # the NLL launch adds to the total the loss launch left
+AUG_NAMES = {"slot_class": "aug_cls", "slot_box": "aug_box", "tgt_box": "aug_tgt_box", "valid": "aug_valid"}
+COUNTERS = ("drop_step", "sched_step", "aug_step")          # the order the engine advances them in
+MASK64 = 2 ** 64 - 1
+FIXED = ("p:", "pb:", "batch:", "class_weights")           # never written within a step: read at its end
 LOG2E = 1.0 / math.log(2.0)
 
 
 class Contract:
     """What a precision mode stores and rounds (see the module docstring).  dropout = (p, seed, k): the step of an engine
-    built with dropout=p, dropout_seed=seed whose counter reads k."""
+    built with dropout=p, dropout_seed=seed whose counter reads k.  The other options follow that precedent:
+    sched = (eps_max, ramp_steps, temperature, top_k, seed, k), augment = (knobs of augment_ref.augment, seed, k),
+    loss = (class weights or None, label smoothing, "iou" | "giou") with at least one of them on, box_nll_weight = the
+    weight of a LayoutConfig(box_head="gaussian") model's NLL term (None: the point head)."""
 
-    def __init__(self, precision, attention="slot", masked=True, gelu_grad_saved=None, paired=None, dropout=None):
+    def __init__(self, precision, attention="slot", masked=True, gelu_grad_saved=None, paired=None, dropout=None, sched=None,
+                 augment=None, loss=None, box_nll_weight=None):
         assert precision in PRECISIONS
-        self.dropout = dropout
-        self.snapshots = BACKWARD_BUFFERS + (DROPOUT_BUFFERS if dropout is not None else ())
+        assert loss is None or loss[0] is not None or loss[1] > 0.0 or loss[2] != "iou"
+        self.dropout, self.sched, self.augment, self.loss, self.box_nll_weight = dropout, sched, augment, loss, box_nll_weight
+        self.snapshots = snapshot_names(dropout is not None, box_nll_weight is not None)
         self.precision, self.attention = precision, attention
         self.store_bf16 = precision == "bf16"
         self.round_operands = precision in ("bf16", "bf16_mfma")
@@ -62,10 +92,22 @@ class Contract:
         self.gelu_grad_saved = precision != "fp32x3" if gelu_grad_saved is None else gelu_grad_saved
         assert not (self.gelu_grad_saved and precision == "fp32x3")
         self.paired = precision in ("fp32", "bf16") if paired is None else paired
-        self.masked = masked and attention == "clip"                 # per-key validity masks (padded_slots)
+        self.masked = masked and attention in ("clip", "factored")   # per-key validity masks (padded_slots)
         self.sfx = "_bf16" if self.store_bf16 else ""
 
+    def counters(self):
+        """{counter name: the k it reads before its advance} of the options that are on"""
+        on = {"drop_step": self.dropout, "sched_step": self.sched, "aug_step": self.augment}
+        return {n: on[n][-1] for n in COUNTERS if on[n] is not None}
+
+    def snap(self, n):
+        """whether buffer n is read from the per-launch snapshots.  Scheduled sampling: pass 2 overwrites every buffer pass 1
+        wrote, so every engine buffer is snapshotted (by the launches that name it)"""
+        return n in self.snapshots or (self.sched is not None and not n.startswith(FIXED))
+
     def dtype(self, buf):
+        if buf in ("mix_cls", "aug_cls"):
+            return torch.int64
         return BF if self.store_bf16 and buf.split("[")[0] in BF16_BUFFERS else torch.float32
 
     def bits(self, a=None, b=None, out=None):
@@ -75,6 +117,10 @@ class Contract:
 
     def weight(self, name):
         return ("pb:" if self.store_bf16 else "p:") + name
+
+
+def snapshot_names(dropout, gaussian):
+    return BACKWARD_BUFFERS + (DROPOUT_BUFFERS if dropout else ()) + (GAUSSIAN_BUFFERS if gaussian else ())
 
 
 class Raw:
@@ -175,16 +221,17 @@ def _clip_rows(t, B, T, N):
     return to_rows(t.permute(0, 2, 1, 3).reshape(B, T, N, -1))
 
 
-def _clip_allowed(valid, B, T, N):
+def _clip_allowed(valid, B, T, N, frame_only=False):
+    """block-causal over the clip; frame_only: tests/frame_walk.py's `visible` - the key's frame is the query's"""
     S = T * N
     frame = torch.arange(S) // N
-    allowed = (frame[None, :] <= frame[:, None])[None, None]
+    allowed = ((frame[None, :] == frame[:, None]) if frame_only else (frame[None, :] <= frame[:, None]))[None, None]
     if valid is not None:
         allowed = allowed & (valid.reshape(B, 1, 1, S) > 0)
     return allowed | torch.eye(S, dtype=torch.bool)[None, None]
 
 
-def clip_attention_fwd(qkv, valid, B, T, N, rnd=ident, detail=None):
+def clip_attention_fwd(qkv, valid, B, T, N, rnd=ident, detail=None, frame_only=False):
     """-> (out rows, lse (B*H*S,) in the log2 domain).  The walk of csrc/attention_clip.hip: 32-key tiles in frame-major
     order, a running maximum per query, P = exp2(s - running max) (rounded by `rnd` only as the operand of P.V, the row sum
     takes it unrounded), O rescaled when the maximum moves, one division by the row sum at the end.  `detail`, a dict,
@@ -192,7 +239,7 @@ def clip_attention_fwd(qkv, valid, B, T, N, rnd=ident, detail=None):
     d = qkv.shape[1] // 3
     q, k, v = (_clip_heads(t, B, T, N) for t in qkv.split(d, dim=-1))
     s = (q @ k.transpose(-1, -2)) * (LOG2E / 8.0)
-    s = s.masked_fill(~_clip_allowed(valid, B, T, N), float("-inf"))
+    s = s.masked_fill(~_clip_allowed(valid, B, T, N, frame_only), float("-inf"))
     S = T * N
     m = torch.full(s.shape[:-1], float("-inf"), dtype=s.dtype)
     l = torch.zeros_like(m)
@@ -214,12 +261,50 @@ def clip_attention_fwd(qkv, valid, B, T, N, rnd=ident, detail=None):
     return _clip_rows(o / l[..., None], B, T, N), (m + torch.log2(l)).reshape(-1)
 
 
-def loss_fwd(out, tgt_class, tgt_box, valid, B, T, N, n_classes=20):
-    """-> (the four loss scalars, dout rows) by oracle.losses and its autograd"""
+def loss_fwd(out, tgt_class, tgt_box, valid, B, T, N, n_classes=20, options=None):
+    """-> (the four loss scalars, dout rows) by oracle.losses and its autograd; options = Contract.loss: by
+    loss_ext_ref.losses.  Columns of `out` past the four raw box means (the Gaussian head's) get a zero gradient here."""
     o = from_rows(out, B, T, N).detach().clone().requires_grad_(True)
-    parts = O.losses(o[..., :n_classes], o[..., n_classes:], tgt_class, tgt_box.to(out.dtype), valid.to(out.dtype))
+    logits, raw = o[..., :n_classes], o[..., n_classes:n_classes + 4]
+    if options is None:
+        parts = O.losses(logits, raw, tgt_class, tgt_box.to(out.dtype), valid.to(out.dtype))
+    else:
+        parts = loss_ext_ref.losses(logits, raw, tgt_class, tgt_box.to(out.dtype), valid.to(out.dtype), *options)
     parts[0].backward()
     return torch.stack([p.detach() for p in parts]), to_rows(o.grad)
+
+
+def box_nll_stage(out, dout, loss_out, tgt_box, valid, B, T, N, C, w_nll):
+    """vlg_layout_box_nll on the rows it read -> (dout, loss_out (8,), boxhead_ref.box_nll_closed's dict): the scale
+    columns' gradient beside the loss launch's columns (kept as they are: the mean is detached), exact zeros in the four
+    padding columns, loss_out[4:8] = {nll, cover, 0, 0} and the total's w_nll * nll share.  Evaluated in fp64 whatever the
+    dtype of `out` (boxhead_ref's rule; its bars are its own units, not a torch-CPU fp32 yardstick)."""
+    ref = boxhead_ref.box_nll_closed(out, tgt_box.float(), valid.float(), B, T, N, C, w_nll)
+    dt = out.dtype
+    d = torch.cat([dout[:, :C + 4], ref["dscale"].to(dt), torch.zeros(dout.shape[0], 4, dtype=dt)], dim=1)
+    tail = torch.stack([ref["nll"], ref["cover"]]).to(dt)
+    lo = torch.cat([(loss_out[0] + w_nll * tail[0]).reshape(1), loss_out[1:4], tail, torch.zeros(2, dtype=dt)])
+    return d, lo, ref
+
+
+def sched_plan(c):
+    """(thr_max, ramp_steps, temperature, top_k, 64-bit seed, k) of Contract.sched: what the mix launch is handed"""
+    eps_max, ramp, temperature, top_k, seed, k = c.sched
+    return sched_ref.thr_max(eps_max), int(ramp), float(temperature), int(top_k), int(seed) & MASK64, k
+
+
+def sched_mix_stage(c, out, slot_class, slot_box, n_classes, k=None):
+    """sched_ref.mix_inputs on the `out` the launch read -> (mixed classes, mixed boxes, replaced, near)"""
+    thr_max, ramp, temperature, top_k, seed, k0 = sched_plan(c)
+    return sched_ref.mix_inputs(out, slot_class, slot_box.float(), n_classes, k0 if k is None else k, thr_max, ramp, temperature,
+                                top_k, seed)
+
+
+def augment_stage(c, batch, n_classes, k=None):
+    """augment_ref.augment on the caller's tensors (fp32, as the kernel reads them) -> its dict"""
+    knobs, seed, k0 = c.augment
+    b = {n: (t if not t.is_floating_point() else t.float()) for n, t in batch.items()}
+    return augment_ref.augment(b, k0 if k is None else k, int(seed) & MASK64, n_classes=n_classes, **knobs)
 
 
 # ------------------------------------------------------------------------------------------------ backward stages
@@ -258,7 +343,7 @@ def slot_attention_bwd(qkv, do, T):
     return q.grad
 
 
-def clip_attention_bwd(qkv, do, out, lse, valid, B, T, N, rnd=ident, detail=None):
+def clip_attention_bwd(qkv, do, out, lse, valid, B, T, N, rnd=ident, detail=None, frame_only=False):
     """-> (dqkv rows, delta (B*H*S,)).  As the two backward kernels: P = exp2(s - lse) from the SAVED lse, delta = <dO, O> on
     the stored values, dS = P (dP - delta) / 8; `rnd` rounds P and dS only as matrix operands."""
     d = qkv.shape[1] // 3
@@ -266,7 +351,7 @@ def clip_attention_bwd(qkv, do, out, lse, valid, B, T, N, rnd=ident, detail=None
     g, o = _clip_heads(do, B, T, N), _clip_heads(out, B, T, N)
     s = (q @ k.transpose(-1, -2)) * (LOG2E / 8.0)
     p = torch.exp2(s - lse.view(s.shape[:-1])[..., None])
-    p = torch.where(_clip_allowed(valid, B, T, N), p, torch.zeros_like(p))
+    p = torch.where(_clip_allowed(valid, B, T, N, frame_only), p, torch.zeros_like(p))
     delta = (g * o).sum(-1)
     ds = p * (g @ v.transpose(-1, -2) - delta[..., None]) * 0.125
     dq, dk, dv = rnd(ds) @ k, rnd(ds).transpose(-1, -2) @ q, rnd(p).transpose(-1, -2) @ g
@@ -288,7 +373,7 @@ def operand_flip_slack(kind, d64, d32, B, T, N):
     """{output: elementwise slack (rows)} of a bf16 per-clip attention launch from the `detail` of its float64 and float32
     evaluations: what the elements of flip_step can move each output by."""
     sp = flip_step(d64["p"], d32["p"])
-    if kind == "clip_fwd":
+    if kind.endswith("_fwd"):
         return {"att": _clip_rows((sp * d64["w"]) @ d64["v"].abs(), B, T, N)}
     sd = flip_step(d64["ds"], d32["ds"])
     parts = (sd @ d64["k"].abs(), sd.transpose(-1, -2) @ d64["q"].abs(), sp.transpose(-1, -2) @ d64["g"].abs())
@@ -308,60 +393,88 @@ def schedule(cfg, c):
     (a name for messages), family, entry (C-ABI name), ops (names of the pointer arguments in order; None = NULL, "arena"
     = a slab arena, "*" = not pinned), flags (projection calls), kind + the operand names the stage function takes.
     Under c.dropout the launches are those of _encode with drop and the `_dropped` backward's (module docstring): a fused entry also
-    carries its site."""
+    carries its site.  Options (module docstring, "Options"): augment first, scheduled sampling's pass 1 and mix, the
+    step, then one advance per counter in the order dropout, sched, augment."""
     L, d, ff = cfg.n_layers, cfg.d, cfg.d_ff
-    clip = c.attention == "clip"
-    valid = "batch:valid" if c.masked else None
+    kinds = layer_kinds(c.attention, L)
+    rows = lse_rows(kinds)
+    assert (c.box_nll_weight is not None) == cfg.gaussian_box, "box_nll_weight goes with LayoutConfig(box_head='gaussian') alone"
+    bn = lambda k: AUG_NAMES[k] if c.augment is not None and k in AUG_NAMES else "batch:" + k     # what the step trains on
+    valid = bn("valid") if c.masked else None
     drop = c.dropout is not None
     P = lambda n: "p:" + n
     out = []
 
-    def ln_f(stage, x, gname, y, i, branch=None):
-        """the layer-norm of statistics slot i; dropout: the fused launch of site i, which first forms x = resid + drop(branch)
-        (resid = the `x` of the launch this one replaces: site 0 has none and runs in place on x[0])"""
-        if drop:
-            src, resid = (x, None) if branch is None else ("ybranch", branch)
-            out.append(dict(stage=stage, kind="drop_ln_fwd", family="ln_fwd", entry="vlg_dropout_add_layernorm_fwd" + c.sfx, y=src,
-                            resid=resid, g=gname, x_out=x, h=y, stat=i, site=i,
-                            ops=(src, resid, P(gname), P(gname[:-1] + "b"), x, y, "stats[%d].mean" % i, "stats[%d].rstd" % i, "drop_step")))
-            return
-        out.append(dict(stage=stage, kind="ln_fwd", family="ln_fwd", entry="vlg_layernorm_fwd" + c.sfx, x=x, g=gname, y=y, stat=i,
-                        ops=(x, P(gname), P(gname[:-1] + "b"), y, "stats[%d].mean" % i, "stats[%d].rstd" % i)))
+    def forward(tag, drop, cls, box):
+        """the launches from the embedding through the head; tag: a prefix of the stage names (scheduled sampling's pass 1)"""
+        def ln_f(stage, x, gname, y, i, branch=None):
+            """the layer-norm of statistics slot i; dropout: the fused launch of site i, which first forms x = resid + drop(branch)
+            (resid = the `x` of the launch this one replaces: site 0 has none and runs in place on x[0])"""
+            if drop:
+                src, resid = (x, None) if branch is None else ("ybranch", branch)
+                out.append(dict(stage=tag + stage, kind="drop_ln_fwd", family="ln_fwd", entry="vlg_dropout_add_layernorm_fwd" + c.sfx, y=src,
+                                resid=resid, g=gname, x_out=x, h=y, stat=i, site=i,
+                                ops=(src, resid, P(gname), P(gname[:-1] + "b"), x, y, "stats[%d].mean" % i, "stats[%d].rstd" % i, "drop_step")))
+                return
+            out.append(dict(stage=tag + stage, kind="ln_fwd", family="ln_fwd", entry="vlg_layernorm_fwd" + c.sfx, x=x, g=gname, y=y, stat=i,
+                            ops=(x, P(gname), P(gname[:-1] + "b"), y, "stats[%d].mean" % i, "stats[%d].rstd" % i)))
 
-    def lin(stage, a, wname, cbuf, epi, aux_in=None, aux_out=None):
-        flags = epi | c.gemm_flags | c.bits(a, True, cbuf)
-        out.append(dict(stage=stage, kind="linear_fwd", family="gemm_head" if wname == "head_w" else "gemm_fwd", entry="vlg_linear_fwd",
-                        a=a, w=wname, c=cbuf, epi=epi, aux_in=aux_in, aux_out=aux_out, flags=flags,
-                        ops=(a, c.weight(wname), P(wname[:-1] + "b"), cbuf, aux_in, aux_out)))
+        def lin(stage, a, wname, cbuf, epi, aux_in=None, aux_out=None):
+            flags = epi | c.gemm_flags | c.bits(a, True, cbuf)
+            out.append(dict(stage=tag + stage, kind="linear_fwd", family="gemm_head" if wname == "head_w" else "gemm_fwd", entry="vlg_linear_fwd",
+                            a=a, w=wname, c=cbuf, epi=epi, aux_in=aux_in, aux_out=aux_out, flags=flags,
+                            ops=(a, c.weight(wname), P(wname[:-1] + "b"), cbuf, aux_in, aux_out)))
 
-    out.append(dict(stage="embedding", kind="embed_fwd", family="embed_fwd", entry="vlg_embed_fwd",
-                    ops=("batch:slot_class", "batch:slot_box", P("cls_emb"), P("box_w"), P("box_b"), P("time_emb"), "x[0]")))
-    epi_ff1 = EPI_BIAS | EPI_GELU | (EPI_GELU_GRAD if c.gelu_grad_saved else 0)
-    for l in range(L):
-        pre = "l%d." % l
-        x, h1, qkv, att, xmid, h2, u, gl = ("%s[%d]" % (n, l) for n in ("x", "h1", "qkv", "att", "xmid", "h2", "u", "gl"))
-        ln_f(pre + "ln1", x, pre + "ln1_g", h1, 2 * l, branch="xmid[%d]" % (l - 1) if l else None)
-        lin(pre + "qkv", h1, pre + "qkv_w", qkv, EPI_BIAS)
-        if clip:
-            out.append(dict(stage=pre + "attention", kind="clip_fwd", family="attn_clip_fwd", entry="vlg_attention_clip_fwd" + c.sfx,
-                            l=l, ops=(qkv, valid, att, "lse[%d]" % l)))
-        else:
-            out.append(dict(stage=pre + "attention", kind="slot_fwd", family="attn_fwd", entry="vlg_attention_fwd" + c.sfx, l=l,
-                            ops=(qkv, att)))
-        if drop:
-            lin(pre + "proj", att, pre + "proj_w", "ybranch", EPI_BIAS)
-        else:
-            lin(pre + "proj", att, pre + "proj_w", xmid, EPI_BIAS | EPI_RESID, aux_in=x)
-        ln_f(pre + "ln2", xmid, pre + "ln2_g", h2, 2 * l + 1, branch=x)
-        lin(pre + "ff1", h2, pre + "ff1_w", gl, epi_ff1, aux_out=u)
-        if drop:
-            lin(pre + "ff2", gl, pre + "ff2_w", "ybranch", EPI_BIAS)
-        else:
-            lin(pre + "ff2", gl, pre + "ff2_w", "x[%d]" % (l + 1), EPI_BIAS | EPI_RESID, aux_in=xmid)
-    ln_f("lnf", "x[%d]" % L, "lnf_g", "xf", 2 * L, branch="xmid[%d]" % (L - 1))
-    lin("head", "xf", "head_w", "out", EPI_BIAS)
-    out.append(dict(stage="loss", kind="loss", family="loss", entry="vlg_layout_loss",
-                    ops=("out", "batch:tgt_class", "batch:tgt_box", "batch:valid", "dout", "loss_out", "loss_scratch")))
+        out.append(dict(stage=tag + "embedding", kind="embed_fwd", family="embed_fwd", entry="vlg_embed_fwd", cls=cls, box=box,
+                        ops=(cls, box, P("cls_emb"), P("box_w"), P("box_b"), P("time_emb"), "x[0]")))
+        epi_ff1 = EPI_BIAS | EPI_GELU | (EPI_GELU_GRAD if c.gelu_grad_saved else 0)
+        for l in range(L):
+            pre = "l%d." % l
+            x, h1, qkv, att, xmid, h2, u, gl = ("%s[%d]" % (n, l) for n in ("x", "h1", "qkv", "att", "xmid", "h2", "u", "gl"))
+            ln_f(pre + "ln1", x, pre + "ln1_g", h1, 2 * l, branch="xmid[%d]" % (l - 1) if l else None)
+            lin(pre + "qkv", h1, pre + "qkv_w", qkv, EPI_BIAS)
+            k = kinds[l]
+            if k.per_clip:      # "clip" (block-causal) or "frame": the same operand list, the lse row of vlg.attention.lse_rows
+                short = k.family.split("_")[1]
+                out.append(dict(stage=tag + pre + "attention", kind=short + "_fwd", family=k.family + "_fwd", entry=k.stem + "_fwd" + c.sfx,
+                                l=l, row=rows[l], valid=valid, ops=(qkv, valid, att, "lse[%d]" % rows[l])))
+            else:
+                out.append(dict(stage=tag + pre + "attention", kind="slot_fwd", family="attn_fwd", entry="vlg_attention_fwd" + c.sfx, l=l,
+                                ops=(qkv, att)))
+            if drop:
+                lin(pre + "proj", att, pre + "proj_w", "ybranch", EPI_BIAS)
+            else:
+                lin(pre + "proj", att, pre + "proj_w", xmid, EPI_BIAS | EPI_RESID, aux_in=x)
+            ln_f(pre + "ln2", xmid, pre + "ln2_g", h2, 2 * l + 1, branch=x)
+            lin(pre + "ff1", h2, pre + "ff1_w", gl, epi_ff1, aux_out=u)
+            if drop:
+                lin(pre + "ff2", gl, pre + "ff2_w", "ybranch", EPI_BIAS)
+            else:
+                lin(pre + "ff2", gl, pre + "ff2_w", "x[%d]" % (l + 1), EPI_BIAS | EPI_RESID, aux_in=xmid)
+        ln_f("lnf", "x[%d]" % L, "lnf_g", "xf", 2 * L, branch="xmid[%d]" % (L - 1))
+        lin("head", "xf", "head_w", "out", EPI_BIAS)
+
+    if c.augment is not None:      # builds the batch every later launch reads (tgt_class stays the caller's)
+        out.append(dict(stage="augment", kind="augment", family="augment", entry="vlg_layout_augment",
+                        ops=tuple("batch:" + k for k in AUG_NAMES) + tuple(AUG_NAMES.values()) + ("aug_step",)))
+    cls, box = bn("slot_class"), bn("slot_box")
+    if c.sched is not None:        # pass 1: the evaluation forward on the true inputs, no dropout, no loss launch; then the mix
+        forward("pass1 ", False, cls, box)
+        out.append(dict(stage="sched mix", kind="sched_mix", family="sched_mix", entry="vlg_layout_mix_inputs", cls=cls, box=box,
+                        ops=("out", cls, box, "mix_cls", "mix_box", "sched_step")))
+        cls, box = "mix_cls", "mix_box"
+    forward("", drop, cls, box)
+    loss = dict(stage="loss", kind="loss", family="loss", tgt_class="batch:tgt_class", tgt_box=bn("tgt_box"), valid=bn("valid"))
+    if c.loss is None:
+        out.append(dict(loss, entry="vlg_layout_loss",
+                        ops=("out", "batch:tgt_class", bn("tgt_box"), bn("valid"), "dout", "loss_out", "loss_scratch")))
+    else:                          # any loss option on: one launch of the _ext entry in its place
+        out.append(dict(loss, entry="vlg_layout_loss_ext",
+                        ops=("out", "batch:tgt_class", bn("tgt_box"), bn("valid"), None if c.loss[0] is None else "class_weights",
+                             "dout", "loss_out", "loss_scratch")))
+    if cfg.gaussian_box:
+        out.append(dict(stage="box nll", kind="box_nll", family="box_nll", entry="vlg_layout_box_nll", tgt_box=bn("tgt_box"),
+                        valid=bn("valid"), ops=("out", bn("tgt_box"), bn("valid"), "dout", "loss_out", "box_nll_scratch")))
 
     # ---- backward
     def wg(stage, dy, x, wname):
@@ -407,18 +520,23 @@ def schedule(cfg, c):
         else:
             wg(pre + "proj", dxy, att, pre + "proj_w")
             dg(pre + "proj", dxy, pre + "proj_w", "dh")
-        if clip:
-            out.append(dict(stage=pre + "attention bwd", kind="clip_bwd", family="attn_clip_bwd", entry="vlg_attention_clip_bwd" + c.sfx,
-                            l=l, ops=(qkv, valid, att, "dh", "lse[%d]" % l, "delta", "dqkv")))
+        k = kinds[l]
+        if k.per_clip:
+            short = k.family.split("_")[1]
+            out.append(dict(stage=pre + "attention bwd", kind=short + "_bwd", family=k.family + "_bwd", entry=k.stem + "_bwd" + c.sfx,
+                            l=l, row=rows[l], valid=valid, pad=bn("valid"),
+                            ops=(qkv, valid, att, "dh", "lse[%d]" % rows[l], "delta", "dqkv")))
         else:
             out.append(dict(stage=pre + "attention bwd", kind="slot_bwd", family="attn_bwd", entry="vlg_attention_bwd" + c.sfx, l=l,
-                            ops=(qkv, "dh", "dqkv")))
+                            pad=bn("valid"), ops=(qkv, "dh", "dqkv")))
         pair(pre + "qkv", "dqkv", pre + "qkv_w", "dh", h1)
         ln_b(pre + "ln1", "dh", x, 2 * l, pre + "ln1_g", "dx")
-    out.append(dict(stage="embedding bwd", kind="embed_bwd", family="embed_bwd", entry="vlg_embed_bwd",
-                    ops=(dxy, "batch:slot_class", "batch:slot_box", "arena")))
-    if drop:
-        out.append(dict(stage="dropout step", kind="advance", family="dropout_step", entry="vlg_dropout_step_advance", ops=("drop_step",)))
+    out.append(dict(stage="embedding bwd", kind="embed_bwd", family="embed_bwd", entry="vlg_embed_bwd", cls=cls, box=box,
+                    ops=(dxy, cls, box, "arena")))
+    for name, stage, family, on in (("drop_step", "dropout step", "dropout_step", drop), ("sched_step", "sched step", "sched_step", c.sched),
+                                    ("aug_step", "augment step", "augment_step", c.augment)):
+        if on:      # (False or None: the option is off)
+            out.append(dict(stage=stage, kind="advance", family=family, entry="vlg_dropout_step_advance", counter=name, ops=(name,)))
     return out
 
 
@@ -430,15 +548,17 @@ def epi_modes(epi):
 
 # ------------------------------------------------------------------------------------------------ the chain
 def run_stage(e, cfg, c, batch, val, detail=None):
-    """One schedule entry on the values `val(name)` hands out (already in the dtype to compute in; None -> None) ->
+    """One schedule entry on the values `val(name)` hands out (floating tensors already in the dtype to compute in, integer
+    ones as they are; None -> None; "batch:*" = the caller's tensors, aug_* / mix_* in the public (B,T,N[,4]) shape) ->
     (outputs {buffer name: unrounded tensor}, parameter gradients {name: tensor} this launch is the source of).
-    `detail`: see clip_attention_fwd."""
+    `batch` gives the shape alone.  `detail`: see clip_attention_fwd; the box-NLL, mix and augment stages leave what their
+    comparisons need there (`nll`, `replaced` / `near`)."""
     B, T, N = batch["slot_class"].shape
     rnd = bf if c.round_operands else ident
     arnd = bf if c.store_bf16 else ident                     # P and dS of the per-clip attention
-    valid = batch["valid"] if c.masked else None
     k = e["kind"]
     o, g = {}, {}
+    detail = {} if detail is None else detail
 
     def wgrad(dy):
         g[e["w"]], g[e["w"][:-1] + "b"] = linear_wgrad(dy, val(e["x"]), rnd)
@@ -447,7 +567,7 @@ def run_stage(e, cfg, c, batch, val, detail=None):
         return linear_dgrad(dy, val(c.weight(e["w"])), rnd, val(e["aux_in"]), epi_modes(e["epi"])[1])
 
     if k == "embed_fwd":
-        o["x[0]"] = embed_fwd(val("p:cls_emb"), val("p:box_w"), val("p:box_b"), val("p:time_emb"), batch["slot_class"], batch["slot_box"])
+        o["x[0]"] = embed_fwd(val("p:cls_emb"), val("p:box_w"), val("p:box_b"), val("p:time_emb"), val(e["cls"]), val(e["box"]))
     elif k == "ln_fwd":
         o[e["y"]], o["stats[%d].mean" % e["stat"]], o["stats[%d].rstd" % e["stat"]] = ln_fwd(
             val(e["x"]), val("p:" + e["g"]), val("p:" + e["g"][:-1] + "b"))
@@ -462,10 +582,22 @@ def run_stage(e, cfg, c, batch, val, detail=None):
             o[e["aux_out"]] = aux
     elif k == "slot_fwd":
         o["att[%d]" % e["l"]] = slot_attention_fwd(val("qkv[%d]" % e["l"]), T)
-    elif k == "clip_fwd":
-        o["att[%d]" % e["l"]], o["lse[%d]" % e["l"]] = clip_attention_fwd(val("qkv[%d]" % e["l"]), valid, B, T, N, arnd, detail)
+    elif k in ("clip_fwd", "frame_fwd"):
+        o["att[%d]" % e["l"]], o["lse[%d]" % e["row"]] = clip_attention_fwd(val("qkv[%d]" % e["l"]), val(e["valid"]), B, T, N, arnd, detail,
+                                                                          k == "frame_fwd")
     elif k == "loss":
-        o["loss_out"], o["dout"] = loss_fwd(val("out"), batch["tgt_class"], batch["tgt_box"], batch["valid"], B, T, N, cfg.n_classes)
+        opts = None if c.loss is None else (None if c.loss[0] is None else val("class_weights"),) + tuple(c.loss[1:])
+        parts, o["dout"] = loss_fwd(val("out"), val(e["tgt_class"]), val(e["tgt_box"]), val(e["valid"]), B, T, N, cfg.n_classes, opts)
+        o["loss_out"] = torch.cat([parts, parts.new_zeros(cfg.loss_tail - 4)])      # (the Gaussian head's tail: the NLL launch's)
+    elif k == "box_nll":
+        o["dout"], o["loss_out"], detail["nll"] = box_nll_stage(val("out"), val("dout"), val("loss_out"), val(e["tgt_box"]), val(e["valid"]),
+                                                                B, T, N, cfg.n_classes, c.box_nll_weight)
+    elif k == "sched_mix":
+        o["mix_cls"], o["mix_box"], detail["replaced"], detail["near"] = sched_mix_stage(c, val("out"), val(e["cls"]), val(e["box"]),
+                                                                                         cfg.n_classes)
+    elif k == "augment":
+        a = augment_stage(c, {n: val("batch:" + n) for n in AUG_NAMES}, cfg.n_classes)
+        o.update({name: a[n] for n, name in AUG_NAMES.items()})
     elif k == "wgrad":
         wgrad(val(e["dy"]))
     elif k == "dgrad":
@@ -485,12 +617,12 @@ def run_stage(e, cfg, c, batch, val, detail=None):
             *site_mask(c, B * T * N, cfg.d, e["site"]))
     elif k == "slot_bwd":
         o["dqkv"] = slot_attention_bwd(val("qkv[%d]" % e["l"]), val("dh"), T)
-    elif k == "clip_bwd":
+    elif k in ("clip_bwd", "frame_bwd"):
         l = e["l"]
-        o["dqkv"], o["delta"] = clip_attention_bwd(val("qkv[%d]" % l), val("dh"), val("att[%d]" % l), val("lse[%d]" % l), valid,
-                                                   B, T, N, arnd, detail)
+        o["dqkv"], o["delta"] = clip_attention_bwd(val("qkv[%d]" % l), val("dh"), val("att[%d]" % l), val("lse[%d]" % e["row"]),
+                                                   val(e["valid"]), B, T, N, arnd, detail, k == "frame_bwd")
     elif k == "embed_bwd":
-        g.update(embed_bwd(val(e["ops"][0]), batch["slot_class"], batch["slot_box"], cfg.vocab, B, T, N))
+        g.update(embed_bwd(val(e["ops"][0]), val(e["cls"]), val(e["box"]), cfg.vocab, B, T, N))
     elif k == "advance":
         pass                                                 # the counter: step_trace.check reads it after every launch
     else:
@@ -498,39 +630,68 @@ def run_stage(e, cfg, c, batch, val, detail=None):
     return o, g
 
 
+def launch_scalars(cfg, c, e):
+    """The scalar arguments the launch of entry `e` must carry (None: it has none that the trace records): the restatement's
+    plan - thresholds as integers, 64-bit seeds, the engine's constants - as step_trace.trace names them."""
+    from vlg.spec import BOX_S_MAX, BOX_S_MIN
+    k = e["kind"]
+    if "site" in e:
+        return dropout_scalars(c, e["site"])
+    if k == "loss" and c.loss is not None:
+        return dict(label_smoothing=float(c.loss[1]), flags=1 if c.loss[2] == "giou" else 0)
+    if k == "box_nll":
+        return dict(s_min=BOX_S_MIN, s_max=BOX_S_MAX, w_nll=float(c.box_nll_weight))
+    if k == "sched_mix":
+        return dict(zip(("thr_max", "ramp_steps", "temperature", "top_k", "seed"), sched_plan(c)))
+    if k == "augment":
+        knobs, seed, _ = c.augment
+        return dict(thr_flip=augment_ref.threshold(knobs.get("flip", 0.0)), thr_drop=augment_ref.threshold(knobs.get("drop", 0.0)),
+                    zoom=float(knobs.get("zoom", 0.0)), shift=float(knobs.get("shift", 0.0)), jitter=float(knobs.get("jitter", 0.0)),
+                    seed=int(seed) & MASK64)
+    return None
+
+
 def emulate(cfg, c, params, batch, dtype, mutate=None):
     """Chain the stage functions along schedule(cfg, c) in `dtype`, storing every buffer as the contract says (bf16
-    buffers as torch.bfloat16 tensors, everything else in `dtype`) -> (records, state) in the record format of
-    step_trace.trace: a record = dict(family, name, flags, ops, after = {backward buffer: clone}); state = every
-    forward buffer, "grads" {name: tensor} and "loss".  In float64 this is the emulated oracle of the mode.
+    buffers as torch.bfloat16 tensors, integer tensors as they are, everything else in `dtype`) -> (records, state) in the
+    record format of step_trace.trace: a record = dict(family, name, flags, ops, scalars, counters, after = {snapshotted
+    buffer: tensor}); state = every forward buffer, "grads" {name: tensor} and "loss".  In float64 this is the emulated
+    oracle of the mode.
     `mutate(entry, val, outputs, grads, record)` may change what a launch leaves behind before it is stored (the checker's
-    own test); an output wrapped in Raw is stored as it is.  Under c.dropout a record also has the scalars of a fused
-    launch and the counter value after the launch (dropout_scalars, "drop_step"), as step_trace.trace records them."""
+    own test); an output wrapped in Raw is stored as it is.  A record has the scalars of its launch (launch_scalars) and the
+    value of every counter after the launch, as step_trace.trace records them."""
     st = {"p:" + k: v.to(dtype) for k, v in params.items()}
     st.update({"pb:" + k: v.to(BF) for k, v in params.items()})
+    st.update({"batch:" + k: v for k, v in batch.items()})
+    if c.loss is not None and c.loss[0] is not None:
+        st["class_weights"] = torch.as_tensor(c.loss[0], dtype=torch.float32)
     grads = {}
-    val = lambda n: None if n is None else st[n].to(dtype)
-    records = []
+    val = lambda n: None if n is None else st[n].to(dtype) if st[n].is_floating_point() else st[n]
+    records, counters, after = [], c.counters(), {}
     for e in schedule(cfg, c):
         o, g = run_stage(e, cfg, c, batch, val)
-        rec = dict(family=e["family"], name=e["entry"], flags=e.get("flags"), ops=e["ops"])
-        if c.dropout is not None:
-            rec["scalars"] = dropout_scalars(c, e["site"]) if "site" in e else None
-            rec["drop_step"] = c.dropout[2] + (e["kind"] == "advance")
+        if e["kind"] == "advance":
+            counters[e["counter"]] += 1
+        rec = dict(family=e["family"], name=e["entry"], flags=e.get("flags"), ops=e["ops"], scalars=launch_scalars(cfg, c, e),
+                   counters=dict(counters))
         if mutate is not None:
             mutate(e, val, o, g, rec)
         for n, t in o.items():
-            st[n] = t.t if isinstance(t, Raw) else t.to(BF if c.dtype(n) == BF else dtype)
+            st[n] = t.t if isinstance(t, Raw) else t if not t.is_floating_point() else t.to(BF if c.dtype(n) == BF else dtype)
         grads.update(g)
-        rec["after"] = {n: st[n].clone() for n in c.snapshots if n in st}
+        if c.sched is not None:      # every buffer, by the launch that wrote it (stored tensors are replaced, never modified)
+            after = dict(after, **{n: st[n] for n in o})
+            rec["after"] = after
+        else:
+            rec["after"] = {n: st[n].clone() for n in c.snapshots if n in st}
         records.append(rec)
-    st["grads"], st["loss"] = grads, st["loss_out"]
+    st["grads"], st["loss"], st["caller"] = grads, st["loss_out"], (batch, batch)
     return records, st
 
 
-def emulated_oracle(cfg, precision, params, batch, attention="slot", masked=True, dropout=None):
+def emulated_oracle(cfg, precision, params, batch, attention="slot", masked=True, dropout=None, **options):
     """Loss scalars and gradients of the mode, chained end to end in float64 with its storage roundings."""
-    _, st = emulate(cfg, Contract(precision, attention, masked, dropout=dropout), params, batch, torch.float64)
+    _, st = emulate(cfg, Contract(precision, attention, masked, dropout=dropout, **options), params, batch, torch.float64)
     return st["loss"], st["grads"]
 
 
@@ -549,7 +710,11 @@ def mode_distance(kw, precision, attention="slot", variable_n=False, seed=7):
         cfg = LayoutConfig(attention=attention, **kw)
         params = O.init_params(param_shapes(cfg), seed=1024)
         batch = O.synthetic_batch(cfg.B, cfg.T, cfg.N, seed=seed, variable_n=variable_n, min_valid=3)
-        parts, grads = O.loss_and_grads(params, batch, cfg.n_layers, attention=attention)
+        if attention == "factored":      # the specification of that mode: tests/factored_ref.py, composed from the oracle
+            import factored_ref
+            parts, grads = factored_ref.loss_and_grads(params, batch, cfg.n_layers)
+        else:
+            parts, grads = O.loss_and_grads(params, batch, cfg.n_layers, attention=attention)
         loss, emu = emulated_oracle(cfg, precision, params, batch, attention, masked=variable_n)
         gmax = max(float(v.norm()) for v in grads.values())
         dist = {n: float((w.double() - emu[n]).norm() / emu[n].norm()) for n, w in grads.items() if float(w.norm()) >= 1e-6 * gmax}

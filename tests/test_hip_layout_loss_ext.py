@@ -94,7 +94,12 @@ def run(H, dev, name, weight, eps, flags, scratch=None, entry="vlg_layout_loss_e
 def reference(name, weight, eps, flags, loss_w=LOSS_W, batch=None):
     """{dtype: (values (4,), d out (M, 24))} in float64 and float32, and the value floors"""
     logits, raw, b0, _, beta = inputs(name)
-    batch = b0 if batch is None else batch
+    return reference_on(logits, raw, b0 if batch is None else batch, beta, weight, eps, flags, loss_w)
+
+
+def reference_on(logits, raw, batch, beta, weight, eps, flags, loss_w=LOSS_W):
+    """`reference` on given tensors: logits (B,T,N,20), raw (B,T,N,4), batch = {tgt_class, tgt_box, valid} (step_trace.check
+    holds the step's loss launch to the same comparison)"""
     ref = {}
     for dt in (torch.float64, torch.float32):
         lg, rw = (t.detach().to(dt, copy=True).requires_grad_(True) for t in (logits, raw))

@@ -95,18 +95,28 @@ def test_three_adam_steps_track_the_specification(dev):
 @pytest.mark.parametrize("precision", ["bf16", "bf16_mfma"])
 def test_factored_step_in_the_bf16_modes(dev, precision):
     """the bars test_bf16_projection_mode uses at this shape (step_stages.end_to_end_bars: loss and per-tensor relative L2,
-    never looser than 2e-2 / 5e-2), against the fp32 specification of THIS mode; training makes progress"""
+    never looser than 2e-2 / 5e-2), against the fp32 specification of THIS mode; training makes progress.  What these bars
+    cannot see - which buffer, lse row, weight copy or mask a frame layer takes - tests/test_hip_step_trace_options.py
+    checks launch by launch."""
     kw = dict(B=2, T=16, N=16, d=256, n_layers=2)
     cfg, eng, p = build(kw, dev, precision=precision)
     batch = O.synthetic_batch(cfg.B, cfg.T, cfg.N, seed=7)
     parts, grads = R.loss_and_grads(p, batch, cfg.n_layers)
-    bar_loss, bar_grad, _ = SS.end_to_end_bars(kw, precision, seed=7)
-    assert bar_loss < 2e-2 and max(bar_grad.values()) <= 5e-2
+    # per quantity the SMALLER of the bar this test always had (derived from the slot model's emulation at this shape) and
+    # the one derived from THIS mode's own specification and emulation (factored_ref against the factored chain of
+    # step_stages): never looser than before.  Both are printed.
+    slot_loss, slot_grad, _ = SS.end_to_end_bars(kw, precision, seed=7)
+    own_loss, own_grad, _ = SS.end_to_end_bars(kw, precision, attention="factored", seed=7)
+    assert slot_loss < 2e-2 and max(slot_grad.values()) <= 5e-2
+    bar_loss = min(slot_loss, own_loss)
+    bar_grad = {n: min(slot_grad.get(n, own_grad.get(n)), own_grad.get(n, slot_grad.get(n))) for n in {**slot_grad, **own_grad}}
+    assert bar_loss <= slot_loss and all(bar_grad[n] <= v for n, v in slot_grad.items())
     loss = eng.forward_backward(to_dev(batch, dev)).cpu()
     errs = {name: float((g.cpu() - grads[name]).norm() / grads[name].norm()) for name, g in eng.named_grads().items() if name in bar_grad}
-    print("\n%s factored: loss off by %.2e (bar %.2e); gradients (rel L2 / bar): %s" % (
-        precision, abs(float(loss[0]) - parts[0]) / abs(parts[0]), bar_loss,
-        ", ".join("%s %.1e/%.1e" % (n, e, bar_grad[n]) for n, e in errs.items())))
+    print("\n%s factored: loss off by %.2e (bar from the slot model %.2e, from the factored model %.2e); gradients (rel L2 / slot-derived bar / "
+          "factored-derived bar): %s" % (precision, abs(float(loss[0]) - parts[0]) / abs(parts[0]), slot_loss, own_loss,
+                                         ", ".join("%s %.1e/%.1e/%.1e" % (n, e, slot_grad.get(n, float("nan")), own_grad.get(n, float("nan")))
+                                                   for n, e in errs.items())))
     assert abs(float(loss[0]) - parts[0]) <= bar_loss * abs(parts[0]), (float(loss[0]), parts[0], bar_loss)
     assert len(errs) >= len(grads) - 2 * cfg.n_layers
     for name, err in errs.items():

@@ -16,7 +16,8 @@ missing rounding, a dropped bias / residual / mask and a short bias gradient at 
 Shapes are the smallest that take each path: (2,16,12) x d=256 x 2 layers - M = 384 is no multiple of 128, and a layer's
 slab bucket rides in the next layer's paired launch; (1,32,8) x d=128 - the T = 32 attention kernels; (3,8,5) x d=64 -
 the generic-T kernel, ragged everything (T*N = 40 is no multiple of 32, so the per-clip attention refuses this one:
-asserted below).  The dropout step has cases of its own at the same shapes (DROP_CASES).  VLG_OVERLAP_WGRAD=1 is not
+asserted below).  The dropout step has cases of its own at the same shapes (DROP_CASES); attention = "factored" and the
+other training options have theirs in tests/test_hip_step_trace_options.py.  VLG_OVERLAP_WGRAD=1 is not
 traced: the synchronising wrapper would serialise it, and test_stream_options_do_not_change_results holds it bitwise to
 the default."""
 import pytest
