@@ -18,6 +18,22 @@
  *   - token-major activations use the INTERNAL row order  m = (b*N + n)*T + t
  *     (all frames of one slot contiguous: one T x d tile per (clip, slot));
  *     inputs/targets keep the public (B,T,N) order and are re-indexed in-kernel
+ *
+ * Grammar (ENFORCED: the Python binding is derived from this file - vlg/cabi.py reads it at import, types every entry
+ * point from its prototype, finds arguments by their parameter names and takes every constant from its #define - and
+ * the reader refuses, quoting the text, whatever is not listed here)
+ *   - comments are of this kind only, never the double-slash kind
+ *   - preprocessor lines: the include guard, the stdint.h include, #ifdef __cplusplus and #ifdef VLG_DIAG with their
+ *     #endif, and `#define VLG_NAME <number>`, the number one integer or one `(x.yf)` float.  No function-like macro, no
+ *     expression as a value, no #if / #elif / #else
+ *   - a prototype returns int, int64_t, void or const char*, and NAMES every parameter; a name is declared once
+ *   - scalar parameters are int, int64_t, uint32_t, uint64_t, float or double (no long, no unsigned, no size_t); every
+ *     other parameter is a pointer, to one of those, to void, char, uint8_t, uint16_t, unsigned long long, or to a type
+ *     this file typedefs.  No struct or typedef by value, no array, function pointer or variadic parameter
+ *   - `stream` is the last parameter wherever it occurs
+ *   - `typedef struct {...} name;` and `typedef <integer type> name;` only make `name` a legal pointer target
+ *   - an enum gives every member its value (`NAME = n`)
+ *   - prototypes between #ifdef VLG_DIAG and its #endif are the diagnostic build's: typed only when the library has them
  */
 #ifndef VLG_HIP_H
 #define VLG_HIP_H

@@ -36,8 +36,8 @@ from oracle import gridnet_spec as GS
 from oracle import hned_spec as HS
 from oracle import image_step_spec as IS
 from oracle import vgg_spec as VS
+from vlg.hip import CEPI_ACCUM, CEPI_CIN4, CEPI_DPRELU, CEPI_RESID      # include/vlg_hip.h VLG_CEPI_*
 
-CEPI_RESID, CEPI_DPRELU, CEPI_ACCUM, CEPI_CIN4 = 2, 8, 16, 32          # include/vlg_hip.h VLG_CEPI_*
 W_L1, W_STYLE, W_CE = 40.0, 20.0, 10.0                                  # reference src/trainer.py:248-250
 IMG_MEAN, IMG_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)        # trainer.py:122-123
 OUT_MEAN, OUT_STD = (-0.03, -0.088, -0.188), (0.448, 0.448, 0.450)      # trainer.py:120-121

@@ -40,7 +40,9 @@ from helpers import check_close, vs_cpu32
 
 F32, F64 = torch.float32, torch.float64
 EPS = PX.EPS
-_FLAGS_AT = {"vlg_conv3x3_fwd": 14, "vlg_conv3x3_dgrad": 14, "vlg_upsample2x_bwd": 6, "vlg_add_rows": 3, "vlg_prep_input": 14}
+# the header's name of the argument a record keeps as its flags (its position: vlg.hip.param_index)
+_FLAGS_PARAM = {"vlg_conv3x3_fwd": "epilogue", "vlg_conv3x3_dgrad": "epilogue", "vlg_upsample2x_bwd": "accumulate",
+                "vlg_add_rows": "accumulate", "vlg_prep_input": "flip"}
 _WRITES = {"vlg_nchw_to_padded": (1,), "vlg_padded_to_nchw": (1,), "vlg_conv3x3_fwd": (3,), "vlg_conv3x3_dgrad": (2, 6),
            "vlg_conv3x3_wgrad": (2,), "vlg_upsample2x_fwd": (1,), "vlg_upsample2x_bwd": (1,), "vlg_add_rows": (0,),
            "vlg_maxpool2x2": (1,), "vlg_maxpool2x2_bwd": (2,), "vlg_score1x1_relu": (3,), "vlg_hed_head": (7,),
@@ -175,9 +177,10 @@ def trace(engine, batch, flip):
                 ops.append(n)
                 if i in _WRITES[base] and n is not None:
                     out[n] = clone(names.snap[n]) if n in names.snap else None
-            rec = dict(name=name, flags=args[_FLAGS_AT[base]] if base in _FLAGS_AT else None, ops=ops, out=out)
+            at = lambda param: args[hip.param_index(name, param)]
+            rec = dict(name=name, flags=at(_FLAGS_PARAM[base]) if base in _FLAGS_PARAM else None, ops=ops, out=out)
             if base == "vlg_conv3x3_wgrad":
-                rec["region"] = ((args[2] - net.slabs.data_ptr()) // 4, out[ops[2]].numel() // args[3], args[3])
+                rec["region"] = ((at("slabs") - net.slabs.data_ptr()) // 4, out[ops[2]].numel() // at("slab_stride"), at("slab_stride"))
             elif base == "vlg_reduce_slabs_table":
                 out["grads_ext"] = clone(net.grads_ext)
                 rec["arena"] = {n: clone(t) for n, t in names.snap.items() if n.startswith("slab:")}

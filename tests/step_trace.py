@@ -53,7 +53,8 @@ from helpers import check_close, vs_cpu32
 from oracle import layout_spec as O
 
 BF = torch.bfloat16
-_FLAGS_AT = {"vlg_linear_fwd": 12, "vlg_linear_dgrad": 10, "vlg_linear_wgrad": 10, "vlg_linear_dgrad_wgrad": 15}
+# the header's name of a GEMM call's flags word (its position: vlg.hip.param_index)
+_FLAGS_PARAM = {"vlg_linear_fwd": "epilogue", "vlg_linear_dgrad": "epilogue", "vlg_linear_wgrad": "flags", "vlg_linear_dgrad_wgrad": "epilogue"}
 
 
 def _buffers(engine, batch, M):
@@ -98,11 +99,11 @@ def _buffers(engine, batch, M):
     return b
 
 
-# where the scalar arguments that launch_scalars names sit in a call (vlg/hip.py SIGNATURES)
-_SCALARS_AT = {"vlg_layout_loss_ext": dict(label_smoothing=18, flags=19),
-               "vlg_layout_box_nll": dict(s_min=11, s_max=12, w_nll=13),
-               "vlg_layout_mix_inputs": dict(thr_max=11, ramp_steps=12, temperature=13, top_k=14, seed=15),
-               "vlg_layout_augment": dict(thr_flip=13, thr_drop=14, zoom=15, shift=16, jitter=17, seed=18)}
+# the scalar arguments that launch_scalars names, by their parameter names in include/vlg_hip.h
+_SCALAR_PARAMS = {"vlg_layout_loss_ext": ("label_smoothing", "flags"),
+                  "vlg_layout_box_nll": ("s_min", "s_max", "w_nll"),
+                  "vlg_layout_mix_inputs": ("thr_max", "ramp_steps", "temperature", "top_k", "seed"),
+                  "vlg_layout_augment": ("thr_flip", "thr_drop", "zoom", "shift", "jitter", "seed")}
 
 
 def trace(engine, batch):
@@ -126,14 +127,15 @@ def trace(engine, batch):
         torch.cuda.synchronize()
         types = hip.SIGNATURES[name][1]
         ops = tuple(None if a == 0 else by_ptr.get(a, "arena") for a, ty in list(zip(args, types))[:-1] if ty is c_void_p)
-        rec = dict(family=family, name=name, flags=args[_FLAGS_AT[name]] if name in _FLAGS_AT else None, ops=ops, scalars=None)
+        rec = dict(family=family, name=name, flags=args[hip.param_index(name, _FLAGS_PARAM[name])] if name in _FLAGS_PARAM else None,
+                   ops=ops, scalars=None)
         if every:
             rec["after"] = dict(records[-1]["after"] if records else {})
             rec["after"].update({n: bufs[n].detach().cpu().clone() for n in set(ops) if n in bufs and not n.startswith(SS.FIXED) and n not in counters})
         else:
             rec["after"] = {n: bufs[n].detach().cpu().clone() for n in snapshots if n in bufs}
-        if name in _SCALARS_AT:
-            rec["scalars"] = {k: args[i] for k, i in _SCALARS_AT[name].items()}
+        if name in _SCALAR_PARAMS:
+            rec["scalars"] = {k: args[hip.param_index(name, k)] for k in _SCALAR_PARAMS[name]}
         elif "dropout" in name and c_uint32 in types:        # the fused entry points: (uint32 thr, float scale, uint64 seed, int site)
             i = types.index(c_uint32)
             rec["scalars"] = dict(zip(("thr", "scale", "seed", "site"), args[i:i + 4]))

@@ -21,6 +21,7 @@ import torch.nn.functional as F
 
 from helpers import check_close
 from test_hip_ops import BF_OUT
+from vlg import hip
 
 EPI_NONE, EPI_BIAS, EPI_GELU, EPI_RESID, EPI_DGELU, EPI_BF16 = 0, 1, 2, 4, 8, 16
 EPI_A_BF16, EPI_B_BF16, EPI_OUT_BF16, EPI_SPLIT3 = 32, 64, 128, 256
@@ -41,7 +42,7 @@ def _cdiv(a, b):
 # mirror_plan returns exactly the fields vlg_linear_plan reports; describe() turns such fields - the mirror's or the
 # library's - into the path label the case table uses.
 F32, BF16_MFMA, F32X3 = 0, 1, 2                          # VLG_GEMM_*
-CALLS = {"fwd": 0, "dgrad": 1, "wgrad": 2, "pair": 3}    # VLG_CALL_*
+CALLS = {"fwd": hip.CALL_FWD, "dgrad": hip.CALL_DGRAD, "wgrad": hip.CALL_WGRAD, "pair": hip.CALL_PAIR}    # VLG_CALL_*
 STORAGE = EPI_A_BF16 | EPI_B_BF16 | EPI_OUT_BF16
 
 

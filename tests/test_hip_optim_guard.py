@@ -16,12 +16,12 @@ import torch.multiprocessing as mp
 from conftest import PKG, ROOT
 from helpers import check_close
 from oracle import layout_spec as O
+# slots of the control record (VLG_CTL_* in include/vlg_hip.h)
+from vlg.optim import APPLY, CLIP_COEF, GRAD_MULT, GRAD_NORM, LR as LR_SLOT, SKIPPED, SQRT_BC2, STEP, STEP_SIZE
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 LR, B1, B2, EPS = 2e-4, 0.5, 0.999, 1e-8
-# slots of the control record (VLG_CTL_* in include/vlg_hip.h)
-STEP_SIZE, SQRT_BC2, STEP, APPLY, GRAD_MULT, GRAD_NORM, LR_SLOT, SKIPPED, CLIP_COEF = range(9)
 
 
 @pytest.fixture(scope="module")

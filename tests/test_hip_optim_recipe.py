@@ -22,6 +22,11 @@ import optim_recipe_ref as R
 from conftest import PKG, ROOT
 from helpers import check_close, reference_args
 from oracle import layout_spec as O
+# slots of the records (VLG_CTL_* / VLG_EXT_* in include/vlg_hip.h)
+from vlg.optim import APPLY, CLIP_COEF, GRAD_MULT, GRAD_NORM, LR as LR_SLOT, SKIPPED, SQRT_BC2, STEP, STEP_SIZE
+from vlg.optim import (EXT_DECAY_MULT as X_DECAY_MULT, EXT_EMA_DECAY as X_EMA, EXT_EMA_OMD as X_EMA_OMD,
+                       EXT_EMA_WARMUP as X_EMA_WARMUP, EXT_LR_EFF as X_LR_EFF, EXT_WARMUP_STEPS as X_WARMUP,
+                       EXT_WEIGHT_DECAY as X_WD)
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -29,9 +34,6 @@ f32 = lambda x: float(np.float32(x))
 LR, B1, B2, EPS = f32(2e-4), 0.5, f32(0.999), f32(1e-8)            # as the kernels see them: floats widened to double
 WD, WARMUP, EMA_D = f32(0.1), 5, 0.5
 RTOL, ATOL = 1e-6, 1e-7
-# slots of the records (VLG_CTL_* / VLG_EXT_* in include/vlg_hip.h)
-STEP_SIZE, SQRT_BC2, STEP, APPLY, GRAD_MULT, GRAD_NORM, LR_SLOT, SKIPPED, CLIP_COEF = range(9)
-X_WD, X_WARMUP, X_EMA, X_EMA_WARMUP, X_LR_EFF, X_DECAY_MULT, X_EMA_OMD = range(7)
 CTL_MARK, EXT_MARK, OUT_MARK = -9.0, -3.0, -5.0                      # reserved slots / not-yet-written outputs
 FULL = dict(weight_decay=WD, warmup_steps=WARMUP, ema_decay=EMA_D, ema_warmup=True)
 

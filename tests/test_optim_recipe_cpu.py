@@ -11,6 +11,7 @@ import torch
 
 import optim_recipe_ref as R
 from helpers import OracleEngine, reference_args
+from vlg import hip
 from vlg.spec import LayoutConfig, param_layout
 
 LR, B1, B2, EPS = 2e-4, 0.5, 0.999, 1e-8
@@ -217,7 +218,8 @@ def test_any_recipe_knob_turns_the_guard_on_and_routes_through_the_new_entry_poi
     opt.update_guarded(torch.zeros(16), torch.zeros(16), 1.0, 0)
     assert [c[0] for c in calls] == ["vlg_grad_sumsq", "vlg_optim_control_ext", "vlg_adamw_ema_step_ctl"]
     args = calls[-1][1]
-    assert len(args) == 15 and (args[5] != 0) == ("ema_decay" in knob) and args[6] == 0 and (args[7] != 0) == ("weight_decay" in knob)
+    ema, ema_shadow, decay_mask = (args[hip.param_index("vlg_adamw_ema_step_ctl", p)] for p in ("ema", "ema_shadow", "decay_mask"))
+    assert len(args) == 15 and (ema != 0) == ("ema_decay" in knob) and ema_shadow == 0 and (decay_mask != 0) == ("weight_decay" in knob)
     assert opt.adam_bytes() == 16 * (28.0 + (8.0 if "ema_decay" in knob else 0.0) + (0.25 if "weight_decay" in knob else 0.0))
 
 

@@ -13,9 +13,12 @@ from typing import Callable, Dict, List, Optional
 
 import torch
 
-# slot indices of include/vlg_hip.h
-SCORED, TOP1, TOPK, IOU_HIT, BOTH_HIT, NONFINITE, UNSCORED, CONF = 0, 1, 2, 3, 4, 5, 6, 8
-NLL, IOU, BOX_L1, IOU_BY_CLASS = 0, 1, 2, 4
+from . import cabi
+
+# slot indices of include/vlg_hip.h: counts, then sums
+SCORED, TOP1, TOPK, IOU_HIT, BOTH_HIT, NONFINITE, UNSCORED, CONF = cabi.values(
+    "VLG_MET_", "SCORED", "TOP1", "TOPK", "IOU_HIT", "BOTH_HIT", "NONFINITE", "UNSCORED", "CONF")
+NLL, IOU, BOX_L1, IOU_BY_CLASS = cabi.values("VLG_MET_", "NLL", "IOU", "BOX_L1", "IOU_BY_CLASS")
 
 
 def n_counts(n_classes: int) -> int:

@@ -24,14 +24,16 @@ from typing import Callable, Dict, Mapping, Optional, Sequence, Tuple
 
 import torch
 
-from . import hip
+from . import cabi, hip
 from .hip import call, ptr
 from .spec import ADAM_BETA2, ADAM_EPS, recipe_options
 
 # slots of ctl (VLG_CTL_* in include/vlg_hip.h)
-STEP_SIZE, SQRT_BC2, STEP, APPLY, GRAD_MULT, GRAD_NORM, LR, SKIPPED, CLIP_COEF, CTL_FLOATS = 0, 1, 2, 3, 4, 5, 6, 7, 8, 16
+STEP_SIZE, SQRT_BC2, STEP, APPLY, GRAD_MULT, GRAD_NORM, LR, SKIPPED, CLIP_COEF, CTL_FLOATS = cabi.values(
+    "VLG_CTL_", "STEP_SIZE", "SQRT_BC2", "STEP", "APPLY", "GRAD_MULT", "GRAD_NORM", "LR", "SKIPPED", "CLIP_COEF", "FLOATS")
 # slots of ext (VLG_EXT_* in include/vlg_hip.h)
-EXT_WEIGHT_DECAY, EXT_WARMUP_STEPS, EXT_EMA_DECAY, EXT_EMA_WARMUP, EXT_LR_EFF, EXT_DECAY_MULT, EXT_EMA_OMD, EXT_FLOATS = 0, 1, 2, 3, 4, 5, 6, 16
+EXT_WEIGHT_DECAY, EXT_WARMUP_STEPS, EXT_EMA_DECAY, EXT_EMA_WARMUP, EXT_LR_EFF, EXT_DECAY_MULT, EXT_EMA_OMD, EXT_FLOATS = cabi.values(
+    "VLG_EXT_", "WEIGHT_DECAY", "WARMUP_STEPS", "EMA_DECAY", "EMA_WARMUP", "LR_EFF", "DECAY_MULT", "EMA_OMD", "FLOATS")
 
 
 def decay_mask_ranges(n: int, ranges: Sequence[Tuple[int, int]]) -> torch.Tensor:

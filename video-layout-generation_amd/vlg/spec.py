@@ -21,6 +21,7 @@ from collections import OrderedDict
 from typing import Dict, Tuple
 
 from .attention import FRAME, MODES, layer_kinds
+from .cabi import values
 
 # ---- reference-real constants -------------------------------------------------
 N_CLASSES = 20                  # reference src/models/gridnet.py:9 (seg_out = 20), trainer.py:31-52
@@ -45,9 +46,8 @@ LN_EPS = 1e-5
 BOX_DIM = 4                     # (cx, cy, w, h), all in [0,1]
 # the Gaussian box head (LayoutConfig.box_head = "gaussian"; DESIGN.md "Gaussian box head"): log sigma = BOX_S_MIN +
 # (BOX_S_MAX - BOX_S_MIN) * sigmoid(raw scale), so sigma lies in [e^-7, 1] on boxes normalised to [0, 1]
-# (VLG_BOX_S_MIN / VLG_BOX_S_MAX of include/vlg_hip.h are the same numbers for the decoding kernels)
-BOX_S_MIN = -7.0
-BOX_S_MAX = 0.0
+# (read from include/vlg_hip.h, where the decoding kernels take them; through the header alone: no library is loaded here)
+BOX_S_MIN, BOX_S_MAX = values("VLG_BOX_S_", "MIN", "MAX")
 BOX_HEADS = ("point", "gaussian")
 BOX_HEAD_EXTRA = 8              # columns a Gaussian head appends to a head-output row: 4 raw scales + 4 of padding
 
