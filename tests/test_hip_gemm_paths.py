@@ -293,6 +293,16 @@ CASES = [
     ("bf16 dgrad mul io6", "dgrad", 33000, 520, 264, EPI_MUL | B16 | EPI_OUT_BF16, "gemm_bf16_kernel 128x128"),
     ("bf16 fwd narrow", "fwd", 33000, 24, 256, EPI_BIAS | B16 | EPI_A_BF16 | EPI_OUT_BF16, "gemm_bf16_kernel 128x32"),
     ("bf16 wgrad narrow", "wgrad", 33000, 24, 256, B16 | EPI_A_BF16, "gemm_bf16_kernel 32x128 splits129"),
+    # kernel rows of gemm_bf16.hip no other case reaches with an edge tile (ragged rows and columns, K = one 64-deep tile + 8)
+    ("bf16 io0 fwd bias ragged", "fwd", 200, 136, 72, EPI_BIAS | EPI_BF16, "gemm_bf16_kernel 128x128"),
+    ("bf16 io0 fwd gelu ragged", "fwd", 200, 136, 72, EPI_BIAS | EPI_GELU | EPI_BF16, "gemm_bf16_kernel 128x128"),
+    ("bf16 io0 fwd resid ragged", "fwd", 200, 136, 72, EPI_BIAS | EPI_RESID | EPI_BF16, "gemm_bf16_kernel 128x128"),
+    ("bf16 io3 fwd bias ragged", "fwd", 200, 136, 72, EPI_BIAS | B16 | EPI_A_BF16, "gemm_bf16_kernel 128x128"),
+    ("bf16 io7 fwd gelu+grad ragged", "fwd", 200, 136, 72, EPI_BIAS | EPI_GELU | EPI_GELU_GRAD | B16 | EPI_A_BF16 | EPI_OUT_BF16,
+     "gemm_bf16_kernel 128x128"),
+    ("bf16 io0 dgrad none ragged", "dgrad", 200, 72, 136, EPI_BF16, "gemm_bf16_kernel 128x128"),
+    ("bf16 io0 dgrad dgelu ragged", "dgrad", 200, 72, 136, EPI_DGELU | EPI_BF16, "gemm_bf16_kernel 128x128"),
+    ("bf16 io0 wgrad ragged", "wgrad", 200, 136, 72, EPI_BF16, "gemm_bf16_kernel 128x128"),
     ("fp32x3 fwd 128 ragged", "fwd", 33000, 520, 264, EPI_BIAS | EPI_SPLIT3, "gemm_split_kernel 128x128"),
     ("fp32x3 dgrad 128 ragged", "dgrad", 33000, 520, 264, EPI_SPLIT3, "gemm_split_kernel 128x128"),
     ("fp32x3 wgrad 128 ragged", "wgrad", 33000, 520, 264, EPI_SPLIT3, "gemm_split_kernel 128x128 splits33"),

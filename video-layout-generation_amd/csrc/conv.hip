@@ -72,9 +72,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void conv_gemm_kernel(const ConvAr
     if (part && bid >= ntail) return;                          // padding
     int split, tile;
     if (!part) {
-        const int j = bid - ntp;
-        const int q = nmain >> 3, rr = nmain & 7, xcd = j & 7;
-        const int swz = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (j >> 3);
+        const int swz = xcd_swizzle(bid - ntp, nmain);
         split = swz / ntile;
         tile = swz - split * ntile;
     } else {

@@ -108,8 +108,7 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs& g, float* const sm
 
     // XCD-aware remap: hardware deals blocks round-robin over 8 XCDs; give each XCD a
     // contiguous run of logical tiles (bijective for any grid size)
-    const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+    const int swz = xcd_swizzle(bid, nwg);
     // N tiles per block: the fast path of the BK = 32 kernels without bias-gradient sums (the host sets it); a compile-time 1
     // elsewhere, so those kernels have no loop around [main loop, epilogue]
     constexpr bool CHAIN = BM == 128 && BN == 128 && BK == 32 && !COLSUM && (EPI & ((1 << 20) | (1 << 21))) == 0;
@@ -494,6 +493,7 @@ __device__ __forceinline__ void gemm_f32_body(const GemmArgs& g, float* const sm
 #endif
     // ---- epilogue.  C/D layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*h.
     // 32 lanes of a half write one 128-B row segment per store.
+    // (emit below is a copy of gemm16_emit, gemm_tile16.h - kept a copy: what is defined beside the fast path moves its registers)
     EO* Cs = static_cast<EO*>(g.C) + (int64_t)split * g.slab_stride;
     const int64_t row0 = m0 + wm * TM * 32 + 4 * h;
     const int col0 = n0 + wn * TN * 32 + l31;

@@ -38,51 +38,27 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& g, bf16_t* const sme
     static_assert(!COLSUM || !A_KC, "column sums are taken from a contraction-major A tile");
     const EA* const gA = static_cast<const EA*>(g.A);
     const EB* const gB = static_cast<const EB*>(g.B);
-    const EO* const gAuxIn = static_cast<const EO*>(g.aux_in);
-    EO* const gAuxOut = static_cast<EO*>(g.aux_out);
-    constexpr int WM = (BM == 128 && BN == 128) ? 2 : (BM == 128 ? 4 : 1);
-    constexpr int WN = 4 / WM;
-    constexpr int TM = BM / (32 * WM), TN = BN / (32 * WN);
+    using W = Waves16<BM, BN>;
+    constexpr int WN = W::WN, TM = W::TM, TN = W::TN;
     using TA = Tile16<BM, A_KC, BK16>;
     using TB = Tile16<BN, B_KC, BK16>;
     bf16_t* const As0 = smem;
     bf16_t* const Bs0 = smem + 2 * TA::ELEMS;
 
-    const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
-    const int ntile = g.tiles_m * g.tiles_n;
-    const int split = swz / ntile;
-    const int tile = swz - split * ntile;
-    const int tm = tile / g.tiles_n, tn = tile - tm * g.tiles_n;
-    const int64_t m0 = (int64_t)tm * BM;
-    const int n0 = tn * BN;
-    const int64_t kbeg = (int64_t)split * g.kc_per_split;
-    int64_t kend = kbeg + g.kc_per_split;
-    if (kend > g.Kc) kend = g.Kc;
+    const Place16 pl = gemm16_place<BM, BN>(g, bid, nwg);
+    const int tn = pl.tn, n0 = pl.n0;
+    const int64_t m0 = pl.m0, kbeg = pl.kbeg, kend = pl.kend;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, h = lane >> 5;
     const int wm = wave / WN, wn = wave - wm * WN;
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    float bv[TN];
+    gemm16_start<EPI>(acc, bv, g, n0 + wn * TN * 32 + l31);
     float csum[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) csum[j] = 0.f;
-    float bv[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        bv[j] = 0.f;
-        if constexpr ((EPI & VLG_EPI_BIAS) != 0) {
-            const int col = n0 + (wn * TN + j) * 32 + l31;
-            bv[j] = g.bias[col < g.N ? col : g.N - 1];
-        }
-    }
 
     const int nk = (int)((kend - kbeg + BK16 - 1) / BK16);
     auto kstep = [&](const bf16_t* as, const bf16_t* bs, int s) {
@@ -144,79 +120,19 @@ __device__ __forceinline__ void gemm16_body(const GemmArgs& g, bf16_t* const sme
             for (int kt = 0; kt < nk; ++kt) iter(kt, sa0, sb0);
         }
     };
-    const bool interior = (m0 + BM <= g.M) && (n0 + BN <= g.N) && (((kend - kbeg) % BK16) == 0);
-    if (interior) mainloop(std::false_type{});
+    if (pl.full && ((kend - kbeg) % BK16) == 0) mainloop(std::false_type{});
     else mainloop(std::true_type{});
 
-    // ---- epilogue (C/D layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*h)
-    EO* Cs = static_cast<EO*>(g.C) + (int64_t)split * g.slab_stride;
-    const int64_t row0 = m0 + wm * TM * 32 + 4 * h;
+    // ---- epilogue (gemm_tile16.h)
+    const int64_t row0 = m0 + wm * TM * 32 + 4 * h;      // the lane's first element of C
     const int col0 = n0 + wn * TN * 32 + l31;
-    const int64_t base = row0 * g.ldc + col0;
-    const bool full = (m0 + BM <= g.M) && (n0 + BN <= g.N);
-    auto emit = [&](auto guard_tag) {
-        constexpr bool GUARD = decltype(guard_tag)::value;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                if (GUARD && col0 + j * 32 >= g.N) continue;
-                float aux[16];
-                if constexpr ((EPI & (VLG_EPI_RESID | VLG_EPI_DGELU | VLG_EPI_MUL)) != 0) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int ro = i * 32 + (r & 3) + 8 * (r >> 2);
-                        aux[r] = (!GUARD || row0 + ro < g.M) ? ld1(gAuxIn + base + ro * g.ldc + j * 32) : 0.f;
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int ro = i * 32 + (r & 3) + 8 * (r >> 2);
-                    if (GUARD && row0 + ro >= g.M) continue;
-                    const int64_t o = base + ro * g.ldc + j * 32;
-                    float v = acc[i][j][r] + bv[j];
-                    if constexpr ((EPI & VLG_EPI_GELU) != 0) {
-                        if constexpr ((EPI & VLG_EPI_GELU_GRAD) != 0) {      // aux_out = gelu'(pre) (common.h, gelu_parts): the backward
-                            float c, pd;                                     // pass then multiplies (VLG_EPI_MUL) instead of recomputing
-                            gelu_parts(v, c, pd);
-                            st1(gAuxOut + o, c + v * pd);
-                            v *= c;
-                        } else {
-                            st1(gAuxOut + o, v);
-                            v = gelu_f(v);
-                        }
-                    }
-                    if constexpr ((EPI & VLG_EPI_RESID) != 0) v += aux[r];
-                    if constexpr ((EPI & VLG_EPI_DGELU) != 0) v *= dgelu_f(aux[r]);
-                    if constexpr ((EPI & VLG_EPI_MUL) != 0) v *= aux[r];
-                    st1(Cs + o, v);
-                }
-            }
-    };
+    EO* Cs = static_cast<EO*>(g.C) + (int64_t)pl.split * g.slab_stride;
     // (An LDS-staged epilogue for bf16 outputs - column pairs packed with a DPP swap, 16-byte row-contiguous stores - was
     // measured and is NOT faster than these 2-byte stores: the kernels are not bound by store requests.)
-    if (full) emit(std::false_type{});
-    else emit(std::true_type{});
+    if (pl.full) gemm16_emit<false, EPI>(g, acc, bv, Cs, row0, col0);
+    else gemm16_emit<true, EPI>(g, acc, bv, Cs, row0, col0);
     if constexpr (COLSUM) {
-        // every thread summed the 8 rows 8*(tid % PER_ROW) .. +7 of the tiles it staged: combine the GEMM_THREADS / PER_ROW
-        // threads that share a row group through LDS (the tiles are dead: the main loop ended on a barrier)
-        if (tn == 0) {
-            float* red = reinterpret_cast<float*>(smem);
-            constexpr int PR = TA::PER_ROW, NT = GEMM_THREADS / PR;         // threads per row group
-            if ((TA::SLOTS % GEMM_THREADS == 0) || tid < TA::SLOTS) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) red[(tid / PR) * BM + 8 * (tid % PR) + j] = csum[j];
-            }
-            __syncthreads();
-            constexpr int NTL = (TA::SLOTS < GEMM_THREADS ? TA::SLOTS : GEMM_THREADS) / PR;
-            if (tid < BM && m0 + tid < g.M) {
-                float s = 0.f;
-#pragma unroll 4
-                for (int t = 0; t < NTL; ++t) s += red[t * BM + tid];
-                st1(Cs + g.colsum_off + m0 + tid, s);
-            }
-            (void)NT;
-        }
+        if (tn == 0) gemm16_colsum_store<TA, BM>(g, csum, reinterpret_cast<float*>(smem), Cs, m0, tid);
     }
 }
 

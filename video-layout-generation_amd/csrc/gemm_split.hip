@@ -7,8 +7,9 @@
 // fp32-grade (measured against fp64 in tests/test_hip_ops.py next to the native v_mfma_f32_32x32x2_f32 path), while six
 // v_mfma_f32_32x32x16_bf16 cost 6/16 of the fp32 MFMA cycles for the same k-depth.  Tensors stay fp32 in HBM.
 //
-// Structure = gemm.hip's (128x128 block tile, 2x2 wave tiles, mid-tile staging, XCD-aware tile order, slab outputs,
-// fused epilogues); tiles = gemm_tile16.h's bf16 images, 16 contraction steps deep, three planes per operand
+// Structure = gemm_bf16.hip's, whose block frame it shares (gemm_tile16.h: 128x128 block tile, 2x2 wave tiles, XCD-aware tile
+// order, slab outputs, fused epilogues, bias-gradient column sums); this file holds what differs - how a tile reaches LDS and
+// the six-term main loop.  Tiles = gemm_tile16.h's bf16 images, 16 contraction steps deep, three planes per operand
 // (36 KB per stage, 72 KB double-buffered: 2 blocks / CU).  The split happens once per element on the way to LDS.
 #include "common.h"
 #include "gemm_tile16.h"
@@ -37,52 +38,27 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_split_kernel(const GemmA
     constexpr int BKS = 16;
     const float* const gA = static_cast<const float*>(g.A);
     const float* const gB = static_cast<const float*>(g.B);
-    const float* const gAuxIn = static_cast<const float*>(g.aux_in);
-    float* const gAuxOut = static_cast<float*>(g.aux_out);
-    constexpr int WM = (BM == 128 && BN == 128) ? 2 : (BM == 128 ? 4 : 1);
-    constexpr int WN = 4 / WM;
-    constexpr int TM = BM / (32 * WM), TN = BN / (32 * WN);
+    using W = Waves16<BM, BN>;
+    constexpr int WN = W::WN, TM = W::TM, TN = W::TN;
     using TA = Tile16<BM, A_KC, BKS>;
     using TB = Tile16<BN, B_KC, BKS>;
     constexpr int STAGE = 3 * (TA::ELEMS + TB::ELEMS);                 // one buffer: A planes 1..3, then B planes 1..3
     __shared__ __attribute__((aligned(16))) bf16_t smem[2 * STAGE];
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
-    const int ntile = g.tiles_m * g.tiles_n;
-    const int split = swz / ntile;
-    const int tile = swz - split * ntile;
-    const int tm = tile / g.tiles_n, tn = tile - tm * g.tiles_n;
-    const int64_t m0 = (int64_t)tm * BM;
-    const int n0 = tn * BN;
-    const int64_t kbeg = (int64_t)split * g.kc_per_split;
-    int64_t kend = kbeg + g.kc_per_split;
-    if (kend > g.Kc) kend = g.Kc;
+    const Place16 pl = gemm16_place<BM, BN>(g, (int)blockIdx.x, (int)gridDim.x);
+    const int tn = pl.tn, n0 = pl.n0;
+    const int64_t m0 = pl.m0, kbeg = pl.kbeg, kend = pl.kend;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, h = lane >> 5;
     const int wm = wave / WN, wn = wave - wm * WN;
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    float bv[TN];
+    gemm16_start<EPI>(acc, bv, g, n0 + wn * TN * 32 + l31);
     float csum[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) csum[j] = 0.f;
-    float bv[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        bv[j] = 0.f;
-        if constexpr ((EPI & VLG_EPI_BIAS) != 0) {
-            const int col = n0 + (wn * TN + j) * 32 + l31;
-            bv[j] = g.bias[col < g.N ? col : g.N - 1];
-        }
-    }
 
     const int nk = (int)((kend - kbeg + BKS - 1) / BKS);
     auto store3 = [&](const Stage16<float, TA::NV>& xa, const Stage16<float, TB::NV>& xb, int buf) {
@@ -178,63 +154,17 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_split_kernel(const GemmA
             __syncthreads();
         }
     };
-    const bool interior = (m0 + BM <= g.M) && (n0 + BN <= g.N) && (((kend - kbeg) % BKS) == 0);
-    if (interior) mainloop(std::false_type{});
+    if (pl.full && ((kend - kbeg) % BKS) == 0) mainloop(std::false_type{});
     else mainloop(std::true_type{});
 
-    // ---- epilogue (C/D layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*h)
-    float* Cs = static_cast<float*>(g.C) + (int64_t)split * g.slab_stride;
-    const int64_t row0 = m0 + wm * TM * 32 + 4 * h;
+    // ---- epilogue (gemm_tile16.h)
+    const int64_t row0 = m0 + wm * TM * 32 + 4 * h;      // the lane's first element of C
     const int col0 = n0 + wn * TN * 32 + l31;
-    const int64_t base = row0 * g.ldc + col0;
-    const bool full = (m0 + BM <= g.M) && (n0 + BN <= g.N);
-    auto emit = [&](auto guard_tag) {
-        constexpr bool GUARD = decltype(guard_tag)::value;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                if (GUARD && col0 + j * 32 >= g.N) continue;
-                float aux[16];
-                if constexpr ((EPI & (VLG_EPI_RESID | VLG_EPI_DGELU)) != 0) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int ro = i * 32 + (r & 3) + 8 * (r >> 2);
-                        aux[r] = (!GUARD || row0 + ro < g.M) ? gAuxIn[base + ro * g.ldc + j * 32] : 0.f;
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int ro = i * 32 + (r & 3) + 8 * (r >> 2);
-                    if (GUARD && row0 + ro >= g.M) continue;
-                    const int64_t o = base + ro * g.ldc + j * 32;
-                    float v = acc[i][j][r] + bv[j];
-                    if constexpr ((EPI & VLG_EPI_GELU) != 0) { gAuxOut[o] = v; v = gelu_f(v); }
-                    if constexpr ((EPI & VLG_EPI_RESID) != 0) v += aux[r];
-                    if constexpr ((EPI & VLG_EPI_DGELU) != 0) v *= dgelu_f(aux[r]);
-                    Cs[o] = v;
-                }
-            }
-    };
-    if (full) emit(std::false_type{});
-    else emit(std::true_type{});
+    float* Cs = static_cast<float*>(g.C) + (int64_t)pl.split * g.slab_stride;
+    if (pl.full) gemm16_emit<false, EPI>(g, acc, bv, Cs, row0, col0);
+    else gemm16_emit<true, EPI>(g, acc, bv, Cs, row0, col0);
     if constexpr (COLSUM) {
-        if (tn == 0) {
-            float* red = reinterpret_cast<float*>(smem);
-            constexpr int PR = TA::PER_ROW;
-            if ((TA::SLOTS % GEMM_THREADS == 0) || tid < TA::SLOTS) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) red[(tid / PR) * BM + 8 * (tid % PR) + j] = csum[j];
-            }
-            __syncthreads();
-            constexpr int NTL = (TA::SLOTS < GEMM_THREADS ? TA::SLOTS : GEMM_THREADS) / PR;
-            if (tid < BM && m0 + tid < g.M) {
-                float s = 0.f;
-#pragma unroll 4
-                for (int t = 0; t < NTL; ++t) s += red[t * BM + tid];
-                Cs[g.colsum_off + m0 + tid] = s;
-            }
-        }
+        if (tn == 0) gemm16_colsum_store<TA, BM>(g, csum, reinterpret_cast<float*>(smem), Cs, m0, tid);
     }
 }
 

@@ -61,6 +61,13 @@ static inline void gemm_apply_plan(GemmArgs& g, const GemmProblem& p, unsigned l
     g.clock_probe = clock_probe;
 }
 
+// XCD-aware block order: the hardware deals blocks round-robin over 8 XCDs; block bid of nwg gets logical number
+// xcd_swizzle(bid, nwg), so that each XCD (one L2) works on a contiguous run of logical tiles (bijective for any grid size)
+__device__ __forceinline__ int xcd_swizzle(int bid, int nwg) {
+    const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7;
+    return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+}
+
 // Pin the staging interleave of one chunk, placed right behind its N_MFMA MFMAs: one LDS write (then one global load)
 // behind each MFMA, so the matrix pipe keeps issuing while the tile is staged (hipcc left alone emits the writes as one blob).
 template <int N_MFMA, int N_ST, int N_LD>

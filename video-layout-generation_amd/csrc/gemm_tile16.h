@@ -1,4 +1,5 @@
-// bf16 operand tiles in LDS for the bf16-MFMA GEMMs (gemm_bf16.hip, gemm_split.hip): images, staging, fragment reads.
+// bf16 operand tiles in LDS for the bf16-MFMA GEMMs (gemm_bf16.hip, gemm_split.hip): images, staging, fragment reads;
+// below them the block frame those kernels share (placement, start-up, epilogue, bias-gradient reduction).
 //   KC image  [row][k]   rows of BK bf16 + 8 pad: per-lane 16-byte fragment reads (ds_read_b128, lane = row, half-wave h
 //                        picks k = 16s + 8h ..+7) are bank-conflict-free for BK = 64 (36-dword rows) and 16 (12-dword rows)
 //   MC image  [k][row]   the operand is contraction-major in memory: stored as it arrives and read with gfx950's
@@ -108,4 +109,130 @@ struct Tile16 {
         }
     }
 };
+
+// ---- The block frame of the GEMM kernels on these tiles (gemm16_body in gemm_bf16.hip, gemm_split_kernel in gemm_split.hip):
+// everything around the main loop, stated once.  A kernel body places its block, starts its accumulators, runs ITS main loop
+// (how a tile reaches LDS, the k-step and the schedule are what the two files differ in), then emits and, for a weight
+// gradient, reduces the bias-gradient column sums.  (gemm.hip's general path has the same shape; it keeps its own copy
+// because its fast path's register allocation depends on what is defined beside it.)
+
+// 4 waves: 128x128 as 2 x 2 waves of 64x64, 128x32 as 4 x 1, 32x128 as 1 x 4 waves of 32x32; TM x TN MFMA tiles per wave
+template <int BM, int BN>
+struct Waves16 {
+    static constexpr int WM = (BM == 128 && BN == 128) ? 2 : (BM == 128 ? 4 : 1);
+    static constexpr int WN = 4 / WM;
+    static constexpr int TM = BM / (32 * WM), TN = BN / (32 * WN);
+};
+
+// where block bid of nwg works: K split, N tile number, first row / column of its tile, its contraction range
+struct Place16 {
+    int split, tn;
+    int64_t m0;
+    int n0;
+    int64_t kbeg, kend;
+    bool full;               // the tile lies inside C: no row / column guards
+};
+template <int BM, int BN>
+__device__ __forceinline__ Place16 gemm16_place(const GemmArgs& g, int bid, int nwg) {
+    const int swz = xcd_swizzle(bid, nwg);
+    const int ntile = g.tiles_m * g.tiles_n;
+    Place16 p;
+    p.split = swz / ntile;
+    const int tile = swz - p.split * ntile;
+    const int tm = tile / g.tiles_n;
+    p.tn = tile - tm * g.tiles_n;
+    p.m0 = (int64_t)tm * BM;
+    p.n0 = p.tn * BN;
+    p.kbeg = (int64_t)p.split * g.kc_per_split;
+    p.kend = p.kbeg + g.kc_per_split;
+    if (p.kend > g.Kc) p.kend = g.Kc;
+    p.full = (p.m0 + BM <= g.M) && (p.n0 + BN <= g.N);
+    return p;
+}
+
+// zero accumulators; the bias of the lane's column of each of its TN tiles (col0 = the lane's column in the first: clamped, so
+// a lane past N reads something valid that the epilogue never stores)
+template <int EPI, int TM, int TN>
+__device__ __forceinline__ void gemm16_start(f32x16 (&acc)[TM][TN], float (&bv)[TN], const GemmArgs& g, int col0) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        bv[j] = 0.f;
+        if constexpr ((EPI & VLG_EPI_BIAS) != 0) {
+            const int col = col0 + j * 32;
+            bv[j] = g.bias[col < g.N ? col : g.N - 1];
+        }
+    }
+}
+
+// The general epilogue, all five VLG_EPI_* bits (C/D layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*h).
+// (row0, col0) = the lane's first element in C; EO = element type of C and of the auxiliary operands.
+template <bool GUARD, int EPI, typename EO, int TM, int TN>
+__device__ __forceinline__ void gemm16_emit(const GemmArgs& g, const f32x16 (&acc)[TM][TN], const float (&bv)[TN], EO* Cs,
+                                            int64_t row0, int col0) {
+    const EO* const gAuxIn = static_cast<const EO*>(g.aux_in);
+    EO* const gAuxOut = static_cast<EO*>(g.aux_out);
+    const int64_t base = row0 * g.ldc + col0;
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            if (GUARD && col0 + j * 32 >= g.N) continue;
+            float aux[16];
+            if constexpr ((EPI & (VLG_EPI_RESID | VLG_EPI_DGELU | VLG_EPI_MUL)) != 0) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int ro = i * 32 + (r & 3) + 8 * (r >> 2);
+                    aux[r] = (!GUARD || row0 + ro < g.M) ? ld1(gAuxIn + base + ro * g.ldc + j * 32) : 0.f;
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int ro = i * 32 + (r & 3) + 8 * (r >> 2);
+                if (GUARD && row0 + ro >= g.M) continue;
+                const int64_t o = base + ro * g.ldc + j * 32;
+                float v = acc[i][j][r] + bv[j];
+                if constexpr ((EPI & VLG_EPI_GELU) != 0) {
+                    if constexpr ((EPI & VLG_EPI_GELU_GRAD) != 0) {      // aux_out = gelu'(pre) (common.h, gelu_parts): the backward
+                        float c, pd;                                     // pass then multiplies (VLG_EPI_MUL) instead of recomputing
+                        gelu_parts(v, c, pd);
+                        st1(gAuxOut + o, c + v * pd);
+                        v *= c;
+                    } else {
+                        st1(gAuxOut + o, v);
+                        v = gelu_f(v);
+                    }
+                }
+                if constexpr ((EPI & VLG_EPI_RESID) != 0) v += aux[r];
+                if constexpr ((EPI & VLG_EPI_DGELU) != 0) v *= dgelu_f(aux[r]);
+                if constexpr ((EPI & VLG_EPI_MUL) != 0) v *= aux[r];
+                st1(Cs + o, v);
+            }
+        }
+}
+
+// Bias gradient of a weight-gradient block (A = dY, contraction-major): every thread summed the 8 rows 8*(tid % PER_ROW) .. +7
+// of the tiles it staged (csum); combine the threads that share a row group through LDS (red = the tiles, which are dead: the
+// main loop ended on a barrier) and write the BM sums behind the block's slab
+template <typename TA, int BM, typename EO>
+__device__ __forceinline__ void gemm16_colsum_store(const GemmArgs& g, const float (&csum)[8], float* red, EO* Cs, int64_t m0, int tid) {
+    constexpr int PR = TA::PER_ROW;
+    if ((TA::SLOTS % GEMM_THREADS == 0) || tid < TA::SLOTS) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) red[(tid / PR) * BM + 8 * (tid % PR) + j] = csum[j];
+    }
+    __syncthreads();
+    constexpr int NTL = (TA::SLOTS < GEMM_THREADS ? TA::SLOTS : GEMM_THREADS) / PR;     // threads per row group
+    if (tid < BM && m0 + tid < g.M) {
+        float s = 0.f;
+#pragma unroll 4
+        for (int t = 0; t < NTL; ++t) s += red[t * BM + tid];
+        st1(Cs + g.colsum_off + m0 + tid, s);
+    }
+}
 
