@@ -426,6 +426,8 @@ int vlg_attention_frame_step_bf16(const vlg_bf16* qkv, const float* valid, vlg_b
  * Every draw of generation, scheduled sampling, augmentation and the Gaussian box head below is a word of Philox4x32-10 on
  * counter (index, step, stream, 0) under key (seed & 0xffffffff, seed >> 32).  `stream` keeps the draws of one (index, step)
  * apart; this is the one table of them, and a new kind of draw takes a new entry.  The rules below name them by number.
+ * The counter rule, word by word:  word 0: the index (token, track or clip);  word 1: the step;  word 2: the stream;
+ * word 3: the sample index, 0 for every other draw - only vlg_layout_decode_samples / vlg_layout_decode_append_samples set it.
  * The dropout mask above is not in it: its third counter word is its SITE, and its own seed keeps it apart from these. */
 enum vlg_rng_stream {
     VLG_RNG_CLASS_DRAW   = 0,   /* u of a sampled class: vlg_layout_decode*, and a replaced token of vlg_layout_mix_inputs */
@@ -509,6 +511,25 @@ int vlg_layout_decode_append_ext(const float* out_last, int ld, int64_t* cls, fl
                                  int B, int T, int N, int n_classes, int pos, int steps, int step,
                                  float temperature, int top_k, float box_temperature, uint64_t seed, int keep_padded,
                                  void* stream);
+/* K futures per clip in one launch: the two _ext steps above - their argument lists plus `clips` and `sample0` before stream -
+ * on a batch whose B clips are B / clips SAMPLES of `clips` prompts, sample-major: batch clip b is prompt b % clips, sample
+ * k = sample0 + b / clips.  Token (b, n) draws with counter (r0, step, stream, k), r0 = (b % clips)*N + n, for the class draw
+ * (stream 0) and the box normal (stream 5) alike, under the call's key; everything else is the rule above, the same device
+ * function.  So a future is a function of (prompt token, step, sample, seed) alone: sample 0 draws what the _ext entries
+ * draw, a launch of sample k alone (B = clips, sample0 = k) gives slice k of the batched launch bit for bit, and
+ * clips = B, sample0 = 0 IS the _ext call.
+ * Refusals as the _ext entries, plus VLG_ERR_SHAPE for clips < 1, B % clips != 0, sample0 < 0, or sample0 + B / clips not
+ * fitting 31 bits. */
+int vlg_layout_decode_samples(const float* out_last, int ld, const int64_t* cls_in, const float* box_in,
+                              int64_t* cls_out, float* box_out, float* valid_out, int64_t* gen_cls, float* gen_box,
+                              int B, int T, int N, int n_classes, int steps, int step,
+                              float temperature, int top_k, float box_temperature, uint64_t seed, int keep_padded,
+                              int clips, int sample0, void* stream);
+int vlg_layout_decode_append_samples(const float* out_last, int ld, int64_t* cls, float* box, float* valid,
+                                     int64_t* gen_cls, float* gen_box, int64_t* frame_cls, float* frame_box,
+                                     int B, int T, int N, int n_classes, int pos, int steps, int step,
+                                     float temperature, int top_k, float box_temperature, uint64_t seed, int keep_padded,
+                                     int clips, int sample0, void* stream);
 
 /* ------------------------------------------------------------------ scheduled sampling (csrc/decode.hip)
  * SELF-ORACLE (tests/sched_ref.py restates it); DESIGN.md, "Scheduled sampling".  Builds the inputs of a training step's
@@ -640,6 +661,66 @@ int vlg_layout_metrics_scratch(void);           /* 8-byte slots of scratch */
 int vlg_layout_metrics(const float* out, int ld, const int64_t* tgt_class, const float* tgt_box, const float* valid,
                        int tgt_T, int t0, int64_t* counts, double* sums, void* scratch,
                        int B, int T, int N, int n_classes, int top_k, float iou_thr, float iou_eps, void* stream);
+
+/* ------------------------------------------------------------------ sampled futures (csrc/samples.hip)
+ * Score K sampled futures of every clip against the frames that really followed, measure how much the K differ, select the
+ * best one: three launches, no host wait.  SELF-ORACLE (tests/samples_ref.py restates them in fp64); DESIGN.md, "Sampled
+ * futures".
+ *   gen_cls (K,B,S,N) int64, gen_box (K,B,S,N,4) fp32   the samples (what K stacked rollouts return), only read
+ *   clip_class (B,tgt_T,N) int64, clip_box (B,tgt_T,N,4) fp32   the truth, read in place as vlg_layout_metrics reads it:
+ *             generated frame s is scored against frame t0 + s
+ * A token is SCORED when 0 <= clip_class < n_classes.  Per scored token, every operation one fp32 rounding (the file is
+ * compiled with floating-point contraction off):
+ *   iou   IoU of the (cx,cy,w,h) boxes gen_box and clip_box, formula and iou_eps of vlg_layout_loss, min / max = fminf /
+ *         fmaxf (a NaN coordinate is ignored by them, a NaN size makes the IoU NaN); 0 when the generated class is >= n_classes
+ *   disp  sqrtf(dx*dx + dy*dy), (dx, dy) the difference of the two centres
+ *   hit   generated class == truth class
+ * Sums are doubles added in a fixed order - no floating-point atomics, no scratch, the same bits on every call.
+ *
+ * vlg_layout_sample_scores: scores (K,B,VLG_SMP_COLS) fp32, per sample and clip.  IOU, ADE, ACC: the mean of iou, disp, hit
+ * over the clip's scored tokens; FDE: the mean of disp over the scored tokens of frame S-1; N_SCORED, N_SCORED_LAST: the two
+ * token counts, as floats (S*N <= 2^24, else VLG_ERR_SHAPE); two columns of zero.  A mean over no token is 0.
+ * vlg_layout_sample_diversity: div (B,2) fp32, per clip, over all sample pairs j < k and the clip's scored tokens:
+ * [0] the mean of 1 - IoU(gen_box_j, gen_box_k) (the formula above, whatever the classes), [1] the share of terms with
+ * gen_cls_j != gen_cls_k.  Both 0 for K = 1 or a clip with no scored token.
+ * vlg_layout_sample_select: criterion = VLG_SMP_IOU | ADE | FDE | ACC names a score column; IOU and ACC are maximised, ADE
+ * and FDE minimised.  best[b] (int32) = the first sample whose score is not NaN and strictly better than every earlier
+ * one's; 0 if all K are NaN - so of equal samples the lowest index wins.  best_cls (B,S,N) / best_box (B,S,N,4) = that sample
+ * of every clip, bit for bit.  It ADDS to `record` (VLG_SMP_REC_SLOTS doubles; the caller zeroes it to start one), summed
+ * over the COUNTED clips, those with N_SCORED > 0:  REC_BEST + c: column c's own optimum over the K samples, chosen by the
+ * rule above;  REC_MEAN + c: its mean over all K (a NaN score makes it NaN);  REC_SELECTED + c: its value at best[b]
+ * (c = IOU, ADE, FDE, ACC);  REC_DIV_BOX, REC_DIV_CLASS: the clip's div;  REC_CLIPS: 1.  The three FDE terms are added only
+ * for a clip with N_SCORED_LAST > 0, counted in REC_CLIPS_FDE.
+ * Cost: all three are launch-bound at every shape the project uses (DESIGN.md gives the bytes): one block per (sample, clip),
+ * one per clip, one block in all.
+ * Refusals, before anything is enqueued.  VLG_ERR_SHAPE: K, B, S or N < 1; S*N > 2^24; K*B >= 2^31; t0 < 0 or t0 + S > tgt_T;
+ * n_classes outside [1, 28]; a criterion that is none of the four; an output overlapping an input or another output.
+ * VLG_ERR_ALIGN: a NULL pointer; a box pointer or scores not 16-byte, a class pointer, div or record not 8-byte, best not
+ * 4-byte aligned. */
+#define VLG_SMP_COLS          8   /* floats per (sample, clip) row of scores                              */
+#define VLG_SMP_IOU           0
+#define VLG_SMP_ADE           1
+#define VLG_SMP_FDE           2
+#define VLG_SMP_ACC           3
+#define VLG_SMP_N_SCORED      4
+#define VLG_SMP_N_SCORED_LAST 5
+#define VLG_SMP_REC_BEST      0   /* record[VLG_SMP_REC_BEST + column], column = IOU, ADE, FDE, ACC        */
+#define VLG_SMP_REC_MEAN      4
+#define VLG_SMP_REC_SELECTED  8
+#define VLG_SMP_REC_DIV_BOX   12
+#define VLG_SMP_REC_DIV_CLASS 13
+#define VLG_SMP_REC_CLIPS     14
+#define VLG_SMP_REC_CLIPS_FDE 15
+#define VLG_SMP_REC_SLOTS     16
+int vlg_layout_sample_record_slots(void);       /* double slots of a record: VLG_SMP_REC_SLOTS */
+int vlg_layout_sample_scores(const int64_t* gen_cls, const float* gen_box, const int64_t* clip_class, const float* clip_box,
+                             float* scores, int K, int B, int S, int N, int tgt_T, int t0, int n_classes, float iou_eps,
+                             void* stream);
+int vlg_layout_sample_diversity(const int64_t* gen_cls, const float* gen_box, const int64_t* clip_class, float* div,
+                                int K, int B, int S, int N, int tgt_T, int t0, int n_classes, float iou_eps, void* stream);
+int vlg_layout_sample_select(const float* scores, const float* div, const int64_t* gen_cls, const float* gen_box,
+                             int* best, int64_t* best_cls, float* best_box, double* record,
+                             int K, int B, int S, int N, int criterion, void* stream);
 
 /* ------------------------------------------------------------------ rasterised layouts (csrc/raster.hip)
  * Draws layouts - the slots of a frame as (class, cx, cy, w, h) - into label maps, and counts a confusion matrix of two

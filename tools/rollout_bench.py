@@ -4,7 +4,10 @@ launches + vlg_head_last_frame + vlg_layout_decode, no host wait inside the loop
 (restated here from forward() + outputs_btn(): training forward with the loss on dummy targets, argmax / sigmoid / cat in
 torch, two copies to the CPU per frame), alternately in one process on the same prompt, fp32 and bf16.
     python tools/rollout_bench.py [B] [T] [N] [d] [--layers L] [--steps S] [--attention slot|clip|factored] [--prompt P] [--no-cache]
-                                  [--clip-cache]
+                                  [--clip-cache] [--samples K]
+--samples K measures K sampled futures of each of the B prompts (DESIGN.md "Sampled futures"): one rollout_samples(samples=K)
+call against K rollout() calls with K seeds, ms per call, alternately on one engine that holds the K*B clips (--prompt P,
+default T; --steps frames, default 8).
 --prompt P (1 <= P < T) measures the short-prompt rollout instead: the prompt pass on its own (steps = 1), and --steps
 frames (default T - P: the history grows to the window) with the cached grow step and with the re-encoding one
 (cache=False), alternately; ms per grown frame = (the call - the prompt pass) / (frames - 1).  --no-cache leaves the
@@ -107,7 +110,49 @@ def prompt_bench(cfg, dev, cls, box, P, frames, with_cache, clip_cache=False):
                 head, float((res["cached"][1][:, 0] - res["re-encode"][1][:, 0]).abs().max()), 100 * same, frames))
 
 
-skip = {i + 1 for i, x in enumerate(sys.argv) if x in ("--layers", "--steps", "--attention", "--prompt")}
+def samples_bench(cfg, dev, cls, box, P, steps, K):
+    """K futures of each of the B prompts: one rollout_samples(samples=K) call against K rollout() calls with K seeds (the
+    launches rollout() always made), alternately, 9 rounds, in one process on one engine whose workspace holds all K*B clips"""
+    cls, box = cls[:, :P].contiguous(), box[:, :P].contiguous()
+    gen = dict(steps=steps, temperature=0.8, top_k=5)
+
+    def batched(eng):
+        c, b = eng.rollout_samples(cls, box, samples=K, seed=7, **gen)
+        return c.cpu(), b.cpu()
+
+    def sequential(eng):
+        out = [eng.rollout(cls, box, seed=7 + k, **gen) for k in range(K)]
+        return torch.stack([c for c, _ in out]).cpu(), torch.stack([b for _, b in out]).cpu()
+
+    paths = {"rollout_samples(K)": batched, "K x rollout()": sequential}
+    big = LayoutConfig(B=K * cfg.B, T=cfg.T, N=cfg.N, d=cfg.d, n_layers=cfg.n_layers, attention=cfg.attention)
+    for precision in ("fp32", "bf16"):
+        eng = LayoutEngine(big, dev, precision=precision, padded_slots=False)
+        res = {k: fn(eng) for k, fn in paths.items()}                        # warm-up
+        same = float((res["rollout_samples(K)"][0][0] == res["K x rollout()"][0][0]).float().mean())
+        print("%-4s sample 0 against rollout(seed): %.2f %% of class ids equal (the same draws; the batch of K*B clips may take "
+              "other GEMM plans than the batch of B, and one near-tie changes every later frame of its clip)" % (precision, 100 * same))
+        count = {k: sum(launches(eng, fn).values()) for k, fn in paths.items()}
+        ts = {k: [] for k in paths}
+        for _ in range(9):
+            for k, fn in paths.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(4):
+                    fn(eng)
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) * 1e3 / 4)
+        for k in paths:
+            t = sorted(ts[k])
+            print("%-4s (B,T,N,d)=(%d,%d,%d,%d) %d layers %s prompt %d, %d frames, K=%d  %-18s: %.3f ms per call (median of 9; min %.3f "
+                  "max %.3f)  %d launches" % (precision, cfg.B, cfg.T, cfg.N, cfg.d, cfg.n_layers, cfg.attention, P, steps, K, k, t[4],
+                                              t[0], t[-1], count[k]))
+        ratio = sorted(a / b for a, b in zip(ts["rollout_samples(K)"], ts["K x rollout()"]))
+        print("%-4s K=%d: rollout_samples / (K x rollout) = %.3f (median of the 9 round-by-round ratios; min %.3f max %.3f)" % (
+            precision, K, ratio[4], ratio[0], ratio[-1]))
+
+
+skip = {i + 1 for i, x in enumerate(sys.argv) if x in ("--layers", "--steps", "--attention", "--prompt", "--samples")}
 a = [x for i, x in enumerate(sys.argv[1:], 1) if not x.startswith("--") and i not in skip]
 B, T, N, d = (int(a[i]) if len(a) > i else v for i, v in enumerate((32, 16, 64, 256)))
 steps = int(opt("--steps", 8))
@@ -115,6 +160,12 @@ cfg = LayoutConfig(B=B, T=T, N=N, d=d, n_layers=int(opt("--layers", 4)), attenti
 dev = torch.device("cuda:0")
 batch = to_device(synthetic_clips(B, T, N, seed=3), dev)
 cls, box = batch["slot_class"], batch["slot_box"]
+if "--samples" in sys.argv:
+    P = int(opt("--prompt", T))
+    if not 1 <= P <= T:
+        sys.exit("--prompt takes 1 <= P <= T")
+    samples_bench(cfg, dev, cls, box, P, steps, int(opt("--samples", 8)))
+    sys.exit(0)
 if "--prompt" in sys.argv:
     P = int(opt("--prompt", 2))
     if not 1 <= P < T:

@@ -17,6 +17,9 @@
 //     box_temperature > 0, a box DRAWN from the Gaussian box head's N(mu, (tau sigma)^2) (Box-Muller on the four words of
 //     one more Philox call, stream VLG_RNG_BOX_NORMAL): a compile-time parameter of the same kernels and of decode_token, so
 //     the instantiation behind the plain entries keeps the rule it always had.
+// vlg_layout_decode_samples / vlg_layout_decode_append_samples  the two _ext steps on a batch that holds B / clips SAMPLES of
+//     `clips` prompts, sample-major: token (b, n) draws with counter (r0, step, stream, k), r0 = (b % clips)*N + n, k = sample0 +
+//     b / clips - one more compile-time parameter of the same kernels (SMP), so every other instantiation keeps its instructions.
 // vlg_layout_mix_inputs  scheduled sampling: the inputs of a training step's second pass, per token the truth or the
 //     model's own prediction decoded by the same decode_token from the first pass's outputs (end of this file).
 // Draws: philox.h (the generator, the word conversions, the seed's key); streams: vlg_rng_stream, include/vlg_hip.h.
@@ -135,11 +138,11 @@ extern "C" int vlg_head_last_frame(const float* x, const float* gamma, const flo
 // become the running sums); prev / prev_box: the token's class and box in the newest frame of the history.
 // BOX (the Gaussian box head, vlg_layout_decode_ext with box_temperature = tau > 0): l holds [logits | raw mean | raw scale]
 // and the box is drawn, box_k = clamp(mu_k + tau sigma_k z_k, 0, 1), z = Box-Muller on the four words of counter
-// (r, step, VLG_RNG_BOX_NORMAL, 0); the class draw is untouched.  BOX = false is the rule as it always was, instruction for
-// instruction.
+// (r, step, VLG_RNG_BOX_NORMAL, smp); the class draw is untouched.  BOX = false is the rule as it always was, instruction for
+// instruction.  smp: the fourth counter word of both draws - the sample index of the _samples entries, 0 from everyone else.
 template <bool BOX>
 __device__ __forceinline__ void decode_token(float* l, int C, int64_t prev, const float* __restrict__ prev_box, int64_t r, int step,
-                                             float temperature, int top_k, uint32_t k0, uint32_t k1, int keep_padded,
+                                             uint32_t smp, float temperature, int top_k, uint32_t k0, uint32_t k1, int keep_padded,
                                              int64_t& cls, float4& box, float box_tau = 0.f) {
     if (keep_padded && prev >= C) {                        // a padded slot stays padded, box and all
         cls = prev;
@@ -149,7 +152,7 @@ __device__ __forceinline__ void decode_token(float* l, int C, int64_t prev, cons
                           1.0f / (1.0f + expf(-l[C + 2])), 1.0f / (1.0f + expf(-l[C + 3])));
         if constexpr (BOX) {
             uint32_t x[4];
-            philox4x32_10((uint32_t)r, (uint32_t)step, VLG_RNG_BOX_NORMAL, 0u, k0, k1, x);
+            philox4x32_10((uint32_t)r, (uint32_t)step, VLG_RNG_BOX_NORMAL, smp, k0, k1, x);
             const float rad0 = sqrtf(-2.0f * logf(philox_unit(x[0]))), ang0 = 6.28318530717958648f * philox_unit(x[1]);
             const float rad1 = sqrtf(-2.0f * logf(philox_unit(x[2]))), ang1 = 6.28318530717958648f * philox_unit(x[3]);
             const float z[4] = {rad0 * cosf(ang0), rad0 * sinf(ang0), rad1 * cosf(ang1), rad1 * sinf(ang1)};
@@ -187,7 +190,7 @@ __device__ __forceinline__ void decode_token(float* l, int C, int64_t prev, cons
                 if ((kept >> c) & 1u) cum += expf(l[c] / temperature - m);
                 l[c] = cum;
             }
-            const uint32_t x0 = philox_word0((uint32_t)r, (uint32_t)step, VLG_RNG_CLASS_DRAW, k0, k1);
+            const uint32_t x0 = philox_word0((uint32_t)r, (uint32_t)step, VLG_RNG_CLASS_DRAW, smp, k0, k1);
             const float u = philox_unit(x0);
             const float thr = u * cum;                     // cum = S
             pick = -1;
@@ -213,12 +216,25 @@ __device__ __forceinline__ int decode_stage(float (*rows)[DEC_LD], const float* 
     return here;
 }
 
-template <bool BOX>
+// SMP (the _samples entries): the counter's index is the token of the PROMPT, r % (clips*N), and its fourth word the sample
+template <bool SMP>
+__device__ __forceinline__ void decode_counter(int64_t r, int64_t clips_n, int sample0, int64_t& r0, uint32_t& smp) {
+    if constexpr (SMP) {
+        const int64_t k = r / clips_n;
+        r0 = r - k * clips_n;
+        smp = (uint32_t)(sample0 + (int)k);
+    } else {
+        r0 = r;
+        smp = 0u;
+    }
+}
+
+template <bool BOX, bool SMP>
 __global__ __launch_bounds__(DEC_BLOCK) void layout_decode_kernel(
     const float* __restrict__ out_last, int ld, const int64_t* __restrict__ cls_in, const float* __restrict__ box_in,
     int64_t* __restrict__ cls_out, float* __restrict__ box_out, float* __restrict__ valid_out,
     int64_t* __restrict__ gen_cls, float* __restrict__ gen_box, int B, int T, int N, int C, int steps, int step,
-    float temperature, int top_k, uint32_t k0, uint32_t k1, int keep_padded, float box_tau) {
+    float temperature, int top_k, uint32_t k0, uint32_t k1, int keep_padded, float box_tau, int64_t clips_n, int sample0) {
     __shared__ float rows[DEC_BLOCK][DEC_LD];
     const int tid = threadIdx.x;
     const int64_t BN = (int64_t)B * N, r_first = (int64_t)blockIdx.x * DEC_BLOCK;
@@ -227,10 +243,12 @@ __global__ __launch_bounds__(DEC_BLOCK) void layout_decode_kernel(
         const int64_t r = r_first + tid;
         const int b = (int)(r / N), n = (int)(r % N);
         const int64_t last = ((int64_t)b * T + (T - 1)) * N + n;
-        int64_t cls;
+        int64_t cls, r0;
+        uint32_t smp;
         float4 box;
-        decode_token<BOX>(rows[tid], C, cls_in[last], box_in + 4 * last, r, step, temperature, top_k, k0, k1, keep_padded, cls, box,
-                          box_tau);
+        decode_counter<SMP>(r, clips_n, sample0, r0, smp);
+        decode_token<BOX>(rows[tid], C, cls_in[last], box_in + 4 * last, r0, step, smp, temperature, top_k, k0, k1, keep_padded, cls,
+                          box, box_tau);
         const int64_t g = ((int64_t)b * steps + step) * N + n;
         gen_cls[g] = cls;
         st4(gen_box + 4 * g, box);
@@ -261,14 +279,18 @@ static inline int dec_box_columns(int n_classes, int ld, float box_temperature, 
 
 // The refusals the four decoding entries share - shape limits, temperature, top_k, steps / step, the box columns, the counter
 // range - and, for a call that passes them, what its launch needs: the grid, the seed's key, the columns of a row it reads.
+// a batch of samples (the _samples entries): B / clips samples of `clips` prompts, the first of them sample `sample0`; the other
+// entries pass none (clips = 0)
+struct DecSamples { int clips, sample0; };
 struct DecCall {
     int64_t BN;                 // tokens of a frame
+    int64_t clips_n;            // tokens of a frame of the prompts: what the counter's index runs over
     int cols;
     dim3 grid;
     PhiloxKey key;
 };
 static int decode_checks(bool ext, int ld, int B, int T, int N, int n_classes, int steps, int step, float temperature, int top_k,
-                         float box_temperature, uint64_t seed, DecCall& c) {
+                         float box_temperature, uint64_t seed, const DecSamples* smp, DecCall& c) {
     if (B < 1 || T < 1 || N < 1 || n_classes < 1 || n_classes + 4 > HL_MAX_OUT) return VLG_ERR_SHAPE;
     if (!(temperature >= 0.f) || !(temperature <= 3.0e38f)) return VLG_ERR_SHAPE;      // negative, inf or NaN
     if (top_k < 0 || top_k > n_classes || steps < 1 || step < 0 || step >= steps) return VLG_ERR_SHAPE;
@@ -276,24 +298,36 @@ static int decode_checks(bool ext, int ld, int B, int T, int N, int n_classes, i
     if (c.cols == 0) return VLG_ERR_SHAPE;
     c.BN = (int64_t)B * N;
     if (!philox_index_fits(c.BN)) return VLG_ERR_SHAPE;                                 // the Philox counter word is the token index
+    c.clips_n = c.BN;
+    if (smp != nullptr) {                                                               // ... and with samples the last word is the sample
+        if (smp->clips < 1 || B % smp->clips != 0 || smp->sample0 < 0) return VLG_ERR_SHAPE;
+        if (!philox_index_fits((int64_t)smp->sample0 + B / smp->clips)) return VLG_ERR_SHAPE;
+        c.clips_n = (int64_t)smp->clips * N;
+    }
     c.grid = dim3((unsigned)((c.BN + DEC_BLOCK - 1) / DEC_BLOCK));
     c.key = philox_key(seed);
     return 0;
 }
-// box sampling is a compile-time parameter of both kernels: the one place where the temperature picks the instantiation
+// box sampling and the sample counter are compile-time parameters of both kernels: the one place where the temperature and
+// the entry pick the instantiation
 template <typename Launch>
-static int decode_launch(float box_temperature, Launch launch) {
-    if (box_temperature > 0.f) launch(std::true_type());
-    else launch(std::false_type());
+static int decode_launch(float box_temperature, const DecSamples* smp, Launch launch) {
+    if (smp != nullptr) {
+        if (box_temperature > 0.f) launch(std::true_type(), std::true_type());
+        else launch(std::false_type(), std::true_type());
+    } else {
+        if (box_temperature > 0.f) launch(std::true_type(), std::false_type());
+        else launch(std::false_type(), std::false_type());
+    }
     return vlg_last_error();
 }
 
 static int decode_front(bool ext, const float* out_last, int ld, const int64_t* cls_in, const float* box_in, int64_t* cls_out,
                         float* box_out, float* valid_out, int64_t* gen_cls, float* gen_box, int B, int T, int N,
                         int n_classes, int steps, int step, float temperature, int top_k, float box_temperature,
-                        uint64_t seed, int keep_padded, void* stream) {
+                        uint64_t seed, int keep_padded, void* stream, const DecSamples* smp = nullptr) {
     DecCall c;
-    const int err = decode_checks(ext, ld, B, T, N, n_classes, steps, step, temperature, top_k, box_temperature, seed, c);
+    const int err = decode_checks(ext, ld, B, T, N, n_classes, steps, step, temperature, top_k, box_temperature, seed, smp, c);
     if (err != 0) return err;
     const int64_t BN = c.BN, M = BN * T;
     if (!out_last || !cls_in || !box_in || !cls_out || !box_out || !gen_cls || !gen_box) return VLG_ERR_SHAPE;
@@ -307,10 +341,12 @@ static int decode_front(bool ext, const float* out_last, int ld, const int64_t* 
             if (vlg_overlap(in_p[i], in_n[i], out_p[j], out_n[j])) return VLG_ERR_SHAPE;
     if (!vlg_aligned16(out_last) || !vlg_aligned16(box_in) || !vlg_aligned16(box_out) || !vlg_aligned16(gen_box) ||
         !vlg_aligned8(cls_in) || !vlg_aligned8(cls_out) || !vlg_aligned8(gen_cls) || !vlg_aligned4(valid_out)) return VLG_ERR_ALIGN;
-    return decode_launch(box_temperature, [&](auto box) {
-        hipLaunchKernelGGL(layout_decode_kernel<decltype(box)::value>, c.grid, dim3(DEC_BLOCK), 0, (hipStream_t)stream, out_last, ld,
-                           cls_in, box_in, cls_out, box_out, valid_out, gen_cls, gen_box, B, T, N, n_classes, steps, step,
-                           temperature, top_k, c.key.k0, c.key.k1, keep_padded, box_temperature);
+    const int sample0 = smp != nullptr ? smp->sample0 : 0;
+    return decode_launch(box_temperature, smp, [&](auto box, auto samples) {
+        hipLaunchKernelGGL((layout_decode_kernel<decltype(box)::value, decltype(samples)::value>), c.grid, dim3(DEC_BLOCK), 0,
+                           (hipStream_t)stream, out_last, ld, cls_in, box_in, cls_out, box_out, valid_out, gen_cls, gen_box, B, T, N,
+                           n_classes, steps, step, temperature, top_k, c.key.k0, c.key.k1, keep_padded, box_temperature, c.clips_n,
+                           sample0);
     });
 }
 
@@ -320,6 +356,16 @@ extern "C" int vlg_layout_decode_ext(const float* out_last, int ld, const int64_
                                      uint64_t seed, int keep_padded, void* stream) {
     return decode_front(true, out_last, ld, cls_in, box_in, cls_out, box_out, valid_out, gen_cls, gen_box, B, T, N, n_classes, steps,
                         step, temperature, top_k, box_temperature, seed, keep_padded, stream);
+}
+
+// the same front end on a batch of samples: the counter's index is the prompt's token, its last word the sample
+extern "C" int vlg_layout_decode_samples(const float* out_last, int ld, const int64_t* cls_in, const float* box_in, int64_t* cls_out,
+                                         float* box_out, float* valid_out, int64_t* gen_cls, float* gen_box, int B, int T, int N,
+                                         int n_classes, int steps, int step, float temperature, int top_k, float box_temperature,
+                                         uint64_t seed, int keep_padded, int clips, int sample0, void* stream) {
+    const DecSamples smp{clips, sample0};
+    return decode_front(true, out_last, ld, cls_in, box_in, cls_out, box_out, valid_out, gen_cls, gen_box, B, T, N, n_classes, steps,
+                        step, temperature, top_k, box_temperature, seed, keep_padded, stream, &smp);
 }
 
 // the ld = n_classes + 4, box_temperature = 0 call of the same front end
@@ -335,12 +381,12 @@ extern "C" int vlg_layout_decode(const float* out_last, const int64_t* cls_in, c
 // The same step while the history is shorter than the window: nothing slides.  Thread i decodes token i from the newest
 // frame pos - 1 and writes frame pos of the window in place, the generated frame and a compact copy of it (the next
 // step's embedding input).  64 B per token out; no other element of any buffer is touched.
-template <bool BOX>
+template <bool BOX, bool SMP>
 __global__ __launch_bounds__(DEC_BLOCK) void layout_decode_append_kernel(
     const float* __restrict__ out_last, int ld, int64_t* __restrict__ cls, float* __restrict__ box, float* __restrict__ valid,
     int64_t* __restrict__ gen_cls, float* __restrict__ gen_box, int64_t* __restrict__ frame_cls, float* __restrict__ frame_box,
     int B, int T, int N, int C, int pos, int steps, int step, float temperature, int top_k, uint32_t k0, uint32_t k1,
-    int keep_padded, float box_tau) {
+    int keep_padded, float box_tau, int64_t clips_n, int sample0) {
     __shared__ float rows[DEC_BLOCK][DEC_LD];
     const int tid = threadIdx.x;
     const int64_t BN = (int64_t)B * N, r_first = (int64_t)blockIdx.x * DEC_BLOCK;
@@ -349,9 +395,12 @@ __global__ __launch_bounds__(DEC_BLOCK) void layout_decode_append_kernel(
     const int64_t r = r_first + tid;
     const int b = (int)(r / N), n = (int)(r % N);
     const int64_t newest = ((int64_t)b * T + (pos - 1)) * N + n, at = newest + N;
-    int64_t c;
+    int64_t c, r0;
+    uint32_t smp;
     float4 bx;
-    decode_token<BOX>(rows[tid], C, cls[newest], box + 4 * newest, r, step, temperature, top_k, k0, k1, keep_padded, c, bx, box_tau);
+    decode_counter<SMP>(r, clips_n, sample0, r0, smp);
+    decode_token<BOX>(rows[tid], C, cls[newest], box + 4 * newest, r0, step, smp, temperature, top_k, k0, k1, keep_padded, c, bx,
+                      box_tau);
     const int64_t g = ((int64_t)b * steps + step) * N + n;
     gen_cls[g] = c;
     st4(gen_box + 4 * g, bx);
@@ -365,9 +414,9 @@ __global__ __launch_bounds__(DEC_BLOCK) void layout_decode_append_kernel(
 static int decode_append_front(bool ext, const float* out_last, int ld, int64_t* cls, float* box, float* valid, int64_t* gen_cls,
                                float* gen_box, int64_t* frame_cls, float* frame_box, int B, int T, int N,
                                int n_classes, int pos, int steps, int step, float temperature, int top_k, float box_temperature,
-                               uint64_t seed, int keep_padded, void* stream) {
+                               uint64_t seed, int keep_padded, void* stream, const DecSamples* smp = nullptr) {
     DecCall c;
-    const int err = decode_checks(ext, ld, B, T, N, n_classes, steps, step, temperature, top_k, box_temperature, seed, c);
+    const int err = decode_checks(ext, ld, B, T, N, n_classes, steps, step, temperature, top_k, box_temperature, seed, smp, c);
     if (err != 0) return err;
     if (pos < 1 || pos >= T) return VLG_ERR_SHAPE;
     const int64_t BN = c.BN, M = BN * T;
@@ -380,10 +429,12 @@ static int decode_append_front(bool ext, const float* out_last, int ld, int64_t*
             if (vlg_overlap(p[i], n[i], p[j], n[j])) return VLG_ERR_SHAPE;
     if (!vlg_aligned16(out_last) || !vlg_aligned16(box) || !vlg_aligned16(gen_box) || !vlg_aligned16(frame_box) ||
         !vlg_aligned8(cls) || !vlg_aligned8(gen_cls) || !vlg_aligned8(frame_cls) || !vlg_aligned4(valid)) return VLG_ERR_ALIGN;
-    return decode_launch(box_temperature, [&](auto box_sampled) {
-        hipLaunchKernelGGL(layout_decode_append_kernel<decltype(box_sampled)::value>, c.grid, dim3(DEC_BLOCK), 0, (hipStream_t)stream,
-                           out_last, ld, cls, box, valid, gen_cls, gen_box, frame_cls, frame_box, B, T, N, n_classes, pos, steps, step,
-                           temperature, top_k, c.key.k0, c.key.k1, keep_padded, box_temperature);
+    const int sample0 = smp != nullptr ? smp->sample0 : 0;
+    return decode_launch(box_temperature, smp, [&](auto box_sampled, auto samples) {
+        hipLaunchKernelGGL((layout_decode_append_kernel<decltype(box_sampled)::value, decltype(samples)::value>), c.grid,
+                           dim3(DEC_BLOCK), 0, (hipStream_t)stream, out_last, ld, cls, box, valid, gen_cls, gen_box, frame_cls, frame_box,
+                           B, T, N, n_classes, pos, steps, step, temperature, top_k, c.key.k0, c.key.k1, keep_padded, box_temperature,
+                           c.clips_n, sample0);
     });
 }
 
@@ -393,6 +444,16 @@ extern "C" int vlg_layout_decode_append_ext(const float* out_last, int ld, int64
                                             float box_temperature, uint64_t seed, int keep_padded, void* stream) {
     return decode_append_front(true, out_last, ld, cls, box, valid, gen_cls, gen_box, frame_cls, frame_box, B, T, N, n_classes, pos,
                                steps, step, temperature, top_k, box_temperature, seed, keep_padded, stream);
+}
+
+extern "C" int vlg_layout_decode_append_samples(const float* out_last, int ld, int64_t* cls, float* box, float* valid,
+                                                int64_t* gen_cls, float* gen_box, int64_t* frame_cls, float* frame_box, int B, int T,
+                                                int N, int n_classes, int pos, int steps, int step, float temperature, int top_k,
+                                                float box_temperature, uint64_t seed, int keep_padded, int clips, int sample0,
+                                                void* stream) {
+    const DecSamples smp{clips, sample0};
+    return decode_append_front(true, out_last, ld, cls, box, valid, gen_cls, gen_box, frame_cls, frame_box, B, T, N, n_classes, pos,
+                               steps, step, temperature, top_k, box_temperature, seed, keep_padded, stream, &smp);
 }
 
 // the ld = n_classes + 4, box_temperature = 0 call of the same front end
@@ -437,8 +498,8 @@ __global__ __launch_bounds__(DEC_BLOCK) void layout_mix_inputs_kernel(
         const int64_t kk = (int64_t)k + 1;
         const uint32_t thr = ramp_steps == 0 ? thr_max
                                              : (uint32_t)((uint64_t)thr_max * (uint64_t)(kk < ramp_steps ? kk : ramp_steps) / (uint64_t)ramp_steps);
-        if (philox_coin(philox_word0((uint32_t)i, (uint32_t)k, VLG_RNG_SCHED_COIN, k0, k1), thr))
-            decode_token<false>(rows[tid], C, c, box + 4 * i, i, k, temperature, top_k, k0, k1, 0, c, bx);
+        if (philox_coin(philox_word0((uint32_t)i, (uint32_t)k, VLG_RNG_SCHED_COIN, 0u, k0, k1), thr))
+            decode_token<false>(rows[tid], C, c, box + 4 * i, i, k, 0u, temperature, top_k, k0, k1, 0, c, bx);
     }
     mix_cls[i] = c;
     st4(mix_box + 4 * i, bx);

@@ -1,7 +1,8 @@
 // The device's random numbers, stated once ("Random draws"): Philox4x32-10 (Salmon et al., Random123) as a
 // stateless function of a 4-word counter and a 2-word key, the three ways a kernel turns an output word into a number, and
-// the host rules that go with them.  A counter is (index, step, stream, 0) under the key of the call's 64-bit seed; `stream`
-// is an entry of vlg_rng_stream (include/vlg_hip.h), the one table of them.  The dropout mask (layernorm_rows.h) is the
+// the host rules that go with them.  A counter is (index, step, stream, sample) under the key of the call's 64-bit seed; `stream`
+// is an entry of vlg_rng_stream (include/vlg_hip.h), the one table of them; `sample` is the sample index of the K-sample decoding
+// entries (vlg_layout_decode_samples) and 0 for every other draw.  The dropout mask (layernorm_rows.h) is the
 // exception: its counter is (row, float4 index, site, step), under a seed of its own.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -20,10 +21,10 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
 }
 
-// word 0 of counter (c0, c1, stream, 0): the same call - the compiler drops what only the other three words need
-__device__ __forceinline__ uint32_t philox_word0(uint32_t c0, uint32_t c1, uint32_t stream, uint32_t k0, uint32_t k1) {
+// word 0 of counter (c0, c1, stream, c3): the same call - the compiler drops what only the other three words need
+__device__ __forceinline__ uint32_t philox_word0(uint32_t c0, uint32_t c1, uint32_t stream, uint32_t c3, uint32_t k0, uint32_t k1) {
     uint32_t x[4];
-    philox4x32_10(c0, c1, stream, 0u, k0, k1, x);
+    philox4x32_10(c0, c1, stream, c3, k0, k1, x);
     return x[0];
 }
 

@@ -74,6 +74,11 @@ args.gen_top_k / VLG_GEN_TOP_K (0 = every class, else only the k largest logits)
 args.seed; the same seed, prompt and weights give the same sequence), args.gen_keep_padded / VLG_GEN_KEEP_PADDED = 1 keeps a
 slot that is padded (reserved class id) in the window's last frame padded in every generated frame.
 args.gen_clip_cache / VLG_GEN_CLIP_CACHE = 1 (off by default) is the engine knob LayoutEngine(clip_cache=True).
+Sampled futures (csrc/samples.hip, vlg/samples.py, DESIGN.md "Sampled futures"; sample_knobs): args.gen_samples /
+VLG_GEN_SAMPLES = K (default 1 = off) is the number of futures generate_samples draws per prompt in one rollout and
+evaluate_samples scores (best-of-K IoU / minADE / minFDE / accuracy, the samples' mean and diversity); args.gen_select /
+VLG_GEN_SELECT = iou (default) | ade | fde | acc is the score evaluate_samples selects the best sample by.  generate_sequence
+and evaluate_rollout do not read them.
 args.attention / VLG_ATTENTION = slot (default) | clip | factored picks the encoder's attention: the kinds of attention, the
 layers each mode gives them to and which modes cache grown frames by default are stated in vlg/attention.py.
 
@@ -113,6 +118,7 @@ from vlg.data import BATCH_KEYS, BucketedClipLoader, ClipLoader, synthetic_clips
 from vlg.dp import GradReducer, bucket_ranges
 from vlg.optim import decayed_lr
 from vlg.raster import parse_size, raster_options
+from vlg.samples import samples_options, select_option
 from vlg.spec import (ADAM_BETA1, ADAM_LR, N_CLASSES, SEED, LayoutConfig, augment_options, dropout_options, loss_options,
                       recipe_options, sched_options, box_options, box_temperature_options)
 
@@ -313,6 +319,15 @@ def generation_knobs(args) -> Dict[str, object]:
     if tau is not None:
         knobs["box_temperature"] = box_temperature_options(tau, box_knobs(args).get("box_head", "point"), "VLG_GEN_BOX_TEMPERATURE")
     return knobs
+
+
+def sample_knobs(args) -> Dict[str, object]:
+    """{samples, select} of generate_samples / evaluate_samples in layout mode, from args.gen_samples / VLG_GEN_SAMPLES (1 = off:
+    one future per prompt) and args.gen_select / VLG_GEN_SELECT (iou | ade | fde | acc; default iou).  Refuses what
+    vlg.samples refuses.  generate_sequence and evaluate_rollout never read them."""
+    select = getattr(args, "gen_select", None) or os.environ.get("VLG_GEN_SELECT") or "iou"
+    return {"samples": samples_options(_knob(args, "gen_samples", "VLG_GEN_SAMPLES", 1), name="VLG_GEN_SAMPLES")[0],
+            "select": select_option(select)}
 
 
 def clip_cache_knob(args) -> Dict[str, object]:
@@ -918,6 +933,51 @@ class Trainer:
                 s.update(pixel_miou=p["miou"], pixel_accuracy=p["pixel_accuracy"], pixel_per_class_iou=p["per_class_iou"],
                          pixel_background_iou=p["background_iou"])
         return out
+
+    def _sampling_knobs(self, what: str, temperature, top_k, seed, keep_padded, samples) -> tuple:
+        """(generation knobs with the given overrides, samples) for the two *_samples methods"""
+        if self.image_mode or not hasattr(self.engine, "rollout_samples"):
+            raise ValueError("%s needs the layout engine with rollout_samples() (vlg.engine.LayoutEngine: the "
+                             "vlg_layout_decode_samples kernels); %s has none" % (what, type(self.engine).__name__))
+        knobs = generation_knobs(self.args)
+        for name, given in (("temperature", temperature), ("top_k", top_k), ("seed", seed), ("keep_padded", keep_padded)):
+            if given is not None:
+                knobs[name] = type(knobs[name])(given)
+        return knobs, sample_knobs(self.args)["samples"] if samples is None else samples_options(samples)[0]
+
+    def generate_samples(self, slot_class, slot_box, steps: int = 8, samples: Optional[int] = None,
+                         temperature: Optional[float] = None, top_k: Optional[int] = None, seed: Optional[int] = None,
+                         keep_padded: Optional[bool] = None):
+        """Layout mode: K = `samples` futures of every prompt from one seed in one device rollout
+        (vlg.engine.LayoutEngine.rollout_samples): slot_class (B,P,N) / slot_box (B,P,N,4) as generate_sequence takes them;
+        returns classes (K,B,steps,N) and boxes (K,B,steps,N,4) on the CPU.  samples: None takes args.gen_samples /
+        VLG_GEN_SAMPLES (sample_knobs; 1 gives generate_sequence's own sequence with a leading axis of 1); the other
+        arguments and knobs are generate_sequence's, the averaged weights are used where it uses them."""
+        knobs, K = self._sampling_knobs("generate_samples", temperature, top_k, seed, keep_padded, samples)
+        with self._eval_weights():
+            gen_c, gen_b = self.engine.rollout_samples(slot_class.to(self.device).contiguous(), slot_box.to(self.device).contiguous(),
+                                                       steps=steps, samples=K, **knobs)
+        return gen_c.cpu(), gen_b.cpu()
+
+    def evaluate_samples(self, clip_class, clip_box, samples: Optional[int] = None, select: Optional[str] = None,
+                         temperature: Optional[float] = None, top_k: Optional[int] = None, seed: Optional[int] = None,
+                         keep_padded: Optional[bool] = None, prompt_frames: Optional[int] = None):
+        """Layout mode: how good the model's DISTRIBUTION over futures is.  clip_class (B,P+S,N) / clip_box (B,P+S,N,4) as
+        evaluate_rollout takes them; K = `samples` futures of the P-frame prompt are drawn in one rollout and scored against
+        the S frames that really followed on the device (vlg.engine.LayoutEngine.evaluate_samples; one host read at the
+        end).  samples / select: None takes args.gen_samples / VLG_GEN_SAMPLES and args.gen_select / VLG_GEN_SELECT
+        (sample_knobs); the other arguments are evaluate_rollout's.  Returns one dict (vlg.samples.SampleRecord.summary):
+        best_iou / best_ade / best_fde / best_acc - the best of the K samples per clip, averaged over clips (minADE, minFDE) -
+        mean_* over the samples, selected_* at the sample `select` picked, diversity_box, diversity_class and clips."""
+        knobs, K = self._sampling_knobs("evaluate_samples", temperature, top_k, seed, keep_padded, samples)
+        select = sample_knobs(self.args)["select"] if select is None else select_option(select)
+        with self._eval_weights():
+            record = self.engine.evaluate_samples(
+                clip_class.to(self.device).contiguous(), clip_box.to(self.device).contiguous(), samples=K, select=select,
+                temperature=knobs["temperature"], sample_top_k=knobs["top_k"], seed=knobs["seed"], keep_padded=knobs["keep_padded"],
+                prompt_frames=prompt_frames,
+                **({"box_temperature": knobs["box_temperature"]} if "box_temperature" in knobs else {}))
+        return record.summary()
 
     def render_layout(self, slot_class, slot_box, size=None, valid=None, what: str = "class", dtype=torch.float32):
         """Layout mode: draw layouts into label maps on the device (LayoutEngine.rasterize) and return them on the CPU.

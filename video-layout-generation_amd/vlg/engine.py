@@ -35,6 +35,7 @@ from . import hip
 from .attention import MODES, cached_by_default, layer_kinds, lse_rows
 from .metrics import MetricsRecord
 from .raster import MAX_SLOTS, WHATS, PixelRecord, raster_options
+from .samples import COLS as SMP_COLS, CRITERIA, SampleRecord, sample_passes, samples_options, select_option
 from .optim import AdamSurface, FlatAdam, build_decay_mask, decays_matrix
 from .slabs import SlabBuckets
 from .hip import (EPI_A_BF16, EPI_B_BF16, EPI_BIAS, EPI_DGELU, EPI_GELU, EPI_NONE, EPI_OUT_BF16, EPI_RESID,
@@ -1043,6 +1044,14 @@ class LayoutEngine(AdamSurface):
         step) under `seed` on a stream of its own - the class draw is what it is without it.  A Gaussian-head engine decodes
         through vlg_layout_decode_ext / vlg_layout_decode_append_ext (row stride n_out) in every step kind, sliding, cached and
         re-encoded alike; a point-head engine's launches are what they always were."""
+        return self._rollout(slot_class, slot_box, steps, temperature, top_k, seed, keep_padded, return_logits, cache,
+                             box_temperature)
+
+    def _rollout(self, slot_class, slot_box, steps, temperature, top_k, seed, keep_padded, return_logits, cache, box_temperature,
+                 smp: Optional[tuple] = None) -> tuple:
+        """rollout()'s loop.  smp = (clips, sample0), from rollout_samples alone: the batch holds B / clips samples of `clips`
+        prompts, sample-major, and every frame is decoded by the _samples entries (the _ext argument lists plus clips and
+        sample0) - nothing else in the loop knows.  None launches what rollout() always launched."""
         cfg, d = self.cfg, self.cfg.d
         box_tau = box_temperature_options(box_temperature, cfg.box_head)
         if slot_class.dim() != 3 or tuple(slot_box.shape) != tuple(slot_class.shape) + (BOX_DIM,):
@@ -1089,7 +1098,10 @@ class LayoutEngine(AdamSurface):
         knobs = (float(temperature), top_k, int(seed) & 0xFFFFFFFFFFFFFFFF, int(bool(keep_padded)), s)
         # the Gaussian head's rows are [logits | raw mean | raw scale | padding]: the _ext entries take the stride and the box draw
         ext, dec_ld, dec_tau = ("_ext", (cfg.n_out,), (box_tau,)) if cfg.gaussian_box else ("", (), ())
-        cur = 0                                                     # the window buffer that holds the history
+        if smp is not None:                                         # K futures per prompt: the sample is the counter's last word
+            ext, dec_ld, dec_tau = "_samples", (cfg.n_out,), (box_tau,)
+            knobs = knobs[:4] + (int(smp[0]), int(smp[1]), s)
+        cur = 0                                                    # the window buffer that holds the history
         for i, (encoder, t_read, pos) in enumerate(grow_schedule(P, T, steps, cached)):
             (cls, box, valid), (ncls, nbox, nvalid) = win[cur], win[cur ^ 1]
             if encoder == "step":                                   # the newest frame alone, against the cache: its rows are the last
@@ -1109,6 +1121,102 @@ class LayoutEngine(AdamSurface):
                         nbytes=4.0 * BN * cfg.n_out + 2.0 * 28 * M)
             cur ^= 1
         return (gen_cls, gen_box, logits) if return_logits else (gen_cls, gen_box)
+
+    # ------------------------------------------------------------- sampled futures
+    def rollout_samples(self, slot_class: torch.Tensor, slot_box: torch.Tensor, steps: int = 8, samples: int = 1, sample0: int = 0,
+                        temperature: float = 0.0, top_k: int = 0, seed: int = 0, keep_padded: bool = False,
+                        return_logits: bool = False, cache: Optional[bool] = None, box_temperature: float = 0.0) -> tuple:
+        """K = `samples` futures of every prompt from ONE seed, in one rollout (DESIGN.md "Sampled futures"): the prompt
+        slot_class (B,P,N) / slot_box (B,P,N,4) and every other argument are rollout()'s.  Returns DEVICE tensors gen_cls
+        (K,B,steps,N) int64, gen_box (K,B,steps,N,4) fp32 and, with return_logits, logits (K,steps,B*N,n_out).
+        The prompt is replicated sample-major into a batch of K*B clips and rollout()'s own loop runs on it - every attention
+        mode, the cached and the re-encoded grow steps and the slide - with the _samples decode entries: the token of prompt b,
+        slot n draws with Philox counter (b*N + n, step, stream, sample0 + k) under `seed`.  So sample k is a function of (prompt,
+        weights, seed, sample0 + k) alone - not of K, of the other prompts' place in the batch or of how the samples were split
+        into passes - and sample 0 draws the random numbers rollout() draws.  When K*B*T*N exceeds the workspace capacity the
+        call runs ceil(K / k_fit) passes of k_fit = capacity // (B*T*N) samples, each with its own first sample index
+        (vlg.samples.sample_passes); ValueError if not even one sample fits.  samples > 1 with temperature 0 and box_temperature
+        0 is refused: all samples would be equal.  samples = 1 with sample0 = 0 IS rollout(): the same launches."""
+        K, k0 = samples_options(samples, sample0)
+        if slot_class.dim() != 3 or tuple(slot_box.shape) != tuple(slot_class.shape) + (BOX_DIM,):
+            raise ValueError("rollout_samples takes slot_class (B,P,N) and slot_box (B,P,N,4)")
+        B, P, N = slot_class.shape
+        box_tau = box_temperature_options(box_temperature, self.cfg.box_head)
+        decode_options(temperature, int(top_k), self.cfg.n_classes)
+        if K > 1 and float(temperature) == 0.0 and box_tau == 0.0:
+            raise ValueError("samples=%d with temperature 0 and box_temperature 0: every sample would be the argmax rollout" % K)
+        if B < 1 or N < 1:
+            raise ValueError("rollout_samples needs at least one clip and one slot")
+        passes = sample_passes(K, k0, B * self.cfg.T * N, self.capacity)
+        steps, outs = int(steps), []
+        for first, k in passes:
+            if k == 1 and first == 0:
+                out = self._rollout(slot_class, slot_box, steps, temperature, top_k, seed, keep_padded, return_logits, cache,
+                                    box_temperature)
+            else:
+                out = self._rollout(slot_class.repeat(k, 1, 1), slot_box.repeat(k, 1, 1, 1), steps, temperature, top_k, seed,
+                                    keep_padded, return_logits, cache, box_temperature, smp=(B, first))
+            out = [out[0].view(k, B, steps, N), out[1].view(k, B, steps, N, BOX_DIM)] + (
+                [out[2].view(steps, k, B * N, self.cfg.n_out).transpose(0, 1)] if return_logits else [])
+            outs.append(out)
+        return tuple(o[0] if len(outs) == 1 else torch.cat(o, dim=0) for o in zip(*outs))
+
+    def sample_record(self) -> SampleRecord:
+        """A zeroed SampleRecord (vlg/samples.py) on the engine's device."""
+        return SampleRecord(self.device)
+
+    def evaluate_samples(self, clip_class: torch.Tensor, clip_box: torch.Tensor, samples: int = 1, select: str = "iou",
+                         record: Optional[SampleRecord] = None, prompt_frames: Optional[int] = None, sample0: int = 0,
+                         temperature: float = 0.0, sample_top_k: int = 0, seed: int = 0, keep_padded: bool = False,
+                         cache: Optional[bool] = None, box_temperature: float = 0.0, return_samples: bool = False):
+        """Best-of-K score of a stochastic model.  clip_class (B,P+S,N) int64 / clip_box (B,P+S,N,4) fp32 as evaluate_rollout
+        takes them: the first P = prompt_frames frames (None: T) prompt rollout_samples(..., steps=S, samples=K) under the
+        sampling knobs, and the K futures are scored against frames P .. P+S-1 of the clip, read in place, by three launches
+        (definitions: include/vlg_hip.h, "sampled futures"): vlg_layout_sample_scores - per sample and clip the mean IoU, the
+        mean and the final-frame displacement of the box centres (ADE / FDE) and the class accuracy of the DRAWN frames over
+        the tokens whose truth is a real class; vlg_layout_sample_diversity - how much a clip's samples differ pairwise;
+        vlg_layout_sample_select - the best sample of every clip by `select` (iou | ade | fde | acc), gathered, and the sums
+        ADDED to `record` (a fresh SampleRecord if None).  No host wait; record.summary() makes the one host read.
+        Returns the record, or with return_samples (record, dict(best (B,) int32, best_cls (B,S,N), best_box (B,S,N,4),
+        gen_cls (K,B,S,N), gen_box (K,B,S,N,4), scores (K,B,VLG_SMP_COLS), div (B,2)))."""
+        cfg = self.cfg
+        criterion = CRITERIA[select_option(select)]
+        if clip_class.dim() != 3 or tuple(clip_box.shape) != tuple(clip_class.shape) + (BOX_DIM,):
+            raise ValueError("evaluate_samples takes clip_class (B,P+S,N) and clip_box (B,P+S,N,4)")
+        B, TS, N = clip_class.shape
+        P = cfg.T if prompt_frames is None else int(prompt_frames)
+        if not 1 <= P <= cfg.T:
+            raise ValueError("prompt_frames must be in [1, T=%d], got %r" % (cfg.T, prompt_frames))
+        S = TS - P
+        if S < 1:
+            raise ValueError("the clip has %d frames: the %d-frame prompt and at least one frame to score" % (TS, P))
+        for t, dt, what in ((clip_class, torch.int64, "clip_class"), (clip_box, torch.float32, "clip_box")):
+            if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous %s HIP tensor" % (what, dt))
+        if record is None:
+            record = self.sample_record()
+        elif not isinstance(record, SampleRecord) or not record.sums.is_cuda:
+            raise ValueError("record must be a SampleRecord on %s (engine.sample_record())" % self.device)
+        gen_cls, gen_box = self.rollout_samples(clip_class[:, :P], clip_box[:, :P], steps=S, samples=samples, sample0=sample0,
+                                                temperature=temperature, top_k=sample_top_k, seed=seed, keep_padded=keep_padded,
+                                                cache=cache, box_temperature=box_temperature)
+        gen_cls, gen_box = gen_cls.contiguous(), gen_box.contiguous()
+        K, C, s = gen_cls.shape[0], cfg.n_classes, self._stream()
+        f32 = dict(dtype=torch.float32, device=self.device)
+        scores, div = torch.empty(K, B, SMP_COLS, **f32), torch.empty(B, 2, **f32)
+        best = torch.empty(B, dtype=torch.int32, device=self.device)
+        best_cls, best_box = torch.empty_like(gen_cls[0]), torch.empty_like(gen_box[0])
+        G = float(K * B * S * N)
+        self._timed("samples", 0.0, "vlg_layout_sample_scores", ptr(gen_cls), ptr(gen_box), ptr(clip_class), ptr(clip_box),
+                    ptr(scores), K, B, S, N, TS, P, C, IOU_EPS, s, nbytes=48.0 * G + 4.0 * SMP_COLS * K * B)
+        self._timed("samples", 0.0, "vlg_layout_sample_diversity", ptr(gen_cls), ptr(gen_box), ptr(clip_class), ptr(div),
+                    K, B, S, N, TS, P, C, IOU_EPS, s, nbytes=24.0 * G + 8.0 * B * S * N + 8.0 * B)
+        self._timed("samples", 0.0, "vlg_layout_sample_select", ptr(scores), ptr(div), ptr(gen_cls), ptr(gen_box), ptr(best),
+                    ptr(best_cls), ptr(best_box), ptr(record.sums), K, B, S, N, criterion, s,
+                    nbytes=4.0 * SMP_COLS * K * B + 48.0 * B * S * N + 12.0 * B)
+        if not return_samples:
+            return record
+        return record, dict(best=best, best_cls=best_cls, best_box=best_box, gen_cls=gen_cls, gen_box=gen_box, scores=scores, div=div)
 
     # --------------------------------------------------------------------- metrics
     def metrics_record(self, rows: int = 1) -> MetricsRecord:
