@@ -388,6 +388,64 @@ def embed_bwd(dx, slot_class, slot_box, vocab, B, T, N):
 
 
 # ------------------------------------------------------------------------------------------------ the schedule
+def forward_launches(out, cfg, c, tag, drop, cls, box, valid, final=True):
+    """Appends to `out` the launches from the embedding through the head (LayoutEngine._encode and the head projection); tag: a
+    prefix of the stage names (scheduled sampling's pass 1); cls, box, valid: the names of what the embedding and the per-clip
+    attention read.  final False: the window encode of a rollout - through x[L], no final norm, no head projection."""
+    L = cfg.n_layers
+    kinds = layer_kinds(c.attention, L)
+    rows = lse_rows(kinds)
+    P = lambda n: "p:" + n
+
+    def ln_f(stage, x, gname, y, i, branch=None):
+        """the layer-norm of statistics slot i; dropout: the fused launch of site i, which first forms x = resid + drop(branch)
+        (resid = the `x` of the launch this one replaces: site 0 has none and runs in place on x[0])"""
+        if drop:
+            src, resid = (x, None) if branch is None else ("ybranch", branch)
+            out.append(dict(stage=tag + stage, kind="drop_ln_fwd", family="ln_fwd", entry="vlg_dropout_add_layernorm_fwd" + c.sfx, y=src,
+                            resid=resid, g=gname, x_out=x, h=y, stat=i, site=i,
+                            ops=(src, resid, P(gname), P(gname[:-1] + "b"), x, y, "stats[%d].mean" % i, "stats[%d].rstd" % i, "drop_step")))
+            return
+        out.append(dict(stage=tag + stage, kind="ln_fwd", family="ln_fwd", entry="vlg_layernorm_fwd" + c.sfx, x=x, g=gname, y=y, stat=i,
+                        ops=(x, P(gname), P(gname[:-1] + "b"), y, "stats[%d].mean" % i, "stats[%d].rstd" % i)))
+
+    def lin(stage, a, wname, cbuf, epi, aux_in=None, aux_out=None):
+        flags = epi | c.gemm_flags | c.bits(a, True, cbuf)
+        out.append(dict(stage=tag + stage, kind="linear_fwd", family="gemm_head" if wname == "head_w" else "gemm_fwd", entry="vlg_linear_fwd",
+                        a=a, w=wname, c=cbuf, epi=epi, aux_in=aux_in, aux_out=aux_out, flags=flags,
+                        ops=(a, c.weight(wname), P(wname[:-1] + "b"), cbuf, aux_in, aux_out)))
+
+    out.append(dict(stage=tag + "embedding", kind="embed_fwd", family="embed_fwd", entry="vlg_embed_fwd", cls=cls, box=box,
+                    ops=(cls, box, P("cls_emb"), P("box_w"), P("box_b"), P("time_emb"), "x[0]")))
+    epi_ff1 = EPI_BIAS | EPI_GELU | (EPI_GELU_GRAD if c.gelu_grad_saved else 0)
+    for l in range(L):
+        pre = "l%d." % l
+        x, h1, qkv, att, xmid, h2, u, gl = ("%s[%d]" % (n, l) for n in ("x", "h1", "qkv", "att", "xmid", "h2", "u", "gl"))
+        ln_f(pre + "ln1", x, pre + "ln1_g", h1, 2 * l, branch="xmid[%d]" % (l - 1) if l else None)
+        lin(pre + "qkv", h1, pre + "qkv_w", qkv, EPI_BIAS)
+        k = kinds[l]
+        if k.per_clip:      # "clip" (block-causal) or "frame": the same operand list, the lse row of vlg.attention.lse_rows
+            short = k.family.split("_")[1]
+            out.append(dict(stage=tag + pre + "attention", kind=short + "_fwd", family=k.family + "_fwd", entry=k.stem + "_fwd" + c.sfx,
+                            l=l, row=rows[l], valid=valid, ops=(qkv, valid, att, "lse[%d]" % rows[l])))
+        else:
+            out.append(dict(stage=tag + pre + "attention", kind="slot_fwd", family="attn_fwd", entry="vlg_attention_fwd" + c.sfx, l=l,
+                            ops=(qkv, att)))
+        if drop:
+            lin(pre + "proj", att, pre + "proj_w", "ybranch", EPI_BIAS)
+        else:
+            lin(pre + "proj", att, pre + "proj_w", xmid, EPI_BIAS | EPI_RESID, aux_in=x)
+        ln_f(pre + "ln2", xmid, pre + "ln2_g", h2, 2 * l + 1, branch=x)
+        lin(pre + "ff1", h2, pre + "ff1_w", gl, epi_ff1, aux_out=u)
+        if drop:
+            lin(pre + "ff2", gl, pre + "ff2_w", "ybranch", EPI_BIAS)
+        else:
+            lin(pre + "ff2", gl, pre + "ff2_w", "x[%d]" % (l + 1), EPI_BIAS | EPI_RESID, aux_in=xmid)
+    if final:
+        ln_f("lnf", "x[%d]" % L, "lnf_g", "xf", 2 * L, branch="xmid[%d]" % (L - 1))
+        lin("head", "xf", "head_w", "out", EPI_BIAS)
+
+
 def schedule(cfg, c):
     """The launches of one forward_backward in order, as vlg/engine.py makes them under contract `c`.  Each entry: stage
     (a name for messages), family, entry (C-ABI name), ops (names of the pointer arguments in order; None = NULL, "arena"
@@ -405,54 +463,7 @@ def schedule(cfg, c):
     P = lambda n: "p:" + n
     out = []
 
-    def forward(tag, drop, cls, box):
-        """the launches from the embedding through the head; tag: a prefix of the stage names (scheduled sampling's pass 1)"""
-        def ln_f(stage, x, gname, y, i, branch=None):
-            """the layer-norm of statistics slot i; dropout: the fused launch of site i, which first forms x = resid + drop(branch)
-            (resid = the `x` of the launch this one replaces: site 0 has none and runs in place on x[0])"""
-            if drop:
-                src, resid = (x, None) if branch is None else ("ybranch", branch)
-                out.append(dict(stage=tag + stage, kind="drop_ln_fwd", family="ln_fwd", entry="vlg_dropout_add_layernorm_fwd" + c.sfx, y=src,
-                                resid=resid, g=gname, x_out=x, h=y, stat=i, site=i,
-                                ops=(src, resid, P(gname), P(gname[:-1] + "b"), x, y, "stats[%d].mean" % i, "stats[%d].rstd" % i, "drop_step")))
-                return
-            out.append(dict(stage=tag + stage, kind="ln_fwd", family="ln_fwd", entry="vlg_layernorm_fwd" + c.sfx, x=x, g=gname, y=y, stat=i,
-                            ops=(x, P(gname), P(gname[:-1] + "b"), y, "stats[%d].mean" % i, "stats[%d].rstd" % i)))
-
-        def lin(stage, a, wname, cbuf, epi, aux_in=None, aux_out=None):
-            flags = epi | c.gemm_flags | c.bits(a, True, cbuf)
-            out.append(dict(stage=tag + stage, kind="linear_fwd", family="gemm_head" if wname == "head_w" else "gemm_fwd", entry="vlg_linear_fwd",
-                            a=a, w=wname, c=cbuf, epi=epi, aux_in=aux_in, aux_out=aux_out, flags=flags,
-                            ops=(a, c.weight(wname), P(wname[:-1] + "b"), cbuf, aux_in, aux_out)))
-
-        out.append(dict(stage=tag + "embedding", kind="embed_fwd", family="embed_fwd", entry="vlg_embed_fwd", cls=cls, box=box,
-                        ops=(cls, box, P("cls_emb"), P("box_w"), P("box_b"), P("time_emb"), "x[0]")))
-        epi_ff1 = EPI_BIAS | EPI_GELU | (EPI_GELU_GRAD if c.gelu_grad_saved else 0)
-        for l in range(L):
-            pre = "l%d." % l
-            x, h1, qkv, att, xmid, h2, u, gl = ("%s[%d]" % (n, l) for n in ("x", "h1", "qkv", "att", "xmid", "h2", "u", "gl"))
-            ln_f(pre + "ln1", x, pre + "ln1_g", h1, 2 * l, branch="xmid[%d]" % (l - 1) if l else None)
-            lin(pre + "qkv", h1, pre + "qkv_w", qkv, EPI_BIAS)
-            k = kinds[l]
-            if k.per_clip:      # "clip" (block-causal) or "frame": the same operand list, the lse row of vlg.attention.lse_rows
-                short = k.family.split("_")[1]
-                out.append(dict(stage=tag + pre + "attention", kind=short + "_fwd", family=k.family + "_fwd", entry=k.stem + "_fwd" + c.sfx,
-                                l=l, row=rows[l], valid=valid, ops=(qkv, valid, att, "lse[%d]" % rows[l])))
-            else:
-                out.append(dict(stage=tag + pre + "attention", kind="slot_fwd", family="attn_fwd", entry="vlg_attention_fwd" + c.sfx, l=l,
-                                ops=(qkv, att)))
-            if drop:
-                lin(pre + "proj", att, pre + "proj_w", "ybranch", EPI_BIAS)
-            else:
-                lin(pre + "proj", att, pre + "proj_w", xmid, EPI_BIAS | EPI_RESID, aux_in=x)
-            ln_f(pre + "ln2", xmid, pre + "ln2_g", h2, 2 * l + 1, branch=x)
-            lin(pre + "ff1", h2, pre + "ff1_w", gl, epi_ff1, aux_out=u)
-            if drop:
-                lin(pre + "ff2", gl, pre + "ff2_w", "ybranch", EPI_BIAS)
-            else:
-                lin(pre + "ff2", gl, pre + "ff2_w", "x[%d]" % (l + 1), EPI_BIAS | EPI_RESID, aux_in=xmid)
-        ln_f("lnf", "x[%d]" % L, "lnf_g", "xf", 2 * L, branch="xmid[%d]" % (L - 1))
-        lin("head", "xf", "head_w", "out", EPI_BIAS)
+    forward = lambda tag, drop, cls, box: forward_launches(out, cfg, c, tag, drop, cls, box, valid)
 
     if c.augment is not None:      # builds the batch every later launch reads (tgt_class stays the caller's)
         out.append(dict(stage="augment", kind="augment", family="augment", entry="vlg_layout_augment",

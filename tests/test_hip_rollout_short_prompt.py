@@ -65,13 +65,14 @@ def _check_short(tr, cls0, box0, P, attention, bf16=False, cache=None, keep_padd
     return out_c, out_b
 
 
-@pytest.mark.parametrize("precision,cache", [("fp32", None), ("fp32x3", None), ("bf16", None), ("fp32", False)],
-                         ids=["fp32", "fp32x3", "bf16", "fp32-reencode"])
+@pytest.mark.parametrize("precision,cache", [("fp32", None), ("fp32x3", None), ("bf16", None), ("fp32", False), ("bf16_mfma", None)],
+                         ids=["fp32", "fp32x3", "bf16", "fp32-reencode", "bf16_mfma"])
 def test_short_prompt_slot(tmp_path, monkeypatch, dev, precision, cache):
     tr, cls0, box0 = _trainer(tmp_path, monkeypatch, "slot", precision=precision)
     assert tr.engine.precision == precision
     for P in PROMPTS:
-        _check_short(tr, cls0, box0, P, "slot", bf16=precision == "bf16", cache=cache)
+        # bf16_mfma rounds a subset of what bf16 rounds (projection operands, no stored activation): that mode's bar
+        _check_short(tr, cls0, box0, P, "slot", bf16=precision in ("bf16", "bf16_mfma"), cache=cache)
 
 
 def test_short_prompt_clip(tmp_path, monkeypatch, dev):
